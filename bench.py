@@ -7,7 +7,13 @@ are split by equal work (the rule of mm/inc/BIN.h:101-122), every rank owns its 
 {exchange x over RCCL/xGMI, local SpMV} — total work is fixed, so scaling is "strong". Inputs are resident in HBM before
 the timed region. Prints ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rmat|banded|lap5|lap7] [--exchange auto|dist|allgather]
+A plain run sets up, warms up, times the steps and prints the line. `--full` adds everything else the line can carry: the CPU baselines
+and the self-check against the oracle (`cpu_baseline`, `max_rel_err`, `parity`), the secondary configs (`also`, `also_banded`,
+`also_spgemm`), the repeated plan build (`plan.build_ms_repeated`) and, at N > 1, the re-measured product time behind `roofline`.
+`--dump-outputs DIR` writes the y of the last timed step (or a fixed sample of its rows, see dump_outputs) as .npy files (bench_outputs/ is
+kept out of git for that use).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rmat|banded|lap5|lap7] [--exchange auto|dist|allgather] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -263,6 +269,29 @@ def config2_spgemm(small, host, capi, torch, runs=10, mkl_threads=14):
     return out
 
 
+DUMP_ROWS = 3_000_000   # rows of y that --dump-outputs writes at most: values + row numbers = 48 MB, inside the 64 MB budget
+
+
+def dump_outputs(out_dir, y_local, r0, n_rows, rank=0, world=1, dist=None, reduce_device="cpu", cap=DUMP_ROWS, seed=20240521):
+    """--dump-outputs: the y of the last timed step, as a caller of the product receives it. All rows where n_rows <= cap, else `cap` rows drawn
+    from a fixed seed (the same rows in every run of the same workload), ascending. DIR/y.npy holds y at those rows (float64), DIR/y_rows.npy
+    the row numbers (float64, exact below 2^53). At N > 1 every rank fills in the rows of its own slab [r0, r0 + len(y_local)) and the sum
+    over the ranks reaches rank 0, which writes."""
+    import numpy as np
+    import torch
+    rows = np.arange(n_rows) if n_rows <= cap else np.sort(np.random.default_rng(seed).choice(n_rows, cap, replace=False))
+    lo, hi = np.searchsorted(rows, [r0, r0 + y_local.numel()])
+    vals = torch.zeros(len(rows), dtype=torch.float64, device=y_local.device)
+    vals[lo:hi] = y_local[torch.from_numpy(rows[lo:hi] - r0).to(y_local.device)]
+    if world > 1:
+        vals = vals.to(reduce_device)
+        dist.all_reduce(vals)                                      # the slabs are disjoint: every row is its owner's value plus zeros
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "y.npy"), vals.cpu().numpy())
+        np.save(os.path.join(out_dir, "y_rows.npy"), rows.astype(np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks as fresh child processes (this process has not
     touched the GPU yet and never will), relay rank 0's JSON line, return the children's exit code."""
@@ -285,9 +314,13 @@ def main():
                     help="auto = dist: the C-ABI multi-GPU product (g4s_spmv_dist_*) with the packed exchange (RCCL send/recv of the referenced x entries, overlapped with "
                          "the own-column product); allgather: the same product with ONE ncclAllGather of the whole vector (also the fallback when the packed wiring fails)")
     ap.add_argument("--small", action="store_true", help="reduced sizes for plumbing checks (not a valid benchmark)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary configs[3] (7-point Laplacian 431^3) measurement reported under `also`")
-    ap.add_argument("--spgemm-runs", type=int, default=10, help="timed runs of the configs[2] SpGEMM call under `also_spgemm` (after 1 warm-up)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: CPU baselines and the self-check against the oracle, the secondary configs (`also`, `also_banded`, "
+                         "`also_spgemm`), the repeated plan build and, at N > 1, the re-measured product time behind `roofline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the y of the last timed step (a fixed sample of its rows above 3M rows) to DIR/y.npy, DIR/y_rows.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline` and the self-check")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary configs under `also`, `also_banded` and `also_spgemm`")
+    ap.add_argument("--spgemm-runs", type=int, default=10, help="with --full: timed runs of the configs[2] SpGEMM call under `also_spgemm` (after 1 warm-up)")
     ap.add_argument("--no-nt", action="store_true", help="plain loads for the matrix stream (A/B against nontemporal)")
     ap.add_argument("--path", default="auto", choices=["auto", "stream", "blocked"],
                     help="SpMV path: auto = the library picks per matrix (propagation-blocked without gather locality, index-free diagonal form for "
@@ -377,15 +410,16 @@ def main():
         A.handle                                                   # g4s_csr_create: the plan is built here, once per matrix
         torch.cuda.synchronize()
         plan_ms = (time.perf_counter() - tp0) * 1e3
-        # the same create once more on a second handle: the library's block cache serves it (the first create of a process that did not call g4s_warm_up also
-        # pays for loading the plan kernels: 25 to 44 ms by box for a build that takes 18.6)
-        A2 = host.CSR(A_full.rowptr, A_full.colids, A_full.values, n_rows, n_cols, spmv_flags=flags)
-        torch.cuda.synchronize()
-        tp0 = time.perf_counter()
-        A2.handle
-        torch.cuda.synchronize()
-        plan_ms_repeated = (time.perf_counter() - tp0) * 1e3
-        del A2
+        if args.full:
+            # the same create once more on a second handle: the library's block cache serves it (the first create of a process that did not call g4s_warm_up also
+            # pays for loading the plan kernels: 25 to 44 ms by box for a build that takes 18.6)
+            A2 = host.CSR(A_full.rowptr, A_full.colids, A_full.values, n_rows, n_cols, spmv_flags=flags)
+            torch.cuda.synchronize()
+            tp0 = time.perf_counter()
+            A2.handle
+            torch.cuda.synchronize()
+            plan_ms_repeated = (time.perf_counter() - tp0) * 1e3
+            del A2
         x_full = host.synth_vector(7, n_cols)
         x_local = x_full
         y_local = torch.empty(n_rows, dtype=torch.float64, device="cuda")
@@ -417,14 +451,17 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y_local, r0, n_rows, rank, world, dist, "cuda" if args.backend == "nccl" else "cpu")
 
     # ---- roofline of the SpMV launch: HIP events on the launch stream around back-to-back launches. One launch of the hot path is
     # spmv_csr_adaptive_kernel (+ the few-µs long-row fixup) on the streaming path, or pb_prepare_kernel + pb_producer_kernel + pb_consumer_kernel on
     # the blocked path (their durations add up to kernel_ms; profiles/ holds the rocprofv3 split). At N=1 the timed region above
-    # IS that; at N>1 it is re-measured without the exchange, outside the timed region.
+    # IS that; at N>1 it is re-measured without the exchange, outside the timed region (--full only: without it `roofline` is null).
+    kernel_ms = None
     if world == 1:
         kernel_ms = ev0.elapsed_time(ev1) / args.steps
-    else:
+    elif args.full:
         k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         k0.record()
         for _ in range(args.steps):
@@ -432,7 +469,7 @@ def main():
         k1.record()
         torch.cuda.synchronize()
         kernel_ms = k0.elapsed_time(k1) / args.steps
-    achieved = info["algorithmic_bytes"] / (kernel_ms * 1e-3) / 1e9
+    achieved = None if kernel_ms is None else info["algorithmic_bytes"] / (kernel_ms * 1e-3) / 1e9
 
     # HBM bytes per launch come from PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, tools/prof_pmc.sh), which cannot run inside this process:
     # the number is read from the stored profile of the same workload and SpMV path, and the line says so (traffic_source).
@@ -477,7 +514,7 @@ def main():
                                     "no: fp64 sums meet in LDS / global atomics, last bits may differ run to run (inside the 1e-10 tolerance)"),
                    **({"backend": "gloo (rehearsal, not a valid multi-GPU number)"} if args.backend != "nccl" else {})},
         "hbm_gbs_algorithmic_whole_job": round((12 * nnz_total + 4 * (n_rows + 1) + 8 * n_rows + 8 * n_cols) * args.steps / elapsed / 1e9, 2),
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "roofline": None if kernel_ms is None else {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
                      "kernel": {0: "spmv_csr_adaptive_kernel", 1: "pb_prepare_kernel+pb_producer_kernel+pb_consumer_kernel (propagation-blocked SpMV)",
                                 3: "spmv_dia_kernel", 4: "spmv_bcsr_kernel"}[info["spmv_path"]], "kernel_ms": round(kernel_ms, 5),
@@ -494,7 +531,7 @@ def main():
         result["roofline"].update({"bytes_model": "csr-algorithmic; the diagonal kernel itself moves kernel_own_bytes (diagonals + row masks + x + y)",
                                    "kernel_own_bytes": own, "kernel_own_gbs": round(own / (kernel_ms * 1e-3) / 1e9, 1),
                                    "kernel_own_frac": round(own / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         base, y_cpu, asum = cpu_baseline(A, x_full)
         result["cpu_baseline"] = base
         # the bench checks itself: the y the timed launches produced against the oracle's, relative to Σ|a_ij·x_j| of the row
@@ -504,7 +541,7 @@ def main():
         result["parity"] = {"against": "oracle/g4s_oracle.c CSR SpMV on the same matrix and x", "tolerance": 1e-10, "ok": bool(err.max() <= 1e-10)}
     elif rank == 0:
         result["cpu_baseline"] = None
-    if not args.no_also and args.workload == "rmat":
+    if args.full and not args.no_also and args.workload == "rmat":
         # the multi-GPU config of BASELINE.json (configs[3]) in the same run, same ranks — R-MAT has no column locality and its strong
         # scaling is exchange-bound by construction; the stencil shows what the row partition does when only halos travel
         torch.cuda.empty_cache()
@@ -519,7 +556,7 @@ def main():
         except Exception as e:                                     # noqa: BLE001
             also_b = {"error": f"{type(e).__name__}: {e}"}
         result["also_banded"] = also_b
-    if not args.no_also and args.workload == "rmat" and world == 1:
+    if args.full and not args.no_also and args.workload == "rmat" and world == 1:
         # BASELINE configs[2] in the driver's own line ("driver-timed SpGEMM"); guarded like `also`
         try:
             del A, x_full, y_local

@@ -3,6 +3,9 @@
 Provenance of each file (inputs + expected outputs only; no reference source is stored):
   graphprocess_dense.npz  xx, w random (seed 42); result = the REFERENCE's GraphProcess (deepmd/source/op/graph.h:21-32,
                           compiled in place into oracle/_ref by oracle/Makefile) driving the OptMatmul gather. Needs /root/reference.
+  graphprocess_ref.npz    The inputs of the tests pinned to the reference's GraphProcess (tests/test_host_callbacks_cpu.py, the driver-loop pin of
+                          tests/test_oracle_cpu.py; seeded uniform(-1, 1)) and that GraphProcess's results on them, with the tests' own callbacks, so
+                          that those tests run where oracle/_ref cannot be built. Needs oracle/_ref, like graphprocess_dense.npz.
   spgemm_rmat8.npz        A = R-MAT scale 8 (n=256, 2048 draws, seed 1); C = A·A and y = A·x from the ORACLE restatement
                           (oracle/g4s_oracle.c). The reference has no buildable SpGEMM/SpMV here ("parity unpinned",
                           DESIGN.md); these vectors pin the oracle against regressions and are cross-checked with scipy below.
@@ -35,8 +38,40 @@ if ref is not None:
     res = np.zeros((29, 7))
     ref.ref_graph_process_dense(29, 13, 7, xx, w, res)
     np.savez(os.path.join(HERE, "graphprocess_dense.npz"), xx=xx, w=w, result=res)
+
+    import ctypes as C
+    import tempfile
+    from pathlib import Path
+    from tests.test_host_callbacks_cpu import _rows, carry_free_callbacks, compile_callbacks
+    from tests.test_oracle_cpu import pin_callbacks
+    g = {}
+    rng = np.random.default_rng(5)                                  # test_unregistered_python_callbacks_run_in_reference_order
+    g["py_xx"], g["py_states"] = rng.uniform(-1, 1, (23, 6)), rng.uniform(-1, 1, 6)
+    g["py_result"] = np.zeros(1 + 23 * 7)
+    ref.ref_graph_process_cb(23, 6, C.cast(_rows(g["py_xx"]), C.c_void_p), g["py_states"].ctypes.data, None, g["py_result"].ctypes.data,
+                             *carry_free_callbacks(6))
+    rng = np.random.default_rng(11)                                 # test_unregistered_c_callbacks_equal_the_reference_build
+    g["c_xx"], g["c_w"] = rng.uniform(-1, 1, (301, 17)), rng.uniform(-1, 1, (17, 9))
+    g["c_result"] = np.zeros(301 * 10)
+    with tempfile.TemporaryDirectory() as d:
+        cb = compile_callbacks(Path(d))
+        C.c_int.in_dll(cb, "g_inner").value, C.c_int.in_dll(cb, "g_degree").value = 17, 9
+        ref.ref_graph_process_cb(301, 9, C.cast(_rows(g["c_xx"]), C.c_void_p), g["c_w"].ctypes.data, None, g["c_result"].ctypes.data,
+                                 C.cast(cb.cb_gather, oracle_lib.FUN_GATHER), C.cast(cb.cb_apply, oracle_lib.FUN_APPLY))
+    rng = np.random.default_rng(23)                                 # test_four_argument_graphprocess_is_the_reference_spelling
+    g["host_xx"], g["host_w"] = rng.uniform(-1, 1, (257, 19)), rng.uniform(-1, 1, (19, 7))
+    g["host_result"] = np.zeros(257 * 7)
+    ref.ref_graph_process_dense(257, 19, 7, g["host_xx"].ravel(), g["host_w"].ravel(), g["host_result"])
+    rng = np.random.default_rng(3)                                  # test_graph_process_pinned_to_reference_build
+    g["pin_xx"], g["pin_w"] = rng.uniform(-1, 1, (37, 19)), rng.uniform(-1, 1, (19, 11))
+    g["pin_dense_result"] = np.zeros((37, 11))
+    ref.ref_graph_process_dense(37, 19, 11, g["pin_xx"], g["pin_w"], g["pin_dense_result"])
+    g["pin_cb_result"] = np.zeros(37 * 6)
+    ref.ref_graph_process_cb(37, 5, C.cast(_rows(g["pin_xx"]), C.c_void_p), np.ascontiguousarray(g["pin_w"].ravel()).ctypes.data, None,
+                             g["pin_cb_result"].ctypes.data, *pin_callbacks(5))
+    np.savez_compressed(os.path.join(HERE, "graphprocess_ref.npz"), **g)
 else:
-    print("oracle/_ref missing: graphprocess_dense.npz not regenerated")
+    print("oracle/_ref missing: graphprocess_dense.npz and graphprocess_ref.npz not regenerated")
 
 n = 256
 arpt, acol, aval = o.rmat_csr(1, 8, n, 2048)

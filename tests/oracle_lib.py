@@ -331,3 +331,20 @@ def load_ref():
     lib.ref_graph_process_cb.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, FUN_GATHER, FUN_APPLY]
     lib.ref_graph_process_dense.argtypes = [C.c_int, C.c_int, C.c_int, _f64, _f64, _f64]
     return lib
+
+
+GRAPHPROCESS_REF = os.path.join(ROOT, "tests", "golden", "graphprocess_ref.npz")
+
+
+def load_graphprocess_ref():
+    """Inputs of the tests pinned to the reference's GraphProcess, and its results on them (tests/golden/make_golden.py, from oracle/_ref)."""
+    return np.load(GRAPHPROCESS_REF)
+
+
+def ref_result(stored, run_ref):
+    """The reference GraphProcess's result for a test: the stored one; where oracle/_ref is built, run_ref(lib) recomputes it live and must agree bit for bit."""
+    ref = load_ref()
+    if ref is not None:
+        live = run_ref(ref)
+        assert np.array_equal(live, stored), "oracle/_ref disagrees with tests/golden/graphprocess_ref.npz"
+    return stored

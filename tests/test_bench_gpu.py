@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def _last_json(out):
 
 
 def test_bench_single_rank_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--small", "--steps", "5", "--warmup", "2", "--path", "blocked"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--small", "--steps", "5", "--warmup", "2", "--path", "blocked", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
@@ -60,7 +61,7 @@ def test_bench_self_launch_two_ranks():
     """`python bench.py --gpus 2` with no launcher around it (how the driver calls --gpus 1) starts its own ranks before touching the GPU."""
     env = dict(os.environ, G4S_BENCH_SAME_DEVICE="1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--small", "--backend", "gloo", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--small", "--backend", "gloo", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _last_json(r.stdout)
@@ -70,7 +71,7 @@ def test_bench_self_launch_two_ranks():
 @pytest.mark.parametrize("workload,exchange", [("rmat", "dist"), ("lap7", "dist"), ("rmat", "allgather"), ("lap7", "allgather")])
 def test_bench_two_ranks_rehearsal(workload, exchange):
     env = dict(os.environ, G4S_BENCH_SAME_DEVICE="1")
-    r = _launch_two_ranks(["--steps", "4", "--warmup", "1", "--small", "--backend", "gloo", "--workload", workload, "--exchange", exchange, "--no-cpu-baseline"], env)
+    r = _launch_two_ranks(["--steps", "4", "--warmup", "1", "--small", "--backend", "gloo", "--workload", workload, "--exchange", exchange, "--no-cpu-baseline", "--full"], env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] > 0 and d["scaling"] == "strong"
@@ -83,8 +84,49 @@ def test_bench_two_ranks_fall_back_together(fail):
     failing rank never posts: the readiness agreement in front of every collective phase keeps it out), or already in the local create: every rank takes the
     library's all-gather exchange instead (it needs no wiring), none hangs."""
     env = dict(os.environ, G4S_BENCH_SAME_DEVICE="1", G4S_DIST_FAIL=fail)
-    r = _launch_two_ranks(["--steps", "3", "--warmup", "1", "--small", "--backend", "gloo", "--no-cpu-baseline"], env)
+    r = _launch_two_ranks(["--steps", "3", "--warmup", "1", "--small", "--backend", "gloo", "--no-cpu-baseline", "--full"], env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["value"] > 0 and "ncclAllGather" in d["config"]["exchange"]
     assert "falls back" in r.stderr
+
+
+def _oracle_y(oracle):
+    """y = A·x of the --small R-MAT workload, computed by the oracle, and Σ|a_ij·x_j| per row (the scale of the 1e-10 tolerance)."""
+    import bench
+    from g4s_amd import host
+    A = bench.build_matrix("rmat", host, True)
+    rp, ci, va = A.to_host()
+    x = host.synth_vector(7, A.cols).cpu().numpy()
+    _, asum = oracle.spmv_ld(rp, ci, va, x)
+    return oracle.spmv(rp, ci, va, x), asum
+
+
+def _dumped_y(d):
+    y, rows = np.load(os.path.join(d, "y.npy")), np.load(os.path.join(d, "y_rows.npy"))
+    assert y.dtype == np.float64 and rows.dtype == np.float64 and y.shape == rows.shape
+    return y, rows
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path, oracle):
+    """Without --full the line carries the headline only; --dump-outputs writes the y of the last timed step (every row at this size), equal to the oracle's."""
+    r = subprocess.run([sys.executable, "bench.py", "--small", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["cpu_baseline"] is None and d["plan"]["build_ms_repeated"] is None and not {"also", "also_banded", "also_spgemm", "max_rel_err", "parity"} & set(d)
+    want, asum = _oracle_y(oracle)
+    y, rows = _dumped_y(tmp_path)
+    assert np.array_equal(rows, np.arange(len(want))) and np.all(np.abs(y - want) <= 1e-10 * asum + 1e-300)
+
+
+def test_bench_two_ranks_dump_the_whole_vector(tmp_path, oracle):
+    """At N > 1 the dumped y is every rank's slab put together on rank 0."""
+    env = dict(os.environ, G4S_BENCH_SAME_DEVICE="1")
+    r = _launch_two_ranks(["--steps", "3", "--warmup", "1", "--small", "--backend", "gloo", "--dump-outputs", str(tmp_path)], env)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    assert _last_json(r.stdout)["n_gpus"] == 2
+    want, asum = _oracle_y(oracle)
+    y, rows = _dumped_y(tmp_path)
+    assert np.array_equal(rows, np.arange(len(want))) and np.all(np.abs(y - want) <= 1e-10 * asum + 1e-300)

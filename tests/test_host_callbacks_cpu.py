@@ -1,6 +1,7 @@
 """The general case of the graph interface (B3): a (gather, apply) pair that is NOT one of the registered patterns runs the reference's driver
 loop on the host, in the product (g4s_spmm_dense / spmm_dense, g4s_amd/csrc/graph.hip). Compared bit for bit with the REFERENCE's own
-GraphProcess (deepmd/source/op/graph.h:21-32) compiled in place into oracle/_ref — the one place a reference-built pin exists. No GPU needed:
+GraphProcess (deepmd/source/op/graph.h:21-32) compiled in place into oracle/_ref — the one place a reference-built pin exists: its results on
+these tests' inputs are stored in tests/golden/graphprocess_ref.npz, and recomputed live where oracle/_ref is built. No GPU needed:
 host callbacks never touch the device."""
 import ctypes as C
 import os
@@ -33,11 +34,8 @@ void cb_apply(int e, const double **ew, const double *st, double *res)
 
 
 @pytest.fixture(scope="module")
-def ref():
-    lib = oracle_lib.load_ref()
-    if lib is None:
-        pytest.skip("oracle/_ref/libref_graph.so not built (no /root/reference here and no prebuilt copy)")
-    return lib
+def gold():
+    return oracle_lib.load_graphprocess_ref()
 
 
 @pytest.fixture(scope="module")
@@ -48,25 +46,38 @@ def g4s():
 
 @pytest.fixture(scope="module")
 def cb(tmp_path_factory):
-    d = tmp_path_factory.mktemp("cb")
-    src, so = d / "cb.c", d / "libcb.so"
-    src.write_text(CB_SRC)
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", str(so), str(src)])
-    return C.CDLL(str(so))
+    return compile_callbacks(tmp_path_factory.mktemp("cb"))
 
 
 def _rows(xx):
     return (C.POINTER(C.c_double) * len(xx))(*[xx[i].ctypes.data_as(C.POINTER(C.c_double)) for i in range(len(xx))])
 
 
-def test_unregistered_python_callbacks_run_in_reference_order(g4s, ref):
+def carry_free_callbacks(deg):
+    """A race-free gather (each (vertex, neighbour) writes its own slot) and an apply that sums its vertex's gathers; result[0] is left alone."""
+    @oracle_lib.FUN_GATHER
+    def gather(vi, nb, ew, st, res):
+        res[1 + vi * (deg + 1) + nb] = ew[vi][nb] * st[nb] + vi
+
+    @oracle_lib.FUN_APPLY
+    def apply(vi, ew, st, res):
+        res[1 + vi * (deg + 1) + deg] = sum(res[1 + vi * (deg + 1) + j] for j in range(deg))
+    return gather, apply
+
+
+def compile_callbacks(d):
+    src, so = d / "cb.c", d / "libcb.so"
+    src.write_text(CB_SRC)
+    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", str(so), str(src)])
+    return C.CDLL(str(so))
+
+
+def test_unregistered_python_callbacks_run_in_reference_order(g4s, gold):
     """One thread, ascending vertices, gather 0 … degree−1 then apply: a gather that depends on what earlier VERTICES left in result (a running
     value carried through result[0]) and an apply that reads its vertex's gathers — any other order changes the bits."""
     from g4s_amd import capi
-    rng = np.random.default_rng(5)
-    M, deg = 23, 6
-    xx = rng.uniform(-1, 1, (M, deg))
-    states = rng.uniform(-1, 1, deg)
+    xx, states = gold["py_xx"], gold["py_states"]                  # default_rng(5): uniform(-1, 1) 23 x 6, then 6
+    M, deg = xx.shape
     rows = _rows(xx)
     calls = []
 
@@ -82,7 +93,7 @@ def test_unregistered_python_callbacks_run_in_reference_order(g4s, ref):
         res[1 + vi * (deg + 1) + deg] = sum(res[1 + vi * (deg + 1) + j] for j in range(deg)) - res[0]
 
     assert g4s.g4s_set_host_callback_policy(capi.HOST_CALLBACKS_SERIAL) == 0
-    got, want = np.zeros(1 + M * (deg + 1)), np.zeros(1 + M * (deg + 1))
+    got = np.zeros(1 + M * (deg + 1))
     secs = C.c_double(-1.0)
     capi.check(g4s.g4s_spmm_dense(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, got.ctypes.data, gather, apply, C.byref(secs), 8))
     mine = list(calls)
@@ -92,18 +103,16 @@ def test_unregistered_python_callbacks_run_in_reference_order(g4s, ref):
     # one thread, which is what OMP_NUM_THREADS cannot force (omp_set_num_threads(8) is hard-coded) — so compare on a carry-free copy below
     # and keep the order assertion above for the sequencing
     del calls[:]
-
-    @oracle_lib.FUN_GATHER
-    def gather2(vi, nb, ew, st, res):
-        res[1 + vi * (deg + 1) + nb] = ew[vi][nb] * st[nb] + vi
-
-    @oracle_lib.FUN_APPLY
-    def apply2(vi, ew, st, res):
-        res[1 + vi * (deg + 1) + deg] = sum(res[1 + vi * (deg + 1) + j] for j in range(deg))
+    gather2, apply2 = carry_free_callbacks(deg)
 
     got[:] = 0.0
     capi.check(g4s.g4s_spmm_dense(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, got.ctypes.data, gather2, apply2, None, 8))
-    ref.ref_graph_process_cb(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, want.ctypes.data, gather2, apply2)
+
+    def live(ref):
+        out = np.zeros_like(got)
+        ref.ref_graph_process_cb(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, out.ctypes.data, gather2, apply2)
+        return out
+    want = oracle_lib.ref_result(gold["py_result"], live)
     assert np.array_equal(got, want)
     # the void reference symbol takes the same path
     got[:] = 0.0
@@ -112,25 +121,29 @@ def test_unregistered_python_callbacks_run_in_reference_order(g4s, ref):
 
 
 @pytest.mark.parametrize("policy,threads", [("serial", 8), ("parallel", 8), ("parallel", 3), ("parallel", 1)])
-def test_unregistered_c_callbacks_equal_the_reference_build(g4s, ref, cb, policy, threads):
+def test_unregistered_c_callbacks_equal_the_reference_build(g4s, gold, cb, policy, threads):
     """Race-free C callbacks (the OptMatmul gather shape): the product's host loop — serial, and with threadNum threads when the caller has declared
     the gather race-free — against the reference's GraphProcess on its 8 OpenMP threads, bit for bit."""
     from g4s_amd import capi
-    rng = np.random.default_rng(11)
-    M, N, K = 301, 17, 9
-    xx, w = rng.uniform(-1, 1, (M, N)), rng.uniform(-1, 1, (N, K))
+    xx, w = gold["c_xx"], gold["c_w"]                              # default_rng(11): uniform(-1, 1) 301 x 17, then 17 x 9
+    (M, N), K = xx.shape, w.shape[1]
     rows = _rows(xx)
     C.c_int.in_dll(cb, "g_inner").value = N
     C.c_int.in_dll(cb, "g_degree").value = K
     gather = C.cast(cb.cb_gather, oracle_lib.FUN_GATHER)
     apply = C.cast(cb.cb_apply, oracle_lib.FUN_APPLY)
-    got, want = np.zeros(M * (K + 1)), np.zeros(M * (K + 1))
+    got = np.zeros(M * (K + 1))
     assert g4s.g4s_set_host_callback_policy(capi.HOST_CALLBACKS_PARALLEL if policy == "parallel" else capi.HOST_CALLBACKS_SERIAL) == 0
     try:
         capi.check(g4s.g4s_spmm_dense(M, K, C.cast(rows, C.c_void_p), w.ctypes.data, None, got.ctypes.data, gather, apply, None, threads))
     finally:
         g4s.g4s_set_host_callback_policy(capi.HOST_CALLBACKS_SERIAL)
-    ref.ref_graph_process_cb(M, K, C.cast(rows, C.c_void_p), w.ctypes.data, None, want.ctypes.data, gather, apply)
+
+    def live(ref):
+        out = np.zeros_like(got)
+        ref.ref_graph_process_cb(M, K, C.cast(rows, C.c_void_p), w.ctypes.data, None, out.ctypes.data, gather, apply)
+        return out
+    want = oracle_lib.ref_result(gold["c_result"], live)
     assert np.array_equal(got, want)
     assert np.allclose(got.reshape(M, K + 1)[:, :K], xx @ w, rtol=1e-13, atol=1e-13)
 
@@ -156,7 +169,7 @@ def test_refusal_stays_reachable(g4s):
     assert g4s.g4s_set_host_callback_policy(7) == capi.ERR_INVALID
 
 
-def test_four_argument_graphprocess_is_the_reference_spelling(tmp_path, ref):
+def test_four_argument_graphprocess_is_the_reference_spelling(tmp_path, gold):
     """include/g4s/graph.hpp's global GraphProcess(graph, result, gather, apply) — the signature of deepmd/source/op/graph.h:21, std::function callbacks, no
     descriptor — in a C++ program that builds the OptMatmul graph the way deepmd/source/op/opt_matmul.cc:43-61 does: against the reference's own GraphProcess
     (oracle/_ref) bit for bit, serial and with the race-free declaration; the refusal policy surfaces as an exception."""
@@ -165,11 +178,14 @@ def test_four_argument_graphprocess_is_the_reference_spelling(tmp_path, ref):
     exe = str(tmp_path / "graph_process_host")
     subprocess.check_call(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "graph_process_host.cpp"),
                            "-L" + lib, "-lg4s_hip", "-Wl,-rpath," + lib, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-pthread", "-o", exe])
-    rng = np.random.default_rng(23)
-    M, N, K = 257, 19, 7
-    xx, w = rng.uniform(-1, 1, (M, N)), rng.uniform(-1, 1, (N, K))
-    want = np.zeros(M * K)
-    ref.ref_graph_process_dense(M, N, K, xx.ravel(), w.ravel(), want)
+    xx, w = gold["host_xx"], gold["host_w"]                        # default_rng(23): uniform(-1, 1) 257 x 19, then 19 x 7
+    (M, N), K = xx.shape, w.shape[1]
+
+    def live(ref):
+        out = np.zeros(M * K)
+        ref.ref_graph_process_dense(M, N, K, xx.ravel(), w.ravel(), out)
+        return out
+    want = oracle_lib.ref_result(gold["host_result"], live)
     payload = f"{M} {N} {K}\n".encode() + xx.tobytes() + w.tobytes()
     for mode in ("serial", "parallel", "scoped_race_free"):        # scoped_race_free: g4s::ScopedRaceFree around the untouched call instead of the process-wide policy
         out = subprocess.run([exe, mode], input=payload, capture_output=True, timeout=120)

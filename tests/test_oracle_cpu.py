@@ -175,26 +175,8 @@ def test_mtx_duplicates_kept_and_errors(tmp_path, oracle):
 
 
 # ------------------------------------------------------------------ graph interface
-def test_graph_process_pinned_to_reference_build(oracle):
-    """oracle_spmm_dense / oracle_dense_rows_times_matrix against the REFERENCE's GraphProcess (graph.h:21-32) built in
-    place into oracle/_ref. Skipped only where neither /root/reference nor a prebuilt oracle/_ref exists."""
-    ref = oracle_lib.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref/libref_graph.so not built (no /root/reference here)")
-    rng = np.random.default_rng(3)
-    M, N, K = 37, 19, 11
-    xx, w = rng.uniform(-1, 1, (M, N)), rng.uniform(-1, 1, (N, K))
-    got = oracle.dense_rows_times_matrix(xx, w)
-    want = np.zeros((M, K))
-    ref.ref_graph_process_dense(M, N, K, xx, w, want)
-    assert np.array_equal(got, want)                       # same k order, multiply then add: bit-identical
-    assert np.allclose(got, xx @ w, rtol=1e-14, atol=1e-14)
-
-    # driver loop order: a race-free gather (writes only result[vi*deg+nb]) and an apply that reads what gather wrote
-    deg = 5
-    rows = (C.POINTER(C.c_double) * M)(*[xx[i].ctypes.data_as(C.POINTER(C.c_double)) for i in range(M)])
-    states = np.ascontiguousarray(w.ravel())
-
+def pin_callbacks(deg):
+    """The callbacks of the driver-loop pin below (tests/golden/make_golden.py runs the reference with them)."""
     @oracle_lib.FUN_GATHER
     def gather(vi, nb, ew, st, res):
         res[vi * (deg + 1) + nb] = ew[vi][nb] * st[nb] + vi
@@ -202,10 +184,38 @@ def test_graph_process_pinned_to_reference_build(oracle):
     @oracle_lib.FUN_APPLY
     def apply(vi, ew, st, res):
         res[vi * (deg + 1) + deg] = sum(res[vi * (deg + 1) + j] for j in range(deg))
+    return gather, apply
 
-    r_or, r_ref = np.zeros(M * (deg + 1)), np.zeros(M * (deg + 1))
+
+def test_graph_process_pinned_to_reference_build(oracle):
+    """oracle_spmm_dense / oracle_dense_rows_times_matrix against the REFERENCE's GraphProcess (graph.h:21-32) built in
+    place into oracle/_ref: its results on these inputs are stored in tests/golden/graphprocess_ref.npz, and recomputed live where oracle/_ref is built."""
+    gold = oracle_lib.load_graphprocess_ref()
+    xx, w = gold["pin_xx"], gold["pin_w"]                   # default_rng(3): uniform(-1, 1) 37 x 19, then 19 x 11
+    (M, N), K = xx.shape, w.shape[1]
+    got = oracle.dense_rows_times_matrix(xx, w)
+
+    def live_dense(ref):
+        out = np.zeros((M, K))
+        ref.ref_graph_process_dense(M, N, K, xx, w, out)
+        return out
+    want = oracle_lib.ref_result(gold["pin_dense_result"], live_dense)
+    assert np.array_equal(got, want)                       # same k order, multiply then add: bit-identical
+    assert np.allclose(got, xx @ w, rtol=1e-14, atol=1e-14)
+
+    # driver loop order: a race-free gather (writes only result[vi*deg+nb]) and an apply that reads what gather wrote
+    deg = 5
+    rows = (C.POINTER(C.c_double) * M)(*[xx[i].ctypes.data_as(C.POINTER(C.c_double)) for i in range(M)])
+    states = np.ascontiguousarray(w.ravel())
+    gather, apply = pin_callbacks(deg)
+    r_or = np.zeros(M * (deg + 1))
     oracle.lib.oracle_spmm_dense(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, r_or.ctypes.data, gather, apply, None, 1)
-    ref.ref_graph_process_cb(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, r_ref.ctypes.data, gather, apply)
+
+    def live_cb(ref):
+        out = np.zeros(M * (deg + 1))
+        ref.ref_graph_process_cb(M, deg, C.cast(rows, C.c_void_p), states.ctypes.data, None, out.ctypes.data, gather, apply)
+        return out
+    r_ref = oracle_lib.ref_result(gold["pin_cb_result"], live_cb)
     assert np.array_equal(r_or, r_ref)
 
 

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 O=$ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $ROOT
-echo "== bench"; timeout -k 10 500 python3 bench.py > $O/bench_rmat.json 2> $O/bench_rmat.err; tail -c 600 $O/bench_rmat.json; echo
+echo "== bench"; timeout -k 10 500 python3 bench.py --full > $O/bench_rmat.json 2> $O/bench_rmat.err; tail -c 600 $O/bench_rmat.json; echo
 echo "== byte table"; timeout -k 10 300 python3 tools/byte_table.py > $O/spmv_byte_table.txt 2>&1; tail -12 $O/spmv_byte_table.txt
 echo "== row classes"; timeout -k 10 300 python3 tools/row_hist.py --ef 3 > $O/spgemm_row_classes.txt 2>&1; tail -5 $O/spgemm_row_classes.txt
 echo "== host phases"; G4S_DEBUG=1 timeout -k 10 300 python3 tools/bench_spgemm.py --ef 3 --runs 3 > $O/spgemm_host_phases.txt 2>&1; tail -30 $O/spgemm_host_phases.txt

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 O=$ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $ROOT
-echo "== bench"; timeout -k 10 500 python3 bench.py > $O/bench_rmat.json 2> $O/bench_rmat.err; tail -c 700 $O/bench_rmat.json; echo
+echo "== bench"; timeout -k 10 500 python3 bench.py --full > $O/bench_rmat.json 2> $O/bench_rmat.err; tail -c 700 $O/bench_rmat.json; echo
 echo "== kernel stats"; timeout -k 10 300 bash tools/prof_kernels.sh $TAG --no-also > $O/kernel_stats.txt 2>&1; grep -E "pb_|spmv" $O/kernel_stats.txt
 cp gpurun_out/kt_$TAG/*/*kernel_stats.csv $O/bench_rmat_kernel_stats.csv 2>/dev/null
 echo "== pmc"; timeout -k 10 600 bash tools/prof_pmc.sh $TAG --no-also > $O/pmc.txt 2>&1; cp gpurun_out/pmc_$TAG/summary.json $O/spmv_rmat_pmc_summary.json 2>/dev/null; tail -3 $O/pmc.txt
