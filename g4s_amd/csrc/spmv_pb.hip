@@ -3,12 +3,13 @@
 // Why: on R-MAT 10M/1e8 the row-streaming CSR kernel (spmv.hip) is bound by the x gather, not by the matrix stream — every
 // 8-byte gather that misses L2 moves a 128-byte line (PMC: 6.1 GB fetched for 1.4 GB of algorithmic bytes; the gathers alone
 // cost 0.89 ms, tools/gather_probe.hip). Blocking turns both random sides into streams:
-//   producer  — nonzeros regrouped by 16K-column band. A workgroup loads that band of x into LDS (128 KiB); each lane takes a
-//               pair of consecutive entries (local column u16, value f64; unit-stride loads), multiplies, and the four lanes
+//   producer  — nonzeros regrouped by W-column band (W = 20 448 where a workgroup may have 160 KiB of LDS, else 16 384). A workgroup
+//               loads that band of x into LDS (159.75 KiB); each lane takes a pair of consecutive entries (local column u16 with the
+//               micro-run head flag in bit 15, value f64; unit-stride loads), multiplies, and the four lanes
 //               of an 8-entry span sum the products of equal rows (a "micro-run": same row, same cell, same span) before
 //               writing them — on R-MAT only ≈0.57 sums per nonzero leave the producer (tools/cell_hist.py: 0.51 distinct
 //               (row, column band) pairs per nonzero).
-//   consumer  — micro-run sums regrouped by 16K-row band. A workgroup keeps that band of y in LDS, streams (sum f64, local row
+//   consumer  — micro-run sums regrouped by W-row band. A workgroup keeps that band of y in LDS, streams (sum f64, local row
 //               u16), accumulates with LDS fp64 atomics, and writes the band of y once.
 // HBM traffic ≈ 10.6 B/nonzero read + 4.4 written by the producer and 5.5 read by the consumer, all sequential, instead of
 // ≈62 B/nonzero of 128-byte line fetches.
@@ -28,8 +29,15 @@ namespace g4s {
 
 namespace {
 
-constexpr int kBandBits = 14;
-constexpr int kBand = 1 << kBandBits;        // 16384 columns / rows per band: 128 KiB of fp64 in LDS
+// Band width W (columns / rows per band) is a property of the plan: the widest multiple of kWindow whose x band and one zero word
+// fit in the LDS a workgroup may have — 20 448 (159.75 KiB + 8 B) where the device grants 160 KiB, 16 384 otherwise
+// (pb_band_width). The kernels that hold a band in LDS are instantiated for both.
+constexpr int kBandWide = 20448;
+constexpr int kBandNarrow = 16384;
+constexpr int kLocalBits = 15;               // colmap[col] = (band << 15) | local column; p_lcol = local column | head bit 15
+constexpr unsigned kLocalMask = (1u << kLocalBits) - 1u;
+constexpr unsigned kHeadBit = 1u << kLocalBits;
+static_assert(kBandWide < (1 << kLocalBits) && kBandWide % 32 == 0, "band width");
 constexpr int kMaxHotBands = 64;             // popularity-ranked column bands in front of the natural ones
 constexpr double kHotFactor = 4.0;           // a hot band must hold this many times the nonzeros of an average natural band
 constexpr int kPbThreads = 1024;
@@ -38,7 +46,6 @@ constexpr int kWindow = 32;                  // entries per merge window (= the 
                                              // is a run of one row inside one cell and one window; column bands start at multiples of it
 constexpr int kProducerChunk = 1 << 17;      // entries per producer workgroup (x band load amortised over ≥ 1.3 MiB of stream)
 constexpr int kConsumerChunk = 1 << 17;      // micro-runs per consumer workgroup of a split (heavy) row band
-constexpr unsigned kPadFlag = 0x8000u;       // local-column flag of a pad slot (its product is forced to 0)
 
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
 typedef unsigned short ushort4_t __attribute__((ext_vector_type(4)));
@@ -91,11 +98,11 @@ inline int prims_bits(int max_value) { int b = 1; while (b < 31 && (max_value >>
 
 // ================================================================================================ plan construction kernels
 // Hot column bands. In a power-law graph a few thousand columns hold a third of the nonzeros, but their ids are scattered over
-// the natural 16 K bands (R-MAT: ids with few 1-bits), so a row's entries in popular columns land in different bands and each
-// costs its own partial sum. Columns are therefore ranked by degree; the top H·16 K go to H extra "hot" bands in rank order (a row
+// the natural W-column bands (R-MAT: ids with few 1-bits), so a row's entries in popular columns land in different bands and each
+// costs its own partial sum. Columns are therefore ranked by degree; the top H·W go to H extra "hot" bands in rank order (a row
 // now merges all its entries of one hot band into one micro-run), the rest keep their natural band. On C2 the distinct
-// (row, band) pairs per nonzero drop from 0.512 to 0.324 (tools/hot_band_probe.py). colmap[col] = (band' << 14) | local column;
-// the x values of the hot columns are gathered into a dense hot_x (H·128 KiB) at the start of every product.
+// (row, band) pairs per nonzero drop from 0.512 to 0.324 (tools/hot_band_probe.py, W = 16 384). colmap[col] = (band' << 15) | local column;
+// the x values of the hot columns are gathered into a dense hot_x (H·W doubles) at the start of every product.
 // (Round 5. The first form was a bare atomicAdd(&deg[colids[k]], 1) per nonzero: 9.4 ms of the 51 ms plan on configs[1] — a power-law column distribution puts
 // 10^5 increments on each of a few addresses, and same-address atomics serialise in L2. Now every workgroup counts its contiguous share of the entries through
 // a small direct-mapped table in LDS: a column that owns its slot is counted there (the popular columns claim theirs within the first few hundred entries), a
@@ -175,18 +182,17 @@ __global__ void pb_iota_kernel(int n, int *__restrict__ v)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = i;
 }
-__global__ void pb_colmap_kernel(int cols, int H, const int *__restrict__ order /* columns by descending degree */, unsigned *__restrict__ colmap)
+__global__ void pb_colmap_kernel(int cols, int H, int W, unsigned *__restrict__ colmap)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cols) return;
-    if (H == 0) { colmap[i] = (unsigned)i; return; }
     // natural position first (every thread writes its own column), hot columns are overwritten by pb_colmap_hot_kernel afterwards
-    colmap[i] = (((unsigned)i >> kBandBits) + (unsigned)H) << kBandBits | ((unsigned)i & (kBand - 1));
+    colmap[i] = ((unsigned)(i / W) + (unsigned)H) << kLocalBits | (unsigned)(i % W);
 }
-__global__ void pb_colmap_hot_kernel(int nhot, const int *__restrict__ order, unsigned *__restrict__ colmap)
+__global__ void pb_colmap_hot_kernel(int nhot, int W, const int *__restrict__ order /* columns by descending degree */, unsigned *__restrict__ colmap)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < nhot) colmap[order[r]] = (unsigned)r;                   // band' = r >> 14 < H, local = r & 16383
+    if (r < nhot) colmap[order[r]] = (unsigned)(r / W) << kLocalBits | (unsigned)(r % W);   // band' = r / W < H
 }
 
 // The regrouping key of CSR entry k is (column band, row band). The entries arrive in CSR order — their row band never decreases — so a STABLE sort by column band
@@ -200,17 +206,17 @@ __global__ void pb_keys_kernel(int rows, long long nnz, const int *__restrict__ 
             const int mid = lo + ((hi - lo) >> 1);
             if (rowptr[mid] <= k) lo = mid; else hi = mid;
         }
-        key[k] = CB - 1 - (int)(colmap[colids[k]] >> kBandBits);
+        key[k] = CB - 1 - (int)(colmap[colids[k]] >> kLocalBits);
         rowid[k] = lo;
         idx[k] = (int)k;
     }
 }
 // the full key of every sorted position: (column band << bits) | row band
 __global__ void pb_full_keys_kernel(long long nnz, const int *__restrict__ sorted_ckey, const int *__restrict__ perm, const int *__restrict__ rowid, int CB, int band_key_bits,
-                                    unsigned *__restrict__ key_s)
+                                    int W, unsigned *__restrict__ key_s)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (long long)gridDim.x * blockDim.x)
-        key_s[i] = ((unsigned)(CB - 1 - sorted_ckey[i]) << band_key_bits) | ((unsigned)rowid[perm[i]] >> kBandBits);
+        key_s[i] = ((unsigned)(CB - 1 - sorted_ckey[i]) << band_key_bits) | (unsigned)(rowid[perm[i]] / W);
 }
 // the windows of the locality probe (pb_should_use), gathered into one buffer: window w = W consecutive column ids from position w·stride on
 __global__ void pb_sample_kernel(int W, int S, long long stride, const int *__restrict__ colids, int *__restrict__ out)
@@ -245,7 +251,7 @@ __global__ void pb_fill_producer_kernel(long long nnz, const int *__restrict__ c
         const unsigned k = perm[i], key = sorted_keys[i];
         const int q = (int)((long long)(key >> band_key_bits) * RB + (key & ((1u << band_key_bits) - 1u)));
         const long long pos = i + shift[q];
-        p_lcol[pos] = (unsigned short)(colmap[colids[k]] & (kBand - 1));
+        p_lcol[pos] = (unsigned short)(colmap[colids[k]] & kLocalMask);   // the head bit is added by pb_span_heads_kernel
         p_val[pos] = values[k];
         if (p_src) p_src[pos] = (int)k;
         t_row[pos] = rowid[k];
@@ -265,7 +271,9 @@ __global__ void pb_update_values_kernel(long long slots, const int *__restrict__
 }
 
 // Micro-run heads of a span: a real entry whose row differs from the previous entry's (or that opens the span). t_row < 0 marks pads.
-__global__ void pb_span_heads_kernel(long long nspans, const int *__restrict__ t_row, const int *__restrict__ t_cell,
+// The head flags go into bit 15 of the local columns (the producer reads them from there), and every pad's local column becomes W: the zero word behind
+// the band of x in the producer's LDS, so a pad's product is 0 · 0 whatever x holds. masks (one byte per span) is a transient of the build.
+__global__ void pb_span_heads_kernel(long long nspans, int W, const int *__restrict__ t_row, const int *__restrict__ t_cell, unsigned short *__restrict__ p_lcol,
                                      unsigned char *__restrict__ masks, int *__restrict__ counts)
 {
     for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < nspans; s += (long long)gridDim.x * blockDim.x) {
@@ -277,8 +285,11 @@ __global__ void pb_span_heads_kernel(long long nspans, const int *__restrict__ t
             prev = t_row[s * kSpan - 1];
         for (int j = 0; j < kSpan; ++j) {
             const int r = t_row[s * kSpan + j];
-            if (r >= 0 && r != prev) m |= 1u << j;
+            const bool head = r >= 0 && r != prev;
+            if (head) m |= 1u << j;
             if (r >= 0) prev = r;
+            unsigned short &lc = p_lcol[s * kSpan + j];
+            lc = r < 0 ? (unsigned short)W : (unsigned short)(lc | (head ? kHeadBit : 0u));
         }
         masks[s] = (unsigned char)m;
         counts[s] = __popc(m);
@@ -298,7 +309,7 @@ __global__ void pb_span_slots_kernel(long long nspans, const int *__restrict__ t
 }
 
 // Local row of every micro-run, at its consumer slot.
-__global__ void pb_fill_consumer_kernel(long long nspans, const int *__restrict__ t_row, const int *__restrict__ t_cell,
+__global__ void pb_fill_consumer_kernel(long long nspans, int W, const int *__restrict__ t_row,
                                         const unsigned char *__restrict__ masks, const int *__restrict__ mbase,
                                         unsigned short *__restrict__ c_lrow)
 {
@@ -307,7 +318,7 @@ __global__ void pb_fill_consumer_kernel(long long nspans, const int *__restrict_
         if (!m) continue;
         int dst = mbase[s];   // already a consumer slot (pb_span_slots_kernel)
         for (int j = 0; j < kSpan; ++j)
-            if ((m >> j) & 1u) c_lrow[dst++] = (unsigned short)(t_row[s * kSpan + j] & (kBand - 1));
+            if ((m >> j) & 1u) c_lrow[dst++] = (unsigned short)(t_row[s * kSpan + j] % W);
     }
 }
 
@@ -333,28 +344,30 @@ __device__ __forceinline__ double row_down_d(double v)
 // Producer: one lane per PAIR of consecutive entries (unit-stride 4-byte / 16-byte loads), four lanes per 8-entry span, sixteen
 // per 32-entry window. The products of a window are summed per micro-run with a backward segmented scan across the window's
 // sixteen lanes (four DPP row shifts), and each lane stores the sums of the micro-runs that START in its pair (0, 1 or 2 stores).
+// A micro-run starts at an entry whose local column carries the head bit; the slot of its sum is the span's base (mbase) plus the
+// heads of the span's earlier entries, counted from two wave ballots (the first and the second entry of every lane's pair).
 #ifndef G4S_PB_PAIR_UNROLL
 #define G4S_PB_PAIR_UNROLL 4
 #endif
 constexpr int kPairUnroll = G4S_PB_PAIR_UNROLL;
 
-__global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerItem *__restrict__ items, int cols, int RB, int H, const double *__restrict__ hot_x,
+template <int W>
+__global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerItem *__restrict__ items, int cols, int H, const double *__restrict__ hot_x,
                                                                   const unsigned short *__restrict__ p_lcol, const double *__restrict__ p_val,
-                                                                  const unsigned char *__restrict__ masks, const int *__restrict__ mbase /* consumer slot of each span's first micro-run */,
+                                                                  const int *__restrict__ mbase /* consumer slot of each span's first micro-run */,
                                                                   const double *__restrict__ x, double *__restrict__ prod)
 {
     extern __shared__ double pb_lds[];
-    double *xs = pb_lds;                                           // kBand doubles
-    (void)RB;
+    double *xs = pb_lds;                                           // W doubles of x, then the zero word the pads point at
     const ProducerItem it = items[blockIdx.x];
-    const bool hot = it.cband < H;                                 // hot bands read the gathered copy; the others a natural 16 K slice of x
-    const int c0 = hot ? it.cband << kBandBits : (it.cband - H) << kBandBits;
+    const bool hot = it.cband < H;                                 // hot bands read the gathered copy; the others a natural W-column slice of x
+    const int c0 = hot ? it.cband * W : (it.cband - H) * W;
     const double *xsrc = hot ? hot_x : x;
-    const int xlimit = hot ? H << kBandBits : cols;
+    const int xlimit = hot ? H * W : cols;
     const int p_end = it.s1 * 4, p_last = p_end - 1;               // pair indices: pair p = entries 2p, 2p+1; span = p >> 2
     constexpr int STEP = kPbThreads * kPairUnroll;
     int base = it.s0 * 4 + (int)threadIdx.x;
-    unsigned lc[kPairUnroll], lc_n[kPairUnroll], mk[kPairUnroll], mk_n[kPairUnroll];
+    unsigned lc[kPairUnroll], lc_n[kPairUnroll];
     int mb[kPairUnroll], mb_n[kPairUnroll];
     double2_t v[kPairUnroll], v_n[kPairUnroll];
     // first tile's stream loads go out before the x band is staged: their latency hides under the staging
@@ -363,35 +376,36 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
         const long long p = min(base + u * kPbThreads, p_last);
         lc[u] = pb_stream_load(reinterpret_cast<const unsigned *>(p_lcol) + p);
         v[u] = pb_stream_load(reinterpret_cast<const double2_t *>(p_val) + p);
-        mk[u] = masks[p >> 2];
         mb[u] = mbase[p >> 2];
     }
 #ifdef G4S_PB_STAGE_LOOP   /* A/B only (tools/build_variant.sh): the staging loop as it was until round 4 */
-    for (int i = threadIdx.x; i < kBand; i += kPbThreads) xs[i] = (c0 + i < xlimit) ? xsrc[c0 + i] : 0.0;
+    for (int i = threadIdx.x; i < W; i += kPbThreads) xs[i] = (c0 + i < xlimit) ? xsrc[c0 + i] : 0.0;
 #else
     {
         // The band of x: ALL of a thread's loads first, then the LDS writes. As a plain loop this compiled to 16 × (load, wait, write) — sixteen round trips in a
         // row, ≈ 6 µs per work item with nothing to overlap them (one workgroup per CU), found in round 4 in the ISA. The index is clamped instead of predicated
         // so that the loads carry no branch. (Then tried: one persistent workgroup per CU walking the items with the NEXT item's descriptor and band of x loaded into
         // registers under the current item's main loop — 0.416 against 0.400 ms on one box, 256 or 512 workgroups: the static order loses more balance than the hidden
-        // ≈ 3 µs per item buy.)
-        constexpr int kPerThread = kBand / kPbThreads;
-        static_assert(kBand % kPbThreads == 0, "band staging");
+        // ≈ 3 µs per item buy.) W need not be a multiple of the workgroup: the last round's loads are clamped like the rest, its LDS writes cut at W.
+        constexpr int kPerThread = (W + kPbThreads - 1) / kPbThreads;
+        const int ilast = min(c0 + W, xlimit) - 1;
         double xv[kPerThread];
 #pragma unroll
         for (int k = 0; k < kPerThread; ++k) {
             const int i = c0 + (int)threadIdx.x + k * kPbThreads;
-            xv[k] = xsrc[min(i, xlimit - 1)];
+            xv[k] = xsrc[min(i, ilast)];
         }
 #pragma unroll
         for (int k = 0; k < kPerThread; ++k) {
             const int i = (int)threadIdx.x + k * kPbThreads;
-            xs[i] = (c0 + i < xlimit) ? xv[k] : 0.0;
+            if (W % kPbThreads == 0 || i < W) xs[i] = (c0 + i < xlimit) ? xv[k] : 0.0;
         }
     }
 #endif
+    if (threadIdx.x == 0) xs[W] = 0.0;
     __syncthreads();
-    const int q = threadIdx.x & 3;                                 // position of this lane's pair inside its span
+    const int g = (int)threadIdx.x & 60;                           // first lane of this lane's span in the wave's ballots
+    const unsigned below = (1u << (threadIdx.x & 3)) - 1u;         // the lanes of the span before this one
     for (; base - (int)threadIdx.x < p_end; base += STEP) {        // uniform trip count per workgroup: every lane takes part in the shuffles
         const bool more = base - (int)threadIdx.x + STEP < p_end;
         if (more) {
@@ -400,7 +414,6 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
                 const long long p = min(base + STEP + u * kPbThreads, p_last);
                 lc_n[u] = pb_stream_load(reinterpret_cast<const unsigned *>(p_lcol) + p);
                 v_n[u] = pb_stream_load(reinterpret_cast<const double2_t *>(p_val) + p);
-                mk_n[u] = masks[p >> 2];
                 mb_n[u] = mbase[p >> 2];
             }
         }
@@ -411,10 +424,12 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
             const int p = base + u * kPbThreads;
             const bool live = p < p_end;                           // whole spans are live or not (p_end is a multiple of 4)
             const unsigned l0 = lc[u] & 0xFFFFu, l1 = lc[u] >> 16;
-            const double p0 = (!live || (l0 & kPadFlag)) ? 0.0 : v[u][0] * xs[l0 & (kBand - 1)];
-            const double p1 = (!live || (l1 & kPadFlag)) ? 0.0 : v[u][1] * xs[l1 & (kBand - 1)];
-            const unsigned m = live ? mk[u] : 0u;
-            const bool h0 = (m >> (2 * q)) & 1u, h1 = (m >> (2 * q + 1)) & 1u;
+            const double p0 = live ? v[u][0] * xs[l0 & kLocalMask] : 0.0;   // a pad reads the zero word xs[W]
+            const double p1 = live ? v[u][1] * xs[l1 & kLocalMask] : 0.0;
+            const bool h0 = live && (l0 & kHeadBit), h1 = live && (l1 & kHeadBit);
+            // heads of the span's earlier lanes: bit j of the nibbles = lane g + j's first / second entry is a head
+            const unsigned n0 = (unsigned)(__ballot(h0) >> g) & 0xFu, n1 = (unsigned)(__ballot(h1) >> g) & 0xFu;
+            const int before = __popc(n0 & below) + __popc(n1 & below);
             // open prefix: the part of this pair that continues a micro-run begun in an earlier lane of the span
             const double op = h0 ? 0.0 : (h1 ? p0 : p0 + p1);
             const bool closed = h0 | h1;
@@ -427,29 +442,30 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
 #undef G4S_PB_SCAN_STEP
             const double ext = row_down_d<1>(S);
             if (live && closed) {
-                const int d0 = mb[u];
-                if (h0) prod[d0 + __popc(m & ((1u << (2 * q)) - 1u))] = h1 ? p0 : p0 + p1 + ext;
-                if (h1) prod[d0 + __popc(m & ((1u << (2 * q + 1)) - 1u))] = p1 + ext;
+                const int d0 = mb[u] + before;
+                if (h0) prod[d0] = h1 ? p0 : p0 + p1 + ext;
+                if (h1) prod[d0 + (int)h0] = p1 + ext;
             }
         }
         if (more) {
 #pragma unroll
-            for (int u = 0; u < kPairUnroll; ++u) { lc[u] = lc_n[u]; v[u] = v_n[u]; mk[u] = mk_n[u]; mb[u] = mb_n[u]; }
+            for (int u = 0; u < kPairUnroll; ++u) { lc[u] = lc_n[u]; v[u] = v_n[u]; mb[u] = mb_n[u]; }
         }
     }
 }
 
-// One launch ahead of the producer: blocks [0, n_split·64) pre-scale y for the row bands whose sums arrive from several consumer
+// One launch ahead of the producer: blocks [0, n_split·⌈W/256⌉) pre-scale y for the row bands whose sums arrive from several consumer
 // workgroups (those add into y with atomics), the remaining blocks gather the x values of the hot columns into hot_x.
+template <int W>
 __global__ void pb_prepare_kernel(int n_split, const int *__restrict__ split_bands, int rows, double *__restrict__ y, double beta,
                                   int nhot, const int *__restrict__ hot_cols, const double *__restrict__ x, double *__restrict__ hot_x)
 {
-    constexpr int kBlocksPerBand = kBand / 256;
+    constexpr int kBlocksPerBand = (W + 255) / 256;
     const int b = blockIdx.x;
     if (b < n_split * kBlocksPerBand) {
-        const int r0 = split_bands[b / kBlocksPerBand] << kBandBits;
-        const int i = r0 + (b % kBlocksPerBand) * 256 + (int)threadIdx.x;
-        if (i < rows) y[i] = beta == 0.0 ? 0.0 : beta * y[i];
+        const int local = (b % kBlocksPerBand) * 256 + (int)threadIdx.x;
+        const int i = split_bands[b / kBlocksPerBand] * W + local;
+        if (local < W && i < rows) y[i] = beta == 0.0 ? 0.0 : beta * y[i];
     } else {
         const int r = (b - n_split * kBlocksPerBand) * 256 + (int)threadIdx.x;
         if (r < nhot) hot_x[r] = x[hot_cols[r]];
@@ -461,6 +477,7 @@ __global__ void pb_prepare_kernel(int n_split, const int *__restrict__ split_ban
 #endif
 constexpr int kPbUnroll = G4S_PB_CONS_UNROLL;   // consumer: groups of 4 consecutive slots per thread per iteration
 
+template <int W>
 __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerItem *__restrict__ items, int rows,
                                                                   const unsigned short *__restrict__ c_lrow, const double *__restrict__ prod,
                                                                   double *__restrict__ y, double alpha, double beta)
@@ -482,7 +499,7 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
             pb[u] = pb_stream_load(reinterpret_cast<const double2_t *>(prod + k + 2));
         }
     }
-    for (int i = threadIdx.x; i < kBand; i += kPbThreads) ys[i] = 0.0;
+    for (int i = threadIdx.x; i < W; i += kPbThreads) ys[i] = 0.0;
     __syncthreads();
     for (; base < it.k1; base += STEP) {
         const bool more = base + STEP < it.k1;
@@ -526,22 +543,23 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
         }
     }
     __syncthreads();
-    const int r0 = it.rband << kBandBits;
+    const int r0 = it.rband * W;
     // All of a thread's sums out of LDS first, and — beta != 0 — all its old y values in flight together: as a loop with a break every row waited for its own
     // LDS read, and for its own round trip to y when beta != 0 (sixteen in a row per work item). Neutral for the bench line (beta = 0: 0.3910 against 0.3919 ms).
-    constexpr int kRowsPerThread = kBand / kPbThreads;
+    constexpr int kRowsPerThread = (W + kPbThreads - 1) / kPbThreads;
     double yv[kRowsPerThread], yo[kRowsPerThread];
     const bool read_y = !it.split && beta != 0.0;                  // (uniform)
+    const int rlast = min(r0 + W, rows) - 1;
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
-        yv[k] = ys[(int)threadIdx.x + k * kPbThreads];
-        const int r = min(r0 + (int)threadIdx.x + k * kPbThreads, rows - 1);
+        yv[k] = ys[min((int)threadIdx.x + k * kPbThreads, W - 1)];
+        const int r = min(r0 + (int)threadIdx.x + k * kPbThreads, rlast);
         yo[k] = read_y ? y[r] : 0.0;
     }
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
         const int r = r0 + (int)threadIdx.x + k * kPbThreads;
-        if (r < rows) {
+        if ((W % kPbThreads == 0 || (int)threadIdx.x + k * kPbThreads < W) && r < rows) {
             if (it.split) {
                 if (yv[k] != 0.0) atomicAdd(&y[r], alpha * yv[k]);  // y was pre-scaled by beta (pb_prepare_kernel)
             } else {
@@ -554,15 +572,38 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
 } // namespace
 
 struct PbPlan {
-    int rows = 0, cols = 0, CB = 0, RB = 0;
+    int rows = 0, cols = 0, CB = 0, RB = 0, W = kBandNarrow;       // W: columns / rows per band (kBandWide or kBandNarrow)
     long long nnz = 0, micro_runs = 0;
-    DevBuf p_lcol, p_val, masks, mbase, c_lrow, prod, delta, pitems, citems, split_bands, hot_cols, hot_x;
+    DevBuf p_lcol, p_val, mbase, c_lrow, prod, delta, pitems, citems, split_bands, hot_cols, hot_x;
     DevBuf p_src;                                                   // G4S_SPMV_UPDATABLE: CSR index of every producer slot
     long long slots = 0;
     int n_pitems = 0, n_citems = 0, n_split = 0, H = 0;
     size_t lds_producer = 0, lds_consumer = 0;
     long long bytes = 0;
 };
+
+// The band width of a new plan: kBandWide where a workgroup may have its band of x and the zero word in LDS (160 KiB on gfx950), else kBandNarrow.
+// G4S_PB_BAND=16384 forces the narrow form (tests, A/B).
+static int pb_band_width()
+{
+    const char *e = getenv("G4S_PB_BAND");
+    if (e && atoi(e) == kBandNarrow) return kBandNarrow;
+    int dev = 0, lds = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return kBandNarrow; }
+    for (hipDeviceAttribute_t a : {hipDeviceAttributeSharedMemPerBlockOptin, hipDeviceAttributeMaxSharedMemoryPerBlock}) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, a, dev) == hipSuccess) lds = std::max(lds, v);
+        else (void)hipGetLastError();
+    }
+    const int need = (int)sizeof(double) * (kBandWide + 1);
+    if (lds < need) return kBandNarrow;
+    // the runtime must also grant it to the kernels (pb_build sets the same attribute again for the plan)
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(pb_producer_kernel<kBandWide>), hipFuncAttributeMaxDynamicSharedMemorySize, need) != hipSuccess) {
+        (void)hipGetLastError();
+        return kBandNarrow;
+    }
+    return kBandWide;
+}
 
 int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowptr, const int *d_colids, const double *d_values, bool keep_value_map)
 {
@@ -573,15 +614,17 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     std::unique_ptr<PbPlan> guard(P);
     P->rows = rows; P->cols = cols; P->nnz = nnz;
     BuildArena arena;                                              // the build's transients (TmpBuf) live in it; declared before them, so it ends after them
-    // 0. hot column bands: rank the columns by degree, take the leading 16 K-column groups that are much denser than a natural band
-    const int CBnat = (cols + kBand - 1) >> kBandBits;
+    const int W = P->W = pb_band_width();
+    // 0. hot column bands: rank the columns by degree, take the leading W-column groups that are much denser than a natural band
+    const int CBnat = (int)(((long long)cols + W - 1) / W);
+    if ((long long)(CBnat + kMaxHotBands) << kLocalBits > (long long)UINT32_MAX) return set_error(G4S_ERR_UNSUPPORTED, "pb_build: too many column bands");
     TmpBuf colmap, deg, deg_s, order_in, order, tmp0;
     G4S_TRY(colmap.alloc(sizeof(unsigned) * (size_t)cols));
     int H = 0;
     {
         const char *e = getenv("G4S_PB_HOT_BANDS");
         const int want = e ? atoi(e) : -1;                          // -1 = decide from the degree distribution
-        const int Hmax = std::min(kMaxHotBands, cols / (2 * kBand));
+        const int Hmax = std::min(kMaxHotBands, cols / (2 * W));
         if (want != 0 && Hmax > 0) {
             G4S_TRY(deg.alloc(sizeof(int) * (size_t)cols)); G4S_TRY(deg_s.alloc(sizeof(int) * (size_t)cols));
             G4S_TRY(order_in.alloc(sizeof(int) * (size_t)cols)); G4S_TRY(order.alloc(sizeof(int) * (size_t)cols));
@@ -608,25 +651,25 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
             hipLaunchKernelGGL(pb_max_kernel, dim3(std::min(grid_for(cols), 1024)), dim3(256), 0, nullptr, cols, deg.as<int>(), d_max);
             G4S_HIP_TRY(hipMemcpy(&h_max, d_max, sizeof(int), hipMemcpyDeviceToHost));
             G4S_TRY(prims::sort_pairs_descending(deg.as<int>(), order_in.as<int>(), deg_s.as<int>(), order.as<int>(), tmp0.as<int>(), tmp0.as<int>() + cols, cols, prims_bits(h_max), nullptr));
-            std::vector<int> top((size_t)Hmax * kBand);
+            std::vector<int> top((size_t)Hmax * W);
             G4S_HIP_TRY(hipMemcpy(top.data(), deg_s.p, sizeof(int) * top.size(), hipMemcpyDeviceToHost));
             if (want > 0) H = std::min(want, Hmax);
             else {
-                // band h of the ranking is worth its 128 KiB gather while it holds kHotFactor times the nonzeros of an average natural band
+                // band h of the ranking is worth its W·8-byte gather while it holds kHotFactor times the nonzeros of an average natural band
                 const double avg = (double)nnz / CBnat;
                 for (int h = 0; h < Hmax; ++h) {
                     long long in_band = 0;
-                    for (int i = 0; i < kBand; ++i) in_band += top[(size_t)h * kBand + i];
+                    for (int i = 0; i < W; ++i) in_band += top[(size_t)h * W + i];
                     if ((double)in_band < kHotFactor * avg) break;
                     H = h + 1;
                 }
             }
         }
     }
-    hipLaunchKernelGGL(pb_colmap_kernel, dim3((cols + 255) / 256), dim3(256), 0, nullptr, cols, H, order.as<int>(), colmap.as<unsigned>());
+    hipLaunchKernelGGL(pb_colmap_kernel, dim3((cols + 255) / 256), dim3(256), 0, nullptr, cols, H, W, colmap.as<unsigned>());
     if (H) {
-        const int nhot = H * kBand;
-        hipLaunchKernelGGL(pb_colmap_hot_kernel, dim3((nhot + 255) / 256), dim3(256), 0, nullptr, nhot, order.as<int>(), colmap.as<unsigned>());
+        const int nhot = H * W;
+        hipLaunchKernelGGL(pb_colmap_hot_kernel, dim3((nhot + 255) / 256), dim3(256), 0, nullptr, nhot, W, order.as<int>(), colmap.as<unsigned>());
         G4S_TRY(P->hot_cols.alloc(sizeof(int) * (size_t)nhot));
         G4S_TRY(P->hot_x.alloc(sizeof(double) * (size_t)nhot));
         G4S_HIP_TRY(hipMemcpy(P->hot_cols.p, order.p, sizeof(int) * (size_t)nhot, hipMemcpyDeviceToDevice));
@@ -636,12 +679,12 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     deg.release(); deg_s.release(); order_in.release(); order.release(); tmp0.release();
     P->H = H;
     const int CB = P->CB = CBnat + H;
-    const int RB = P->RB = (rows + kBand - 1) >> kBandBits;
+    const int RB = P->RB = (int)(((long long)rows + W - 1) / W);
     int bits = 1;
     while ((1 << bits) < std::max(CB, RB)) ++bits;
     if (2 * bits > 32) return set_error(G4S_ERR_UNSUPPORTED, "pb_build: too many bands");
-    P->lds_producer = sizeof(double) * kBand;
-    P->lds_consumer = sizeof(double) * kBand;
+    P->lds_producer = sizeof(double) * (W + 1);                    // the band of x and the zero word
+    P->lds_consumer = sizeof(double) * W;
     const long long ncells = (long long)CB * RB;
 
     // 1. regroup: stable sort of the CSR entries by (column band, row band)
@@ -656,7 +699,7 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
         TmpBuf ckey_s, tk, tv;                                      // sorted band keys, the sort's ping-pong partners
         G4S_TRY(ckey_s.alloc(n4)); G4S_TRY(tk.alloc(n4)); G4S_TRY(tv.alloc(n4));
         G4S_TRY(prims::sort_pairs_descending(key.as<int>(), idx.as<int>(), ckey_s.as<int>(), perm.as<int>(), tk.as<int>(), tv.as<int>(), (int)nnz, prims_bits(CB - 1), nullptr));
-        hipLaunchKernelGGL(pb_full_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, nullptr, nnz, ckey_s.as<int>(), perm.as<int>(), rowid.as<int>(), CB, bits, key_s.as<unsigned>());
+        hipLaunchKernelGGL(pb_full_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, nullptr, nnz, ckey_s.as<int>(), perm.as<int>(), rowid.as<int>(), CB, bits, W, key_s.as<unsigned>());
         G4S_HIP_TRY(hipGetLastError());
         G4S_HIP_TRY(hipDeviceSynchronize());
     }
@@ -688,7 +731,7 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     G4S_TRY(P->p_val.alloc(sizeof(double) * (size_t)(totP + 64)));
     G4S_TRY(t_row.alloc(sizeof(int) * (size_t)(totP + 64)));
     G4S_TRY(t_cell.alloc(sizeof(int) * (size_t)(totP + 64)));
-    G4S_HIP_TRY(hipMemset(P->p_lcol.p, 0xFF, P->p_lcol.bytes));   // pad flag everywhere; real entries overwrite it
+    G4S_HIP_TRY(hipMemset(P->p_lcol.p, 0xFF, P->p_lcol.bytes));   // real entries overwrite it, pb_span_heads_kernel points the pads at the zero word
     G4S_HIP_TRY(hipMemset(P->p_val.p, 0, P->p_val.bytes));
     G4S_HIP_TRY(hipMemset(t_row.p, 0xFF, t_row.bytes));           // −1 = pad
     G4S_HIP_TRY(hipMemset(t_cell.p, 0, t_cell.bytes));
@@ -704,12 +747,15 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     G4S_HIP_TRY(hipDeviceSynchronize());
     key_s.release(); perm.release(); rowid.release(); startP.release(); colmap.release();
 
-    // 3. micro-runs: head mask per span, exclusive scan → index of each span's first micro-run
-    G4S_TRY(P->masks.alloc((size_t)nspans + 64));
+    // 3. micro-runs: heads of every span (bit 15 of p_lcol for the producer, a byte mask per span for the consumer layout below), exclusive scan → index of
+    //    each span's first micro-run
+    TmpBuf masks;
+    G4S_TRY(masks.alloc((size_t)nspans + 64));
     G4S_TRY(counts.alloc(sizeof(int) * ((size_t)nspans + 1)));
     G4S_TRY(P->mbase.alloc(sizeof(int) * ((size_t)nspans + 64)));
     G4S_HIP_TRY(hipMemset(counts.p, 0, counts.bytes));
-    hipLaunchKernelGGL(pb_span_heads_kernel, dim3(grid_for(nspans)), dim3(256), 0, nullptr, nspans, t_row.as<int>(), t_cell.as<int>(), P->masks.as<unsigned char>(), counts.as<int>());
+    hipLaunchKernelGGL(pb_span_heads_kernel, dim3(grid_for(nspans)), dim3(256), 0, nullptr, nspans, W, t_row.as<int>(), t_cell.as<int>(), P->p_lcol.as<unsigned short>(),
+                       masks.as<unsigned char>(), counts.as<int>());
     G4S_HIP_TRY(hipGetLastError());
     G4S_TRY(prims::exclusive_scan(counts.as<int>(), P->mbase.as<int>(), nspans + 1, nullptr));
 
@@ -742,8 +788,8 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     G4S_HIP_TRY(hipMemset(P->c_lrow.p, 0, P->c_lrow.bytes));
     G4S_HIP_TRY(hipMemset(P->prod.p, 0, P->prod.bytes));          // pad slots stay 0 for ever: the producer never writes them
     hipLaunchKernelGGL(pb_span_slots_kernel, dim3(grid_for(nspans)), dim3(256), 0, nullptr, nspans, t_cell.as<int>(), P->delta.as<int>(), P->mbase.as<int>());
-    hipLaunchKernelGGL(pb_fill_consumer_kernel, dim3(grid_for(nspans)), dim3(256), 0, nullptr, nspans, t_row.as<int>(), t_cell.as<int>(),
-                       P->masks.as<unsigned char>(), P->mbase.as<int>(), P->c_lrow.as<unsigned short>());
+    hipLaunchKernelGGL(pb_fill_consumer_kernel, dim3(grid_for(nspans)), dim3(256), 0, nullptr, nspans, W, t_row.as<int>(),
+                       masks.as<unsigned char>(), P->mbase.as<int>(), P->c_lrow.as<unsigned short>());
     G4S_HIP_TRY(hipGetLastError());
     // 5. work items, heaviest first (the tail of each launch is then made of light bands)
     // Work-item sizes follow the matrix: the full C2 matrix runs best at 128 K entries / 128 K micro-runs per item (sweeps in
@@ -783,14 +829,16 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     if (!pit.empty()) G4S_HIP_TRY(hipMemcpy(P->pitems.p, pit.data(), sizeof(ProducerItem) * pit.size(), hipMemcpyHostToDevice));
     if (!cit.empty()) G4S_HIP_TRY(hipMemcpy(P->citems.p, cit.data(), sizeof(ConsumerItem) * cit.size(), hipMemcpyHostToDevice));
     if (!split.empty()) G4S_HIP_TRY(hipMemcpy(P->split_bands.p, split.data(), sizeof(int) * split.size(), hipMemcpyHostToDevice));
-    G4S_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pb_producer_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_producer));
-    G4S_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pb_consumer_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_consumer));
+    const void *producer = W == kBandWide ? reinterpret_cast<const void *>(pb_producer_kernel<kBandWide>) : reinterpret_cast<const void *>(pb_producer_kernel<kBandNarrow>);
+    const void *consumer = W == kBandWide ? reinterpret_cast<const void *>(pb_consumer_kernel<kBandWide>) : reinterpret_cast<const void *>(pb_consumer_kernel<kBandNarrow>);
+    G4S_HIP_TRY(hipFuncSetAttribute(producer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_producer));
+    G4S_HIP_TRY(hipFuncSetAttribute(consumer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_consumer));
     G4S_HIP_TRY(hipDeviceSynchronize());
-    P->bytes = (long long)(P->p_src.bytes + P->p_lcol.bytes + P->p_val.bytes + P->masks.bytes + P->mbase.bytes + P->c_lrow.bytes + P->prod.bytes + P->delta.bytes +
+    P->bytes = (long long)(P->p_src.bytes + P->p_lcol.bytes + P->p_val.bytes + P->mbase.bytes + P->c_lrow.bytes + P->prod.bytes + P->delta.bytes +
                            P->pitems.bytes + P->citems.bytes + P->split_bands.bytes + P->hot_cols.bytes + P->hot_x.bytes);
     if (getenv("G4S_DEBUG"))
-        fprintf(stderr, "g4s blocked SpMV plan: %d x %d bands (%d hot), nnz %lld, padded %lld, micro-runs %lld (%.3f per nonzero), %d producer / %d consumer items, %d split bands, %.2f GB\n",
-                CB, RB, H, nnz, totP, P->micro_runs, (double)P->micro_runs / (double)nnz, P->n_pitems, P->n_citems, P->n_split, P->bytes / 1e9);
+        fprintf(stderr, "g4s blocked SpMV plan: band %d, %d x %d bands (%d hot), nnz %lld, padded %lld, micro-runs %lld (%.3f per nonzero), %d producer / %d consumer items, %d split bands, %.2f GB\n",
+                W, CB, RB, H, nnz, totP, P->micro_runs, (double)P->micro_runs / (double)nnz, P->n_pitems, P->n_citems, P->n_split, P->bytes / 1e9);
     *out = guard.release();
     return G4S_OK;
 }
@@ -809,17 +857,27 @@ int pb_update_values(PbPlan *P, const double *d_values, hipStream_t s)
     return G4S_OK;
 }
 
+template <int W>
+static void pb_launch(PbPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
+{
+    if (P->n_split || P->H) {
+        // split bands: one block per 256 rows of each band; hot columns: one per 256 of them (H·W of them, whole blocks either way)
+        const int blocks = P->n_split * ((W + 255) / 256) + (P->H * W + 255) / 256;
+        hipLaunchKernelGGL(pb_prepare_kernel<W>, dim3(blocks), dim3(256), 0, s, P->n_split, P->split_bands.as<int>(), P->rows, y, beta,
+                           P->H * W, P->hot_cols.as<int>(), x, P->hot_x.as<double>());
+    }
+    if (P->n_pitems)
+        hipLaunchKernelGGL(pb_producer_kernel<W>, dim3(P->n_pitems), dim3(kPbThreads), P->lds_producer, s, P->pitems.as<ProducerItem>(), P->cols, P->H, P->hot_x.as<double>(),
+                           P->p_lcol.as<unsigned short>(), P->p_val.as<double>(), P->mbase.as<int>(), x, P->prod.as<double>());
+    if (P->n_citems)
+        hipLaunchKernelGGL(pb_consumer_kernel<W>, dim3(P->n_citems), dim3(kPbThreads), P->lds_consumer, s, P->citems.as<ConsumerItem>(), P->rows,
+                           P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta);
+}
+
 int pb_spmv(PbPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
 {
-    if (P->n_split || P->H)
-        hipLaunchKernelGGL(pb_prepare_kernel, dim3((P->n_split + P->H) * (kBand / 256)), dim3(256), 0, s, P->n_split, P->split_bands.as<int>(), P->rows, y, beta,
-                           P->H * kBand, P->hot_cols.as<int>(), x, P->hot_x.as<double>());
-    if (P->n_pitems)
-        hipLaunchKernelGGL(pb_producer_kernel, dim3(P->n_pitems), dim3(kPbThreads), P->lds_producer, s, P->pitems.as<ProducerItem>(), P->cols, P->RB, P->H, P->hot_x.as<double>(),
-                           P->p_lcol.as<unsigned short>(), P->p_val.as<double>(), P->masks.as<unsigned char>(), P->mbase.as<int>(), x, P->prod.as<double>());
-    if (P->n_citems)
-        hipLaunchKernelGGL(pb_consumer_kernel, dim3(P->n_citems), dim3(kPbThreads), P->lds_consumer, s, P->citems.as<ConsumerItem>(), P->rows,
-                           P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta);
+    if (P->W == kBandWide) pb_launch<kBandWide>(P, x, y, alpha, beta, s);
+    else pb_launch<kBandNarrow>(P, x, y, alpha, beta, s);
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;
 }
