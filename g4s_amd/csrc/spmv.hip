@@ -19,6 +19,7 @@
 #include "prims.hpp"
 #include "spmv_pb.hpp"
 #include "spmv_bcsr.hpp"
+#include "spmm.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -328,6 +329,7 @@ struct g4s_csr_s {
     bool stream_plan = false;       // the row-streaming plan exists (a large matrix that took the blocked path builds it only if it ever needs it)
     g4s::PbPlan *pb = nullptr;      // propagation-blocked path (spmv_pb.hip) for matrices without gather locality
     g4s::BcsrPlan *bcsr = nullptr;  // block-row form of an assembled FE matrix (spmv_bcsr.hip)
+    g4s::SpmmWork *spmm = nullptr;  // g4s_spmm's workspace (spmm.hip), built by g4s_csr_spmm_reserve or a first g4s_spmm
 };
 
 namespace {
@@ -530,6 +532,7 @@ void release(g4s_csr_s *A)
     (void)hipFree(A->d_dia_mask);
     g4s::pb_destroy(A->pb);
     g4s::bcsr_destroy(A->bcsr);
+    g4s::spmm_work_destroy(A->spmm);
     delete A;
 }
 
@@ -773,6 +776,35 @@ G4S_API g4s_status g4s_csr_device_arrays(g4s_csr_t A, const int32_t **rowptr, co
     if (rowptr) *rowptr = A->d_rowptr;
     if (colids) *colids = A->d_colids;
     if (values) *values = A->d_values;
+    return G4S_OK;
+}
+
+// SpMM (spmm.hip) runs on the CSR arrays and the row-streaming plan of every handle, whichever path its SpMV takes.
+static_assert(sizeof(LongChunk) == sizeof(int4) && sizeof(LongRow) == sizeof(int4), "the SpMM view hands the plan over as int4");
+int g4s_csr_spmm_view(g4s_csr_t A, g4s::CsrSpmmView *v)
+{
+    G4S_REQUIRE(A && v, "NULL argument");
+    v->rows = A->rows; v->cols = A->cols; v->nnz = A->nnz;
+    v->rowptr = A->d_rowptr; v->colids = A->d_colids; v->values = A->d_values;
+    v->spmv_path = A->pb ? 1 : (A->d_dia ? 3 : (A->bcsr ? 4 : 0));
+    v->stream_plan = A->stream_plan;
+    v->tile_nnz = TILE_NNZ; v->tile_rows = TILE_ROWS; v->long_chunk = LONG_CHUNK;
+    v->blocks = A->d_blocks; v->n_blocks = A->n_stream;
+    v->chunks = reinterpret_cast<const int4 *>(A->d_chunks); v->n_chunks = A->n_chunks;
+    v->long_rows = reinterpret_cast<const int4 *>(A->d_long_rows); v->n_long = A->n_long;
+    v->work = &A->spmm;
+    v->plan_bytes = &A->plan_bytes;
+    return G4S_OK;
+}
+
+// The row-streaming plan of a handle that took the blocked path without one (what g4s_csr_update_values builds on its fallback); NULL stream, synchronous.
+int g4s_csr_build_stream_plan(g4s_csr_t A)
+{
+    G4S_REQUIRE(A, "NULL handle");
+    if (A->stream_plan) return G4S_OK;
+    const int64_t other = A->plan_bytes;                            // the blocked plan's bytes: finish_plan sets plan_bytes to the stream plan's alone
+    G4S_TRY(build_plan_device(A));
+    A->plan_bytes += other;
     return G4S_OK;
 }
 

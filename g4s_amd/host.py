@@ -4,6 +4,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   CSR            — mm/inc/CSR.h:22-100 (rows, cols, nnz, rowptr, colids, values, zerobased)
   HashSpGEMM     — mm/inc/hash_mult.h:1028-1057 (sortOutput flag; multiply/add are the arithmetic semiring only)
   spmv           — the CSR mat-vec the build defines for mv/ (DESIGN.md §SpMV), y = alpha·A·x + beta·y
+  spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
 """
 import ctypes as C
@@ -78,6 +79,34 @@ class CSR:
         capi.check(capi.load().g4s_spmv(self.handle, _ptr(x), _ptr(y), float(alpha), float(beta), _stream()))
         return y
 
+    def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
+        """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
+        X.stride(1) == 1, column-major when X.stride(0) == 1 (k > 1); the leading dimension is the other stride, Y has X's layout. A new Y
+        (beta == 0) is allocated in X's layout."""
+        assert X.dtype == torch.float64 and X.is_cuda and X.dim() == 2 and X.shape[0] == self.cols
+        k = X.shape[1]
+        if Y is None:
+            assert beta == 0.0
+            Y = torch.empty(k, self.rows, dtype=torch.float64, device=X.device).t() if X.stride(0) == 1 and k > 1 and X.stride(1) != 1 else \
+                torch.empty(self.rows, k, dtype=torch.float64, device=X.device)
+        assert Y.dtype == torch.float64 and Y.is_cuda and Y.dim() == 2 and tuple(Y.shape) == (self.rows, k)
+        if k == 0 or self.rows == 0:
+            return Y
+        cm = False                                                  # row-major when both blocks are, else column-major when both are
+        ldx, ldy = _spmm_ld(X, False), _spmm_ld(Y, False)
+        if ldx is None or ldy is None:
+            cm = True
+            ldx, ldy = _spmm_ld(X, True), _spmm_ld(Y, True)
+        if ldx is None or ldy is None:
+            raise ValueError(f"X and Y must both be row-major (stride(1) == 1) or both column-major (stride(0) == 1); strides {tuple(X.stride())}, {tuple(Y.stride())}")
+        flags = capi.SPMM_COL_MAJOR if cm else 0
+        capi.check(capi.load().g4s_spmm(self.handle, k, _ptr(X), ldx, _ptr(Y), ldy, float(alpha), float(beta), flags, _stream()))
+        return Y
+
+    def spmm_reserve(self, k_max):
+        """Build now what spmm needs for up to k_max vectors (synchronous), so that later calls never allocate — before a stream capture."""
+        capi.check(capi.load().g4s_csr_spmm_reserve(self.handle, int(k_max)))
+
     def update_values(self, values):
         """New values for the same pattern (g4s_csr_update_values), in place: `values` (device tensor, nnz doubles) replaces self.values — the handle borrows
         the tensor's memory from here on — and the plan's own copy is refreshed on the current torch stream."""
@@ -100,6 +129,24 @@ class CSR:
 
 def spmv(A, x, y=None, alpha=1.0, beta=0.0):
     return A.spmv(x, y, alpha, beta)
+
+
+def _spmm_ld(M, col_major):
+    """The leading dimension of a 2-D block M read in the given layout (row-major: element (i, j) at [i·ld + j], column-major: [i + j·ld]), or None
+    when M is not laid out that way. A stride along an axis of extent 1 is never used and does not count."""
+    r, k = M.shape
+    inner, outer, n_outer, n_inner = (0, 1, k, r) if col_major else (1, 0, r, k)
+    if n_inner > 1 and M.stride(inner) != 1:
+        return None
+    if n_outer <= 1:
+        return max(n_inner, 1)
+    return M.stride(outer) if M.stride(outer) >= n_inner else None
+
+
+def spmm(A, X, Y=None, alpha=1.0, beta=0.0):
+    """Y = alpha·A·X + beta·Y (g4s_spmm) — CSR.spmm as a function, like spmv."""
+    _require_gpu()
+    return A.spmm(X, Y, alpha, beta)
 
 
 def get_flop(A, B):

@@ -142,6 +142,42 @@ g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowpt
                                 const double *values, const double *x, double *y,
                                 double alpha, double beta, unsigned flags);
 
+/* ------------------------------------------------------------------ B2 with k vectors: CSR SpMM  Y = alpha·A·X + beta·Y */
+/* The sparse form of the reference's dense comparison driver (mm/src/cblas_dxxmm.c: a .mtx matrix times a dense dim × dim column-major B
+ * with cblas_dgemm), and what several right-hand sides, block Krylov solvers or multi-source walks do instead of k g4s_spmv calls: the
+ * matrix is read once per call (per tile of 32 vectors), not once per vector. X is cols × k, Y is rows × k.
+ *   When it pays: one SpMM beats k g4s_spmv calls only where the SpMV path of the handle is not much faster per vector than a CSR walk — it
+ *     is a CSR kernel on every handle. On the blocked path (power-law graphs) the k-call loop is faster at every k measured, and at small k the
+ *     loop can be faster on the other paths too; DESIGN.md §4.1 (e) has the measured ratios per path and k.
+ *   Layout: row-major by default, element (i, j) at [i·ld + j], needs ldx >= k and ldy >= k; with G4S_SPMM_COL_MAJOR element (i, j) is at
+ *     [i + j·ld] and ldx >= cols, ldy >= rows are needed.
+ *   Padding is never touched: entries of Y outside the rows × k block are neither read nor written.
+ *   Any alignment: any 8-byte-aligned base pointer and any ld (odd ld, offset sub-views); 16-byte aligned X and Y with even ld are the fast case.
+ *   beta == 0 never reads Y (BLAS convention: NaN in Y does not leak). k == 0 and rows == 0 are no-ops; nnz == 0 gives Y = beta·Y.
+ *   X and Y must not overlap: overlapping address ranges return G4S_ERR_INVALID. Argument checks run before any HIP call.
+ *   Summation is deterministic on every handle (no atomics): each (row, column) of a row of at most tile_nnz entries is summed in stored order,
+ *     bit-identical to a column-by-column oracle SpMV; longer rows are split into chunks whose partial sums are added in a fixed order.
+ *   One product in flight per handle: g4s_spmm and g4s_spmv share the concurrency rule of g4s_csr_create.
+ *   New values (g4s_csr_update_values) are used by the next g4s_spmm, owned and borrowed handles alike.
+ *   k == 1 with unit-stride X and Y (column-major, or ld = 1) is g4s_spmv on the streaming, diagonal and block-row paths; on the blocked path it
+ *     stays on the SpMM kernels, which are reproducible where the blocked SpMV is not. */
+#define G4S_SPMM_COL_MAJOR 256u /* X and Y column-major: element (i, j) at [i + j·ld]; default row-major: [i·ld + j] */
+
+/* Asynchronous on `stream` like g4s_spmv; X_dev and Y_dev are device pointers. Workspace: the SpMM kernels run on the handle's row-streaming
+ * plan (which a large blocked-path handle builds on demand) and need n_long_chunks × k_max doubles of their own. Once g4s_csr_spmm_reserve(A, k_max)
+ * has run, a call with k <= k_max only enqueues kernels — no allocation, no synchronisation, no host read — and may be recorded in a hipGraph.
+ * A call with k above the reserved k_max (every handle starts at 0) first reserves k: on the NULL stream, synchronously, as a create does; if `stream`
+ * is capturing at that moment (hipStreamIsCapturing) the call returns G4S_ERR_INVALID and enqueues nothing — reserve before the capture. */
+g4s_status g4s_spmm(g4s_csr_t A, int32_t k, const double *X_dev, int64_t ldx, double *Y_dev, int64_t ldy,
+                    double alpha, double beta, unsigned flags, void *stream);
+/* Builds now what g4s_spmm needs for up to k_max vectors (synchronous, NULL stream), so that later calls with k <= k_max — and stream capture — never allocate. */
+g4s_status g4s_csr_spmm_reserve(g4s_csr_t A, int32_t k_max);
+/* One-shot form, like g4s_spmv_csr_i32_f64 (synchronous): G4S_HOST_POINTERS / G4S_DEVICE_POINTERS for all arrays, | G4S_SPMM_COL_MAJOR.
+ * With host pointers only the rows × k block of Y is read (beta != 0) and written back. */
+g4s_status g4s_spmm_csr_i32_f64(int32_t rows, int32_t cols, int32_t k, const int32_t *rowptr, const int32_t *colids,
+                                const double *values, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                                double alpha, double beta, unsigned flags);
+
 /* ---- B2 on several GPUs: the 1-D row-partitioned product (SURVEY.md §8b "g4s_spmv_dist_*", §8e). One process per GPU. Rank r owns rows
  * [row_offsets[r], row_offsets[r+1]) of a square operator and the same slab of x and y; the local rows are given as CSR with GLOBAL column
  * ids. The reference has no multi-device code on this path; the pattern replaced is CitcomS's per-mat-vec neighbour exchange

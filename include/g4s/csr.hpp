@@ -142,4 +142,13 @@ void SpMV(const CSR<IT, NT> &a, const NT *x, NT *y, NT alpha = 1.0, NT beta = 0.
     check(g4s_spmv_csr_i32_f64(a.rows, a.cols, a.rowptr, a.colids, a.values, x, y, alpha, beta, G4S_HOST_POINTERS), "SpMV");
 }
 
+// Y = alpha·A·X + beta·Y with host blocks X (cols × k) and Y (rows × k): row-major by default (ld >= k), column-major as in cblas_dxxmm.c's
+// B and C (ld >= cols / rows) with col_major = true.
+template <typename IT, typename NT>
+void SpMM(const CSR<IT, NT> &a, int32_t k, const NT *X, int64_t ldx, NT *Y, int64_t ldy, NT alpha = 1.0, NT beta = 0.0, bool col_major = false)
+{
+    check(g4s_spmm_csr_i32_f64(a.rows, a.cols, k, a.rowptr, a.colids, a.values, X, ldx, Y, ldy, alpha, beta,
+                               G4S_HOST_POINTERS | (col_major ? G4S_SPMM_COL_MAJOR : 0u)), "SpMM");
+}
+
 } // namespace g4s
