@@ -25,6 +25,8 @@
 // Numeric classes use the EXACT row sizes known from symbolic, so the tables are at most half full.
 // Integer results (crpt, ccol) are exact; fp64 sums are accumulated with LDS/HBM atomics, i.e. in a different order than
 // the reference's (j outer, k inner): equal within the 1e-10 relative tolerance of the north star, not bit for bit.
+// The numeric kernels are templates on a value policy (semiring.hpp: plus-times, min-plus, max-plus, or-and), chosen once per call from the
+// G4S_SEMIRING_* flag bits (spgemm_numeric_impl); min and max atomics do not depend on the order of arrival, so those values are exact.
 #include "common.hpp"
 #ifndef G4S_SPGEMM_UPR
 #define G4S_SPGEMM_UPR 6   /* 4 until the end of round 4; with a round's descriptors requested together 5 / 6 / 7 / 8 units ran 31.2 / 31.0 / 31.25 / 31.75 ms against 31.6 (2: 34.1) */
@@ -33,6 +35,7 @@
 #define G4S_KO 0   // timing-only knock-outs of the big-row numeric kernel (wrong results; tools/ab_variants.sh): 1 no halvings, 2 no LDS atomics, 4 no bucket index, 8 no stores, 16 no accumulate step
 #endif
 #include "prims.hpp"
+#include "semiring.hpp"
 #include "readback.hpp"
 #include <algorithm>
 #include <chrono>
@@ -43,6 +46,7 @@
 
 namespace {
 
+namespace sr = g4s::semiring;                                      // the value operations of the numeric kernels (semiring.hpp)
 constexpr int kHashScal = 107; // HASH_SCAL, mm/inc/define.h:12
 constexpr int kEmpty = -1;
 
@@ -543,7 +547,7 @@ __global__ __launch_bounds__(WGSIZE) void spgemm_symbolic_lds_kernel(
     }
 }
 
-template <int WGSIZE, int THREADS, int TABLE>
+template <int WGSIZE, int THREADS, int TABLE, typename SR>
 __global__ __launch_bounds__(WGSIZE) void spgemm_numeric_lds_kernel(
     const int *__restrict__ rows, int nrows, const int *__restrict__ arpt, const int *__restrict__ acol, const double *__restrict__ aval,
     const int *__restrict__ brpt, const int *__restrict__ bcol, const double *__restrict__ bval, const long long *__restrict__ row_flop,
@@ -561,7 +565,7 @@ __global__ __launch_bounds__(WGSIZE) void spgemm_numeric_lds_kernel(
     int *K = lds_i + RPB * TABLE * 2 + sub * TABLE;
     int4 *longs = reinterpret_cast<int4 *>(lds_i + RPB * TABLE * 3);   // RPB == 1 kernels only (TABLE·12 bytes is a multiple of 16)
     const int long_thr = RPB == 1 ? long_b_threshold(THREADS) : (1 << 30);
-    for (int s = t; s < TABLE; s += THREADS) { K[s] = kEmpty; V[s] = 0.0; }
+    for (int s = t; s < TABLE; s += THREADS) { K[s] = kEmpty; V[s] = SR::identity(); }
     if (RPB == 1 && t == 0) longs[0].x = 0;
     __syncthreads();
     if (row >= 0) {
@@ -571,18 +575,18 @@ __global__ __launch_bounds__(WGSIZE) void spgemm_numeric_lds_kernel(
             int h = hash_of<TABLE>(key);
             for (int probes = 0; probes < TABLE; ++probes) {       // bounded: a wrong crpt from the caller must not hang the GPU
                 const int old = atomicCAS(&K[h], kEmpty, key);
-                if (old == kEmpty || old == key) { atomicAdd(&V[h], tv); break; }   // addop, hash_mult.h:588-593
+                if (old == kEmpty || old == key) { SR::lds_acc(&V[h], tv); break; }   // addop, hash_mult.h:588-593
                 h = (h + 1) & (TABLE - 1);
             }
         };
         walk_a_entries<true>(a0, a1, t >> gs, THREADS >> gs, acol, aval, brpt, brpt + 1, [&](int b0, int b1, double av) {
             if (RPB == 1 && defer_long_b(longs, b0, b1, av, t & gmask, gmask, long_thr)) return true;
-            for (int k = b0 + (t & gmask); k < b1; k += gmask + 1) insert(bcol[k], av * bval[k]);   // multop, hash_mult.h:583
+            for (int k = b0 + (t & gmask); k < b1; k += gmask + 1) insert(bcol[k], SR::mul(av, bval[k]));   // multop, hash_mult.h:583
             return true;
         });
         if (RPB == 1) {
             __syncthreads();                                        // uniform: with RPB == 1 every thread of the workgroup has this row
-            for_deferred_rows<true>(longs, t, THREADS, bcol, bval, [&](int col, double bv, double av) { insert(col, av * bv); });
+            for_deferred_rows<true>(longs, t, THREADS, bcol, bval, [&](int col, double bv, double av) { insert(col, SR::mul(av, bv)); });
         }
     }
     __syncthreads();
@@ -740,7 +744,7 @@ constexpr int kTinyCap = 64;                                     // the same ker
                                                                   // instead of 7.5 — the CU holds 32 such waves instead of 20, and these rows are all latency (round 5)
 template <bool NUMERIC, int CAP = kSmallCap>
 constexpr int small_wave_ints() { return CAP + (NUMERIC ? 2 * CAP : 0) + CAP / 2 + CAP / 4; }   // columns | products (fp64) | source index per rank (u16) | run per product (u8)
-template <bool NUMERIC, int CAP = kSmallCap>
+template <bool NUMERIC, int CAP = kSmallCap, typename SR = sr::PlusTimes>
 __global__ __launch_bounds__(256) void spgemm_small_wave_kernel(
     const int *__restrict__ rows, int nrows, const int *__restrict__ arpt, const int *__restrict__ acol, const double *__restrict__ aval,
     const int *__restrict__ brpt, const int *__restrict__ bcol, const double *__restrict__ bval,
@@ -796,7 +800,7 @@ __global__ __launch_bounds__(256) void spgemm_small_wave_kernel(
         if (NUMERIC) {                                             // (every lane takes part in the shuffles: a run's owner lane may hold no product of this pass)
             const long long bits = __double_as_longlong(av);
             const int lo32 = __shfl((int)(bits & 0xFFFFFFFFll), e, 64), hi32 = __shfl((int)(bits >> 32), e, 64);
-            prod = __longlong_as_double(((long long)hi32 << 32) | (unsigned)lo32) * bval[rb0 + (i - rP)];   // multop, hash_mult.h:583
+            prod = SR::mul(__longlong_as_double(((long long)hi32 << 32) | (unsigned)lo32), bval[rb0 + (i - rP)]);   // multop, hash_mult.h:583
         }
         if (i0 + lane < flop) {
             Cin[i] = col;
@@ -842,7 +846,7 @@ __global__ __launch_bounds__(256) void spgemm_small_wave_kernel(
             for (int m = i + 1; m < flop; ++m) {                   // addop in run order, hash_mult.h:588-593
                 const int s2 = Src[m];
                 if (Cin[s2] != col) break;
-                sum += Vin[s2];
+                sum = SR::combine(sum, Vin[s2]);
             }
             const int o = off + base + __popcll(mask & ((1ull << lane) - 1ull));
             ccol[o] = col;
@@ -1593,7 +1597,7 @@ __global__ __launch_bounds__(256) void unit_task_kernel(long long bound /* threa
     }
 }
 
-template <int T, bool UNITS>
+template <int T, bool UNITS, typename SR>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void spgemm_numeric_big_kernel(
     const int *__restrict__ rows, int nrows, int nz_lo, int nz_hi /* rows with nz outside (nz_lo, nz_hi] are left to the other shape */,
     int *__restrict__ next_row /* not NULL: rows are handed out one at a time through this counter (a list sorted longest first) */, int N, int K, const int *__restrict__ wsplit, const int *__restrict__ arpt, const int *__restrict__ acol, const double *__restrict__ aval,
@@ -1722,7 +1726,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
         }
 #pragma unroll
         for (int q = 0; q < kU; ++q)
-            if (in[q] && !(G4S_KO & 2)) atomicAdd(&V[lo[q] & (kBigChunk - 1)], av[q] * bv[q]);   // (the mask: a stale bucket can only be read with a wrong crpt from the caller — stay inside the chunk)
+            if (in[q] && !(G4S_KO & 2)) SR::lds_acc(&V[lo[q] & (kBigChunk - 1)], SR::mul(av[q], bv[q]));   // (the mask: a stale bucket can only be read with a wrong crpt from the caller — stay inside the chunk)
     };
     // The chunk's sorted columns are issued a chunk ahead (they are consumed at the top of the next chunk, a whole accumulation pass later).
     auto fetch_chunk = [&](int q0) { fetch_from(po >= 0 ? pre_cols + po + q0 : ccol + off + q0, min(kBigChunk, nz - q0)); };
@@ -1730,7 +1734,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
 #pragma unroll
         for (int u = 0; u < kPerThread; ++u) {
             const int i = t + u * kBigThreads;
-            if (i < qn) { KC[i] = cc[u]; V[i] = 0.0; }
+            if (i < qn) { KC[i] = cc[u]; V[i] = SR::identity(); }
         }
     };
     auto chunk_span = [&](int qn) {                                // after the barrier behind open_chunk
@@ -1946,7 +1950,8 @@ __global__ __launch_bounds__(256) void hub_prefix_kernel(const int *__restrict__
     if (t == 0 && row_nz) row_nz[slot_rows[slot]] = s_carry;
 }
 
-// Column ids of a hub row in ascending order, values zeroed (products are accumulated afterwards).
+// Column ids of a hub row in ascending order, values set to the identity (products are accumulated afterwards).
+template <typename SR>
 __global__ __launch_bounds__(256) void hub_emit_kernel(const int *__restrict__ slot_rows, int W, const unsigned *__restrict__ bitmap,
                                                         const int *__restrict__ prefix, const int *__restrict__ crpt,
                                                         int *__restrict__ ccol, double *__restrict__ cval)
@@ -1962,12 +1967,13 @@ __global__ __launch_bounds__(256) void hub_emit_kernel(const int *__restrict__ s
             const int b = __ffs(bits) - 1;
             bits &= bits - 1;
             ccol[pos] = (w << 5) + b;
-            cval[pos] = 0.0;
+            cval[pos] = SR::identity();
             ++pos;
         }
     }
 }
 
+template <typename SR>
 __global__ __launch_bounds__(256) void hub_accumulate_kernel(const HubItem *__restrict__ items, int W,
                                                               const int *__restrict__ acol, const double *__restrict__ aval,
                                                               const int *__restrict__ brpt, const int *__restrict__ bcol,
@@ -1987,7 +1993,7 @@ __global__ __launch_bounds__(256) void hub_accumulate_kernel(const HubItem *__re
         const int col = bcol[k];
         const int w = col >> 5;
         const int pos = pf[w] + __popc(bm[w] & ((1u << (col & 31)) - 1u));
-        atomicAdd(&out[pos], av * bval[k]);
+        SR::global_acc(&out[pos], SR::mul(av, bval[k]));
     };
     for (int j = it.j0 + (t >> 5); j < it.j1; j += 8) {
         const int c = acol[j];
@@ -2090,6 +2096,7 @@ int allow_lds(Kernel k, size_t bytes)
 }
 
 // Hub rows: mark → prefix (→ counts) [→ emit → accumulate], in batches bounded by the bitmap workspace.
+template <typename SR = sr::PlusTimes>
 int run_hub_rows(bool numeric, const std::vector<int> &hub_rows, const std::vector<int> &h_arpt_of_rows /*2 per row*/, int N,
                  const int *arpt, const int *acol, const double *aval, const int *brpt, const int *bcol, const double *bval,
                  int *row_nz, const int *crpt, int *ccol, double *cval, hipStream_t s)
@@ -2121,10 +2128,10 @@ int run_hub_rows(bool numeric, const std::vector<int> &hub_rows, const std::vect
                            numeric ? nullptr : row_nz);
         if (numeric) {
             const int gx = std::min(64, (W + 255) / 256);
-            hipLaunchKernelGGL(hub_emit_kernel, dim3(gx, nslots), dim3(256), 0, s, slot_rows.as<int>(), W, bitmap.as<unsigned>(), prefix.as<int>(),
+            hipLaunchKernelGGL(hub_emit_kernel<SR>, dim3(gx, nslots), dim3(256), 0, s, slot_rows.as<int>(), W, bitmap.as<unsigned>(), prefix.as<int>(),
                                crpt, ccol, cval);
             if (!h_items.empty())
-                hipLaunchKernelGGL(hub_accumulate_kernel, dim3((unsigned)h_items.size()), dim3(256), 0, s, items.as<HubItem>(), W, acol, aval, brpt,
+                hipLaunchKernelGGL(hub_accumulate_kernel<SR>, dim3((unsigned)h_items.size()), dim3(256), 0, s, items.as<HubItem>(), W, acol, aval, brpt,
                                    bcol, bval, bitmap.as<unsigned>(), prefix.as<int>(), crpt, cval);
         }
         G4S_HIP_TRY(hipGetLastError());
@@ -2926,14 +2933,16 @@ G4S_API g4s_status g4s_spgemm_symbolic(int32_t M, int32_t K, int32_t N,
 }
 
 namespace {
-int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
-                        const int32_t *arpt, const int32_t *acol, const double *aval,
-                        const int32_t *brpt, const int32_t *bcol, const double *bval,
-                        const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream, const PreSorted *pre)
+// One instantiation per semiring (semiring.hpp): the host logic is the same for all four, only the numeric kernels it launches differ.
+template <typename SR>
+int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
+                       const int32_t *arpt, const int32_t *acol, const double *aval,
+                       const int32_t *brpt, const int32_t *bcol, const double *bval,
+                       const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream, const PreSorted *pre)
 {
     const long long *pre_off = pre ? pre->d_off : nullptr;
     const int *pre_cols = pre ? pre->d_cols : nullptr;
-    (void)flags; // rows always come out sorted by column: the sorted form is the only ordering contract (hash_mult.h:530-551)
+    (void)flags; // the semiring bits chose SR (spgemm_numeric_impl); rows always come out sorted by column: the sorted form is the only ordering contract (hash_mult.h:530-551)
     G4S_REQUIRE(M >= 0 && N >= 0, "negative dimension");
     G4S_REQUIRE(arpt && brpt && crpt, "NULL argument");
     hipStream_t s = g4s::as_stream(stream);
@@ -3070,7 +3079,7 @@ int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
                            (const RankChunk *)chunks->as<RankChunk>(), ritems->as<RankItem>());
         // split by size (spgemm_rank.hpp): the chunks of at most kRankSmallCap outputs take the 512-thread shape, two workgroups per CU
         const bool two_shapes = !getenv("G4S_SPGEMM_RANK_ONE_SHAPE");
-        auto *sflag = mk(), *spos = mk(), *rbig = mk(), *rsmall = mk(), *rcounts = mk();
+        DevBuf *sflag = mk(), *spos = mk(), *rbig = mk(), *rsmall = mk(), *rcounts = mk();
         const RankItem *big_items = ritems->as<RankItem>();
         const int *n_big = nullptr;
         if (two_shapes) {
@@ -3082,11 +3091,11 @@ int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
                                rsmall->as<RankItem>(), rcounts->as<int>());
             big_items = rbig->as<RankItem>(); n_big = rcounts->as<int>();
         }
-        auto k = spgemm_numeric_rank2_kernel<T, kRankChunk, G4S_SPGEMM_RANK_UPR>;
+        auto k = spgemm_numeric_rank2_kernel<T, kRankChunk, G4S_SPGEMM_RANK_UPR, SR>;
         G4S_TRY(allow_lds(k, lds));
         hipLaunchKernelGGL(k, dim3(big_grid(nchunks, 1)), dim3(T), lds, s, nchunks, n_big, big_items, wcol, (const BPack *)bpack->as<BPack>(), (const UnitDesc *)ud->as<UnitDesc>(), ccol, cval);
         if (two_shapes) {
-            auto ks = spgemm_numeric_rank2_kernel<kRankSmallT, kRankSmallCap, 8>;
+            auto ks = spgemm_numeric_rank2_kernel<kRankSmallT, kRankSmallCap, 8, SR>;
             constexpr size_t lds_s = rank_lds_bytes(kRankSmallCap);
             G4S_TRY(allow_lds(ks, lds_s));
             hipLaunchKernelGGL(ks, dim3(big_grid(nchunks, 2)), dim3(kRankSmallT), lds_s, s, nchunks, (const int *)(rcounts->as<int>() + 1), (const RankItem *)rsmall->as<RankItem>(), wcol,
@@ -3106,26 +3115,26 @@ int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
         // (the lists of a carried symbolic classification are cut by PRODUCTS: its tiny class fits the 64-product form; the numeric classes are cut by outputs)
         const int nt = reuse_rc ? rc.count[CLS_TINY] : 0;
         if (nt) {
-            auto k = spgemm_small_wave_kernel<true, kTinyCap>;
+            auto k = spgemm_small_wave_kernel<true, kTinyCap, SR>;
             constexpr size_t lds = sizeof(int) * 4 * small_wave_ints<true, kTinyCap>();
             hipLaunchKernelGGL(k, dim3((nt + 3) / 4), dim3(256), lds, s, rc.list(CLS_TINY), nt, arpt, acol, aval, brpt, bcol, bval, (int *)nullptr, crpt, ccol,
                                cval, small_ovf.as<int>(), small_ovf_n.as<int>());
         }
         if (n - nt) {
-            auto k = spgemm_small_wave_kernel<true>;
+            auto k = spgemm_small_wave_kernel<true, kSmallCap, SR>;
             hipLaunchKernelGGL(k, dim3((n - nt + 3) / 4), dim3(256), sizeof(int) * 4 * small_wave_ints<true>(), s, rc.list(CLS_TINY) + nt, n - nt, arpt, acol, aval, brpt, bcol, bval, (int *)nullptr, crpt,
                                ccol, cval, small_ovf.as<int>(), small_ovf_n.as<int>());
         }
-        auto k2 = spgemm_numeric_lds_kernel<256, 256, 1024>;
+        auto k2 = spgemm_numeric_lds_kernel<256, 256, 1024, SR>;
         hipLaunchKernelGGL(k2, dim3(std::min(n, 256)), dim3(256), num_lds_bytes(1024), s, small_ovf.as<int>(), 0, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval,
                            (const int *)small_ovf_n.as<int>());
     } else {
     if (int n = rc.count[CLS_TINY]) {
-        auto k = spgemm_numeric_lds_kernel<256, 64, 64>;
+        auto k = spgemm_numeric_lds_kernel<256, 64, 64, SR>;
         hipLaunchKernelGGL(k, dim3((n + 3) / 4), dim3(256), 4 * 64 * 12, s, rc.list(CLS_TINY), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
     }
     if (int n = rc.count[CLS_SMALL]) {
-        auto k = spgemm_numeric_lds_kernel<256, 256, 1024>;
+        auto k = spgemm_numeric_lds_kernel<256, 256, 1024, SR>;
         hipLaunchKernelGGL(k, dim3(n), dim3(256), num_lds_bytes(1024), s, rc.list(CLS_SMALL), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
     }
     }
@@ -3210,12 +3219,12 @@ int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
         G4S_TRY(rmeta->alloc(sizeof(NumRowMeta) * (size_t)n));
         hipLaunchKernelGGL(num_row_meta_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, arpt, crpt, pre_off, ul.U ? ul.item_off : (const long long *)nullptr, ul.uoff, rmeta->as<NumRowMeta>());
         if (ul.U) {
-            auto k = spgemm_numeric_big_kernel<T, true>;
+            auto k = spgemm_numeric_big_kernel<T, true, SR>;
             G4S_TRY(allow_lds(k, lds));
             hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, nz_lo, nz_hi, next_row, N2, K, wsplit, arpt, acol, aval, brpt, wcol, winv, bval, row_flop.as<long long>(), crpt, ccol, cval, pre_off, pre_cols,
                                ul.item_off, ul.uoff, ul.U, rmeta->as<NumRowMeta>());
         } else {
-            auto k = spgemm_numeric_big_kernel<T, false>;
+            auto k = spgemm_numeric_big_kernel<T, false, SR>;
             G4S_TRY(allow_lds(k, lds));
             hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, nz_lo, nz_hi, next_row, N2, K, wsplit, arpt, acol, aval, brpt, wcol, winv, bval, row_flop.as<long long>(), crpt, ccol, cval, pre_off, pre_cols,
                                (const long long *)nullptr, (const int *)nullptr, (const UnitDesc *)nullptr, rmeta->as<NumRowMeta>());
@@ -3241,18 +3250,18 @@ int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
     } else {
     if (t_med && xn_large) { G4S_TRY(big(t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM])); }
     else if (int n = rc.count[CLS_MEDIUM]) {
-        auto k = spgemm_numeric_lds_kernel<256, 256, 2048>;
+        auto k = spgemm_numeric_lds_kernel<256, 256, 2048, SR>;
         hipLaunchKernelGGL(k, dim3(n), dim3(256), num_lds_bytes(2048), s, rc.list(CLS_MEDIUM), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
     }
     if (xn_large) { G4S_TRY(big(t_large, rc.list(CLS_LARGE), rc.count[CLS_LARGE])); }
     else if (int n = rc.count[CLS_LARGE]) {
-        auto k = spgemm_numeric_lds_kernel<512, 512, 4096>;
+        auto k = spgemm_numeric_lds_kernel<512, 512, 4096, SR>;
         G4S_TRY(allow_lds(k, num_lds_bytes(4096)));
         hipLaunchKernelGGL(k, dim3(n), dim3(512), num_lds_bytes(4096), s, rc.list(CLS_LARGE), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
     }
     if (xn_m2) { G4S_TRY(big(t_m2, rc.list(CLS_M2), rc.count[CLS_M2])); }
     else if (int n = rc.count[CLS_M2]) {
-        auto k = spgemm_numeric_lds_kernel<1024, 1024, 8192>;
+        auto k = spgemm_numeric_lds_kernel<1024, 1024, 8192, SR>;
         G4S_TRY(allow_lds(k, num_lds_bytes(8192)));
         hipLaunchKernelGGL(k, dim3(n), dim3(1024), num_lds_bytes(8192), s, rc.list(CLS_M2), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
     }
@@ -3279,11 +3288,20 @@ int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
     dbg.mark("big-launch(+sync)");
     std::vector<int> hub, ranges;
     G4S_TRY(fetch_rows_and_ranges(rc.list(CLS_HUB), rc.count[CLS_HUB], arpt, hub, ranges, s));
-    G4S_TRY(run_hub_rows(true, hub, ranges, N, arpt, acol, aval, brpt, bcol, bval, nullptr, crpt, ccol, cval, s));
+    G4S_TRY(run_hub_rows<SR>(true, hub, ranges, N, arpt, acol, aval, brpt, bcol, bval, nullptr, crpt, ccol, cval, s));
     G4S_HIP_TRY(g4s::reads_sync(s));
     t_idle = true;                                                 // (cleared by the next call on this thread)
     dbg.mark("hub+sync");
     return G4S_OK;
+}
+int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
+                        const int32_t *arpt, const int32_t *acol, const double *aval,
+                        const int32_t *brpt, const int32_t *bcol, const double *bval,
+                        const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream, const PreSorted *pre)
+{
+    return sr::dispatch(flags, [&](auto policy) {
+        return spgemm_numeric_run<decltype(policy)>(M, K, N, arpt, acol, aval, brpt, bcol, bval, crpt, ccol, cval, flags, stream, pre);
+    });
 }
 } // namespace
 

@@ -230,7 +230,7 @@ __global__ void rank_split_items_kernel(int n, const RankItem *__restrict__ item
     if (it.qn <= kRankSmallCap) small[spos[i]] = it; else big[i - spos[i]] = it;
 }
 
-template <int T, int CAP, int KU>
+template <int T, int CAP, int KU, typename SR>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void spgemm_numeric_rank2_kernel(
     int nitems_max, const int *__restrict__ nitems_dev /* not NULL: the list's length (the grid is sized by nitems_max) */, const RankItem *__restrict__ items, const int *__restrict__ bcol2 /* compact column per entry of B */, const BPack *__restrict__ bpack,
     const UnitDesc *__restrict__ U, int *__restrict__ ccol, double *__restrict__ cval)
@@ -278,11 +278,11 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
         if (wr < 0) return;
         const unsigned long long w = BM[wr >> 6];
         const int slot = min((int)(w >> 48) + (int)__popcll(w & ((1ull << (wr & 63)) - 1ull)), (int)CAP - 1);   // (the clamp: stay inside the chunk whatever the arrays hold; all-int, or min() goes through fp64)
-        atomicAdd(&V[slot], prod);
+        SR::lds_acc(&V[slot], prod);
         KC[slot] = col;
     };
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) if (t + u * T < CAP) { V[t + u * T] = 0.0; KC[t + u * T] = 0; }
+    for (int u = 0; u < kPer; ++u) if (t + u * T < CAP) { V[t + u * T] = SR::identity(); KC[t + u * T] = 0; }
 #pragma unroll
     for (int j = 0; j < kWPT; ++j) BM[t + j * T] = 0ull;
     int g = blockIdx.x;
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
         for (int r = 0; r < kR; ++r)
 #pragma unroll
             for (int q = 0; q < kU; ++q)                             // multop / addop, hash_mult.h:583-593
-                accumulate(wr[r][q], rec[r][q].y, d_val(dc, r, q) * __longlong_as_double(((long long)rec[r][q].w << 32) | (unsigned)rec[r][q].z));
+                accumulate(wr[r][q], rec[r][q].y, SR::mul(d_val(dc, r, q), __longlong_as_double(((long long)rec[r][q].w << 32) | (unsigned)rec[r][q].z)));
 #ifdef G4S_PROFILE_BIG
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         BIG_PROF(15);                                              // the register rounds' accumulate alone
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
                     for (int q = 0; q < kGA; ++q)
                         if (e0 + q < ne) {
                             const double av = __longlong_as_double(((long long)__builtin_amdgcn_readlane(dx.w, e0 + q) << 32) | (unsigned)__builtin_amdgcn_readlane(dx.z, e0 + q));
-                            accumulate(place_rec(c[q].x, cur.pbase, lane < __builtin_amdgcn_readlane(dx.y, e0 + q)), c[q].y, av * __longlong_as_double(((long long)c[q].w << 32) | (unsigned)c[q].z));
+                            accumulate(place_rec(c[q].x, cur.pbase, lane < __builtin_amdgcn_readlane(dx.y, e0 + q)), c[q].y, SR::mul(av, __longlong_as_double(((long long)c[q].w << 32) | (unsigned)c[q].z)));
                         }
                 });
             if (ne < 64) break;
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
 #pragma unroll
                 for (int u = 0; u < kH; ++u) {
                     const int i = t + (h * kH + u) * T;
-                    if (h * kH + u < kPer && i < cur.qn) { cval[(long long)cur.out0 + i] = val[u]; ccol[(long long)cur.out0 + i] = col[u]; V[i] = 0.0; }
+                    if (h * kH + u < kPer && i < cur.qn) { cval[(long long)cur.out0 + i] = val[u]; ccol[(long long)cur.out0 + i] = col[u]; V[i] = SR::identity(); }
                 }
             }
 #pragma unroll

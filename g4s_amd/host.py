@@ -2,7 +2,7 @@
 
 Names and argument meaning follow the reference so that tests read like tests of the reference would:
   CSR            — mm/inc/CSR.h:22-100 (rows, cols, nnz, rowptr, colids, values, zerobased)
-  HashSpGEMM     — mm/inc/hash_mult.h:1028-1057 (sortOutput flag; multiply/add are the arithmetic semiring only)
+  HashSpGEMM     — mm/inc/hash_mult.h:1028-1057 (sortOutput flag; multiply/add: plus-times, min-plus, max-plus or or-and)
   spmv           — the CSR mat-vec the build defines for mv/ (DESIGN.md §SpMV), y = alpha·A·x + beta·y
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
@@ -202,10 +202,17 @@ def _view(ptr, count, typestr, dtype, device):
     return torch.as_tensor(_LibraryBuffer(ptr.value if hasattr(ptr, "value") else ptr, count, typestr), device=device)
 
 
-def HashSpGEMM(a, b, sortOutput=True, two_phase=False):
+SEMIRINGS = {"plus_times": capi.SEMIRING_PLUS_TIMES, "min_plus": capi.SEMIRING_MIN_PLUS, "max_plus": capi.SEMIRING_MAX_PLUS, "or_and": capi.SEMIRING_OR_AND}
+
+
+def HashSpGEMM(a, b, sortOutput=True, two_phase=False, semiring="plus_times"):
     """C = A·B — HashSpGEMM, mm/inc/hash_mult.h:1028-1057. One call into the library (symbolic → crpt, numeric → ccol/cval, the sorted
     columns of the large rows carried from the first phase to the second); `two_phase=True` issues g4s_spgemm_symbolic and
-    g4s_spgemm_numeric separately into torch-owned arrays. The result's `timings` holds the library's stage times (one-call form)."""
+    g4s_spgemm_numeric separately into torch-owned arrays. The result's `timings` holds the library's stage times (one-call form).
+    `semiring` picks the multiply/add pair (include/g4s.h, G4S_SEMIRING_*): "plus_times" (Σ a·b), "min_plus" (min(a + b)), "max_plus"
+    (max(a + b)) or "or_and" (1.0 where any a != 0 and b != 0, else 0.0); the pattern of C is the same for all four."""
+    if semiring not in SEMIRINGS:
+        raise ValueError(f"unknown semiring {semiring!r}; expected one of {sorted(SEMIRINGS)}")
     _require_gpu()
     assert a.cols == b.rows
     lib = capi.load()
@@ -213,7 +220,7 @@ def HashSpGEMM(a, b, sortOutput=True, two_phase=False):
     if not two_phase:
         crpt_p, ccol_p, cval_p = C.c_void_p(), C.c_void_p(), C.c_void_p()
         cnnz, tm = C.c_int64(0), capi.Timings()
-        flags = capi.DEVICE_POINTERS | (capi.SORT_OUTPUT if sortOutput else 0)
+        flags = capi.DEVICE_POINTERS | (capi.SORT_OUTPUT if sortOutput else 0) | SEMIRINGS[semiring]
         capi.check(lib.g4s_spgemm_csr_i32_f64(_ptr(a.rowptr), _ptr(a.colids), _ptr(a.values), _ptr(b.rowptr), _ptr(b.colids), _ptr(b.values),
                                               C.byref(crpt_p), C.byref(ccol_p), C.byref(cval_p), a.rows, a.cols, b.cols, C.byref(cnnz), C.byref(tm), flags))
         c = CSR(_view(crpt_p, a.rows + 1, "<i4", torch.int32, dev), _view(ccol_p, cnnz.value, "<i4", torch.int32, dev),
@@ -226,7 +233,7 @@ def HashSpGEMM(a, b, sortOutput=True, two_phase=False):
                                        _ptr(crpt), C.byref(cnnz), _stream()))
     ccol = torch.empty(cnnz.value, dtype=torch.int32, device=dev)
     cval = torch.empty(cnnz.value, dtype=torch.float64, device=dev)
-    flags = capi.DEVICE_POINTERS | (capi.SORT_OUTPUT if sortOutput else 0)
+    flags = capi.DEVICE_POINTERS | (capi.SORT_OUTPUT if sortOutput else 0) | SEMIRINGS[semiring]
     capi.check(lib.g4s_spgemm_numeric(a.rows, a.cols, b.cols, _ptr(a.rowptr), _ptr(a.colids), _ptr(a.values),
                                       _ptr(b.rowptr), _ptr(b.colids), _ptr(b.values), _ptr(crpt), _ptr(ccol), _ptr(cval),
                                       flags, _stream()))

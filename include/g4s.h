@@ -298,7 +298,28 @@ g4s_status g4s_spgemm_flop(int32_t M, const int32_t *arpt, const int32_t *acol, 
  * outputs allocated by the callee — with g4s_malloc for host pointers (free with g4s_free), with
  * g4s_dev_alloc for G4S_DEVICE_POINTERS (free with g4s_dev_free). A is M×K, B is K×N, C is M×N.
  * cnnz is int64; G4S_ERR_OVERFLOW is returned (and nothing allocated) if it exceeds INT32_MAX,
- * because crpt keeps the reference's int32 type. timings may be NULL. */
+ * because crpt keeps the reference's int32 type. timings may be NULL.
+ *
+ * Semirings (HashSpGEMM's MultiplyOperation / AddOperation pair, mm/inc/hash_mult.h:583-593, as a closed set on the device): one of the values below,
+ * or-ed into the flags of g4s_spgemm_csr_i32_f64 and g4s_spgemm_numeric (host or device pointers, with or without G4S_SORT_OUTPUT). g4s_spgemm_symbolic
+ * takes no flags: the pattern does not depend on the semiring. No other entry point reads these bits.
+ *   Pattern: crpt and ccol are bit-identical to the plus-times product of the same inputs (structural entries, repeated columns inside a row, unsorted B
+ *     and empty rows included) — an entry exists wherever a product exists, whatever its value.
+ *   Values, per output entry, over the products a·b that make it up:
+ *     PLUS_TIMES  Σ a·b (identity 0.0) — today's behaviour, within 1e-10 relative of the reference's order of summation;
+ *     MIN_PLUS    min(a + b) (identity +inf) — distance products: shortest paths by repeated squaring, k-hop distances;
+ *     MAX_PLUS    max(a + b) (identity −inf) — longest / critical paths in a DAG;
+ *     OR_AND      1.0 if any product has a != 0 && b != 0, else 0.0 (what std::logical_and / std::logical_or store; NaN counts as nonzero). An entry whose
+ *                 products are all false stays in C with the value 0.0 — reachability, transitive closure.
+ *   min, max and or do not depend on the order in which products arrive, and each min/max-plus product is one IEEE add: the values of the three are exact and
+ *   deterministic on every path. Outside the contract: the sign of a zero result of min/max-plus, and the value of an entry that has a NaN product or a
+ *   (+inf) + (−inf) product (the other entries are unaffected).
+ *   Two-call form: the state carried from g4s_spgemm_symbolic is structural only, so successive numeric calls on the same arrays may each use another semiring. */
+#define G4S_SEMIRING_PLUS_TIMES    0u /* default: C = Σ a·b */
+#define G4S_SEMIRING_MIN_PLUS    512u /* C = min(a + b) */
+#define G4S_SEMIRING_MAX_PLUS   1024u /* C = max(a + b) */
+#define G4S_SEMIRING_OR_AND     1536u /* C = OR(a != 0 && b != 0) as 1.0 / 0.0 */
+#define G4S_SEMIRING_MASK       1536u
 g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *acol, const double *aval,
                                   const int32_t *brpt, const int32_t *bcol, const double *bval,
                                   int32_t **crpt, int32_t **ccol, double **cval,

@@ -108,16 +108,40 @@ public:
     bool zerobased;
 };
 
-// C = A·B on the device, result adopted by `c`. Only the arithmetic semiring can run on the GPU; any other functor is refused.
+// The add operations of the tropical semirings, as ordinary callables (they keep their meaning in host code).
+template <class NT>
+struct min_op {
+    NT operator()(const NT &x, const NT &y) const { return y < x ? y : x; }
+};
+template <class NT>
+struct max_op {
+    NT operator()(const NT &x, const NT &y) const { return x < y ? y : x; }
+};
+
+// (multiply, add) functor pair → the device semiring flag (include/g4s.h, G4S_SEMIRING_*). Only these four pairs exist on the device.
+template <class Mul, class Add, class NT>
+struct semiring_flag { static constexpr bool supported = false; };
+template <class NT>
+struct semiring_flag<std::multiplies<NT>, std::plus<NT>, NT> { static constexpr bool supported = true; static constexpr unsigned value = G4S_SEMIRING_PLUS_TIMES; };
+template <class NT>
+struct semiring_flag<std::plus<NT>, min_op<NT>, NT> { static constexpr bool supported = true; static constexpr unsigned value = G4S_SEMIRING_MIN_PLUS; };
+template <class NT>
+struct semiring_flag<std::plus<NT>, max_op<NT>, NT> { static constexpr bool supported = true; static constexpr unsigned value = G4S_SEMIRING_MAX_PLUS; };
+template <class NT>
+struct semiring_flag<std::logical_and<NT>, std::logical_or<NT>, NT> { static constexpr bool supported = true; static constexpr unsigned value = G4S_SEMIRING_OR_AND; };
+
+// C = A·B on the device, result adopted by `c`. The (multop, addop) pair must be one of the four device semirings (semiring_flag); any other
+// functor is refused at compile time — there is no host loop.
 template <bool vectorProbing = false, bool sortOutput = true, typename IT, typename NT, typename Mul, typename Add>
 void HashSpGEMM(const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c, Mul, Add, Timings *timing = nullptr)
 {
-    static_assert(std::is_same<Mul, std::multiplies<NT>>::value && std::is_same<Add, std::plus<NT>>::value,
-                  "device SpGEMM implements multiplies/plus only (the functors every call site of the reference passes)");
+    static_assert(semiring_flag<Mul, Add, NT>::supported,
+                  "device SpGEMM implements four (multop, addop) pairs only: (std::multiplies, std::plus), (std::plus, g4s::min_op), "
+                  "(std::plus, g4s::max_op), (std::logical_and, std::logical_or)");
     c.make_empty();
     int64_t cnnz = 0;
     check(g4s_spgemm_csr_i32_f64(a.rowptr, a.colids, a.values, b.rowptr, b.colids, b.values, &c.rowptr, &c.colids, &c.values,
-                                 a.rows, a.cols, b.cols, &cnnz, timing, sortOutput ? G4S_SORT_OUTPUT : 0u),
+                                 a.rows, a.cols, b.cols, &cnnz, timing, (sortOutput ? G4S_SORT_OUTPUT : 0u) | semiring_flag<Mul, Add, NT>::value),
           "HashSpGEMM");
     c.rows = a.rows; c.cols = b.cols; c.nnz = (IT)cnnz; c.zerobased = true;
 }

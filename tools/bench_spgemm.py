@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """SpGEMM benchmark in the reference's protocol (mm/src/mkl_spgemm.cpp:60-85): 1 warm-up + mean of N runs of C = A·A, GFLOPS = 2·flop/t.
 BASELINE configs[2]: R-MAT scale 21 (n = 2 097 152); edge factor 3 is the largest whose nnz(C) fits the reference's int32 crpt.
-usage: python tools/bench_spgemm.py [--ef 3] [--runs 3] [--scale 21]"""
+usage: python tools/bench_spgemm.py [--ef 3] [--runs 3] [--scale 21] [--two-phase] [--semiring plus_times|min_plus|max_plus|or_and]"""
 import argparse
 import ctypes as C
 import json
@@ -18,6 +18,7 @@ ap.add_argument("--ef", type=float, default=3.0)
 ap.add_argument("--scale", type=int, default=21)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--two-phase", action="store_true", help="time g4s_spgemm_symbolic and g4s_spgemm_numeric as two calls instead of the one-call form")
+ap.add_argument("--semiring", default="plus_times", choices=sorted(host.SEMIRINGS), help="the value semiring of the product (G4S_SEMIRING_*); the pattern is the same for all")
 ap.add_argument("--cpu-sample-ef", type=float, default=0.0, help="also time the oracle's hash SpGEMM (1 host thread) on this smaller edge factor")
 ap.add_argument("--mkl", type=int, default=0, metavar="THREADS",
                 help="also time the REFERENCE's call sequence (mm/inc/mkl_mult.h:40-111 on oneMKL, oracle/mkl_ref.py) on the SAME input with this many threads "
@@ -37,7 +38,7 @@ def run():
     t0 = time.perf_counter()
     if not args.two_phase:
         # the call the reference times: mkl(A, B, C, timing) / HashSpGEMM(A, B, C) as one unit (mkl_spgemm.cpp:67-81)
-        c = host.HashSpGEMM(A, A)
+        c = host.HashSpGEMM(A, A, semiring=args.semiring)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         cnnz.value = c.nnz
@@ -52,7 +53,8 @@ def run():
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     capi.check(lib.g4s_spgemm_numeric(n, n, n, A.rowptr.data_ptr(), A.colids.data_ptr(), A.values.data_ptr(), A.rowptr.data_ptr(), A.colids.data_ptr(),
-                                      A.values.data_ptr(), crpt.data_ptr(), ccol.data_ptr(), cval.data_ptr(), capi.DEVICE_POINTERS | capi.SORT_OUTPUT, None))
+                                      A.values.data_ptr(), crpt.data_ptr(), ccol.data_ptr(), cval.data_ptr(),
+                                      capi.DEVICE_POINTERS | capi.SORT_OUTPUT | host.SEMIRINGS[args.semiring], None))
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     del ccol, cval
@@ -112,7 +114,7 @@ print(json.dumps({"cpu_baseline": cpu, "reference_baseline": ref,
                   "roofline": {"bound": "hbm (row re-reads of B served by L2/MALL) / LDS atomics", "model": "12*nnz(A) + 4*rows + 12*flop + 12*nnz(C) + 8*rows (SURVEY 8d)",
                                "model_bytes": model_bytes, "achieved": round(model_bytes / ((s + m) * 1e-3) / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                                "frac": round(model_bytes / ((s + m) * 1e-3) / 1e9 / 8000.0, 4)}, "metric": "fp64 SpGEMM A*A GFLOPS (2*flop/t)", "value": round(2 * flop / ((s + m) * 1e-3) / 1e9, 3), "unit": "GFLOPS",
-                  "config": {"workload": f"R-MAT scale {args.scale}, edge factor {args.ef}, C = A*A", "rows": n, "nnz_A": A.nnz, "flop": flop, "nnz_C": cnnz.value,
+                  "config": {"workload": f"R-MAT scale {args.scale}, edge factor {args.ef}, C = A*A", "semiring": args.semiring, "rows": n, "nnz_A": A.nnz, "flop": flop, "nnz_C": cnnz.value,
                              "compression": round(flop / max(cnnz.value, 1), 3)},
                   **({"symbolic_ms": round(s, 2), "numeric_ms": round(m, 2)} if args.two_phase else {"call_ms": round(m, 2), "form": "one call (g4s_spgemm_csr_i32_f64, device pointers)"}), "runs": args.runs,
                   "compulsory_bytes": 12 * (2 * A.nnz + cnnz.value), "compulsory_GBps": round(12 * (2 * A.nnz + cnnz.value) / ((s + m) * 1e-3) / 1e9, 1)}))
