@@ -12,7 +12,8 @@ LIB_PATH = os.environ.get("G4S_LIB") or os.path.join(_HERE, "lib", "libg4s_hip.s
 OK, ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_OVERFLOW, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 HOST_POINTERS, DEVICE_POINTERS, SORT_OUTPUT, SPMV_NO_NT, SPMV_BLOCKED, SPMV_STREAM, DIST_LOOPBACK, DIST_ALLGATHER, SPMV_UPDATABLE = 0, 1, 2, 4, 8, 16, 32, 64, 128
 SPMM_COL_MAJOR = 256
-SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM value semiring (g4s.h)
+SPMV_ACCUMULATE = 2048                                                   # semiring SpMV: y := y ⊕ (A ⊗ x) (g4s.h)
+SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM / SpMV value semiring (g4s.h)
 PATTERN_ELEMENT_BLOCK_MATVEC, PATTERN_DENSE_ROW_TIMES_MATRIX, PATTERN_SYM_QUADRATIC_FORM = 1, 2, 3
 DENSE_DGEMM, DENSE_DSYMM, DENSE_DTRMM, DENSE_DGEMV, DENSE_DSYMV, DENSE_DTRMV, DENSE_DSPMV = 1, 2, 3, 4, 5, 6, 7
 
@@ -104,6 +105,8 @@ SIGNATURES = {
     "g4s_csr_device_arrays": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "g4s_spmv": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp]),
     "g4s_spmv_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_uint]),
+    "g4s_spmv_semiring": (C.c_int, [vp, vp, vp, C.c_uint, vp]),
+    "g4s_spmv_semiring_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_uint]),
     "g4s_spmm": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint, vp]),
     "g4s_csr_spmm_reserve": (C.c_int, [vp, C.c_int32]),
     "g4s_spmm_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint]),

@@ -20,6 +20,7 @@
 #include "spmv_pb.hpp"
 #include "spmv_bcsr.hpp"
 #include "spmm.hpp"
+#include "semiring.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -45,10 +46,16 @@ __device__ __forceinline__ T stream_load(const T *p)
     else return *p;
 }
 
+// Every kernel of this file is a template on a value policy (semiring.hpp): PlusTimes for g4s_spmv, MinPlus / MaxPlus / OrAnd for g4s_spmv_semiring.
+// The sums below go through S::identity / S::mul / S::combine, which PlusTimes spells as 0.0, a * b and a + b: its kernels compile to the code they had
+// before the policy existed. The semiring kernels read alpha / beta as "beta != 0: combine with the old y" (ACCUMULATE) and ignore alpha.
+using g4s::semiring::PlusTimes;
+
+template <class S>
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    for (int off = 32; off > 0; off >>= 1) v = S::combine(v, __shfl_down(v, off, 64));
     return v;
 }
 
@@ -56,8 +63,13 @@ __device__ __forceinline__ double wave_sum(double v)
 #define G4S_STREAM_NT_Y 0
 #endif
 // y stores: plain by default (a nontemporal variant measured no gain on the stencil matrices and −4 % on the cache-resident one)
+template <class S>
 __device__ __forceinline__ void store_y(double *y, int r, double s, double alpha, double beta)
 {
+    if constexpr (!g4s::semiring::is_plus_times<S>) {
+        y[r] = beta == 0.0 ? s : S::combine(s, S::normalize(y[r]));   // semiring: the row's result, or y ⊕ it (ACCUMULATE)
+        return;
+    }
     const double v = beta == 0.0 ? alpha * s : alpha * s + beta * y[r];
 #if G4S_STREAM_NT_Y
     __builtin_nontemporal_store(v, y + r);
@@ -66,7 +78,7 @@ __device__ __forceinline__ void store_y(double *y, int r, double s, double alpha
 #endif
 }
 
-template <bool NT>
+template <bool NT, class S>
 __global__ __launch_bounds__(WG) void spmv_csr_adaptive_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colids, const double *__restrict__ values,
     const double *__restrict__ x, double *__restrict__ y,
@@ -82,7 +94,7 @@ __global__ __launch_bounds__(WG) void spmv_csr_adaptive_kernel(
         // ---- long-row chunk: strided private sums, then workgroup reduction
         if ((int)blockIdx.x >= n_chunks) return;
         const LongChunk c = chunks[blockIdx.x];
-        double acc = 0.0;
+        double acc = S::identity();
         int k = c.k0 + tid;
         for (; k + 3 * WG < c.k1; k += 4 * WG) {
             const int c0 = stream_load<NT>(colids + k), c1 = stream_load<NT>(colids + k + WG);
@@ -90,13 +102,13 @@ __global__ __launch_bounds__(WG) void spmv_csr_adaptive_kernel(
             const double v0 = stream_load<NT>(values + k), v1 = stream_load<NT>(values + k + WG);
             const double v2 = stream_load<NT>(values + k + 2 * WG), v3 = stream_load<NT>(values + k + 3 * WG);
             const double x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
-            acc += v0 * x0; acc += v1 * x1; acc += v2 * x2; acc += v3 * x3;
+            acc = S::combine(acc, S::mul(v0, x0)); acc = S::combine(acc, S::mul(v1, x1)); acc = S::combine(acc, S::mul(v2, x2)); acc = S::combine(acc, S::mul(v3, x3));
         }
-        for (; k < c.k1; k += WG) acc += stream_load<NT>(values + k) * x[stream_load<NT>(colids + k)];
-        acc = wave_sum(acc);
+        for (; k < c.k1; k += WG) acc = S::combine(acc, S::mul(stream_load<NT>(values + k), x[stream_load<NT>(colids + k)]));
+        acc = wave_sum<S>(acc);
         if ((tid & 63) == 0) prod[tid >> 6] = acc;
         __syncthreads();
-        if (tid == 0) partials[c.slot] = (prod[0] + prod[1]) + (prod[2] + prod[3]);
+        if (tid == 0) partials[c.slot] = S::combine(S::combine(prod[0], prod[1]), S::combine(prod[2], prod[3]));
         return;
     }
 
@@ -123,7 +135,7 @@ __global__ __launch_bounds__(WG) void spmv_csr_adaptive_kernel(
             val[i] = stream_load<NT>(values + k0 + j);
         }
 #pragma unroll
-        for (int i = 0; i < UNROLL; ++i) val[i] = val[i] * x[cidx[i]];
+        for (int i = 0; i < UNROLL; ++i) val[i] = S::mul(val[i], x[cidx[i]]);
 #pragma unroll
         for (int i = 0; i < UNROLL; ++i) prod[i * WG + tid] = val[i];   // slots >= nnzb are written but never read
     }
@@ -140,35 +152,36 @@ __global__ __launch_bounds__(WG) void spmv_csr_adaptive_kernel(
         __syncthreads();
         for (int r = tid; r < nrows; r += WG) {
             const int a = rp[r] - k0, b = rp[r + 1] - k0;
-            if (b - a > kLaneRowMax) { const int h = atomicAdd(&n_heavy, 1); if (h < TILE_NNZ / kLaneRowMax) heavy[h] = r; else { double s = 0.0; for (int j = a; j < b; ++j) s += prod[j]; store_y(y, r0 + r, s, alpha, beta); } continue; }
-            double s = 0.0;
-            for (int j = a; j < b; ++j) s += prod[j];
-            store_y(y, r0 + r, s, alpha, beta);
+            if (b - a > kLaneRowMax) { const int h = atomicAdd(&n_heavy, 1); if (h < TILE_NNZ / kLaneRowMax) heavy[h] = r; else { double s = S::identity(); for (int j = a; j < b; ++j) s = S::combine(s, prod[j]); store_y<S>(y, r0 + r, s, alpha, beta); } continue; }
+            double s = S::identity();
+            for (int j = a; j < b; ++j) s = S::combine(s, prod[j]);
+            store_y<S>(y, r0 + r, s, alpha, beta);
         }
         __syncthreads();
         const int nh = min(n_heavy, TILE_NNZ / kLaneRowMax);        // (no more such rows fit a block; the guard above is for safety)
         for (int h = tid >> 6; h < nh; h += WG / 64) {              // one wavefront per heavy row: strided partial sums, then a shuffle reduction
             const int r = heavy[h], a = rp[r] - k0, b = rp[r + 1] - k0;
-            double s = 0.0;
-            for (int j = a + (tid & 63); j < b; j += 64) s += prod[j];
-            s = wave_sum(s);
-            if ((tid & 63) == 0) store_y(y, r0 + r, s, alpha, beta);
+            double s = S::identity();
+            for (int j = a + (tid & 63); j < b; j += 64) s = S::combine(s, prod[j]);
+            s = wave_sum<S>(s);
+            if ((tid & 63) == 0) store_y<S>(y, r0 + r, s, alpha, beta);
         }
     } else {
         // tpr lanes per row (power of two, <= 64, tpr·nrows <= WG), strided partials + shuffle reduction
         int tpr = 64;
         while (tpr * nrows > WG) tpr >>= 1;
         const int g = tid / tpr, sub = tid & (tpr - 1);
-        double s = 0.0;
+        double s = S::identity();                                 // (groups with g >= nrows hold the identity)
         if (g < nrows) {
             const int a = rp[g] - k0, b = rp[g + 1] - k0;
-            for (int j = a + sub; j < b; j += tpr) s += prod[j];
+            for (int j = a + sub; j < b; j += tpr) s = S::combine(s, prod[j]);
         }
-        for (int off = tpr >> 1; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if (g < nrows && sub == 0) store_y(y, r0 + g, s, alpha, beta);
+        for (int off = tpr >> 1; off > 0; off >>= 1) s = S::combine(s, __shfl_down(s, off, 64));
+        if (g < nrows && sub == 0) store_y<S>(y, r0 + g, s, alpha, beta);
     }
 }
 
+template <class S>
 __global__ void spmv_long_fixup_kernel(const LongRow *__restrict__ lrows, int n_long,
                                        const double *__restrict__ partials, double *__restrict__ y,
                                        double alpha, double beta)
@@ -176,9 +189,9 @@ __global__ void spmv_long_fixup_kernel(const LongRow *__restrict__ lrows, int n_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_long) return;
     const LongRow lr = lrows[i];
-    double s = 0.0;
-    for (int j = 0; j < lr.nslots; ++j) s += partials[lr.slot0 + j];
-    store_y(y, lr.row, s, alpha, beta);
+    double s = S::identity();
+    for (int j = 0; j < lr.nslots; ++j) s = S::combine(s, partials[lr.slot0 + j]);
+    store_y<S>(y, lr.row, s, alpha, beta);
 }
 
 // ---- diagonal-structured matrices (stencils, banded): the index-free path.
@@ -199,7 +212,7 @@ struct DiaOffsets { int off[kMaxDiags]; };
 // profiles/r03_ab_lap7_walks.txt) — the kernel is not bound by the bytes that cross the fabric — and were removed in round 4. Likewise the switch back to one
 // row per lane (two rows per lane: −4 % / −10 %, profiles/r03, tools history).
 
-template <int ND, bool NT>
+template <int ND, bool NT, class S>
 __global__ __launch_bounds__(WG) void spmv_dia_kernel(int rows, int cols, int nd, DiaOffsets offs, long long ld, const double *__restrict__ dia,
                                                        const unsigned *__restrict__ mask, const double *__restrict__ x, double *__restrict__ y,
                                                        double alpha, double beta, int blocks_per_xcd, int row0 /* first row of this launch */)
@@ -218,11 +231,11 @@ __global__ __launch_bounds__(WG) void spmv_dia_kernel(int rows, int cols, int nd
             const int c = min(max(row + offs.off[d], 0), cols - 1);       // absent entries read a clamped (unused) position
             xv[d] = x[c];
         }
-    double s = 0.0;
+    double s = S::identity();
 #pragma unroll
     for (int d = 0; d < ND; ++d)
-        if (d < nd && ((m >> d) & 1u)) s += v[d] * xv[d];
-    store_y(y, row, s, alpha, beta);
+        if (d < nd && ((m >> d) & 1u)) s = S::combine(s, S::mul(v[d], xv[d]));
+    store_y<S>(y, row, s, alpha, beta);
 }
 
 // Two consecutive rows per lane: the diagonal values, the masks and y move as 16-byte / 8-byte accesses per lane instead of 8 / 4 (the memory pipeline's
@@ -230,7 +243,7 @@ __global__ __launch_bounds__(WG) void spmv_dia_kernel(int rows, int cols, int nd
 // has at most 16 diagonals (registers); the last lane of an odd row count takes the one-row path above through `rows2`.
 typedef double dia_double2 __attribute__((ext_vector_type(2)));
 typedef unsigned dia_uint2 __attribute__((ext_vector_type(2)));
-template <int ND, bool NT>
+template <int ND, bool NT, class S>
 __global__ __launch_bounds__(WG) void spmv_dia2_kernel(int rows2 /* even part of the row count */, int cols, int nd, DiaOffsets offs, long long ld, const double *__restrict__ dia,
                                                         const unsigned *__restrict__ mask, const double *__restrict__ x, double *__restrict__ y,
                                                         double alpha, double beta, int blocks_per_xcd)
@@ -251,15 +264,21 @@ __global__ __launch_bounds__(WG) void spmv_dia2_kernel(int rows2 /* even part of
             x0[d] = x[min(max(c, 0), cols - 1)];
             x1[d] = x[min(max(c + 1, 0), cols - 1)];
         }
-    double s0 = 0.0, s1 = 0.0;
+    double s0 = S::identity(), s1 = S::identity();
 #pragma unroll
     for (int d = 0; d < ND; ++d)
         if (d < nd) {
-            if ((m[0] >> d) & 1u) s0 += v[d][0] * x0[d];
-            if ((m[1] >> d) & 1u) s1 += v[d][1] * x1[d];
+            if ((m[0] >> d) & 1u) s0 = S::combine(s0, S::mul(v[d][0], x0[d]));
+            if ((m[1] >> d) & 1u) s1 = S::combine(s1, S::mul(v[d][1], x1[d]));
         }
     dia_double2 out;
-    if (beta == 0.0) { out[0] = alpha * s0; out[1] = alpha * s1; }
+    if constexpr (!g4s::semiring::is_plus_times<S>) {
+        if (beta == 0.0) { out[0] = s0; out[1] = s1; }
+        else {
+            const dia_double2 old = *reinterpret_cast<const dia_double2 *>(y + row);
+            out[0] = S::combine(s0, S::normalize(old[0])); out[1] = S::combine(s1, S::normalize(old[1]));
+        }
+    } else if (beta == 0.0) { out[0] = alpha * s0; out[1] = alpha * s1; }
     else {
         const dia_double2 old = *reinterpret_cast<const dia_double2 *>(y + row);
         out[0] = alpha * s0 + beta * old[0]; out[1] = alpha * s1 + beta * old[1];
@@ -808,16 +827,19 @@ int g4s_csr_build_stream_plan(g4s_csr_t A)
     return G4S_OK;
 }
 
-G4S_API g4s_status g4s_spmv(g4s_csr_t A, const double *x_dev, double *y_dev, double alpha, double beta, void *stream)
+namespace {
+// The launches of one product on the handle's path, for one value policy (PlusTimes: g4s_spmv; the others: g4s_spmv_semiring, alpha = 1, beta = 0 or 1).
+template <class S>
+int spmv_launch(g4s_csr_s *A, const double *x_dev, double *y_dev, double alpha, double beta, hipStream_t s)
 {
-    G4S_REQUIRE(A, "NULL handle");
-    if (A->rows == 0) return G4S_OK;
-    G4S_REQUIRE(y_dev, "y is NULL");
-    G4S_REQUIRE(x_dev || A->nnz == 0, "x is NULL");
-    G4S_REQUIRE((const void *)x_dev != (const void *)y_dev, "x and y must not alias");
-    hipStream_t s = g4s::as_stream(stream);
-    if (A->pb) return g4s::pb_spmv(A->pb, x_dev, y_dev, alpha, beta, s);
-    if (A->bcsr) return g4s::bcsr_spmv(A->bcsr, x_dev, y_dev, alpha, beta, s);
+    if (A->pb) {
+        if constexpr (g4s::semiring::is_plus_times<S>) return g4s::pb_spmv(A->pb, x_dev, y_dev, alpha, beta, s);
+        else return g4s::pb_spmv_semiring(A->pb, x_dev, y_dev, S::kFlag, beta != 0.0, s);
+    }
+    if (A->bcsr) {
+        if constexpr (g4s::semiring::is_plus_times<S>) return g4s::bcsr_spmv(A->bcsr, x_dev, y_dev, alpha, beta, s);
+        else return g4s::bcsr_spmv_semiring(A->bcsr, x_dev, y_dev, S::kFlag, beta != 0.0, s);
+    }
     if (A->d_dia) {
         // two rows per lane where it applies (≤ 16 diagonals, y 16-byte aligned): the even part of the rows; an odd last row by the one-row kernel
         const bool two = A->dia_nd <= 16 && (reinterpret_cast<uintptr_t>(y_dev) & 15u) == 0 && A->rows >= 2;
@@ -827,8 +849,8 @@ G4S_API g4s_status g4s_spmv(g4s_csr_t A, const double *x_dev, double *y_dev, dou
             const dim3 grid((unsigned)(per_xcd * g4s::kXcds)), block(WG);
 #define G4S_DIA2_LAUNCH(ND)                                                                                                                                           \
     do {                                                                                                                                                          \
-        if (A->use_nt) hipLaunchKernelGGL((spmv_dia2_kernel<ND, true>), grid, block, 0, s, rows2, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd);  \
-        else hipLaunchKernelGGL((spmv_dia2_kernel<ND, false>), grid, block, 0, s, rows2, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd);           \
+        if (A->use_nt) hipLaunchKernelGGL((spmv_dia2_kernel<ND, true, S>), grid, block, 0, s, rows2, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd);  \
+        else hipLaunchKernelGGL((spmv_dia2_kernel<ND, false, S>), grid, block, 0, s, rows2, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd);           \
     } while (0)
             if (A->dia_nd <= 8) G4S_DIA2_LAUNCH(8);
             else G4S_DIA2_LAUNCH(16);
@@ -841,8 +863,8 @@ G4S_API g4s_status g4s_spmv(g4s_csr_t A, const double *x_dev, double *y_dev, dou
             const dim3 grid((unsigned)(per_xcd * g4s::kXcds)), block(WG);
 #define G4S_DIA_LAUNCH(ND)                                                                                                                                            \
     do {                                                                                                                                                          \
-        if (A->use_nt) hipLaunchKernelGGL((spmv_dia_kernel<ND, true>), grid, block, 0, s, A->rows, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd, tail0);  \
-        else hipLaunchKernelGGL((spmv_dia_kernel<ND, false>), grid, block, 0, s, A->rows, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd, tail0);           \
+        if (A->use_nt) hipLaunchKernelGGL((spmv_dia_kernel<ND, true, S>), grid, block, 0, s, A->rows, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd, tail0);  \
+        else hipLaunchKernelGGL((spmv_dia_kernel<ND, false, S>), grid, block, 0, s, A->rows, A->cols, A->dia_nd, A->dia_offs, A->dia_ld, A->d_dia, A->d_dia_mask, x_dev, y_dev, alpha, beta, per_xcd, tail0);           \
     } while (0)
             if (A->dia_nd <= 8) G4S_DIA_LAUNCH(8);
             else if (A->dia_nd <= 16) G4S_DIA_LAUNCH(16);
@@ -855,31 +877,55 @@ G4S_API g4s_status g4s_spmv(g4s_csr_t A, const double *x_dev, double *y_dev, dou
     const int grid = A->chunks_pad + A->stream_per_xcd * g4s::kXcds;
     if (grid > 0) {
         if (A->use_nt)
-            hipLaunchKernelGGL(spmv_csr_adaptive_kernel<true>, dim3(grid), dim3(WG), 0, s, A->d_rowptr, A->d_colids, A->d_values,
+            hipLaunchKernelGGL((spmv_csr_adaptive_kernel<true, S>), dim3(grid), dim3(WG), 0, s, A->d_rowptr, A->d_colids, A->d_values,
                                x_dev, y_dev, A->d_blocks, A->n_stream, A->xcd_runs ? A->stream_per_xcd : 0, A->d_chunks, A->n_chunks,
                                A->chunks_pad, A->d_partials, alpha, beta);
         else
-            hipLaunchKernelGGL(spmv_csr_adaptive_kernel<false>, dim3(grid), dim3(WG), 0, s, A->d_rowptr, A->d_colids, A->d_values,
+            hipLaunchKernelGGL((spmv_csr_adaptive_kernel<false, S>), dim3(grid), dim3(WG), 0, s, A->d_rowptr, A->d_colids, A->d_values,
                                x_dev, y_dev, A->d_blocks, A->n_stream, A->xcd_runs ? A->stream_per_xcd : 0, A->d_chunks, A->n_chunks,
                                A->chunks_pad, A->d_partials, alpha, beta);
         G4S_HIP_TRY(hipGetLastError());
     }
     if (A->n_long > 0) {
-        hipLaunchKernelGGL(spmv_long_fixup_kernel, dim3((A->n_long + 255) / 256), dim3(256), 0, s, A->d_long_rows, A->n_long,
+        hipLaunchKernelGGL(spmv_long_fixup_kernel<S>, dim3((A->n_long + 255) / 256), dim3(256), 0, s, A->d_long_rows, A->n_long,
                            A->d_partials, y_dev, alpha, beta);
         G4S_HIP_TRY(hipGetLastError());
     }
     return G4S_OK;
 }
+} // namespace
 
-G4S_API g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids,
-                                        const double *values, const double *x, double *y,
-                                        double alpha, double beta, unsigned flags)
+G4S_API g4s_status g4s_spmv(g4s_csr_t A, const double *x_dev, double *y_dev, double alpha, double beta, void *stream)
 {
-    G4S_REQUIRE(rows >= 0 && cols >= 0, "negative dimension");
-    G4S_REQUIRE(rowptr, "rowptr is NULL");
-    if (rows == 0) return G4S_OK;
-    G4S_REQUIRE(y, "y is NULL");
+    G4S_REQUIRE(A, "NULL handle");
+    if (A->rows == 0) return G4S_OK;
+    G4S_REQUIRE(y_dev, "y is NULL");
+    G4S_REQUIRE(x_dev || A->nnz == 0, "x is NULL");
+    G4S_REQUIRE((const void *)x_dev != (const void *)y_dev, "x and y must not alias");
+    return spmv_launch<PlusTimes>(A, x_dev, y_dev, alpha, beta, g4s::as_stream(stream));
+}
+
+// y := A ⊗ x or y ⊕ (A ⊗ x) over a semiring (include/g4s.h): the kernels of g4s_spmv, instantiated for the policy the flags select; plus-times IS g4s_spmv.
+G4S_API g4s_status g4s_spmv_semiring(g4s_csr_t A, const double *x_dev, double *y_dev, unsigned flags, void *stream)
+{
+    G4S_REQUIRE((flags & ~(G4S_SEMIRING_MASK | G4S_SPMV_ACCUMULATE)) == 0u, "g4s_spmv_semiring: flags other than G4S_SEMIRING_* | G4S_SPMV_ACCUMULATE");
+    G4S_REQUIRE(A, "NULL handle");
+    if (A->rows == 0) return G4S_OK;
+    G4S_REQUIRE(y_dev, "y is NULL");
+    G4S_REQUIRE(x_dev || A->nnz == 0, "x is NULL");
+    G4S_REQUIRE((const void *)x_dev != (const void *)y_dev, "x and y must not alias");
+    const double beta = (flags & G4S_SPMV_ACCUMULATE) ? 1.0 : 0.0;
+    const hipStream_t s = g4s::as_stream(stream);
+    return g4s::semiring::dispatch(flags, [&](auto policy) { return spmv_launch<decltype(policy)>(A, x_dev, y_dev, 1.0, beta, s); });
+}
+
+namespace {
+// The one-shot forms: a handle on the streaming path (unless G4S_SPMV_BLOCKED), one product, synchronous. flags: G4S_DEVICE_POINTERS and the path flags.
+// `product` runs the product on the handle and device x / y; read_y: y is an input (uploaded first with host pointers).
+template <class Product>
+int one_shot(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids, const double *values, const double *x, double *y, bool read_y,
+             unsigned flags, Product &&product)
+{
     const bool dev = (flags & G4S_DEVICE_POINTERS) != 0;
     int32_t nnz32 = 0;
     if (dev) G4S_HIP_TRY(hipMemcpy(&nnz32, rowptr + rows, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -891,7 +937,7 @@ G4S_API g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_
     G4S_TRY(g4s_csr_create(&A, rows, cols, nnz32, rowptr, colids, values, flags));
     int st = G4S_OK;
     if (dev) {
-        st = g4s_spmv(A, x, y, alpha, beta, nullptr);
+        st = product(A, x, y);
         if (st == G4S_OK && hipStreamSynchronize(nullptr) != hipSuccess) st = g4s::set_error(G4S_ERR_HIP, "synchronize failed");
     } else {
         double *dx = nullptr, *dy = nullptr;
@@ -899,10 +945,10 @@ G4S_API g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_
             g4s::device_malloc((void **)&dy, sizeof(double) * (size_t)rows) != hipSuccess) {
             st = g4s::set_error(G4S_ERR_NOMEM, "hipMalloc of x/y failed");
         } else if ((cols && hipMemcpy(dx, x, sizeof(double) * (size_t)cols, hipMemcpyHostToDevice) != hipSuccess) ||
-                   (beta != 0.0 && hipMemcpy(dy, y, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess)) {
+                   (read_y && hipMemcpy(dy, y, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess)) {
             st = g4s::set_error(G4S_ERR_HIP, "H2D copy of x/y failed");
         } else {
-            st = g4s_spmv(A, dx, dy, alpha, beta, nullptr);
+            st = product(A, dx, dy);
             if (st == G4S_OK && hipMemcpy(y, dy, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
                 st = g4s::set_error(G4S_ERR_HIP, "D2H copy of y failed");
         }
@@ -911,4 +957,34 @@ G4S_API g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_
     }
     g4s_csr_destroy(A);
     return st;
+}
+} // namespace
+
+G4S_API g4s_status g4s_spmv_semiring_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids, const double *values,
+                                                 const double *x, double *y, unsigned flags)
+{
+    constexpr unsigned kPathFlags = G4S_DEVICE_POINTERS | G4S_SPMV_BLOCKED | G4S_SPMV_STREAM;
+    G4S_REQUIRE((flags & ~(kPathFlags | G4S_SEMIRING_MASK | G4S_SPMV_ACCUMULATE)) == 0u,
+                "g4s_spmv_semiring_csr_i32_f64: flags other than G4S_SEMIRING_* | G4S_SPMV_ACCUMULATE | pointer kind | G4S_SPMV_BLOCKED / G4S_SPMV_STREAM");
+    G4S_REQUIRE(rows >= 0 && cols >= 0, "negative dimension");
+    G4S_REQUIRE(rowptr, "rowptr is NULL");
+    if (rows == 0) return G4S_OK;
+    G4S_REQUIRE(y, "y is NULL");
+    G4S_REQUIRE(x || cols == 0, "x is NULL");
+    G4S_REQUIRE((const void *)x != (const void *)y, "x and y must not alias");
+    const unsigned op = flags & (G4S_SEMIRING_MASK | G4S_SPMV_ACCUMULATE);
+    return one_shot(rows, cols, rowptr, colids, values, x, y, (flags & G4S_SPMV_ACCUMULATE) != 0, flags & kPathFlags,
+                    [op](g4s_csr_t A, const double *dx, double *dy) { return g4s_spmv_semiring(A, dx, dy, op, nullptr); });
+}
+
+G4S_API g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids,
+                                        const double *values, const double *x, double *y,
+                                        double alpha, double beta, unsigned flags)
+{
+    G4S_REQUIRE(rows >= 0 && cols >= 0, "negative dimension");
+    G4S_REQUIRE(rowptr, "rowptr is NULL");
+    if (rows == 0) return G4S_OK;
+    G4S_REQUIRE(y, "y is NULL");
+    return one_shot(rows, cols, rowptr, colids, values, x, y, beta != 0.0, flags,
+                    [alpha, beta](g4s_csr_t A, const double *dx, double *dy) { return g4s_spmv(A, dx, dy, alpha, beta, nullptr); });
 }

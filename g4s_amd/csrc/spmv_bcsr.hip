@@ -12,6 +12,7 @@
 // row is bit-identical to the oracle (the CSR kernel reduces rows this long with several lanes and shuffles).
 #include "common.hpp"
 #include "spmv_bcsr.hpp"
+#include "semiring.hpp"
 #include <algorithm>
 #include <memory>
 #include <vector>
@@ -73,7 +74,8 @@ __global__ void bcsr_fill_kernel(int rows, int b, const int32_t *__restrict__ ro
 
 struct Item { int brow0, nbrows, blk0, nblk; };   // a run of whole block-rows: ≤ kTile entries, ≤ kMaxBrows block-rows
 
-template <int B, bool NT>
+// S: the value policy (semiring.hpp) — PlusTimes for g4s_spmv, spelled as before; the others for g4s_spmv_semiring (beta != 0: y ⊕ the row, alpha unused).
+template <int B, bool NT, class S>
 __global__ __launch_bounds__(kWG) void spmv_bcsr_kernel(const Item *__restrict__ items, const int32_t *__restrict__ rowptr /* of the CSR matrix: block-row n starts at block rowptr[B·n] / B² */,
                                                          const int32_t *__restrict__ bcol, const double *__restrict__ bval, const double *__restrict__ x,
                                                          double *__restrict__ y, double alpha, double beta)
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(kWG) void spmv_bcsr_kernel(const Item *__restrict__
             col[u] = bcol[it.blk0 + blk] * B + (e - blk * BB) % B;
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) v[u] = v[u] * x[col[u]];
+        for (int u = 0; u < kUnroll; ++u) v[u] = S::mul(v[u], x[col[u]]);
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) prod[u * kWG + tid] = v[u];   // slots past ne are written, never read
     }
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(kWG) void spmv_bcsr_kernel(const Item *__restrict__
     for (int r = tid; r < it.nbrows * B; r += kWG) {
         const int n = r / B, d = r - n * B;
         const int j0 = first_blk[n], j1 = first_blk[n + 1];
-        double s = 0.0;
+        double s = S::identity();
         int j = j0;
         for (; j + 4 <= j1; j += 4) {                              // four blocks' products read together, then added in order: the chain waits for LDS once per 4·B adds
             double t[4 * B];
@@ -116,14 +118,15 @@ __global__ __launch_bounds__(kWG) void spmv_bcsr_kernel(const Item *__restrict__
 #pragma unroll
                 for (int c = 0; c < B; ++c) t[q * B + c] = prod[(j + q) * BB + d * B + c];
 #pragma unroll
-            for (int q = 0; q < 4 * B; ++q) s += t[q];
+            for (int q = 0; q < 4 * B; ++q) s = S::combine(s, t[q]);
         }
         for (; j < j1; ++j) {
 #pragma unroll
-            for (int c = 0; c < B; ++c) s += prod[j * BB + d * B + c];
+            for (int c = 0; c < B; ++c) s = S::combine(s, prod[j * BB + d * B + c]);
         }
         const int row = it.brow0 * B + r;
-        y[row] = beta == 0.0 ? alpha * s : alpha * s + beta * y[row];
+        if constexpr (g4s::semiring::is_plus_times<S>) y[row] = beta == 0.0 ? alpha * s : alpha * s + beta * y[row];
+        else y[row] = beta == 0.0 ? s : S::combine(s, S::normalize(y[row]));
     }
 }
 
@@ -200,14 +203,15 @@ void bcsr_destroy(BcsrPlan *P) { delete P; }
 long long bcsr_bytes(const BcsrPlan *P) { return P ? P->bytes : 0; }
 int bcsr_block(const BcsrPlan *P) { return P ? P->b : 0; }
 
-int bcsr_spmv(BcsrPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
+template <class S>
+static int bcsr_launch(BcsrPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
 {
     if (!P->n_items) return G4S_OK;
 
 #define G4S_BCSR_LAUNCH(B)                                                                                                                              \
     do {                                                                                                                                               \
-        if (P->use_nt) hipLaunchKernelGGL((spmv_bcsr_kernel<B, true>), dim3(P->n_items), dim3(kWG), 0, s, P->items.as<Item>(), P->d_rowptr, P->bcol.as<int32_t>(), P->bval.as<double>(), x, y, alpha, beta); \
-        else hipLaunchKernelGGL((spmv_bcsr_kernel<B, false>), dim3(P->n_items), dim3(kWG), 0, s, P->items.as<Item>(), P->d_rowptr, P->bcol.as<int32_t>(), P->bval.as<double>(), x, y, alpha, beta);         \
+        if (P->use_nt) hipLaunchKernelGGL((spmv_bcsr_kernel<B, true, S>), dim3(P->n_items), dim3(kWG), 0, s, P->items.as<Item>(), P->d_rowptr, P->bcol.as<int32_t>(), P->bval.as<double>(), x, y, alpha, beta); \
+        else hipLaunchKernelGGL((spmv_bcsr_kernel<B, false, S>), dim3(P->n_items), dim3(kWG), 0, s, P->items.as<Item>(), P->d_rowptr, P->bcol.as<int32_t>(), P->bval.as<double>(), x, y, alpha, beta);         \
     } while (0)
     if (P->b == 3) G4S_BCSR_LAUNCH(3);
     else if (P->b == 2) G4S_BCSR_LAUNCH(2);
@@ -215,6 +219,13 @@ int bcsr_spmv(BcsrPlan *P, const double *x, double *y, double alpha, double beta
 #undef G4S_BCSR_LAUNCH
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;
+}
+
+int bcsr_spmv(BcsrPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s) { return bcsr_launch<semiring::PlusTimes>(P, x, y, alpha, beta, s); }
+
+int bcsr_spmv_semiring(BcsrPlan *P, const double *x, double *y, unsigned sr_flag, bool accumulate, hipStream_t s)
+{
+    return semiring::dispatch(sr_flag, [&](auto policy) { return bcsr_launch<decltype(policy)>(P, x, y, 1.0, accumulate ? 1.0 : 0.0, s); });
 }
 
 } // namespace g4s

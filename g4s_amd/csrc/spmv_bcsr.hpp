@@ -12,4 +12,5 @@ void bcsr_destroy(BcsrPlan *plan);
 long long bcsr_bytes(const BcsrPlan *plan);
 int bcsr_block(const BcsrPlan *plan);
 int bcsr_spmv(BcsrPlan *plan, const double *x, double *y, double alpha, double beta, hipStream_t stream);
+int bcsr_spmv_semiring(BcsrPlan *plan, const double *x, double *y, unsigned semiring, bool accumulate, hipStream_t stream);   // G4S_SEMIRING_* other than plus-times
 } // namespace g4s

@@ -17,10 +17,12 @@
 // numbered consecutively on both sides and one per-cell offset maps a producer micro-run to its consumer slot.
 // The regrouping is built once per matrix (g4s_csr_create) with the library's own radix sort and scan (prims.hpp; round 5 — rocPRIM was the last vendor-library
 // call in the product); the values are stored a second time in producer order. Sums are accumulated by LDS atomics: equal to the oracle within the fp64 tolerance, not bit for bit,
-// and the last bits may differ from run to run.
+// and the last bits may differ from run to run. The semiring forms (g4s_spmv_semiring: min-plus, max-plus, or-and) fold with ds_min/max_f64 instead and are
+// exact and deterministic: min and max do not depend on the order of arrival.
 #include "common.hpp"
 #include "spmv_pb.hpp"
 #include "prims.hpp"
+#include "semiring.hpp"
 #include <algorithm>
 #include <memory>
 #include <vector>
@@ -333,12 +335,21 @@ __device__ __forceinline__ int row_down_i(int v)
 {
     return __builtin_amdgcn_update_dpp(0, v, 0x100 + SHIFT, 0xF, 0xF, true);
 }
-template <int SHIFT>
+// The fp64 form reads 0.0 past the row for plus-times. For the other semirings 0.0 is not neutral (it would enter a min as a real value): lanes whose
+// source is past the row keep `old` instead (bound_ctrl off), the halves of Sr::identity().
+template <int SHIFT, class Sr>
 __device__ __forceinline__ double row_down_d(double v)
 {
     const long long b = __double_as_longlong(v);
-    const int lo = row_down_i<SHIFT>((int)(b & 0xFFFFFFFFll)), hi = row_down_i<SHIFT>((int)(b >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+    if constexpr (semiring::is_plus_times<Sr>) {
+        const int lo = row_down_i<SHIFT>((int)(b & 0xFFFFFFFFll)), hi = row_down_i<SHIFT>((int)(b >> 32));
+        return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+    } else {
+        const long long o = __double_as_longlong(Sr::identity());
+        const int lo = __builtin_amdgcn_update_dpp((int)(o & 0xFFFFFFFFll), (int)(b & 0xFFFFFFFFll), 0x100 + SHIFT, 0xF, 0xF, false);
+        const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(b >> 32), 0x100 + SHIFT, 0xF, 0xF, false);
+        return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+    }
 }
 
 // Producer: one lane per PAIR of consecutive entries (unit-stride 4-byte / 16-byte loads), four lanes per 8-entry span, sixteen
@@ -351,14 +362,17 @@ __device__ __forceinline__ double row_down_d(double v)
 #endif
 constexpr int kPairUnroll = G4S_PB_PAIR_UNROLL;
 
-template <int W>
+// Sr: the value policy (semiring.hpp). PlusTimes is g4s_spmv, spelled as before. For the other semirings a pad's product must be the identity, not 0:
+// the word behind the band of x holds Sr::fill() (+inf / −inf / 0), so that a pad (value 0.0) multiplies to it, and dead lanes, the open prefix of a pair
+// that opens a micro-run and the DPP lanes past the row hold the identity.
+template <int W, class Sr>
 __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerItem *__restrict__ items, int cols, int H, const double *__restrict__ hot_x,
                                                                   const unsigned short *__restrict__ p_lcol, const double *__restrict__ p_val,
                                                                   const int *__restrict__ mbase /* consumer slot of each span's first micro-run */,
                                                                   const double *__restrict__ x, double *__restrict__ prod)
 {
     extern __shared__ double pb_lds[];
-    double *xs = pb_lds;                                           // W doubles of x, then the zero word the pads point at
+    double *xs = pb_lds;                                           // W doubles of x, then the word the pads point at (0.0 for plus-times: the zero word)
     const ProducerItem it = items[blockIdx.x];
     const bool hot = it.cband < H;                                 // hot bands read the gathered copy; the others a natural W-column slice of x
     const int c0 = hot ? it.cband * W : (it.cband - H) * W;
@@ -402,7 +416,7 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
         }
     }
 #endif
-    if (threadIdx.x == 0) xs[W] = 0.0;
+    if (threadIdx.x == 0) xs[W] = Sr::fill();
     __syncthreads();
     const int g = (int)threadIdx.x & 60;                           // first lane of this lane's span in the wave's ballots
     const unsigned below = (1u << (threadIdx.x & 3)) - 1u;         // the lanes of the span before this one
@@ -424,27 +438,32 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
             const int p = base + u * kPbThreads;
             const bool live = p < p_end;                           // whole spans are live or not (p_end is a multiple of 4)
             const unsigned l0 = lc[u] & 0xFFFFu, l1 = lc[u] >> 16;
-            const double p0 = live ? v[u][0] * xs[l0 & kLocalMask] : 0.0;   // a pad reads the zero word xs[W]
-            const double p1 = live ? v[u][1] * xs[l1 & kLocalMask] : 0.0;
+            const double p0 = live ? Sr::mul(v[u][0], xs[l0 & kLocalMask]) : Sr::identity();   // a pad reads the word xs[W]
+            const double p1 = live ? Sr::mul(v[u][1], xs[l1 & kLocalMask]) : Sr::identity();
             const bool h0 = live && (l0 & kHeadBit), h1 = live && (l1 & kHeadBit);
             // heads of the span's earlier lanes: bit j of the nibbles = lane g + j's first / second entry is a head
             const unsigned n0 = (unsigned)(__ballot(h0) >> g) & 0xFu, n1 = (unsigned)(__ballot(h1) >> g) & 0xFu;
             const int before = __popc(n0 & below) + __popc(n1 & below);
             // open prefix: the part of this pair that continues a micro-run begun in an earlier lane of the span
-            const double op = h0 ? 0.0 : (h1 ? p0 : p0 + p1);
+            const double op = h0 ? Sr::identity() : (h1 ? p0 : Sr::combine(p0, p1));
             const bool closed = h0 | h1;
             // S_j = op_j + (closed_j ? 0 : S_{j+1}) over the 16 lanes of the window, by doubling; ext = S of the next lane = what the
             // following lanes add to the micro-run that contains this pair's last entry
             double S = op;
             int f = (int)closed;
-#define G4S_PB_SCAN_STEP(D) { const double sv = row_down_d<D>(S); const int sf = row_down_i<D>(f); if (!f) S += sv; f |= sf; }
+#define G4S_PB_SCAN_STEP(D) { const double sv = row_down_d<D, Sr>(S); const int sf = row_down_i<D>(f); if (!f) S = Sr::combine(S, sv); f |= sf; }
             G4S_PB_SCAN_STEP(1) G4S_PB_SCAN_STEP(2) G4S_PB_SCAN_STEP(4) G4S_PB_SCAN_STEP(8)
 #undef G4S_PB_SCAN_STEP
-            const double ext = row_down_d<1>(S);
+            const double ext = row_down_d<1, Sr>(S);
             if (live && closed) {
                 const int d0 = mb[u] + before;
-                if (h0) prod[d0] = h1 ? p0 : p0 + p1 + ext;
-                if (h1) prod[d0 + (int)h0] = p1 + ext;
+                if constexpr (semiring::is_plus_times<Sr>) {                 // (spelled out: the combine form schedules the stores differently)
+                    if (h0) prod[d0] = h1 ? p0 : p0 + p1 + ext;
+                    if (h1) prod[d0 + (int)h0] = p1 + ext;
+                } else {
+                    if (h0) prod[d0] = h1 ? p0 : Sr::combine(Sr::combine(p0, p1), ext);
+                    if (h1) prod[d0 + (int)h0] = Sr::combine(p1, ext);
+                }
             }
         }
         if (more) {
@@ -455,8 +474,9 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
 }
 
 // One launch ahead of the producer: blocks [0, n_split·⌈W/256⌉) pre-scale y for the row bands whose sums arrive from several consumer
-// workgroups (those add into y with atomics), the remaining blocks gather the x values of the hot columns into hot_x.
-template <int W>
+// workgroups (those add into y with atomics), the remaining blocks gather the x values of the hot columns into hot_x. Semirings: the split bands start from
+// the identity, or from y itself (normalised for or-and) under ACCUMULATE (beta != 0).
+template <int W, class Sr>
 __global__ void pb_prepare_kernel(int n_split, const int *__restrict__ split_bands, int rows, double *__restrict__ y, double beta,
                                   int nhot, const int *__restrict__ hot_cols, const double *__restrict__ x, double *__restrict__ hot_x)
 {
@@ -465,7 +485,11 @@ __global__ void pb_prepare_kernel(int n_split, const int *__restrict__ split_ban
     if (b < n_split * kBlocksPerBand) {
         const int local = (b % kBlocksPerBand) * 256 + (int)threadIdx.x;
         const int i = split_bands[b / kBlocksPerBand] * W + local;
-        if (local < W && i < rows) y[i] = beta == 0.0 ? 0.0 : beta * y[i];
+        if constexpr (semiring::is_plus_times<Sr>) {
+            if (local < W && i < rows) y[i] = beta == 0.0 ? 0.0 : beta * y[i];
+        } else {
+            if (local < W && i < rows) y[i] = beta == 0.0 ? Sr::identity() : Sr::normalize(y[i]);
+        }
     } else {
         const int r = (b - n_split * kBlocksPerBand) * 256 + (int)threadIdx.x;
         if (r < nhot) hot_x[r] = x[hot_cols[r]];
@@ -477,11 +501,15 @@ __global__ void pb_prepare_kernel(int n_split, const int *__restrict__ split_ban
 #endif
 constexpr int kPbUnroll = G4S_PB_CONS_UNROLL;   // consumer: groups of 4 consecutive slots per thread per iteration
 
-template <int W>
+// Semirings (Sr other than PlusTimes): the band of y starts from the identity, and the pad slots of a band — [band_end[rband], next multiple of 4): value 0
+// for local row 0, which a min or max would take for a real value — are read as the identity. Sums are folded with Sr::lds_acc / Sr::global_acc
+// (ds_min/max_f64, global_atomic_min/max_f64): exact, in any order of arrival. beta != 0: ACCUMULATE; alpha unused. band_end is not read for PlusTimes.
+template <int W, class Sr>
 __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerItem *__restrict__ items, int rows,
                                                                   const unsigned short *__restrict__ c_lrow, const double *__restrict__ prod,
-                                                                  double *__restrict__ y, double alpha, double beta)
+                                                                  double *__restrict__ y, double alpha, double beta, const int *__restrict__ band_end)
 {
+    constexpr bool kPlus = semiring::is_plus_times<Sr>;
     extern __shared__ double pb_lds[];
     double *ys = pb_lds;
     const ConsumerItem it = items[blockIdx.x];                     // [k0, k1): multiples of 4; pad slots carry 0 for local row 0
@@ -499,7 +527,9 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
             pb[u] = pb_stream_load(reinterpret_cast<const double2_t *>(prod + k + 2));
         }
     }
-    for (int i = threadIdx.x; i < W; i += kPbThreads) ys[i] = 0.0;
+    for (int i = threadIdx.x; i < W; i += kPbThreads) ys[i] = Sr::identity();
+    int bend = 0;                                                  // the band's real end: slots at or past it are pads
+    if constexpr (!kPlus) bend = band_end[it.rband];
     __syncthreads();
     for (; base < it.k1; base += STEP) {
         const bool more = base + STEP < it.k1;
@@ -517,6 +547,12 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
             const bool active = base + u * 4 * kPbThreads < it.k1;     // varies per lane in the tail wave of a band: the cross-lane part below runs
                                                                         // for the whole wave, lanes past the end contribute zeros
             double p[4] = {pa[u][0], pa[u][1], pb[u][0], pb[u][1]};
+            if constexpr (!kPlus) {
+                const int k = base + u * 4 * kPbThreads;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k + j >= bend) p[j] = Sr::identity();
+            }
             // Consecutive slots of one row (a hub row cut into many micro-runs inside a hot cell) would hit one LDS address from
             // every lane of the wave, and ds_add_f64 serialises same-address lanes. Equal neighbours are summed in registers
             // first; a wave whose 256 slots all belong to one row reduces across lanes and issues a single atomic.
@@ -524,17 +560,17 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
             const bool lane_uniform = r0_ == r3_ && lr[u][1] == r0_ && lr[u][2] == r0_;
             const unsigned first_row = (unsigned)__builtin_amdgcn_readfirstlane((int)r0_);
             if (__all(active && lane_uniform && r0_ == first_row)) {     // wave-uniform branch, every lane active: the shuffles read live registers
-                double t = (p[0] + p[1]) + (p[2] + p[3]);
+                double t = Sr::combine(Sr::combine(p[0], p[1]), Sr::combine(p[2], p[3]));
 #pragma unroll
-                for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-                if ((threadIdx.x & 63) == 0) atomicAdd(&ys[first_row], t);
+                for (int off = 32; off > 0; off >>= 1) t = Sr::combine(t, __shfl_down(t, off, 64));
+                if ((threadIdx.x & 63) == 0) Sr::lds_acc(&ys[first_row], t);
             } else if (active) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
-                    if (lr[u][j] == lr[u][j + 1]) { p[j + 1] += p[j]; p[j] = 0.0; }
+                    if (lr[u][j] == lr[u][j + 1]) { p[j + 1] = Sr::combine(p[j + 1], p[j]); p[j] = Sr::identity(); }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (p[j] != 0.0) atomicAdd(&ys[lr[u][j]], p[j]);
+                    if (p[j] != Sr::identity()) Sr::lds_acc(&ys[lr[u][j]], p[j]);
             }
         }
         if (more) {
@@ -560,7 +596,13 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
     for (int k = 0; k < kRowsPerThread; ++k) {
         const int r = r0 + (int)threadIdx.x + k * kPbThreads;
         if ((W % kPbThreads == 0 || (int)threadIdx.x + k * kPbThreads < W) && r < rows) {
-            if (it.split) {
+            if constexpr (!kPlus) {
+                if (it.split) {
+                    if (yv[k] != Sr::identity()) Sr::global_acc(&y[r], yv[k]);   // y holds the identity or the old y (pb_prepare_kernel)
+                } else {
+                    y[r] = beta == 0.0 ? yv[k] : Sr::combine(yv[k], Sr::normalize(yo[k]));
+                }
+            } else if (it.split) {
                 if (yv[k] != 0.0) atomicAdd(&y[r], alpha * yv[k]);  // y was pre-scaled by beta (pb_prepare_kernel)
             } else {
                 y[r] = beta == 0.0 ? alpha * yv[k] : alpha * yv[k] + beta * yo[k];
@@ -576,6 +618,7 @@ struct PbPlan {
     long long nnz = 0, micro_runs = 0;
     DevBuf p_lcol, p_val, mbase, c_lrow, prod, delta, pitems, citems, split_bands, hot_cols, hot_x;
     DevBuf p_src;                                                   // G4S_SPMV_UPDATABLE: CSR index of every producer slot
+    DevBuf band_end;                                                // RB ints: the first pad slot of each row band (semiring consumers)
     long long slots = 0;
     int n_pitems = 0, n_citems = 0, n_split = 0, H = 0;
     size_t lds_producer = 0, lds_consumer = 0;
@@ -598,7 +641,7 @@ static int pb_band_width()
     const int need = (int)sizeof(double) * (kBandWide + 1);
     if (lds < need) return kBandNarrow;
     // the runtime must also grant it to the kernels (pb_build sets the same attribute again for the plan)
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(pb_producer_kernel<kBandWide>), hipFuncAttributeMaxDynamicSharedMemorySize, need) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(pb_producer_kernel<kBandWide, semiring::PlusTimes>), hipFuncAttributeMaxDynamicSharedMemorySize, need) != hipSuccess) {
         (void)hipGetLastError();
         return kBandNarrow;
     }
@@ -768,7 +811,7 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     hipLaunchKernelGGL(pb_gather_kernel, dim3(grid_for(ncells + 1)), dim3(256), 0, nullptr, ncells + 1, d_soc.as<int>(), P->mbase.as<int>(), d_mstart.as<int>());
     G4S_HIP_TRY(hipMemcpy(mstart.data(), d_mstart.p, sizeof(int) * mstart.size(), hipMemcpyDeviceToHost));
     P->micro_runs = mstart[ncells];
-    std::vector<int> h_delta((size_t)ncells), bandC((size_t)RB + 1);
+    std::vector<int> h_delta((size_t)ncells), bandC((size_t)RB + 1), bandE((size_t)RB);
     long long totC = 0;
     for (int r = 0; r < RB; ++r) {
         totC = (totC + 3) & ~3ll;
@@ -778,11 +821,14 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
             h_delta[q] = (int)(totC - mstart[q]);
             totC += mstart[q + 1] - mstart[q];
         }
+        bandE[r] = (int)totC;                                        // the band's real end; [bandE[r], bandC[r + 1]) are pad slots
     }
     totC = (totC + 3) & ~3ll;
     bandC[RB] = (int)totC;
     G4S_TRY(P->delta.alloc(sizeof(int) * h_delta.size()));
     G4S_HIP_TRY(hipMemcpy(P->delta.p, h_delta.data(), sizeof(int) * h_delta.size(), hipMemcpyHostToDevice));
+    G4S_TRY(P->band_end.alloc(sizeof(int) * bandE.size()));
+    G4S_HIP_TRY(hipMemcpy(P->band_end.p, bandE.data(), sizeof(int) * bandE.size(), hipMemcpyHostToDevice));
     G4S_TRY(P->c_lrow.alloc(sizeof(unsigned short) * (size_t)(totC + 64)));
     G4S_TRY(P->prod.alloc(sizeof(double) * (size_t)(totC + 64)));
     G4S_HIP_TRY(hipMemset(P->c_lrow.p, 0, P->c_lrow.bytes));
@@ -829,13 +875,20 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     if (!pit.empty()) G4S_HIP_TRY(hipMemcpy(P->pitems.p, pit.data(), sizeof(ProducerItem) * pit.size(), hipMemcpyHostToDevice));
     if (!cit.empty()) G4S_HIP_TRY(hipMemcpy(P->citems.p, cit.data(), sizeof(ConsumerItem) * cit.size(), hipMemcpyHostToDevice));
     if (!split.empty()) G4S_HIP_TRY(hipMemcpy(P->split_bands.p, split.data(), sizeof(int) * split.size(), hipMemcpyHostToDevice));
-    const void *producer = W == kBandWide ? reinterpret_cast<const void *>(pb_producer_kernel<kBandWide>) : reinterpret_cast<const void *>(pb_producer_kernel<kBandNarrow>);
-    const void *consumer = W == kBandWide ? reinterpret_cast<const void *>(pb_consumer_kernel<kBandWide>) : reinterpret_cast<const void *>(pb_consumer_kernel<kBandNarrow>);
-    G4S_HIP_TRY(hipFuncSetAttribute(producer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_producer));
-    G4S_HIP_TRY(hipFuncSetAttribute(consumer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_consumer));
+    for (unsigned sr : {G4S_SEMIRING_PLUS_TIMES, G4S_SEMIRING_MIN_PLUS, G4S_SEMIRING_MAX_PLUS, G4S_SEMIRING_OR_AND}) {   // every policy's kernels of this band width
+        const int st = semiring::dispatch(sr, [&](auto policy) -> int {
+            using Sr = decltype(policy);
+            const void *producer = W == kBandWide ? reinterpret_cast<const void *>(pb_producer_kernel<kBandWide, Sr>) : reinterpret_cast<const void *>(pb_producer_kernel<kBandNarrow, Sr>);
+            const void *consumer = W == kBandWide ? reinterpret_cast<const void *>(pb_consumer_kernel<kBandWide, Sr>) : reinterpret_cast<const void *>(pb_consumer_kernel<kBandNarrow, Sr>);
+            G4S_HIP_TRY(hipFuncSetAttribute(producer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_producer));
+            G4S_HIP_TRY(hipFuncSetAttribute(consumer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->lds_consumer));
+            return G4S_OK;
+        });
+        if (st != G4S_OK) return st;
+    }
     G4S_HIP_TRY(hipDeviceSynchronize());
     P->bytes = (long long)(P->p_src.bytes + P->p_lcol.bytes + P->p_val.bytes + P->mbase.bytes + P->c_lrow.bytes + P->prod.bytes + P->delta.bytes +
-                           P->pitems.bytes + P->citems.bytes + P->split_bands.bytes + P->hot_cols.bytes + P->hot_x.bytes);
+                           P->pitems.bytes + P->citems.bytes + P->split_bands.bytes + P->hot_cols.bytes + P->hot_x.bytes + P->band_end.bytes);
     if (getenv("G4S_DEBUG"))
         fprintf(stderr, "g4s blocked SpMV plan: band %d, %d x %d bands (%d hot), nnz %lld, padded %lld, micro-runs %lld (%.3f per nonzero), %d producer / %d consumer items, %d split bands, %.2f GB\n",
                 W, CB, RB, H, nnz, totP, P->micro_runs, (double)P->micro_runs / (double)nnz, P->n_pitems, P->n_citems, P->n_split, P->bytes / 1e9);
@@ -857,27 +910,38 @@ int pb_update_values(PbPlan *P, const double *d_values, hipStream_t s)
     return G4S_OK;
 }
 
-template <int W>
+template <int W, class Sr>
 static void pb_launch(PbPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
 {
     if (P->n_split || P->H) {
         // split bands: one block per 256 rows of each band; hot columns: one per 256 of them (H·W of them, whole blocks either way)
         const int blocks = P->n_split * ((W + 255) / 256) + (P->H * W + 255) / 256;
-        hipLaunchKernelGGL(pb_prepare_kernel<W>, dim3(blocks), dim3(256), 0, s, P->n_split, P->split_bands.as<int>(), P->rows, y, beta,
+        hipLaunchKernelGGL((pb_prepare_kernel<W, Sr>), dim3(blocks), dim3(256), 0, s, P->n_split, P->split_bands.as<int>(), P->rows, y, beta,
                            P->H * W, P->hot_cols.as<int>(), x, P->hot_x.as<double>());
     }
     if (P->n_pitems)
-        hipLaunchKernelGGL(pb_producer_kernel<W>, dim3(P->n_pitems), dim3(kPbThreads), P->lds_producer, s, P->pitems.as<ProducerItem>(), P->cols, P->H, P->hot_x.as<double>(),
+        hipLaunchKernelGGL((pb_producer_kernel<W, Sr>), dim3(P->n_pitems), dim3(kPbThreads), P->lds_producer, s, P->pitems.as<ProducerItem>(), P->cols, P->H, P->hot_x.as<double>(),
                            P->p_lcol.as<unsigned short>(), P->p_val.as<double>(), P->mbase.as<int>(), x, P->prod.as<double>());
     if (P->n_citems)
-        hipLaunchKernelGGL(pb_consumer_kernel<W>, dim3(P->n_citems), dim3(kPbThreads), P->lds_consumer, s, P->citems.as<ConsumerItem>(), P->rows,
-                           P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta);
+        hipLaunchKernelGGL((pb_consumer_kernel<W, Sr>), dim3(P->n_citems), dim3(kPbThreads), P->lds_consumer, s, P->citems.as<ConsumerItem>(), P->rows,
+                           P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta, P->band_end.as<int>());
 }
 
 int pb_spmv(PbPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
 {
-    if (P->W == kBandWide) pb_launch<kBandWide>(P, x, y, alpha, beta, s);
-    else pb_launch<kBandNarrow>(P, x, y, alpha, beta, s);
+    if (P->W == kBandWide) pb_launch<kBandWide, semiring::PlusTimes>(P, x, y, alpha, beta, s);
+    else pb_launch<kBandNarrow, semiring::PlusTimes>(P, x, y, alpha, beta, s);
+    G4S_HIP_TRY(hipGetLastError());
+    return G4S_OK;
+}
+
+int pb_spmv_semiring(PbPlan *P, const double *x, double *y, unsigned sr_flag, bool accumulate, hipStream_t s)
+{
+    const double beta = accumulate ? 1.0 : 0.0;
+    semiring::dispatch(sr_flag, [&](auto policy) {
+        if (P->W == kBandWide) pb_launch<kBandWide, decltype(policy)>(P, x, y, 1.0, beta, s);
+        else pb_launch<kBandNarrow, decltype(policy)>(P, x, y, 1.0, beta, s);
+    });
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;
 }

@@ -10,5 +10,7 @@ int pb_update_values(PbPlan *plan, const double *d_values, hipStream_t stream); 
 void pb_destroy(PbPlan *plan);
 long long pb_bytes(const PbPlan *plan);
 int pb_spmv(PbPlan *plan, const double *x, double *y, double alpha, double beta, hipStream_t stream);
+// y := A ⊗ x (accumulate: y ⊕ (A ⊗ x)) over the semiring of `semiring` (G4S_SEMIRING_MIN_PLUS / MAX_PLUS / OR_AND): exact and deterministic
+int pb_spmv_semiring(PbPlan *plan, const double *x, double *y, unsigned semiring, bool accumulate, hipStream_t stream);
 bool pb_should_use(int rows, int cols, long long nnz, const int *d_colids);
 } // namespace g4s

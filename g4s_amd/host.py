@@ -4,6 +4,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   CSR            — mm/inc/CSR.h:22-100 (rows, cols, nnz, rowptr, colids, values, zerobased)
   HashSpGEMM     — mm/inc/hash_mult.h:1028-1057 (sortOutput flag; multiply/add: plus-times, min-plus, max-plus or or-and)
   spmv           — the CSR mat-vec the build defines for mv/ (DESIGN.md §SpMV), y = alpha·A·x + beta·y
+  spmv_semiring  — the same over min-plus, max-plus or or-and (SEMIRINGS): y = A ⊗ x, or y ⊕ (A ⊗ x)
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
 """
@@ -79,6 +80,18 @@ class CSR:
         capi.check(capi.load().g4s_spmv(self.handle, _ptr(x), _ptr(y), float(alpha), float(beta), _stream()))
         return y
 
+    def spmv_semiring(self, x, y=None, semiring="min_plus", accumulate=False):
+        """y := A ⊗ x, or y := y ⊕ (A ⊗ x) with accumulate=True, over `semiring` (a name of SEMIRINGS; include/g4s.h, g4s_spmv_semiring), on the current
+        torch stream (asynchronous). min_plus: min(a + x), max_plus: max(a + x), or_and: 1.0 where any a != 0 and x != 0, else 0.0; an empty row gets the
+        identity (+inf, −inf, 0.0), or leaves y unchanged when accumulating. plus_times is spmv(x, y, 1, accumulate ? 1 : 0)."""
+        flags = _spmv_semiring_flags(semiring, accumulate, y)
+        assert x.dtype == torch.float64 and x.is_cuda and x.numel() == self.cols
+        if y is None:
+            y = torch.empty(self.rows, dtype=torch.float64, device=x.device)
+        assert y.dtype == torch.float64 and y.is_cuda and y.numel() == self.rows
+        capi.check(capi.load().g4s_spmv_semiring(self.handle, _ptr(x), _ptr(y), flags, _stream()))
+        return y
+
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
         X.stride(1) == 1, column-major when X.stride(0) == 1 (k > 1); the leading dimension is the other stride, Y has X's layout. A new Y
@@ -129,6 +142,21 @@ class CSR:
 
 def spmv(A, x, y=None, alpha=1.0, beta=0.0):
     return A.spmv(x, y, alpha, beta)
+
+
+def _spmv_semiring_flags(semiring, accumulate, y):
+    """The flags of g4s_spmv_semiring; ValueError (before any GPU call) for an unknown name or for accumulating into no y."""
+    if semiring not in SEMIRINGS:
+        raise ValueError(f"unknown semiring {semiring!r}; expected one of {sorted(SEMIRINGS)}")
+    if accumulate and y is None:
+        raise ValueError("accumulate=True needs the y to combine with (y is None)")
+    return SEMIRINGS[semiring] | (capi.SPMV_ACCUMULATE if accumulate else 0)
+
+
+def spmv_semiring(A, x, y=None, semiring="min_plus", accumulate=False):
+    """y := A ⊗ x or y ⊕ (A ⊗ x) over a semiring (g4s_spmv_semiring) — CSR.spmv_semiring as a function, like spmv."""
+    _spmv_semiring_flags(semiring, accumulate, y)
+    return A.spmv_semiring(x, y, semiring, accumulate)
 
 
 def _spmm_ld(M, col_major):

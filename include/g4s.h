@@ -302,7 +302,8 @@ g4s_status g4s_spgemm_flop(int32_t M, const int32_t *arpt, const int32_t *acol, 
  *
  * Semirings (HashSpGEMM's MultiplyOperation / AddOperation pair, mm/inc/hash_mult.h:583-593, as a closed set on the device): one of the values below,
  * or-ed into the flags of g4s_spgemm_csr_i32_f64 and g4s_spgemm_numeric (host or device pointers, with or without G4S_SORT_OUTPUT). g4s_spgemm_symbolic
- * takes no flags: the pattern does not depend on the semiring. No other entry point reads these bits.
+ * takes no flags: the pattern does not depend on the semiring. g4s_spmv_semiring and g4s_spmv_semiring_csr_i32_f64 (below) read them too; no other
+ * entry point does.
  *   Pattern: crpt and ccol are bit-identical to the plus-times product of the same inputs (structural entries, repeated columns inside a row, unsorted B
  *     and empty rows included) — an entry exists wherever a product exists, whatever its value.
  *   Values, per output entry, over the products a·b that make it up:
@@ -320,6 +321,29 @@ g4s_status g4s_spgemm_flop(int32_t M, const int32_t *arpt, const int32_t *acol, 
 #define G4S_SEMIRING_MAX_PLUS   1024u /* C = max(a + b) */
 #define G4S_SEMIRING_OR_AND     1536u /* C = OR(a != 0 && b != 0) as 1.0 / 0.0 */
 #define G4S_SEMIRING_MASK       1536u
+
+/* Semiring SpMV: y := A ⊗ x, or y := y ⊕ (A ⊗ x) with G4S_SPMV_ACCUMULATE, over one of the semirings above — the mat-vec that graph algorithms iterate
+ * (Bellman-Ford relaxes d := d ⊕ (Aᵀ ⊗ d) over min-plus, BFS expands a frontier over or-and, longest paths in a DAG use max-plus).
+ *   flags: one G4S_SEMIRING_* value, optionally | G4S_SPMV_ACCUMULATE. The one-shot form also takes G4S_HOST_POINTERS / G4S_DEVICE_POINTERS and
+ *     G4S_SPMV_BLOCKED / G4S_SPMV_STREAM, with the meaning they have in g4s_spmv_csr_i32_f64. Any other bit returns G4S_ERR_INVALID before any HIP call,
+ *     and so do a NULL handle, a NULL x or y and an x that aliases y (the checks of g4s_spmv).
+ *   Values, per row i, over the stored entries a_ij of the row (repeated columns included):
+ *     MIN_PLUS    min(a_ij + x_j) (identity +inf);
+ *     MAX_PLUS    max(a_ij + x_j) (identity −inf);
+ *     OR_AND      1.0 if any a_ij != 0 && x_j != 0, else 0.0 (NaN counts as nonzero, as in SpGEMM).
+ *     An empty row gets the identity. With G4S_SPMV_ACCUMULATE the row's result is combined with y by ⊕ (an empty row leaves y unchanged); for OR_AND the
+ *     stored value is always 1.0 / 0.0, so a y of 5.0 becomes 1.0. Without it y is never read (the BLAS rule for beta = 0).
+ *   PLUS_TIMES through this entry point is g4s_spmv(A, x, y, 1.0, ACCUMULATE ? 1.0 : 0.0): the same kernels and the same result.
+ *   min, max and or do not depend on the order in which products arrive, and each min/max-plus product is one IEEE add: the values of the three are exact and
+ *   deterministic on every SpMV path (the blocked one included). Outside the contract, as for SpGEMM: the sign of a zero result, and the value of a row that
+ *   has a NaN product or a (+inf) + (−inf) product (the other rows are unaffected).
+ *   Concurrency and stream order are those of g4s_spmv: one product in flight per handle; the call only enqueues kernels on `stream` — no allocation, no
+ *   synchronisation, no host read — and may be recorded in a hipGraph. New values from g4s_csr_update_values are used by the next call. */
+#define G4S_SPMV_ACCUMULATE 2048u /* semiring SpMV: y := y ⊕ (A ⊗ x) instead of y := A ⊗ x */
+g4s_status g4s_spmv_semiring(g4s_csr_t A, const double *x_dev, double *y_dev, unsigned flags, void *stream);
+/* One-shot form, like g4s_spmv_csr_i32_f64 (synchronous). With host pointers y is uploaded only under G4S_SPMV_ACCUMULATE. */
+g4s_status g4s_spmv_semiring_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids, const double *values,
+                                         const double *x, double *y, unsigned flags);
 g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *acol, const double *aval,
                                   const int32_t *brpt, const int32_t *bcol, const double *bval,
                                   int32_t **crpt, int32_t **ccol, double **cval,

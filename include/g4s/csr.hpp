@@ -4,6 +4,7 @@
 //   mkl(a,b,c,timing)                  mm/inc/mkl_mult.h:113-124 (the call the shipped benchmark times)
 //   Timings                            mm/inc/Timings.h:4-23, mm/src/Timings.cpp:36-65
 //   SpMV(a,x,y,alpha,beta)             the CSR mat-vec this build defines for mv/ 
+//   SpMVSemiring(a,x,y,multop,addop)   the same over min-plus, max-plus or or-and (y := A ⊗ x, or y ⊕ (A ⊗ x))
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
 #pragma once
@@ -164,6 +165,18 @@ template <typename IT, typename NT>
 void SpMV(const CSR<IT, NT> &a, const NT *x, NT *y, NT alpha = 1.0, NT beta = 0.0)
 {
     check(g4s_spmv_csr_i32_f64(a.rows, a.cols, a.rowptr, a.colids, a.values, x, y, alpha, beta, G4S_HOST_POINTERS), "SpMV");
+}
+
+// y := A ⊗ x, or y := y ⊕ (A ⊗ x) with accumulate, over the semiring of a (multop, addop) pair (semiring_flag: the pairs of HashSpGEMM), host arrays.
+// Its own name, not an overload of SpMV: SpMV(a, x, y, alpha, beta) keeps its one meaning whatever the argument types.
+template <typename IT, typename NT, typename Mul, typename Add>
+void SpMVSemiring(const CSR<IT, NT> &a, const NT *x, NT *y, Mul, Add, bool accumulate = false)
+{
+    static_assert(semiring_flag<Mul, Add, NT>::supported,
+                  "device SpMV implements four (multop, addop) pairs only: (std::multiplies, std::plus), (std::plus, g4s::min_op), "
+                  "(std::plus, g4s::max_op), (std::logical_and, std::logical_or)");
+    check(g4s_spmv_semiring_csr_i32_f64(a.rows, a.cols, a.rowptr, a.colids, a.values, x, y,
+                                        G4S_HOST_POINTERS | semiring_flag<Mul, Add, NT>::value | (accumulate ? G4S_SPMV_ACCUMULATE : 0u)), "SpMVSemiring");
 }
 
 // Y = alpha·A·X + beta·Y with host blocks X (cols × k) and Y (rows × k): row-major by default (ld >= k), column-major as in cblas_dxxmm.c's
