@@ -107,6 +107,11 @@ SIGNATURES = {
     "g4s_spmv_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_uint]),
     "g4s_spmv_semiring": (C.c_int, [vp, vp, vp, C.c_uint, vp]),
     "g4s_spmv_semiring_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_uint]),
+    "g4s_csr_transpose": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
+    "g4s_csr_transpose_reserve": (C.c_int, [vp]),
+    "g4s_csr_transpose_info": (C.c_int, [vp, C.POINTER(CsrInfo)]),
+    "g4s_spmv_transpose": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp]),
+    "g4s_spmv_semiring_transpose": (C.c_int, [vp, vp, vp, C.c_uint, vp]),
     "g4s_spmm": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint, vp]),
     "g4s_csr_spmm_reserve": (C.c_int, [vp, C.c_int32]),
     "g4s_spmm_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint]),

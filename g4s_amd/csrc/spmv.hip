@@ -20,6 +20,7 @@
 #include "spmv_pb.hpp"
 #include "spmv_bcsr.hpp"
 #include "spmm.hpp"
+#include "transpose.hpp"
 #include "semiring.hpp"
 #include <algorithm>
 #include <vector>
@@ -349,6 +350,7 @@ struct g4s_csr_s {
     g4s::PbPlan *pb = nullptr;      // propagation-blocked path (spmv_pb.hip) for matrices without gather locality
     g4s::BcsrPlan *bcsr = nullptr;  // block-row form of an assembled FE matrix (spmv_bcsr.hip)
     g4s::SpmmWork *spmm = nullptr;  // g4s_spmm's workspace (spmm.hip), built by g4s_csr_spmm_reserve or a first g4s_spmm
+    g4s::TransposeWork *tr = nullptr;   // Aᵀ and its handle (transpose.hip), built by g4s_csr_transpose_reserve or a first transposed product
 };
 
 namespace {
@@ -552,6 +554,7 @@ void release(g4s_csr_s *A)
     g4s::pb_destroy(A->pb);
     g4s::bcsr_destroy(A->bcsr);
     g4s::spmm_work_destroy(A->spmm);
+    g4s::transpose_work_destroy(A->tr);
     delete A;
 }
 
@@ -730,9 +733,9 @@ __global__ __launch_bounds__(256) void dia_refill_kernel(int rows, int nd, long 
 // before every Stokes solve and inside the viscosity iteration). The CSR array is replaced (owned copy: copied into; borrowed: the handle borrows the new
 // array), then whatever the plan keeps of the values in another order is refreshed on `stream`: the regrouped producer stream of the blocked path (one
 // gather pass through its value map), the diagonals, the block-major copy; the row-streaming kernel reads the CSR array itself.
-G4S_API g4s_status g4s_csr_update_values(g4s_csr_t A, const double *values, unsigned flags, void *stream)
+namespace {
+int update_values(g4s_csr_s *A, const double *values, unsigned flags, void *stream)
 {
-    G4S_REQUIRE(A, "NULL handle");
     if (A->nnz == 0) return G4S_OK;
     hipStream_t s = g4s::as_stream(stream);
     const bool dev = (flags & G4S_DEVICE_POINTERS) != 0;
@@ -769,6 +772,20 @@ G4S_API g4s_status g4s_csr_update_values(g4s_csr_t A, const double *values, unsi
     }
     if (A->bcsr) return g4s::bcsr_update_values(A->bcsr, A->d_colids, A->d_values, s);
     return G4S_OK;
+}
+} // namespace
+
+// A transpose, where one exists, follows on the same stream (one gather through its entry map from the handle's current array, then its own
+// handle's update), also after a failed regrouping above: the CSR array has been replaced by then.
+G4S_API g4s_status g4s_csr_update_values(g4s_csr_t A, const double *values, unsigned flags, void *stream)
+{
+    G4S_REQUIRE(A, "NULL handle");
+    int st = update_values(A, values, flags, stream);
+    if (A->tr) {
+        const int st2 = g4s::transpose_update_values(A->tr, A->d_values, g4s::as_stream(stream));
+        if (st == G4S_OK) st = st2;
+    }
+    return st;
 }
 
 G4S_API g4s_status g4s_csr_destroy(g4s_csr_t A)
@@ -813,6 +830,15 @@ int g4s_csr_spmm_view(g4s_csr_t A, g4s::CsrSpmmView *v)
     v->long_rows = reinterpret_cast<const int4 *>(A->d_long_rows); v->n_long = A->n_long;
     v->work = &A->spmm;
     v->plan_bytes = &A->plan_bytes;
+    return G4S_OK;
+}
+
+// The handle's transpose slot (transpose.hip builds what it points to; release frees it) and the flags the handle was created with.
+int g4s_csr_transpose_slot(g4s_csr_t A, g4s::TransposeWork ***slot, unsigned *create_flags)
+{
+    G4S_REQUIRE(A && slot && create_flags, "NULL argument");
+    *slot = &A->tr;
+    *create_flags = A->flags;
     return G4S_OK;
 }
 

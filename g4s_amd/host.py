@@ -6,6 +6,8 @@ Names and argument meaning follow the reference so that tests read like tests of
   spmv           — the CSR mat-vec the build defines for mv/ (DESIGN.md §SpMV), y = alpha·A·x + beta·y
   spmv_semiring  — the same over min-plus, max-plus or or-and (SEMIRINGS): y = A ⊗ x, or y ⊕ (A ⊗ x)
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
+  csr_transpose  — Aᵀ as a CSR (the CSC form of A; mm/inc/CSR.h:171-230, mm/inc/convert.h), stable: entries of a column keep their order
+  spmv_transpose — y = alpha·Aᵀ·x + beta·y on a handle of A (spmv_semiring_transpose: the semiring form), through the handle's own transpose
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
 """
 import ctypes as C
@@ -92,6 +94,43 @@ class CSR:
         capi.check(capi.load().g4s_spmv_semiring(self.handle, _ptr(x), _ptr(y), flags, _stream()))
         return y
 
+    def transpose(self):
+        """Aᵀ as a new CSR (cols × rows) with the same spmv_flags, built on the device by g4s_csr_transpose (stable: see csr_transpose)."""
+        trp, tci, tva = csr_transpose(self.rowptr, self.colids, self.values, self.rows, self.cols)
+        return CSR(trp, tci, tva, self.cols, self.rows, spmv_flags=self._spmv_flags)
+
+    def transpose_reserve(self):
+        """Build the handle's transpose now (g4s_csr_transpose_reserve; synchronous), so that transposed products only enqueue kernels — before a capture."""
+        torch.cuda.current_stream().synchronize()
+        capi.check(capi.load().g4s_csr_transpose_reserve(self.handle))
+
+    def transpose_info(self):
+        """g4s_csr_transpose_info: the info of the handle's Aᵀ (its spmv_path, plan_bytes with the transpose's arrays, …); an error before a reserve."""
+        inf = capi.CsrInfo()
+        capi.check(capi.load().g4s_csr_transpose_info(self.handle, C.byref(inf)))
+        return {n: getattr(inf, n) for n, _ in capi.CsrInfo._fields_}
+
+    def spmv_transpose(self, x, y=None, alpha=1.0, beta=0.0):
+        """y = alpha·Aᵀ·x + beta·y (x: rows, y: cols) on the current torch stream (asynchronous once the transpose exists; the first call reserves it)."""
+        assert x.dtype == torch.float64 and x.is_cuda and x.numel() == self.rows
+        if y is None:
+            assert beta == 0.0
+            y = torch.empty(self.cols, dtype=torch.float64, device=x.device)
+        assert y.dtype == torch.float64 and y.is_cuda and y.numel() == self.cols
+        capi.check(capi.load().g4s_spmv_transpose(self.handle, _ptr(x), _ptr(y), float(alpha), float(beta), _stream()))
+        return y
+
+    def spmv_semiring_transpose(self, x, y=None, semiring="min_plus", accumulate=False):
+        """y := Aᵀ ⊗ x, or y ⊕ (Aᵀ ⊗ x) with accumulate=True (x: rows, y: cols) — spmv_semiring with Aᵀ: pull-style relaxation on a graph stored by
+        out-edges, without a second matrix."""
+        flags = _spmv_semiring_flags(semiring, accumulate, y)
+        assert x.dtype == torch.float64 and x.is_cuda and x.numel() == self.rows
+        if y is None:
+            y = torch.empty(self.cols, dtype=torch.float64, device=x.device)
+        assert y.dtype == torch.float64 and y.is_cuda and y.numel() == self.cols
+        capi.check(capi.load().g4s_spmv_semiring_transpose(self.handle, _ptr(x), _ptr(y), flags, _stream()))
+        return y
+
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
         X.stride(1) == 1, column-major when X.stride(0) == 1 (k > 1); the leading dimension is the other stride, Y has X's layout. A new Y
@@ -157,6 +196,53 @@ def spmv_semiring(A, x, y=None, semiring="min_plus", accumulate=False):
     """y := A ⊗ x or y ⊕ (A ⊗ x) over a semiring (g4s_spmv_semiring) — CSR.spmv_semiring as a function, like spmv."""
     _spmv_semiring_flags(semiring, accumulate, y)
     return A.spmv_semiring(x, y, semiring, accumulate)
+
+
+def spmv_transpose(A, x, y=None, alpha=1.0, beta=0.0):
+    """y = alpha·Aᵀ·x + beta·y (g4s_spmv_transpose) — CSR.spmv_transpose as a function, like spmv."""
+    return A.spmv_transpose(x, y, alpha, beta)
+
+
+def spmv_semiring_transpose(A, x, y=None, semiring="min_plus", accumulate=False):
+    """y := Aᵀ ⊗ x or y ⊕ (Aᵀ ⊗ x) (g4s_spmv_semiring_transpose) — CSR.spmv_semiring_transpose as a function."""
+    _spmv_semiring_flags(semiring, accumulate, y)
+    return A.spmv_semiring_transpose(x, y, semiring, accumulate)
+
+
+def csr_transpose(rowptr, colids, values, rows, cols, with_perm=False):
+    """Aᵀ of a rows × cols CSR through g4s_csr_transpose: (trowptr, tcolids, tvalues) as CUDA tensors, plus perm with with_perm=True. numpy inputs go
+    through host pointers, CUDA tensors through device pointers (on the current torch stream). values may be None: the pattern only (tvalues None).
+    Stable: perm = argsort(colids, kind="stable"), tcolids = row_of_entry[perm], tvalues = values[perm]."""
+    _require_gpu()
+    rows, cols = int(rows), int(cols)
+    lib = capi.load()
+    if isinstance(rowptr, torch.Tensor):
+        assert rowptr.is_cuda and colids.is_cuda and (values is None or values.is_cuda)
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        assert rowptr.dtype == torch.int32 and colids.dtype == torch.int32 and rowptr.numel() == rows + 1
+        values = None if values is None else values.contiguous()
+        assert values is None or (values.dtype == torch.float64 and values.numel() == colids.numel())
+        nnz, dev = colids.numel(), rowptr.device
+        trp = torch.empty(cols + 1, dtype=torch.int32, device=dev)
+        tci = torch.empty(nnz, dtype=torch.int32, device=dev)
+        tva = None if values is None else torch.empty(nnz, dtype=torch.float64, device=dev)
+        perm = torch.empty(nnz, dtype=torch.int32, device=dev) if with_perm else None
+        capi.check(lib.g4s_csr_transpose(rows, cols, nnz, _ptr(rowptr), _ptr(colids), _ptr(values), _ptr(trp), _ptr(tci), _ptr(tva), _ptr(perm),
+                                         capi.DEVICE_POINTERS, _stream()))
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        values = None if values is None else np.ascontiguousarray(values, np.float64)
+        assert rowptr.size == rows + 1 and (values is None or values.size == colids.size)
+        nnz = colids.size
+        trp, tci = np.empty(cols + 1, np.int32), np.empty(nnz, np.int32)
+        tva = None if values is None else np.empty(nnz, np.float64)
+        perm = np.empty(nnz, np.int32) if with_perm else None
+        P = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size > 0 else C.c_void_p(0)
+        capi.check(lib.g4s_csr_transpose(rows, cols, nnz, P(rowptr), P(colids), P(values), P(trp), P(tci), P(tva), P(perm), capi.HOST_POINTERS,
+                                         _stream()))
+        cu = lambda a: None if a is None else torch.from_numpy(a).cuda()
+        trp, tci, tva, perm = cu(trp), cu(tci), cu(tva), cu(perm)
+    return (trp, tci, tva, perm) if with_perm else (trp, tci, tva)
 
 
 def _spmm_ld(M, col_major):

@@ -344,6 +344,47 @@ g4s_status g4s_spmv_semiring(g4s_csr_t A, const double *x_dev, double *y_dev, un
 /* One-shot form, like g4s_spmv_csr_i32_f64 (synchronous). With host pointers y is uploaded only under G4S_SPMV_ACCUMULATE. */
 g4s_status g4s_spmv_semiring_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids, const double *values,
                                          const double *x, double *y, unsigned flags);
+
+/* ---- Transpose: Aᵀ of a rows × cols CSR as a cols × rows CSR (equivalently, the CSC form of A), on the device — the role of the reference's
+ * CSR(const CSC&) / CSR(const CSC&, bool transpose) (mm/inc/CSR.h:171-230) and mm/inc/convert.h. Caller-allocated outputs: trowptr (cols + 1),
+ * tcolids, tvalues and perm (nnz each).
+ *   Order is stable: row j of Aᵀ lists the entries of column j of A in increasing entry index, so rows ascend and repeated columns keep their stored
+ *     order. perm[k] is the entry of A that went to slot k, and tvalues[k] == values[perm[k]] bit for bit. In numpy terms: perm =
+ *     argsort(colids, kind="stable"), tcolids = row_of_entry[perm], tvalues = values[perm], trowptr = the scan of the column counts — which is also
+ *     scipy.sparse.csr_matrix(A).T.tocsr() without sum_duplicates. The result is the same on every run.
+ *   Inputs follow the rules of g4s_csr_create: zero-based, rowptr non-decreasing, rowptr[0] == 0, rowptr[rows] == nnz <= INT32_MAX, colids in
+ *     [0, cols). Rows need not be sorted; duplicates are kept, not summed. A violation returns G4S_ERR_INVALID and leaves the outputs unspecified.
+ *   Optional outputs: values and tvalues may both be NULL (the pattern only; one without the other is G4S_ERR_INVALID); perm may be NULL.
+ *   flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS for all arrays; any other bit returns G4S_ERR_INVALID. Argument checks (sizes, NULLs, flag bits)
+ *     come before any HIP call.
+ *   Synchronous: runs on `stream` and returns when the outputs are complete; device inputs must be complete with respect to that stream. Scratch
+ *     (about 24·nnz + 4·cols bytes, plus device copies of the arrays with G4S_HOST_POINTERS) is freed before the call returns. rows, cols or nnz of 0
+ *     are valid (nnz == 0: trowptr is all zeros). */
+g4s_status g4s_csr_transpose(int32_t rows, int32_t cols, int64_t nnz, const int32_t *rowptr, const int32_t *colids, const double *values,
+                             int32_t *trowptr, int32_t *tcolids, double *tvalues, int32_t *perm, unsigned flags, void *stream);
+
+/* Transposed products on a handle: y(cols) = alpha·Aᵀ·x(rows) + beta·y, and y := Aᵀ ⊗ x or y ⊕ (Aᵀ ⊗ x) over a semiring — pull-style graph
+ * relaxation on a graph stored by out-edges (Bellman-Ford's d := d ⊕ (Aᵀ ⊗ d) above, BFS), and the Dᵀ of a Uzawa iteration, without a second matrix.
+ *   g4s_csr_transpose_reserve runs g4s_csr_transpose on the handle's device arrays (NULL stream, synchronous), keeps perm, and creates an inner handle of
+ *     Aᵀ on arrays of its own, with A's path flags (G4S_SPMV_NO_NT, _BLOCKED, _STREAM, _UPDATABLE) — for owned and borrowed handles alike.
+ *     g4s_csr_destroy releases all of it. Peak device memory of a reserve: the kept arrays (4·(cols + 1) + 20·nnz bytes) plus the larger of the
+ *     transpose's scratch (about 24·nnz bytes) and the inner g4s_csr_create's own transients.
+ *   g4s_csr_transpose_info: the g4s_csr_info of the inner handle (rows = A's cols, its spmv_path, …); plan_bytes also counts the four kept arrays.
+ *     G4S_ERR_INVALID before a reserve. g4s_csr_get_info(A) does not change.
+ *   The products run the SpMV kernels of the inner handle, at the speed of a forward product on Aᵀ. Semiring flags, G4S_SPMV_ACCUMULATE, the beta == 0
+ *     rule and the argument checks are those of g4s_spmv / g4s_spmv_semiring, with x of length rows and y of length cols. The semiring form takes exactly
+ *     the flags of g4s_spmv_semiring; transposition never goes through a flag bit.
+ *   Result: bit-identical to g4s_spmv / g4s_spmv_semiring on a handle created (G4S_DEVICE_POINTERS) from g4s_csr_transpose's output with the same flags —
+ *     on every path for the three semirings, on paths 0, 3 and 4 for plus-times; on the blocked path plus-times is within 1e-10·Σ|a·x| (its LDS atomic
+ *     sums are not reproducible run to run).
+ *   First call without a reserve: reserves synchronously, like g4s_spmm; on a capturing stream it returns G4S_ERR_INVALID and enqueues nothing. After a
+ *     reserve a call only enqueues kernels on `stream` and may be recorded in a hipGraph.
+ *   g4s_csr_update_values(A, …) refreshes Aᵀ on the same stream when it exists: one gather tvalues[k] = values[perm[k]], then the inner handle's own
+ *     update under the same rules (one pass with G4S_SPMV_UPDATABLE). One product in flight per handle, forward or transposed. */
+g4s_status g4s_csr_transpose_reserve(g4s_csr_t A);
+g4s_status g4s_csr_transpose_info(g4s_csr_t A, g4s_csr_info *info);
+g4s_status g4s_spmv_transpose(g4s_csr_t A, const double *x_dev, double *y_dev, double alpha, double beta, void *stream);
+g4s_status g4s_spmv_semiring_transpose(g4s_csr_t A, const double *x_dev, double *y_dev, unsigned flags, void *stream);
 g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *acol, const double *aval,
                                   const int32_t *brpt, const int32_t *bcol, const double *bval,
                                   int32_t **crpt, int32_t **ccol, double **cval,

@@ -5,6 +5,7 @@
 //   Timings                            mm/inc/Timings.h:4-23, mm/src/Timings.cpp:36-65
 //   SpMV(a,x,y,alpha,beta)             the CSR mat-vec this build defines for mv/ 
 //   SpMVSemiring(a,x,y,multop,addop)   the same over min-plus, max-plus or or-and (y := A ⊗ x, or y ⊕ (A ⊗ x))
+//   Transpose(a,at)                    Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
 #pragma once
@@ -177,6 +178,21 @@ void SpMVSemiring(const CSR<IT, NT> &a, const NT *x, NT *y, Mul, Add, bool accum
                   "(std::plus, g4s::max_op), (std::logical_and, std::logical_or)");
     check(g4s_spmv_semiring_csr_i32_f64(a.rows, a.cols, a.rowptr, a.colids, a.values, x, y,
                                         G4S_HOST_POINTERS | semiring_flag<Mul, Add, NT>::value | (accumulate ? G4S_SPMV_ACCUMULATE : 0u)), "SpMVSemiring");
+}
+
+// at = Aᵀ (a.cols × a.rows) on the device through g4s_csr_transpose, host arrays. Stable: row j of at lists the entries of column j of a in their
+// stored order (duplicates kept), so at is also the CSC form of a. at's old arrays are released first.
+template <typename IT, typename NT>
+void Transpose(const CSR<IT, NT> &a, CSR<IT, NT> &at)
+{
+    at.make_empty();
+    at.rowptr = (IT *)g4s_malloc(sizeof(IT) * ((size_t)a.cols + 1));
+    at.colids = (IT *)g4s_malloc(sizeof(IT) * ((size_t)a.nnz + 1));
+    at.values = (NT *)g4s_malloc(sizeof(NT) * ((size_t)a.nnz + 1));
+    if (!at.rowptr || !at.colids || !at.values) { at.make_empty(); throw std::runtime_error("Transpose: host allocation failed"); }
+    check(g4s_csr_transpose(a.rows, a.cols, a.nnz, a.rowptr, a.colids, a.values, at.rowptr, at.colids, a.values ? at.values : nullptr, nullptr, G4S_HOST_POINTERS, nullptr),
+          "Transpose");
+    at.rows = a.cols; at.cols = a.rows; at.nnz = a.nnz; at.zerobased = true;
 }
 
 // Y = alpha·A·X + beta·Y with host blocks X (cols × k) and Y (rows × k): row-major by default (ld >= k), column-major as in cblas_dxxmm.c's
