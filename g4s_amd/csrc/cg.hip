@@ -19,7 +19,7 @@ namespace g4s { int64_t dist_smallest_slab(g4s_spmv_dist_t h); }   // dist.hip
 #include <cmath>
 #include <functional>
 
-// opaque handle types of the two operators, defined in graph.hip / spmv.hip
+// opaque handle types of the two operators, defined in graph.hip / csr_handle.hpp
 extern "C" g4s_status g4s_elem_op_apply(g4s_elem_op_t op, const double *u_dev, double *Au_dev, void *stream);
 extern "C" g4s_status g4s_spmv(g4s_csr_t A, const double *x_dev, double *y_dev, double alpha, double beta, void *stream);
 

@@ -34,6 +34,26 @@ void big_release_all();
 void release_cached_device_memory();   // big_release_all + the SpGEMM column scratch (what g4s_trim does)
 hipError_t device_malloc(void **p, size_t bytes);   // hipMalloc that drops the library's caches and retries once on out-of-memory
 
+// An owned device allocation (device_malloc / hipFree): freed when it goes out of scope, on every path. `bytes` is what was asked for.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    int alloc(size_t n)
+    {
+        release();
+        const hipError_t e = device_malloc(&p, n ? n : 1);
+        if (e != hipSuccess) return set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "hipMalloc(%zu): %s", n, hipGetErrorString(e));
+        bytes = n;
+        return G4S_OK;
+    }
+    void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
 // 8 XCDs, each with its own L2: block b and b+8 share one (MI355X_MICROARCH.md, Workgroup dispatch).
 constexpr int kXcds = 8;
 

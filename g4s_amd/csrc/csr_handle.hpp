@@ -1,0 +1,60 @@
+// csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip.
+#pragma once
+#include "common.hpp"
+#include "spmv_stream.hpp"
+#include "spmv_pb.hpp"
+#include "spmv_dia.hpp"
+#include "spmv_bcsr.hpp"
+#include <functional>
+
+namespace g4s {
+
+// spmm.hip: the handle's SpMM workspace (reserved k_max, the partial sums of long-row chunks for k_max vectors)
+struct SpmmWork;
+void spmm_work_destroy(SpmmWork *w);
+long long spmm_work_bytes(const SpmmWork *w);
+
+// transpose.hip: the arrays of Aᵀ, the entry map perm and the inner handle of Aᵀ
+struct TransposeWork;
+void transpose_work_destroy(TransposeWork *w);
+// tvalues[k] = values[perm[k]] on `stream`, then the inner handle's own g4s_csr_update_values (after the forward handle's update)
+int transpose_update_values(TransposeWork *w, const double *values, hipStream_t stream);
+
+} // namespace g4s
+
+struct g4s_csr_s {
+    int32_t rows = 0, cols = 0;
+    int64_t nnz = 0;
+    const int32_t *d_rowptr = nullptr;
+    const int32_t *d_colids = nullptr;
+    const double *d_values = nullptr;   // current values (g4s_csr_update_values swaps a borrowed array)
+    bool owns = false;
+    bool use_nt = true;
+    unsigned flags = 0;                 // of g4s_csr_create
+    bool rowptr_checked = false;        // stream_check_rowptr_device has passed
+    // At most one of pb / dia / bcsr exists: the handle's SpMV path. Without one it is the row-streaming plan, which SpMM runs on whatever the path.
+    g4s::StreamPlan stream;             // row-streaming path (spmv.hip)
+    g4s::PbPlan *pb = nullptr;          // propagation-blocked path (spmv_pb.hip) for matrices without gather locality
+    g4s::DiaPlan *dia = nullptr;        // diagonal form of a stencil or band (spmv_dia.hip)
+    g4s::BcsrPlan *bcsr = nullptr;      // block-row form of an assembled FE matrix (spmv_bcsr.hip)
+    g4s::SpmmWork *spmm = nullptr;      // g4s_spmm's workspace (spmm.hip), built by g4s_csr_spmm_reserve or a first g4s_spmm
+    g4s::TransposeWork *tr = nullptr;   // Aᵀ and its handle (transpose.hip), built by g4s_csr_transpose_reserve or a first transposed product
+};
+
+namespace g4s {
+
+int csr_spmv_path(const g4s_csr_s *A);   // g4s_csr_info.spmv_path: 0 row-streaming, 1 blocked, 3 diagonal, 4 block-row
+
+// The argument rules of a product y(n_out) = A·x or Aᵀ·x on a handle, in g4s_spmv's order; an empty product (n_out == 0) passes whatever x and y are.
+int check_spmv_args(const char *fn, const g4s_csr_s *A, int32_t n_out, const double *x, const double *y);
+
+// The one-shot forms: a handle on host or device CSR arrays (create_flags: G4S_DEVICE_POINTERS and the path flags; the streaming path unless
+// G4S_SPMV_BLOCKED), one `product(handle, device x, device y)`, synchronous, the handle destroyed. Host pointers: x (nx doubles) is staged on the
+// device, y (ny doubles) too when read_y, and y is read back after the product.
+int csr_one_shot(int32_t rows, int32_t cols, const int32_t *rowptr, const int32_t *colids, const double *values, unsigned create_flags,
+                 const double *x, size_t nx, double *y, size_t ny, bool read_y, const std::function<int(g4s_csr_t, const double *, double *)> &product);
+
+} // namespace g4s
+
+// The row-streaming plan of a handle that took the blocked path without one (SpMM runs on it; g4s_csr_update_values falls back to it); NULL stream, synchronous.
+int g4s_csr_build_stream_plan(g4s_csr_t A);

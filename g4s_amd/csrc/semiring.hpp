@@ -1,4 +1,4 @@
-// semiring.hpp — the value operations of the numeric SpGEMM kernels (spgemm.hip, spgemm_rank.hpp) and of the SpMV kernels (spmv.hip, spmv_pb.hip,
+// semiring.hpp — the value operations of the numeric SpGEMM kernels (spgemm.hip, spgemm_rank.hpp) and of the SpMV kernels (spmv.hip, spmv_dia.hip, spmv_pb.hip,
 // spmv_bcsr.hip), one policy per G4S_SEMIRING_* value.
 // Every accumulation site of the numeric phase goes through these five calls; the pattern (symbolic phase, row classes, bitmaps, chunks) does
 // not depend on them. Each policy maps onto one native instruction per product:

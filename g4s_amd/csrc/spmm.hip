@@ -2,7 +2,7 @@
 //
 // k SpMVs read the matrix k times; this reads it once per column tile (up to 32 vectors) and, on a row-major X, gathers k contiguous doubles per entry
 // instead of one. One kernel family serves every handle, whichever of the four SpMV paths it took: it runs on the handle's CSR arrays and on the
-// row-streaming plan of spmv.hip (row-aligned blocks of <= 2048 entries, 2048-entry chunks of longer rows), which a blocked-path handle builds on demand.
+// row-streaming plan of spmv.hip (spmv_stream.hpp: row-aligned blocks of <= 2048 entries, 2048-entry chunks of longer rows), which a blocked-path handle builds on demand.
 //
 //   * spmm_csr_kernel<KT, MODE> — one workgroup per (plan block, tile of KT columns). The block's column ids and values are staged in LDS with
 //     coalesced loads; then a group of KT/2 lanes (1 lane for KT = 1) owns one row and the tile, each lane two columns, and walks the row's entries
@@ -15,7 +15,7 @@
 // alignment, odd ld), 2 = column-major (element (i, j) at [i + j·ld]; strided, correct but slower). Columns past k in the last tile are masked:
 // those lanes load and store nothing, so padding of Y is never touched.
 #include "common.hpp"
-#include "spmm.hpp"
+#include "csr_handle.hpp"
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -23,11 +23,11 @@
 namespace {
 
 constexpr int WG = 256;
-constexpr int kTileNnz = 2048;   // = TILE_NNZ / LONG_CHUNK of spmv.hip (checked against the handle's plan at run time)
-#ifndef G4S_TILE_ROWS
-#define G4S_TILE_ROWS 1024
-#endif
-constexpr int kTileRows = G4S_TILE_ROWS;
+using g4s::TILE_NNZ;
+using g4s::TILE_ROWS;
+using g4s::LongChunk;
+using g4s::LongRow;
+static_assert(g4s::LONG_CHUNK <= TILE_NNZ, "a long-row chunk is staged in the LDS tile of a block");
 constexpr int kMaxTile = 32;     // vectors per column tile
 
 typedef double spmm_double2 __attribute__((ext_vector_type(2)));
@@ -103,15 +103,15 @@ template <int KT, int MODE>
 __global__ __launch_bounds__(WG) void spmm_csr_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colids, const double *__restrict__ values,
     const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int k,
-    const int4 *__restrict__ blocks, const int4 *__restrict__ chunks, int n_chunks, double *__restrict__ partials, int kmax,
+    const int4 *__restrict__ blocks, const LongChunk *__restrict__ chunks, int n_chunks, double *__restrict__ partials, int kmax,
     double alpha, double beta)
 {
     constexpr int CPL = KT >= 2 ? 2 : 1;   // columns per lane
     constexpr int G = KT / CPL;            // lanes per row
     constexpr int NG = WG / G;             // row groups per workgroup
-    __shared__ int32_t s_col[kTileNnz];
-    __shared__ double s_val[kTileNnz];
-    __shared__ int32_t s_rp[kTileRows + 1];
+    __shared__ int32_t s_col[TILE_NNZ];
+    __shared__ double s_val[TILE_NNZ];
+    __shared__ int32_t s_rp[TILE_ROWS + 1];
     __shared__ double s_part[NG * KT];
 
     const int tid = (int)threadIdx.x, g = tid / G, l = tid % G;
@@ -120,11 +120,11 @@ __global__ __launch_bounds__(WG) void spmm_csr_kernel(
 
     if ((int)blockIdx.x < n_chunks) {
         // ---- one chunk of a long row: contiguous pieces per group, the pieces' sums added in group order
-        const int4 c = chunks[blockIdx.x];                            // {row, k0, k1, slot}
-        const int n = c.z - c.y;
+        const LongChunk c = chunks[blockIdx.x];
+        const int n = c.k1 - c.k0;
         for (int i = tid; i < n; i += WG) {
-            s_col[i] = __builtin_nontemporal_load(colids + c.y + i);
-            s_val[i] = __builtin_nontemporal_load(values + c.y + i);
+            s_col[i] = __builtin_nontemporal_load(colids + c.k0 + i);
+            s_val[i] = __builtin_nontemporal_load(values + c.k0 + i);
         }
         __syncthreads();
         const int per = (n + NG - 1) / NG, a = min(n, g * per), b = min(n, a + per);
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(WG) void spmm_csr_kernel(
             if (jj < k) {
                 double s = 0.0;
                 for (int q = 0; q < NG; ++q) s += s_part[q * KT + tid];
-                partials[(long long)c.w * kmax + jj] = s;
+                partials[(long long)c.slot * kmax + jj] = s;
             }
         }
         return;
@@ -162,43 +162,44 @@ __global__ __launch_bounds__(WG) void spmm_csr_kernel(
 
 // Rows longer than a block: per (long row, column) the chunk partials in chunk order, then alpha / beta.
 template <int MODE>
-__global__ void spmm_long_fixup_kernel(const int4 *__restrict__ long_rows, int n_long, int k, const double *__restrict__ partials, int kmax,
+__global__ void spmm_long_fixup_kernel(const LongRow *__restrict__ long_rows, int n_long, int k, const double *__restrict__ partials, int kmax,
                                        double *__restrict__ Y, long long ldy, double alpha, double beta)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)n_long * k) return;
     const int i = (int)(t / k), jj = (int)(t % k);
-    const int4 lr = long_rows[i];                                     // {row, slot0, nslots, -}
+    const LongRow lr = long_rows[i];
     double s = 0.0;
-    for (int q = 0; q < lr.z; ++q) s += partials[(long long)(lr.y + q) * kmax + jj];
-    double *p = Y + at<MODE == 2 ? 2 : 1>(lr.x, jj, ldy);
+    for (int q = 0; q < lr.nslots; ++q) s += partials[(long long)(lr.slot0 + q) * kmax + jj];
+    double *p = Y + at<MODE == 2 ? 2 : 1>(lr.row, jj, ldy);
     *p = combine(s, alpha, beta, beta != 0.0 ? *p : 0.0);
 }
 
 template <int KT, int MODE>
-void launch_tiles(const g4s::CsrSpmmView &v, const double *X, long long ldx, double *Y, long long ldy, int k, double *partials, int kmax,
+void launch_tiles(const g4s_csr_s &A, const double *X, long long ldx, double *Y, long long ldy, int k, double *partials, int kmax,
                   double alpha, double beta, hipStream_t s)
 {
-    const dim3 grid((unsigned)(v.n_chunks + v.n_blocks), (unsigned)((k + KT - 1) / KT)), block(WG);
-    hipLaunchKernelGGL((spmm_csr_kernel<KT, MODE>), grid, block, 0, s, v.rowptr, v.colids, v.values, X, ldx, Y, ldy, k, v.blocks, v.chunks, v.n_chunks,
-                       partials, kmax, alpha, beta);
+    const g4s::StreamPlan &P = A.stream;
+    const dim3 grid((unsigned)(P.n_chunks + P.n_stream), (unsigned)((k + KT - 1) / KT)), block(WG);
+    hipLaunchKernelGGL((spmm_csr_kernel<KT, MODE>), grid, block, 0, s, A.d_rowptr, A.d_colids, A.d_values, X, ldx, Y, ldy, k, P.blocks.as<int4>(),
+                       P.chunks.as<LongChunk>(), P.n_chunks, partials, kmax, alpha, beta);
 }
 
 template <int MODE>
-void launch_mode(const g4s::CsrSpmmView &v, const double *X, long long ldx, double *Y, long long ldy, int k, double *partials, int kmax,
+void launch_mode(const g4s_csr_s &A, const double *X, long long ldx, double *Y, long long ldy, int k, double *partials, int kmax,
                  double alpha, double beta, hipStream_t s)
 {
     // the smallest tile that holds k (at most 32); larger k is covered by tiles along the grid's y dimension, the last one masked
-    if (k <= 1) launch_tiles<1, MODE>(v, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
-    else if (k <= 2) launch_tiles<2, MODE>(v, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
-    else if (k <= 4) launch_tiles<4, MODE>(v, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
-    else if (k <= 8) launch_tiles<8, MODE>(v, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
-    else if (k <= 16) launch_tiles<16, MODE>(v, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
-    else launch_tiles<kMaxTile, MODE>(v, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
-    if (v.n_long > 0) {
-        const long long n = (long long)v.n_long * k;
-        hipLaunchKernelGGL((spmm_long_fixup_kernel<MODE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v.long_rows, v.n_long, k, partials, kmax, Y, ldy,
-                           alpha, beta);
+    if (k <= 1) launch_tiles<1, MODE>(A, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
+    else if (k <= 2) launch_tiles<2, MODE>(A, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
+    else if (k <= 4) launch_tiles<4, MODE>(A, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
+    else if (k <= 8) launch_tiles<8, MODE>(A, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
+    else if (k <= 16) launch_tiles<16, MODE>(A, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
+    else launch_tiles<kMaxTile, MODE>(A, X, ldx, Y, ldy, k, partials, kmax, alpha, beta, s);
+    if (A.stream.n_long > 0) {
+        const long long n = (long long)A.stream.n_long * k;
+        hipLaunchKernelGGL((spmm_long_fixup_kernel<MODE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A.stream.long_rows.as<LongRow>(), A.stream.n_long, k,
+                           partials, kmax, Y, ldy, alpha, beta);
     }
 }
 
@@ -237,40 +238,29 @@ int check_args(const char *fn, int32_t rows, int32_t cols, int32_t k, const doub
 namespace g4s {
 struct SpmmWork {
     int kmax = 0;
-    double *partials = nullptr;   // n_chunks × kmax
+    DevBuf partials;   // n_chunks × kmax doubles
 };
-void spmm_work_destroy(SpmmWork *w)
-{
-    if (!w) return;
-    (void)hipFree(w->partials);
-    delete w;
-}
+void spmm_work_destroy(SpmmWork *w) { delete w; }
+long long spmm_work_bytes(const SpmmWork *w) { return w ? (long long)w->partials.bytes : 0; }
 } // namespace g4s
 
 namespace {
 // Workspace for up to k_max vectors: the row-streaming plan (blocked-path handles) and the chunk partials. NULL stream, synchronous.
-int reserve(g4s_csr_t A, g4s::CsrSpmmView &v, int32_t k_max)
+int reserve(g4s_csr_t A, int32_t k_max)
 {
-    if (v.tile_nnz != kTileNnz || v.long_chunk != kTileNnz || v.tile_rows != kTileRows)
-        return g4s::set_error(G4S_ERR_INVALID, "g4s_spmm: the handle's plan limits (%d, %d, %d) differ from this build's SpMM kernels", v.tile_nnz, v.tile_rows, v.long_chunk);
-    if (!v.stream_plan) {
-        G4S_TRY(g4s_csr_build_stream_plan(A));
-        G4S_TRY(g4s_csr_spmm_view(A, &v));
+    G4S_TRY(g4s_csr_build_stream_plan(A));
+    if (!A->spmm) {
+        A->spmm = new (std::nothrow) g4s::SpmmWork();
+        if (!A->spmm) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
     }
-    g4s::SpmmWork *w = *v.work;
-    if (!w) {
-        w = new (std::nothrow) g4s::SpmmWork();
-        if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
-        *v.work = w;
-    }
+    g4s::SpmmWork *w = A->spmm;
     if (k_max <= w->kmax) return G4S_OK;
-    if (v.n_chunks > 0) {
-        double *p = nullptr;
-        G4S_HIP_TRY(g4s::device_malloc((void **)&p, sizeof(double) * (size_t)v.n_chunks * (size_t)k_max));
+    if (A->stream.n_chunks > 0) {
+        g4s::DevBuf grown;
+        G4S_TRY(grown.alloc(sizeof(double) * (size_t)A->stream.n_chunks * (size_t)k_max));
         G4S_HIP_TRY(hipDeviceSynchronize());                           // the old workspace may still be in use by an earlier product
-        (void)hipFree(w->partials);
-        w->partials = p;
-        *v.plan_bytes += (int64_t)sizeof(double) * v.n_chunks * ((int64_t)k_max - w->kmax);
+        std::swap(w->partials.p, grown.p);
+        std::swap(w->partials.bytes, grown.bytes);
     }
     w->kmax = k_max;
     return G4S_OK;
@@ -281,39 +271,35 @@ G4S_API g4s_status g4s_csr_spmm_reserve(g4s_csr_t A, int32_t k_max)
 {
     G4S_REQUIRE(A, "NULL handle");
     G4S_REQUIRE(k_max >= 0, "k_max is negative");
-    g4s::CsrSpmmView v;
-    G4S_TRY(g4s_csr_spmm_view(A, &v));
-    return reserve(A, v, std::max(k_max, 1));
+    return reserve(A, std::max(k_max, 1));
 }
 
 G4S_API g4s_status g4s_spmm(g4s_csr_t A, int32_t k, const double *X_dev, int64_t ldx, double *Y_dev, int64_t ldy, double alpha, double beta,
                             unsigned flags, void *stream)
 {
     G4S_REQUIRE(A, "NULL handle");
-    g4s::CsrSpmmView v;
-    G4S_TRY(g4s_csr_spmm_view(A, &v));
     const bool cm = (flags & G4S_SPMM_COL_MAJOR) != 0;
-    G4S_TRY(check_args("g4s_spmm", v.rows, v.cols, k, X_dev, ldx, Y_dev, ldy, cm));
-    if (k == 0 || v.rows == 0) return G4S_OK;
-    if (v.nnz == 0 || v.cols == 0) X_dev = nullptr;                     // nothing is gathered
+    G4S_TRY(check_args("g4s_spmm", A->rows, A->cols, k, X_dev, ldx, Y_dev, ldy, cm));
+    if (k == 0 || A->rows == 0) return G4S_OK;
+    if (A->nnz == 0 || A->cols == 0) X_dev = nullptr;                     // nothing is gathered
     hipStream_t s = g4s::as_stream(stream);
     // one vector with unit stride: the handle's own SpMV, except on the blocked path (its LDS atomics are not reproducible run to run)
-    if (k == 1 && v.spmv_path != 1 && (cm || (ldx == 1 && ldy == 1))) return g4s_spmv(A, X_dev, Y_dev, alpha, beta, stream);
+    if (k == 1 && !A->pb && (cm || (ldx == 1 && ldy == 1))) return g4s_spmv(A, X_dev, Y_dev, alpha, beta, stream);
 
-    g4s::SpmmWork *w = *v.work;
-    if (!w || k > w->kmax) {
+    if (!A->spmm || k > A->spmm->kmax) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
         if (cs != hipStreamCaptureStatusNone)
             return g4s::set_error(G4S_ERR_INVALID, "g4s_spmm: the handle has no workspace for k = %d and the stream is capturing; call g4s_csr_spmm_reserve before the capture", k);
-        G4S_TRY(reserve(A, v, k));
-        w = *v.work;
+        G4S_TRY(reserve(A, k));
     }
-    if (v.n_blocks + v.n_chunks == 0) return G4S_OK;
+    if (A->stream.n_stream + A->stream.n_chunks == 0) return G4S_OK;
+    double *partials = A->spmm->partials.as<double>();
+    const int kmax = A->spmm->kmax;
     const bool pairs = !cm && k >= 2 && ((reinterpret_cast<uintptr_t>(X_dev) | reinterpret_cast<uintptr_t>(Y_dev)) & 15u) == 0 && (ldx % 2) == 0 && (ldy % 2) == 0;
-    if (cm) launch_mode<2>(v, X_dev, ldx, Y_dev, ldy, k, w->partials, w->kmax, alpha, beta, s);
-    else if (pairs) launch_mode<0>(v, X_dev, ldx, Y_dev, ldy, k, w->partials, w->kmax, alpha, beta, s);
-    else launch_mode<1>(v, X_dev, ldx, Y_dev, ldy, k, w->partials, w->kmax, alpha, beta, s);
+    if (cm) launch_mode<2>(*A, X_dev, ldx, Y_dev, ldy, k, partials, kmax, alpha, beta, s);
+    else if (pairs) launch_mode<0>(*A, X_dev, ldx, Y_dev, ldy, k, partials, kmax, alpha, beta, s);
+    else launch_mode<1>(*A, X_dev, ldx, Y_dev, ldy, k, partials, kmax, alpha, beta, s);
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;
 }
@@ -326,47 +312,24 @@ G4S_API g4s_status g4s_spmm_csr_i32_f64(int32_t rows, int32_t cols, int32_t k, c
     G4S_TRY(check_args("g4s_spmm_csr_i32_f64", rows, cols, k, X, ldx, Y, ldy, cm));
     G4S_REQUIRE(rowptr, "rowptr is NULL");
     if (k == 0 || rows == 0) return G4S_OK;
-    int32_t nnz32 = 0;
-    if (dev) G4S_HIP_TRY(hipMemcpy(&nnz32, rowptr + rows, sizeof(int32_t), hipMemcpyDeviceToHost));
-    else nnz32 = rowptr[rows];
-    G4S_REQUIRE(nnz32 >= 0, "rowptr[rows] is negative");
-    unsigned cflags = (flags & (G4S_DEVICE_POINTERS | G4S_SPMV_BLOCKED | G4S_SPMV_NO_NT));
-    // one call: the blocked path's regrouping cannot pay off — the streaming plan unless asked (as g4s_spmv_csr_i32_f64)
-    if (!(cflags & G4S_SPMV_BLOCKED)) cflags |= G4S_SPMV_STREAM;
-    g4s_csr_t A = nullptr;
-    G4S_TRY(g4s_csr_create(&A, rows, cols, nnz32, rowptr, colids, values, cflags));
-    int st = G4S_OK;
-    if (dev) {
-        st = g4s_spmm(A, k, X, ldx, Y, ldy, alpha, beta, flags & G4S_SPMM_COL_MAJOR, nullptr);
-        if (st == G4S_OK && hipStreamSynchronize(nullptr) != hipSuccess) st = g4s::set_error(G4S_ERR_HIP, "synchronize failed");
-    } else {
-        // host blocks are packed into compact device blocks (ld = k row-major, rows / cols column-major) and only the rows × k block of Y comes back
-        const size_t nx = (size_t)cols * (size_t)k, ny = (size_t)rows * (size_t)k;
-        std::vector<double> hx(nx), hy(ny);
-        auto pack = [&](const double *M, int64_t ld, int32_t n, double *out) {
-            for (int32_t i = 0; i < n; ++i)
-                for (int32_t j = 0; j < k; ++j) out[cm ? (size_t)i + (size_t)j * n : (size_t)i * k + j] = M[cm ? i + (int64_t)j * ld : (int64_t)i * ld + j];
-        };
-        if (cols > 0) pack(X, ldx, cols, hx.data());
-        if (beta != 0.0) pack(Y, ldy, rows, hy.data());
-        double *dx = nullptr, *dy = nullptr;
-        if (g4s::device_malloc((void **)&dx, sizeof(double) * std::max<size_t>(nx, 1)) != hipSuccess ||
-            g4s::device_malloc((void **)&dy, sizeof(double) * ny) != hipSuccess) {
-            st = g4s::set_error(G4S_ERR_NOMEM, "hipMalloc of X/Y failed");
-        } else if ((nx && hipMemcpy(dx, hx.data(), sizeof(double) * nx, hipMemcpyHostToDevice) != hipSuccess) ||
-                   (beta != 0.0 && hipMemcpy(dy, hy.data(), sizeof(double) * ny, hipMemcpyHostToDevice) != hipSuccess)) {
-            st = g4s::set_error(G4S_ERR_HIP, "H2D copy of X/Y failed");
-        } else {
-            st = g4s_spmm(A, k, dx, cm ? std::max(cols, 1) : k, dy, cm ? rows : k, alpha, beta, flags & G4S_SPMM_COL_MAJOR, nullptr);
-            if (st == G4S_OK && hipMemcpy(hy.data(), dy, sizeof(double) * ny, hipMemcpyDeviceToHost) != hipSuccess)
-                st = g4s::set_error(G4S_ERR_HIP, "D2H copy of Y failed");
-            if (st == G4S_OK)
-                for (int32_t i = 0; i < rows; ++i)
-                    for (int32_t j = 0; j < k; ++j) Y[cm ? i + (int64_t)j * ldy : (int64_t)i * ldy + j] = hy[cm ? (size_t)i + (size_t)j * rows : (size_t)i * k + j];
-        }
-        (void)hipFree(dx);
-        (void)hipFree(dy);
-    }
-    g4s_csr_destroy(A);
-    return st;
+    const unsigned cflags = flags & (G4S_DEVICE_POINTERS | G4S_SPMV_BLOCKED | G4S_SPMV_NO_NT);
+    if (dev)
+        return g4s::csr_one_shot(rows, cols, rowptr, colids, values, cflags, X, 0, Y, 0, false, [&](g4s_csr_t A, const double *dx, double *dy) {
+            return g4s_spmm(A, k, dx, ldx, dy, ldy, alpha, beta, flags & G4S_SPMM_COL_MAJOR, nullptr);
+        });
+    // host blocks are packed into compact device blocks (ld = k row-major, rows / cols column-major) and only the rows × k block of Y comes back
+    const size_t nx = (size_t)cols * (size_t)k, ny = (size_t)rows * (size_t)k;
+    std::vector<double> hx(nx), hy(ny);
+    auto pack = [&](const double *M, int64_t ld, int32_t n, double *out) {
+        for (int32_t i = 0; i < n; ++i)
+            for (int32_t j = 0; j < k; ++j) out[cm ? (size_t)i + (size_t)j * n : (size_t)i * k + j] = M[cm ? i + (int64_t)j * ld : (int64_t)i * ld + j];
+    };
+    if (cols > 0) pack(X, ldx, cols, hx.data());
+    if (beta != 0.0) pack(Y, ldy, rows, hy.data());
+    G4S_TRY(g4s::csr_one_shot(rows, cols, rowptr, colids, values, cflags, hx.data(), nx, hy.data(), ny, beta != 0.0, [&](g4s_csr_t A, const double *dx, double *dy) {
+        return g4s_spmm(A, k, dx, cm ? std::max(cols, 1) : k, dy, cm ? rows : k, alpha, beta, flags & G4S_SPMM_COL_MAJOR, nullptr);
+    }));
+    for (int32_t i = 0; i < rows; ++i)
+        for (int32_t j = 0; j < k; ++j) Y[cm ? i + (int64_t)j * ldy : (int64_t)i * ldy + j] = hy[cm ? (size_t)i + (size_t)j * rows : (size_t)i * k + j];
+    return G4S_OK;
 }

@@ -26,21 +26,6 @@ namespace {
 // entries (8 KiB of products) per workgroup: see the note behind the kernel for the sizes measured
 constexpr int kWG = 256, kTile = G4S_BCSR_TILE, kUnroll = kTile / kWG, kMaxBrows = 512;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        const hipError_t e = g4s::device_malloc(&p, n ? n : 1);
-        if (e != hipSuccess) return set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "hipMalloc(%zu): %s", n, hipGetErrorString(e));
-        bytes = n;
-        return G4S_OK;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // fail |= 1 unless block-row n (rows bn … bn+b−1) is b equal-length rows with identical, aligned column runs
 __global__ void bcsr_check_kernel(int nbr, int b, int tile_blocks, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colids, int *__restrict__ fail)
 {
@@ -221,11 +206,9 @@ static int bcsr_launch(BcsrPlan *P, const double *x, double *y, double alpha, do
     return G4S_OK;
 }
 
-int bcsr_spmv(BcsrPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s) { return bcsr_launch<semiring::PlusTimes>(P, x, y, alpha, beta, s); }
-
-int bcsr_spmv_semiring(BcsrPlan *P, const double *x, double *y, unsigned sr_flag, bool accumulate, hipStream_t s)
+int bcsr_spmv(BcsrPlan *P, const double *x, double *y, unsigned sr_flag, double alpha, double beta, hipStream_t s)
 {
-    return semiring::dispatch(sr_flag, [&](auto policy) { return bcsr_launch<decltype(policy)>(P, x, y, 1.0, accumulate ? 1.0 : 0.0, s); });
+    return semiring::dispatch(sr_flag, [&](auto policy) { return bcsr_launch<decltype(policy)>(P, x, y, alpha, beta, s); });
 }
 
 } // namespace g4s

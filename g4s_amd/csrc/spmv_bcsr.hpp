@@ -1,4 +1,4 @@
-// spmv_bcsr.hpp — interface of the block-row SpMV path (spmv_bcsr.hip) used by the CSR handle (spmv.hip).
+// spmv_bcsr.hpp — interface of the block-row SpMV path (spmv_bcsr.hip) used by the CSR handle (csr.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -11,6 +11,6 @@ int bcsr_update_values(BcsrPlan *plan, const int32_t *d_colids, const double *d_
 void bcsr_destroy(BcsrPlan *plan);
 long long bcsr_bytes(const BcsrPlan *plan);
 int bcsr_block(const BcsrPlan *plan);
-int bcsr_spmv(BcsrPlan *plan, const double *x, double *y, double alpha, double beta, hipStream_t stream);
-int bcsr_spmv_semiring(BcsrPlan *plan, const double *x, double *y, unsigned semiring, bool accumulate, hipStream_t stream);   // G4S_SEMIRING_* other than plus-times
+// `semiring`: a G4S_SEMIRING_* value; other than plus-times: y := A ⊗ x (beta != 0: y ⊕ (A ⊗ x)), alpha unused
+int bcsr_spmv(BcsrPlan *plan, const double *x, double *y, unsigned semiring, double alpha, double beta, hipStream_t stream);
 } // namespace g4s

@@ -66,22 +66,6 @@ __device__ __forceinline__ T pb_stream_load(const T *p)
 #endif
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        hipError_t e = g4s::device_malloc(&p, n);
-        if (e != hipSuccess) return set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "hipMalloc(%zu): %s", n, hipGetErrorString(e));
-        bytes = n;
-        return G4S_OK;
-    }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // A transient of the plan build: a piece of the build's arena (runtime.cpp: arena_enter … arena_leave around pb_build) — no driver call to get it and none to
 // give it back. (Round 5: the transients were hipMalloc / hipFree pairs, twenty of them per create, every hipFree a device-wide wait; and the first scratch
 // request of a process created the stream-ordered pool, 3 ms in the middle of the first create.)
@@ -927,20 +911,11 @@ static void pb_launch(PbPlan *P, const double *x, double *y, double alpha, doubl
                            P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta, P->band_end.as<int>());
 }
 
-int pb_spmv(PbPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
+int pb_spmv(PbPlan *P, const double *x, double *y, unsigned sr_flag, double alpha, double beta, hipStream_t s)
 {
-    if (P->W == kBandWide) pb_launch<kBandWide, semiring::PlusTimes>(P, x, y, alpha, beta, s);
-    else pb_launch<kBandNarrow, semiring::PlusTimes>(P, x, y, alpha, beta, s);
-    G4S_HIP_TRY(hipGetLastError());
-    return G4S_OK;
-}
-
-int pb_spmv_semiring(PbPlan *P, const double *x, double *y, unsigned sr_flag, bool accumulate, hipStream_t s)
-{
-    const double beta = accumulate ? 1.0 : 0.0;
     semiring::dispatch(sr_flag, [&](auto policy) {
-        if (P->W == kBandWide) pb_launch<kBandWide, decltype(policy)>(P, x, y, 1.0, beta, s);
-        else pb_launch<kBandNarrow, decltype(policy)>(P, x, y, 1.0, beta, s);
+        if (P->W == kBandWide) pb_launch<kBandWide, decltype(policy)>(P, x, y, alpha, beta, s);
+        else pb_launch<kBandNarrow, decltype(policy)>(P, x, y, alpha, beta, s);
     });
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;

@@ -1,4 +1,4 @@
-// spmv_pb.hpp — interface of the propagation-blocked SpMV path (spmv_pb.hip) used by the CSR handle (spmv.hip).
+// spmv_pb.hpp — interface of the propagation-blocked SpMV path (spmv_pb.hip) used by the CSR handle (csr.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,8 +9,7 @@ bool pb_has_value_map(const PbPlan *plan);
 int pb_update_values(PbPlan *plan, const double *d_values, hipStream_t stream);   // needs keep_value_map
 void pb_destroy(PbPlan *plan);
 long long pb_bytes(const PbPlan *plan);
-int pb_spmv(PbPlan *plan, const double *x, double *y, double alpha, double beta, hipStream_t stream);
-// y := A ⊗ x (accumulate: y ⊕ (A ⊗ x)) over the semiring of `semiring` (G4S_SEMIRING_MIN_PLUS / MAX_PLUS / OR_AND): exact and deterministic
-int pb_spmv_semiring(PbPlan *plan, const double *x, double *y, unsigned semiring, bool accumulate, hipStream_t stream);
+// y = alpha·A·x + beta·y for G4S_SEMIRING_PLUS_TIMES; for MIN_PLUS / MAX_PLUS / OR_AND y := A ⊗ x (beta != 0: y ⊕ (A ⊗ x)), alpha unused: exact and deterministic
+int pb_spmv(PbPlan *plan, const double *x, double *y, unsigned semiring, double alpha, double beta, hipStream_t stream);
 bool pb_should_use(int rows, int cols, long long nnz, const int *d_colids);
 } // namespace g4s

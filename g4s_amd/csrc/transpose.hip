@@ -17,7 +17,7 @@
 // products are the inner handle's g4s_spmv / g4s_spmv_semiring, and g4s_csr_update_values of A refreshes it with one gather through perm.
 #include "common.hpp"
 #include "prims.hpp"
-#include "transpose.hpp"
+#include "csr_handle.hpp"
 #include <algorithm>
 #include <new>
 
@@ -232,49 +232,47 @@ namespace {
 constexpr unsigned kInnerFlags = G4S_SPMV_NO_NT | G4S_SPMV_BLOCKED | G4S_SPMV_STREAM | G4S_SPMV_UPDATABLE;
 
 // §1 on the handle's device arrays, then the inner handle; NULL stream, synchronous. Nothing is kept on failure.
-int reserve(g4s_csr_t A, g4s::TransposeWork **slot, unsigned create_flags)
+int reserve(g4s_csr_t A)
 {
-    if (*slot) return G4S_OK;
-    g4s_csr_info inf{};
-    G4S_TRY(g4s_csr_get_info(A, &inf));
-    const int32_t *rp = nullptr, *ci = nullptr;
-    const double *va = nullptr;
-    G4S_TRY(g4s_csr_device_arrays(A, &rp, &ci, &va));
+    if (A->tr) return G4S_OK;
     G4S_HIP_TRY(hipDeviceSynchronize());                           // value updates and products on other streams are complete
     g4s::TransposeWork *w = new (std::nothrow) g4s::TransposeWork();
     if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
-    const size_t n = (size_t)inf.nnz;
-    int st = dev_array(&w->rowptr, (size_t)inf.cols + 1);
+    const size_t n = (size_t)A->nnz;
+    int st = dev_array(&w->rowptr, (size_t)A->cols + 1);
     if (st == G4S_OK) st = dev_array(&w->colids, n);
     if (st == G4S_OK) st = dev_array(&w->values, n);
     if (st == G4S_OK) st = dev_array(&w->perm, n);
-    if (st == G4S_OK) st = transpose_device(inf.rows, inf.cols, inf.nnz, rp, ci, va, w->rowptr, w->colids, w->values, w->perm, nullptr);
+    if (st == G4S_OK) st = transpose_device(A->rows, A->cols, A->nnz, A->d_rowptr, A->d_colids, A->d_values, w->rowptr, w->colids, w->values, w->perm, nullptr);
     if (st == G4S_OK)
-        st = g4s_csr_create(&w->inner, inf.cols, inf.rows, inf.nnz, w->rowptr, w->colids, w->values, (create_flags & kInnerFlags) | G4S_DEVICE_POINTERS);
+        st = g4s_csr_create(&w->inner, A->cols, A->rows, A->nnz, w->rowptr, w->colids, w->values, (A->flags & kInnerFlags) | G4S_DEVICE_POINTERS);
     if (st != G4S_OK) {
         g4s::transpose_work_destroy(w);
         return st;
     }
-    w->nnz = inf.nnz;
-    w->bytes = 4 * ((int64_t)inf.cols + 1) + 16 * inf.nnz + 4 * inf.nnz;
-    *slot = w;
+    w->nnz = A->nnz;
+    w->bytes = 4 * ((int64_t)A->cols + 1) + 16 * A->nnz + 4 * A->nnz;
+    A->tr = w;
     return G4S_OK;
 }
 
-// The handle's transpose for a product on `s`: reserved now (synchronously) if it does not exist yet, refused on a capturing stream.
-int ready(g4s_csr_t A, hipStream_t s, g4s::TransposeWork **out, const char *fn)
+// The checks of g4s_spmv with the two lengths swapped (the aliasing check comes before the handle is read), then the handle's transpose for a product on `s`:
+// reserved now (synchronously) if it does not exist yet, refused on a capturing stream. *inner stays NULL for an empty product.
+int ready(const char *fn, g4s_csr_t A, const double *x_dev, const double *y_dev, hipStream_t s, g4s_csr_t *inner)
 {
-    g4s::TransposeWork **slot = nullptr;
-    unsigned flags = 0;
-    G4S_TRY(g4s_csr_transpose_slot(A, &slot, &flags));
-    if (!*slot) {
+    *inner = nullptr;
+    if (!A) return g4s::set_error(G4S_ERR_INVALID, "%s: NULL handle", fn);
+    if (x_dev && (const void *)x_dev == (const void *)y_dev) return g4s::set_error(G4S_ERR_INVALID, "%s: x and y must not alias", fn);
+    G4S_TRY(g4s::check_spmv_args(fn, A, A->cols, x_dev, y_dev));
+    if (A->cols == 0) return G4S_OK;
+    if (!A->tr) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
         if (cs != hipStreamCaptureStatusNone)
             return g4s::set_error(G4S_ERR_INVALID, "%s: the handle has no transpose yet and the stream is capturing; call g4s_csr_transpose_reserve before the capture", fn);
-        G4S_TRY(reserve(A, slot, flags));
+        G4S_TRY(reserve(A));
     }
-    *out = *slot;
+    *inner = A->tr->inner;
     return G4S_OK;
 }
 
@@ -283,52 +281,30 @@ int ready(g4s_csr_t A, hipStream_t s, g4s::TransposeWork **out, const char *fn)
 G4S_API g4s_status g4s_csr_transpose_reserve(g4s_csr_t A)
 {
     G4S_REQUIRE(A, "NULL handle");
-    g4s::TransposeWork **slot = nullptr;
-    unsigned flags = 0;
-    G4S_TRY(g4s_csr_transpose_slot(A, &slot, &flags));
-    return reserve(A, slot, flags);
+    return reserve(A);
 }
 
 G4S_API g4s_status g4s_csr_transpose_info(g4s_csr_t A, g4s_csr_info *info)
 {
     G4S_REQUIRE(A && info, "NULL argument");
-    g4s::TransposeWork **slot = nullptr;
-    unsigned flags = 0;
-    G4S_TRY(g4s_csr_transpose_slot(A, &slot, &flags));
-    G4S_REQUIRE(*slot, "the handle has no transpose: call g4s_csr_transpose_reserve first");
-    G4S_TRY(g4s_csr_get_info((*slot)->inner, info));
-    info->plan_bytes += (*slot)->bytes;
+    G4S_REQUIRE(A->tr, "the handle has no transpose: call g4s_csr_transpose_reserve first");
+    G4S_TRY(g4s_csr_get_info(A->tr->inner, info));
+    info->plan_bytes += A->tr->bytes;
     return G4S_OK;
 }
 
-// y(cols) = alpha·Aᵀ·x(rows) + beta·y: the checks of g4s_spmv with the two lengths swapped (the aliasing check comes before the handle is read)
+// y(cols) = alpha·Aᵀ·x(rows) + beta·y
 G4S_API g4s_status g4s_spmv_transpose(g4s_csr_t A, const double *x_dev, double *y_dev, double alpha, double beta, void *stream)
 {
-    G4S_REQUIRE(A, "NULL handle");
-    G4S_REQUIRE(!x_dev || (const void *)x_dev != (const void *)y_dev, "x and y must not alias");
-    g4s_csr_info inf{};
-    G4S_TRY(g4s_csr_get_info(A, &inf));
-    if (inf.cols == 0) return G4S_OK;
-    G4S_REQUIRE(y_dev, "y is NULL");
-    G4S_REQUIRE(x_dev || inf.nnz == 0, "x is NULL");
-    const hipStream_t s = g4s::as_stream(stream);
-    g4s::TransposeWork *w = nullptr;
-    G4S_TRY(ready(A, s, &w, "g4s_spmv_transpose"));
-    return g4s_spmv(w->inner, x_dev, y_dev, alpha, beta, stream);
+    g4s_csr_t inner = nullptr;
+    G4S_TRY(ready(__func__, A, x_dev, y_dev, g4s::as_stream(stream), &inner));
+    return inner ? g4s_spmv(inner, x_dev, y_dev, alpha, beta, stream) : G4S_OK;
 }
 
 G4S_API g4s_status g4s_spmv_semiring_transpose(g4s_csr_t A, const double *x_dev, double *y_dev, unsigned flags, void *stream)
 {
     G4S_REQUIRE((flags & ~(G4S_SEMIRING_MASK | G4S_SPMV_ACCUMULATE)) == 0u, "g4s_spmv_semiring_transpose: flags other than G4S_SEMIRING_* | G4S_SPMV_ACCUMULATE");
-    G4S_REQUIRE(A, "NULL handle");
-    G4S_REQUIRE(!x_dev || (const void *)x_dev != (const void *)y_dev, "x and y must not alias");
-    g4s_csr_info inf{};
-    G4S_TRY(g4s_csr_get_info(A, &inf));
-    if (inf.cols == 0) return G4S_OK;
-    G4S_REQUIRE(y_dev, "y is NULL");
-    G4S_REQUIRE(x_dev || inf.nnz == 0, "x is NULL");
-    const hipStream_t s = g4s::as_stream(stream);
-    g4s::TransposeWork *w = nullptr;
-    G4S_TRY(ready(A, s, &w, "g4s_spmv_semiring_transpose"));
-    return g4s_spmv_semiring(w->inner, x_dev, y_dev, flags, stream);
+    g4s_csr_t inner = nullptr;
+    G4S_TRY(ready(__func__, A, x_dev, y_dev, g4s::as_stream(stream), &inner));
+    return inner ? g4s_spmv_semiring(inner, x_dev, y_dev, flags, stream) : G4S_OK;
 }

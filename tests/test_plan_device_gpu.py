@@ -1,4 +1,4 @@
-"""g4s_csr_create plans large device-resident matrices on the device (csrc/spmv.hip: build_plan_device); the host builder stays for small
+"""g4s_csr_create plans large device-resident matrices on the device (csrc/spmv.hip: stream_build_device); the host builder stays for small
 ones and for host arrays. Both must give the same products: bit-identical wherever rows are summed by one lane (stencil, band — including the
 short blocks the device builder's forced cuts leave), within 1e-10·Σ|terms| elsewhere; the long rows found must be the same."""
 import ctypes as C

@@ -1,5 +1,5 @@
-// xcd_probe.hip — which XCD does workgroup b of a 1-D launch run on? The XCD-aware walks of the SpMV kernels (csrc/spmv.hip: the diagonal path's plane-sliced
-// walk, the CSR kernel's per-XCD row runs) assume "XCD = b mod 8" (round-robin dispatch). The kernel records HW_REG_XCC_ID per workgroup; the host prints how
+// xcd_probe.hip — which XCD does workgroup b of a 1-D launch run on? The XCD-aware walks of the SpMV kernels (csrc/spmv_dia.hip: the diagonal path's plane-sliced
+// walk; csrc/spmv.hip: the CSR kernel's per-XCD row runs) assume "XCD = b mod 8" (round-robin dispatch). The kernel records HW_REG_XCC_ID per workgroup; the host prints how
 // consistent that is for launches of the shapes those kernels use.
 // Build: hipcc --offload-arch=gfx950 -O3 tools/xcd_probe.hip -o gpurun_out/xcd_probe
 #include <hip/hip_runtime.h>
