@@ -13,6 +13,7 @@ OK, ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_OVERFLOW, ERR_UNSUPPORTED = 0, -1, -2, 
 HOST_POINTERS, DEVICE_POINTERS, SORT_OUTPUT, SPMV_NO_NT, SPMV_BLOCKED, SPMV_STREAM, DIST_LOOPBACK, DIST_ALLGATHER, SPMV_UPDATABLE = 0, 1, 2, 4, 8, 16, 32, 64, 128
 SPMM_COL_MAJOR = 256
 SPMV_ACCUMULATE = 2048                                                   # semiring SpMV: y := y ⊕ (A ⊗ x) (g4s.h)
+TRAVERSE_PUSH, TRAVERSE_PULL, TRAVERSE_SYMMETRIC, TRAVERSE_BATCH = 4096, 8192, 16384, 16   # g4s_sssp / g4s_bfs (g4s.h)
 SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM / SpMV value semiring (g4s.h)
 PATTERN_ELEMENT_BLOCK_MATVEC, PATTERN_DENSE_ROW_TIMES_MATRIX, PATTERN_SYM_QUADRATIC_FORM = 1, 2, 3
 DENSE_DGEMM, DENSE_DSYMM, DENSE_DTRMM, DENSE_DGEMV, DENSE_DSYMV, DENSE_DTRMV, DENSE_DSPMV = 1, 2, 3, 4, 5, 6, 7
@@ -31,6 +32,12 @@ class CsrInfo(C.Structure):
                 ("stream_blocks", C.c_int32), ("long_rows", C.c_int32), ("long_chunks", C.c_int32),
                 ("tile_nnz", C.c_int32), ("tile_rows", C.c_int32), ("long_chunk_nnz", C.c_int32),
                 ("algorithmic_bytes", C.c_int64), ("plan_bytes", C.c_int64), ("spmv_path", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TraverseInfo(C.Structure):
+    """g4s_traverse_info: what a g4s_sssp / g4s_bfs call did."""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("push_steps", C.c_int32), ("pull_steps", C.c_int32),
+                ("host_waits", C.c_int32), ("reserved", C.c_int32), ("reached", C.c_int64), ("edges_relaxed", C.c_int64)]
 
 
 class DistInfo(C.Structure):
@@ -112,6 +119,9 @@ SIGNATURES = {
     "g4s_csr_transpose_info": (C.c_int, [vp, C.POINTER(CsrInfo)]),
     "g4s_spmv_transpose": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp]),
     "g4s_spmv_semiring_transpose": (C.c_int, [vp, vp, vp, C.c_uint, vp]),
+    "g4s_csr_traverse_reserve": (C.c_int, [vp, C.c_uint]),
+    "g4s_sssp": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint, C.POINTER(TraverseInfo), vp]),
+    "g4s_bfs": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint, C.POINTER(TraverseInfo), vp]),
     "g4s_spmm": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint, vp]),
     "g4s_csr_spmm_reserve": (C.c_int, [vp, C.c_int32]),
     "g4s_spmm_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint]),

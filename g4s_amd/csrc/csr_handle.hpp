@@ -1,4 +1,5 @@
-// csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip.
+// csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip,
+// traverse.hip.
 #pragma once
 #include "common.hpp"
 #include "spmv_stream.hpp"
@@ -19,6 +20,14 @@ struct TransposeWork;
 void transpose_work_destroy(TransposeWork *w);
 // tvalues[k] = values[perm[k]] on `stream`, then the inner handle's own g4s_csr_update_values (after the forward handle's update)
 int transpose_update_values(TransposeWork *w, const double *values, hipStream_t stream);
+// the kept arrays of Aᵀ and its inner handle (traverse.hip: the pull steps)
+void transpose_work_view(const TransposeWork *w, const int32_t **rowptr, const int32_t **colids, const double **values, g4s_csr_t *inner);
+
+// traverse.hip: the workspace of g4s_sssp / g4s_bfs (frontier queues, marks, the pull step's vector, the state block)
+struct TraverseWork;
+void traverse_work_destroy(TraverseWork *w);
+long long traverse_work_bytes(const TraverseWork *w);
+void traverse_values_changed(TraverseWork *w);   // g4s_csr_update_values: whether a stored value is zero has to be found out again
 
 } // namespace g4s
 
@@ -39,6 +48,7 @@ struct g4s_csr_s {
     g4s::BcsrPlan *bcsr = nullptr;      // block-row form of an assembled FE matrix (spmv_bcsr.hip)
     g4s::SpmmWork *spmm = nullptr;      // g4s_spmm's workspace (spmm.hip), built by g4s_csr_spmm_reserve or a first g4s_spmm
     g4s::TransposeWork *tr = nullptr;   // Aᵀ and its handle (transpose.hip), built by g4s_csr_transpose_reserve or a first transposed product
+    g4s::TraverseWork *trv = nullptr;   // g4s_sssp / g4s_bfs workspace (traverse.hip), built by g4s_csr_traverse_reserve or a first traversal
 };
 
 namespace g4s {

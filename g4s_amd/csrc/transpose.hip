@@ -216,6 +216,11 @@ void transpose_work_destroy(TransposeWork *w)
     delete w;
 }
 
+void transpose_work_view(const TransposeWork *w, const int32_t **rowptr, const int32_t **colids, const double **values, g4s_csr_t *inner)
+{
+    *rowptr = w->rowptr; *colids = w->colids; *values = w->values; *inner = w->inner;
+}
+
 int transpose_update_values(TransposeWork *w, const double *values, hipStream_t s)
 {
     if (w->nnz > 0) {

@@ -1,0 +1,571 @@
+// traverse.hip — g4s_sssp and g4s_bfs (include/g4s.h): single-source / multi-source shortest paths and BFS levels on a CSR handle stored by
+// out-edges, with a per-step choice between a push from the frontier and the dense pull d := d ⊕ (Aᵀ ⊗ d).
+//
+// State lives on the device (traverse.hpp, TravState): two frontier queues, the length and out-edge count of the current one, the step counter
+// and a `stop` word. Every step is ONE kernel; the workgroup that finishes last (a ticket counter, no waiting) swaps the queues, counts the
+// step and sets `stop`: 1 frontier empty, 2 iteration cap, 3 the next step wants to pull, 4 the frontier outgrew the launch grid. A kernel
+// that finds stop != 0 returns at once, so the host enqueues kBatch (doubling to kBatchMax) push launches blind and reads the 80-byte state once per batch, as
+// g4s_conj_grad does. Kernel boundaries are the only ordering between workgroups; nothing spins and every loop is bounded by
+// the queue length (<= rows) or a row length.
+//
+//   push    a workgroup takes 256 queue entries, scans their degrees in LDS and its lanes walk the concatenated edge range (binary search in
+//           the scan, monotone per lane). Vertices above kHubCut edges sit at the BACK of the queue and are walked by all workgroups in
+//           chunks of kHubChunk edges. SSSP: cand = d[u] + w; plain load of d[v]; global_atomic_min_f64 only when cand < d[v]; the vertex is
+//           appended when the atomic returned a larger value and its step stamp (atomicMax on mark[v]) shows it is not queued yet.
+//           BFS: compare-and-swap of level[v] from −1. Appends are one atomicAdd per wave.
+//   pull    SSSP: y := Aᵀ ⊗ d by the inner handle's semiring kernels (any path), then sssp_combine_kernel: d := min(d, y), the changed vertices
+//           are the next queue. BFS: bfs_pull_kernel over the arrays of Aᵀ, LPR lanes per unvisited vertex, stopping at the first in-edge
+//           whose tail has level == step (the level array IS the frontier set; a vertex is written by its own group only).
+// Where it loses (profiles/traverse.txt): a traversal of a few dense steps — configs[1] from its hub, 8 steps — is faster as the host loop over
+// g4s_spmv_semiring_transpose (3.8 ms against 8.4 for SSSP, 4.0 against 14.0 for BFS): every changed vertex goes through append()'s one tail counter,
+// which holds a step to about 7 G edges/s, in push and pull alike. It wins where steps are many and frontiers small (1000 x 1000 grid: 1.4x / 3.7x).
+// min is order-independent and IEEE addition is monotone, so every schedule ends at the same bits (g4s.h has the argument).
+#include "common.hpp"
+#include "csr_handle.hpp"
+#include "readback.hpp"
+#include "traverse.hpp"
+#include <algorithm>
+#include <climits>
+#include <new>
+#include <vector>
+
+namespace {
+
+using g4s::TravState;
+
+constexpr int WG = 256;
+constexpr int kHubCut = 4096;     // a queued vertex with more out-edges goes to the hub end of the queue
+constexpr int kHubChunk = 1024;   // edges of a hub per workgroup visit
+constexpr int kBatch = G4S_TRAVERSE_BATCH;   // push launches behind one state read, at least; doubles up to kBatchMax
+constexpr int kBatchMax = 64;
+constexpr long long kEdgesPerWg = 2048;      // the launch grid of a batch: one workgroup per 2048 frontier edges, 8..2 per CU
+constexpr long long kGridGrowth = 8;         // stop = 4 once the frontier has 8 times the edges the grid was sized for
+
+enum { KIND_INIT = 0, KIND_PUSH = 1, KIND_PULL = 2 };
+
+struct StepArgs {
+    long long nnz;
+    long long threshold;   // a frontier with more out-edges wants a pull (auto); −1: always pull; LLONG_MAX: never
+    long long grid_cap;    // push only: more out-edges than this ask for a larger grid
+    int max_iter;
+    int resume;            // push only: the first launch of a batch goes on from stop == 4
+};
+
+// One atomicAdd per wave for the vertices its lanes append. Called by every lane that is active at the call site.
+__device__ __forceinline__ void append(bool want, int v, int deg, int rows, int *__restrict__ q, TravState *st, long long &deg_sum)
+{
+    const bool hub = want && deg > kHubCut;
+    const bool nor = want && !hub;
+    const unsigned long long m = __ballot(nor);
+    if (nor) {
+        const int lane = __lane_id();
+        const int leader = __ffsll((long long)m) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(&st->n_next, __popcll(m));
+        base = __shfl(base, leader);
+        const int idx = base + __popcll(m & ((1ull << lane) - 1ull));
+        if ((unsigned)idx < (unsigned)rows) q[idx] = v;            // a vertex is appended once per step: idx < rows by construction
+    }
+    if (hub) {
+        const int h = atomicAdd(&st->n_hub_next, 1);
+        if ((unsigned)h < (unsigned)rows) q[rows - 1 - h] = v;
+    }
+    if (want) deg_sum += deg;
+}
+
+// The end of a step kernel: the block's share of the next frontier's out-edges, then the ticket; the last block to arrive turns the page.
+__device__ __forceinline__ void finish(TravState *st, long long deg_sum, int kind, const StepArgs a)
+{
+    __shared__ long long s_red[WG / 64];
+    __shared__ int s_last;
+    for (int o = 32; o > 0; o >>= 1) deg_sum += __shfl_down(deg_sum, o);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = deg_sum;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long sum = 0;
+        for (int w = 0; w < (int)blockDim.x / 64; ++w) sum += s_red[w];
+        if (sum) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)sum);
+        __threadfence();
+        s_last = atomicAdd(&st->tickets, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last || threadIdx.x != 0) return;
+    __threadfence();
+    const int n = atomicAdd(&st->n_next, 0), nh = atomicAdd(&st->n_hub_next, 0);
+    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
+    if (kind == KIND_PUSH) { st->edges_relaxed += st->edges_cur; st->push_steps += 1; st->iter += 1; }
+    if (kind == KIND_PULL) { st->edges_relaxed += a.nnz; st->pull_steps += 1; st->iter += 1; }
+    st->n_cur = n; st->n_hub_cur = nh; st->edges_cur = e;
+    st->n_next = 0; st->n_hub_next = 0; st->edges_next = 0;
+    st->cur ^= 1;
+    st->tickets = 0;
+    st->stop = (n + nh == 0) ? 1 : (st->iter >= a.max_iter ? 2 : (e > a.threshold ? 3 : (e > a.grid_cap ? 4 : 0)));
+}
+
+template <bool BFS>
+__global__ __launch_bounds__(WG) void init_fill_kernel(int rows, double *__restrict__ dist, int *__restrict__ level, int *__restrict__ mark)
+{
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) {
+        if constexpr (BFS) level[i] = -1;
+        else { dist[i] = __builtin_inf(); mark[i] = 0; }
+    }
+}
+
+// One workgroup: the state from zero, the (distinct) sources at 0 and in queue 0. `src` is queue 1, where the host staged them.
+template <bool BFS>
+__global__ __launch_bounds__(WG) void init_sources_kernel(int rows, int n_src, const int *__restrict__ src, const int *__restrict__ rowptr, double *__restrict__ dist,
+                                                          int *__restrict__ level, int *__restrict__ q0, TravState *st, const StepArgs a)
+{
+    if (threadIdx.x == 0) {
+        const int zero_values = st->zero_values;
+        *st = TravState{};
+        st->zero_values = zero_values;
+        st->cur = 1;                                               // finish() flips it: queue 0 is the first frontier
+    }
+    __syncthreads();
+    long long deg_sum = 0;
+    for (int i0 = 0; i0 < n_src; i0 += WG) {
+        const int i = i0 + (int)threadIdx.x;
+        const bool valid = i < n_src;
+        int v = 0, deg = 0;
+        if (valid) {
+            v = src[i];
+            deg = rowptr[v + 1] - rowptr[v];
+            if constexpr (BFS) level[v] = 0;
+            else dist[v] = 0.0;
+        }
+        append(valid, v, deg, rows, q0, st, deg_sum);
+    }
+    finish(st, deg_sum, KIND_INIT, a);
+}
+
+// One relaxation of the edge u → v (entry k); true when v has to join the next frontier.
+template <bool BFS, bool VALUES>
+__device__ __forceinline__ bool relax(int k, int v, double du, int stamp, const double *__restrict__ values, double *dist, int *level, int *mark)
+{
+    if constexpr (BFS) {
+        if constexpr (VALUES) {
+            if (!(values[k] != 0.0)) return false;                 // or-and: a stored 0.0 is no edge (NaN counts as one)
+        }
+        if (level[v] != -1) return false;
+        return atomicCAS(level + v, -1, stamp) == -1;
+    } else {
+        const double cand = du + values[k];
+        if (!(cand < dist[v])) return false;                       // a stale read is only ever too large: the atomic below decides
+        const double old = __hip_atomic_fetch_min(dist + v, cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!(cand < old)) return false;
+        return atomicMax(mark + v, stamp) < stamp;                 // first improvement of v in this step
+    }
+}
+
+template <bool BFS, bool VALUES>
+__global__ __launch_bounds__(WG) void push_kernel(int rows, const int *__restrict__ rowptr, const int *__restrict__ colids, const double *__restrict__ values,
+                                                  double *dist, int *level, int *mark, int *q0, int *q1, TravState *st, const StepArgs a)
+{
+    __shared__ int s_scan[WG + 1];
+    __shared__ int s_start[WG];
+    __shared__ double s_du[WG];
+    __shared__ int s_wsum[WG / 64];
+    if (st->stop != 0 && !(st->stop == 4 && a.resume)) return;     // the same word for every block: it changes only after the last ticket
+    const int cur = st->cur, n = st->n_cur, nh = st->n_hub_cur, stamp = st->iter + 1;
+    const int *q = cur ? q1 : q0;
+    int *qn = cur ? q0 : q1;
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, G = (int)gridDim.x;
+    long long deg_sum = 0;
+
+    for (int s0 = (int)blockIdx.x * WG; s0 < n; s0 += G * WG) {
+        const int i = s0 + t;
+        int start = 0, deg = 0;
+        double du = 0.0;
+        if (i < n) {
+            const int u = q[i];
+            start = rowptr[u];
+            deg = rowptr[u + 1] - start;
+            if constexpr (!BFS) du = dist[u];
+        }
+        int x = deg;                                               // inclusive scan of the 256 degrees
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_wsum[wave] = x;
+        s_start[t] = start;
+        s_du[t] = du;
+        __syncthreads();
+        int off = 0;
+        for (int w = 0; w < wave; ++w) off += s_wsum[w];
+        s_scan[t + 1] = off + x;
+        if (t == 0) s_scan[0] = 0;
+        __syncthreads();
+        const int total = s_scan[WG];                              // distinct vertices: at most nnz <= INT32_MAX
+        int lo = 0;                                                // the last entry with s_scan[lo] <= e: never decreases as e grows
+        for (int e0 = 0; e0 < total; e0 += WG) {
+            const int e = e0 + t;
+            bool want = false;
+            int v = 0, vdeg = 0;
+            if (e < total) {
+                int hi = WG - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (s_scan[mid] <= e) lo = mid;
+                    else hi = mid - 1;
+                }
+                const int k = s_start[lo] + (e - s_scan[lo]);
+                v = colids[k];
+                want = relax<BFS, VALUES>(k, v, s_du[lo], stamp, values, dist, level, mark);
+                if (want) vdeg = rowptr[v + 1] - rowptr[v];
+            }
+            append(want, v, vdeg, rows, qn, st, deg_sum);
+        }
+        __syncthreads();
+    }
+
+    for (int h = 0; h < nh; ++h) {                                 // hubs: chunk c of hub h belongs to block (c + 4h) mod G
+        const int u = q[rows - 1 - h];
+        const int start = rowptr[u], deg = rowptr[u + 1] - start;
+        const double du = BFS ? 0.0 : dist[u];
+        const int chunks = (deg + kHubChunk - 1) / kHubChunk;
+        int first = (int)(((long long)blockIdx.x - 4ll * h) % G);
+        if (first < 0) first += G;
+        for (int c = first; c < chunks; c += G) {
+            for (int j = 0; j < kHubChunk; j += WG) {
+                const int e = c * kHubChunk + j + t;
+                bool want = false;
+                int v = 0, vdeg = 0;
+                if (e < deg) {
+                    const int k = start + e;
+                    v = colids[k];
+                    want = relax<BFS, VALUES>(k, v, du, stamp, values, dist, level, mark);
+                    if (want) vdeg = rowptr[v + 1] - rowptr[v];
+                }
+                append(want, v, vdeg, rows, qn, st, deg_sum);
+            }
+        }
+    }
+    finish(st, deg_sum, KIND_PUSH, a);
+}
+
+// The second half of an SSSP pull step: y = Aᵀ ⊗ d has been computed; d := min(d, y), and the vertices that changed are the next frontier.
+__global__ __launch_bounds__(WG) void sssp_combine_kernel(int rows, const int *__restrict__ rowptr, double *__restrict__ dist, const double *__restrict__ y, int *q0, int *q1,
+                                                          TravState *st, const StepArgs a)
+{
+    int *qn = st->cur ? q0 : q1;
+    long long deg_sum = 0;
+    for (long long i0 = (long long)blockIdx.x * WG; i0 < rows; i0 += (long long)gridDim.x * WG) {
+        const long long i = i0 + threadIdx.x;
+        bool want = false;
+        int deg = 0;
+        if (i < rows) {
+            const double yv = y[i];
+            if (yv < dist[i]) {
+                dist[i] = yv;
+                want = true;
+                deg = rowptr[i + 1] - rowptr[i];
+            }
+        }
+        append(want, (int)i, deg, rows, qn, st, deg_sum);
+    }
+    finish(st, deg_sum, KIND_PULL, a);
+}
+
+// Bottom-up BFS step on Aᵀ (row v: the tails u of the edges u → v): LPR lanes per unvisited vertex, done at the first tail in the frontier.
+template <int LPR, bool VALUES>
+__global__ __launch_bounds__(WG) void bfs_pull_kernel(int rows, const int *__restrict__ rowptr, const int *__restrict__ trowptr, const int *__restrict__ tcolids,
+                                                      const double *__restrict__ tvalues, int *level, int *q0, int *q1, TravState *st, const StepArgs a)
+{
+    constexpr int GPB = WG / LPR;
+    int *qn = st->cur ? q0 : q1;
+    const int depth = st->iter, stamp = depth + 1;
+    const int t = (int)threadIdx.x, lig = t % LPR, lane = t & 63;
+    const unsigned long long gmask = LPR == 64 ? ~0ull : (((1ull << (LPR % 64)) - 1ull) << (lane - lig));
+    long long deg_sum = 0;
+    for (long long r0 = (long long)blockIdx.x * GPB; r0 < rows; r0 += (long long)gridDim.x * GPB) {
+        const long long v = r0 + t / LPR;
+        bool found = false;
+        if (v < rows && level[v] == -1) {
+            const int end = trowptr[v + 1];
+            for (int k0 = trowptr[v]; k0 < end; k0 += LPR) {       // the same trip count for the lanes of a group
+                const int k = k0 + lig;
+                bool hit = false;
+                if (k < end) {
+                    hit = level[tcolids[k]] == depth;
+                    if constexpr (VALUES) hit = hit && (tvalues[k] != 0.0);
+                }
+                if constexpr (LPR > 1) hit = (__ballot(hit) & gmask) != 0ull;
+                if (hit) { found = true; break; }
+            }
+        }
+        const bool want = found && lig == 0;
+        int deg = 0;
+        if (want) {
+            level[v] = stamp;                                      // written by v's own group only; readers compare with `depth`, never with stamp
+            deg = rowptr[v + 1] - rowptr[v];
+        }
+        append(want, (int)v, deg, rows, qn, st, deg_sum);
+    }
+    finish(st, deg_sum, KIND_PULL, a);
+}
+
+// reached := vertices with a finite distance / a level >= 0, once the traversal has ended (stop 1 or 2); a no-op before.
+template <bool BFS>
+__global__ __launch_bounds__(WG) void count_kernel(int rows, const double *__restrict__ dist, const int *__restrict__ level, TravState *st)
+{
+    __shared__ int s_red[WG / 64];
+    if (st->stop != 1 && st->stop != 2) return;
+    int c = 0;
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) c += BFS ? (level[i] >= 0) : (dist[i] < __builtin_inf());
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long sum = 0;
+        for (int w = 0; w < WG / 64; ++w) sum += s_red[w];
+        if (sum) atomicAdd((unsigned long long *)&st->reached, (unsigned long long)sum);
+    }
+}
+
+// zero_values |= 1 when a stored value is 0.0: BFS then has to read the values (or-and: a stored zero is no edge)
+__global__ __launch_bounds__(WG) void any_zero_kernel(long long nnz, const double *__restrict__ values, TravState *st)
+{
+    int z = 0;
+    for (long long k = (long long)blockIdx.x * WG + threadIdx.x; k < nnz; k += (long long)gridDim.x * WG) z |= values[k] == 0.0;
+    if (z) atomicOr(&st->zero_values, 1);
+}
+
+inline int grid_rows(long long n, int cus) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, 8LL * cus)); }
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------ the handle's workspace
+namespace g4s {
+
+struct TraverseWork {
+    int32_t *queue[2] = {nullptr, nullptr};   // rows ints each: frontier vertices from the front, hubs from the back
+    int32_t *mark = nullptr;                  // rows ints: the step in which a vertex last joined a queue (SSSP)
+    double *dist2 = nullptr;                  // rows doubles: y of the pull step
+    TravState *state = nullptr;
+    int cus = 1;
+    int values_state = 0;                     // 0 unknown, 1 no stored value is zero, 2 some are
+    int64_t bytes = 0;
+};
+
+void traverse_work_destroy(TraverseWork *w)
+{
+    if (!w) return;
+    (void)hipFree(w->queue[0]);
+    (void)hipFree(w->queue[1]);
+    (void)hipFree(w->mark);
+    (void)hipFree(w->dist2);
+    (void)hipFree(w->state);
+    delete w;
+}
+
+long long traverse_work_bytes(const TraverseWork *w) { return w ? w->bytes : 0; }
+
+void traverse_values_changed(TraverseWork *w) { if (w) w->values_state = 0; }
+
+} // namespace g4s
+
+namespace {
+
+constexpr unsigned kDirFlags = G4S_TRAVERSE_PUSH | G4S_TRAVERSE_PULL;
+constexpr unsigned kAllFlags = kDirFlags | G4S_TRAVERSE_SYMMETRIC;
+
+// Does any stored value equal 0.0? One pass and one read, at reserve and after g4s_csr_update_values. Synchronises `s`.
+int scan_values(g4s_csr_s *A, hipStream_t s, int *waits)
+{
+    g4s::TraverseWork *w = A->trv;
+    if (w->values_state != 0) return G4S_OK;
+    int h = 0;
+    if (A->nnz > 0) {
+        G4S_HIP_TRY(hipMemsetAsync(&w->state->zero_values, 0, sizeof(int), s));
+        hipLaunchKernelGGL(any_zero_kernel, dim3(grid_rows(A->nnz, w->cus)), dim3(WG), 0, s, (long long)A->nnz, A->d_values, w->state);
+        G4S_HIP_TRY(hipGetLastError());
+        G4S_HIP_TRY(g4s::read_small(&h, &w->state->zero_values, sizeof(int), s));
+        G4S_HIP_TRY(g4s::reads_sync(s));
+        if (waits) *waits += 1;
+    }
+    w->values_state = h ? 2 : 1;
+    return G4S_OK;
+}
+
+// The workspace (once) and, unless the flags rule a pull out or declare A symmetric, the handle's transpose. NULL stream, synchronous.
+int reserve(g4s_csr_s *A, unsigned flags)
+{
+    if (!A->trv) {
+        g4s::TraverseWork *w = new (std::nothrow) g4s::TraverseWork();
+        if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
+        const size_t n = (size_t)std::max(A->rows, 1);
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->queue[0], sizeof(int32_t) * n);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->queue[1], sizeof(int32_t) * n);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->mark, sizeof(int32_t) * n);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->dist2, sizeof(double) * n);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->state, sizeof(TravState));
+        if (e == hipSuccess) e = hipMemset(w->state, 0, sizeof(TravState));
+        if (e != hipSuccess) {
+            g4s::traverse_work_destroy(w);
+            return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "g4s_csr_traverse_reserve: %s", hipGetErrorString(e));
+        }
+        w->cus = std::max(w->cus, 1);
+        w->bytes = (int64_t)(3 * sizeof(int32_t) + sizeof(double)) * (int64_t)n + (int64_t)sizeof(TravState);
+        A->trv = w;
+    }
+    G4S_TRY(scan_values(A, nullptr, nullptr));
+    if (!(flags & (G4S_TRAVERSE_SYMMETRIC | G4S_TRAVERSE_PUSH)) && !A->tr) G4S_TRY(g4s_csr_transpose_reserve(A));
+    return G4S_OK;
+}
+
+// push while the frontier has at most nnz / alpha out-edges. Defaults from the sweep in profiles/traverse.txt: SSSP 8 (configs[1]: 8.4 ms
+// against 8.9 at 16, 8.5 at 4, 16.1 at 2); BFS 1, i.e. never pull — on configs[1] the bottom-up step loses to the push at every switch point measured
+// (14.0 ms at 1, 16.5 at 2, 24.5 at 4..64). The grid of configs[0] never reaches either threshold.
+double switch_alpha(bool bfs)
+{
+    if (const char *e = getenv("G4S_TRAVERSE_ALPHA")) {
+        const double a = atof(e);
+        if (a > 0.0) return a;
+    }
+    return bfs ? 1.0 : 8.0;
+}
+
+template <bool BFS>
+int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *dist, int32_t *level, int32_t cap, unsigned flags, g4s_traverse_info *info, hipStream_t s)
+{
+    const char *fn = BFS ? "g4s_bfs" : "g4s_sssp";
+    if (A->rows != A->cols) return g4s::set_error(G4S_ERR_INVALID, "%s: the handle is %d x %d, a traversal needs a square matrix", fn, A->rows, A->cols);
+    std::vector<int32_t> src(sources, sources + n_sources);
+    for (int32_t v : src)
+        if (v < 0 || v >= A->rows) return g4s::set_error(G4S_ERR_INVALID, "%s: source %d is outside [0, %d)", fn, v, A->rows);
+    std::sort(src.begin(), src.end());
+    src.erase(std::unique(src.begin(), src.end()), src.end());
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its state back and cannot be captured", fn);
+
+    const bool symmetric = (flags & G4S_TRAVERSE_SYMMETRIC) != 0;
+    const int mode = (flags & G4S_TRAVERSE_PUSH) ? KIND_PUSH : (flags & G4S_TRAVERSE_PULL) ? KIND_PULL : 0;
+    if (!A->trv || (mode != KIND_PUSH && !symmetric && !A->tr)) G4S_TRY(reserve(A, flags));
+    g4s::TraverseWork *w = A->trv;
+    int waits = 0;
+    if (BFS) G4S_TRY(scan_values(A, s, &waits));
+    const bool values = w->values_state == 2;
+
+    // the pull side: Aᵀ (its inner handle and arrays), or A itself when the caller declares it symmetric
+    g4s_csr_t pull_handle = A;
+    const int32_t *trowptr = A->d_rowptr, *tcolids = A->d_colids;
+    const double *tvalues = A->d_values;
+    if (mode != KIND_PUSH && !symmetric) g4s::transpose_work_view(A->tr, &trowptr, &tcolids, &tvalues, &pull_handle);
+
+    const int rows = A->rows;
+    StepArgs a;
+    a.nnz = A->nnz;
+    a.max_iter = cap > 0 ? cap : (BFS ? INT_MAX : rows);
+    a.threshold = mode == KIND_PUSH ? LLONG_MAX : mode == KIND_PULL ? -1 : (long long)((double)A->nnz / switch_alpha(BFS));
+    a.grid_cap = LLONG_MAX;
+    a.resume = 0;
+    const int max_grid = 2 * w->cus, min_grid = 8;
+    TravState *st = w->state;
+    int *q0 = w->queue[0], *q1 = w->queue[1];
+
+    auto fail = [&](int code) { (void)g4s::reads_sync(s); return code; };   // also settles a noted read of h
+#define TV_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(g4s::set_error(G4S_ERR_HIP, "%s: %s: %s", fn, #expr, hipGetErrorString(e_))); } while (0)
+    TV_HIP(hipMemcpyAsync(q1, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(init_fill_kernel<BFS>, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, dist, level, w->mark);
+    hipLaunchKernelGGL(init_sources_kernel<BFS>, dim3(1), dim3(WG), 0, s, rows, (int)src.size(), q1, A->d_rowptr, dist, level, q0, st, a);
+    TV_HIP(hipGetLastError());
+
+    TravState h{};
+    h.stop = mode == KIND_PULL ? 3 : 0;                            // what the init kernel is bound to decide when the direction is forced
+    bool know = false;                                             // h is the device's state
+    int batch = kBatch;
+    for (;;) {
+        if (h.stop == 3) {                                         // one pull step
+            if constexpr (BFS) {
+                const long long avg = rows ? A->nnz / rows : 0;
+                const int g = grid_rows((long long)rows * (avg <= 4 ? 4 : avg <= 16 ? 16 : 64), w->cus);
+#define TV_PULL(LPR) do { if (values) hipLaunchKernelGGL((bfs_pull_kernel<LPR, true>), dim3(g), dim3(WG), 0, s, rows, A->d_rowptr, trowptr, tcolids, tvalues, level, q0, q1, st, a); \
+                          else hipLaunchKernelGGL((bfs_pull_kernel<LPR, false>), dim3(g), dim3(WG), 0, s, rows, A->d_rowptr, trowptr, tcolids, tvalues, level, q0, q1, st, a); } while (0)
+                if (avg <= 4) TV_PULL(4);
+                else if (avg <= 16) TV_PULL(16);
+                else TV_PULL(64);
+#undef TV_PULL
+            } else {
+                const int st_mv = g4s_spmv_semiring(pull_handle, dist, w->dist2, G4S_SEMIRING_MIN_PLUS, s);
+                if (st_mv != G4S_OK) return fail(st_mv);
+                hipLaunchKernelGGL(sssp_combine_kernel, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, A->d_rowptr, dist, w->dist2, q0, q1, st, a);
+            }
+            TV_HIP(hipGetLastError());
+        }
+        if (mode != KIND_PULL) {                                   // a batch of push steps: no-ops from the first stop on
+            int grid = max_grid;
+            if (know && h.stop != 3) grid = (int)std::max((long long)min_grid, std::min((long long)max_grid, (h.edges_cur + h.n_cur + h.n_hub_cur) / kEdgesPerWg));
+            a.grid_cap = grid == max_grid ? LLONG_MAX : (long long)grid * kEdgesPerWg * kGridGrowth;
+            for (int b = 0; b < batch; ++b) {
+                a.resume = b == 0;
+                if (values || !BFS) hipLaunchKernelGGL((push_kernel<BFS, true>), dim3(grid), dim3(WG), 0, s, rows, A->d_rowptr, A->d_colids, A->d_values, dist, level, w->mark, q0, q1, st, a);
+                else hipLaunchKernelGGL((push_kernel<BFS, false>), dim3(grid), dim3(WG), 0, s, rows, A->d_rowptr, A->d_colids, A->d_values, dist, level, w->mark, q0, q1, st, a);
+            }
+            TV_HIP(hipGetLastError());
+            a.grid_cap = LLONG_MAX;
+            a.resume = 0;
+            if (know) batch = std::min(kBatchMax, batch * 2);
+        }
+        hipLaunchKernelGGL(count_kernel<BFS>, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, dist, level, st);
+        TV_HIP(hipGetLastError());
+        TV_HIP(g4s::read_small(&h, st, sizeof(TravState), s));
+        TV_HIP(g4s::reads_sync(s));
+        ++waits;
+        know = true;
+        if (h.stop == 1 || h.stop == 2) break;
+    }
+#undef TV_HIP
+    if (info) {
+        info->iterations = h.iter;
+        info->converged = h.stop == 1;
+        info->push_steps = h.push_steps;
+        info->pull_steps = h.pull_steps;
+        info->host_waits = waits;
+        info->reserved = 0;
+        info->reached = h.reached;
+        info->edges_relaxed = h.edges_relaxed;
+    }
+    return G4S_OK;
+}
+
+int check_args(const char *fn, g4s_csr_t A, const int32_t *sources, int32_t n_sources, const void *out, int32_t cap, unsigned flags)
+{
+    const char *what = (flags & ~kAllFlags) ? "flags other than G4S_TRAVERSE_PUSH / _PULL / _SYMMETRIC"
+                       : (flags & kDirFlags) == kDirFlags ? "G4S_TRAVERSE_PUSH and G4S_TRAVERSE_PULL together"
+                       : !A ? "NULL handle" : !sources ? "sources is NULL" : !out ? "the output array is NULL"
+                       : n_sources < 1 ? "n_sources < 1" : cap < 0 ? "negative iteration cap" : nullptr;
+    return what ? g4s::set_error(G4S_ERR_INVALID, "%s: %s", fn, what) : (int)G4S_OK;
+}
+
+} // namespace
+
+G4S_API g4s_status g4s_csr_traverse_reserve(g4s_csr_t A, unsigned flags)
+{
+    G4S_REQUIRE((flags & ~kAllFlags) == 0u, "flags other than G4S_TRAVERSE_PUSH / _PULL / _SYMMETRIC");
+    G4S_REQUIRE((flags & kDirFlags) != kDirFlags, "G4S_TRAVERSE_PUSH and G4S_TRAVERSE_PULL together");
+    G4S_REQUIRE(A, "NULL handle");
+    G4S_REQUIRE(A->rows == A->cols, "a traversal needs a square matrix");
+    G4S_HIP_TRY(hipDeviceSynchronize());
+    return reserve(A, flags);
+}
+
+G4S_API g4s_status g4s_sssp(g4s_csr_t A, const int32_t *sources, int32_t n_sources, double *dist_dev, int32_t max_iterations, unsigned flags,
+                            g4s_traverse_info *info, void *stream)
+{
+    G4S_TRY(check_args(__func__, A, sources, n_sources, dist_dev, max_iterations, flags));
+    return traverse<false>(A, sources, n_sources, dist_dev, nullptr, max_iterations, flags, info, g4s::as_stream(stream));
+}
+
+G4S_API g4s_status g4s_bfs(g4s_csr_t A, const int32_t *sources, int32_t n_sources, int32_t *level_dev, int32_t max_depth, unsigned flags,
+                           g4s_traverse_info *info, void *stream)
+{
+    G4S_TRY(check_args(__func__, A, sources, n_sources, level_dev, max_depth, flags));
+    return traverse<true>(A, sources, n_sources, nullptr, level_dev, max_depth, flags, info, g4s::as_stream(stream));
+}

@@ -7,6 +7,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   spmv_semiring  — the same over min-plus, max-plus or or-and (SEMIRINGS): y = A ⊗ x, or y ⊕ (A ⊗ x)
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
   csr_transpose  — Aᵀ as a CSR (the CSC form of A; mm/inc/CSR.h:171-230, mm/inc/convert.h), stable: entries of a column keep their order
+  sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
   spmv_transpose — y = alpha·Aᵀ·x + beta·y on a handle of A (spmv_semiring_transpose: the semiring form), through the handle's own transpose
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
 """
@@ -131,6 +132,32 @@ class CSR:
         capi.check(capi.load().g4s_spmv_semiring_transpose(self.handle, _ptr(x), _ptr(y), flags, _stream()))
         return y
 
+    def traverse_reserve(self, symmetric=False, direction="auto"):
+        """Build now what sssp / bfs need (g4s_csr_traverse_reserve; synchronous): the workspace and — unless symmetric or direction="push" — Aᵀ."""
+        flags = _traverse_flags(direction, symmetric)
+        torch.cuda.current_stream().synchronize()
+        capi.check(capi.load().g4s_csr_traverse_reserve(self.handle, flags))
+
+    def _traverse(self, fn, sources, out, cap, direction, symmetric):
+        flags = _traverse_flags(direction, symmetric)
+        src = np.ascontiguousarray(np.atleast_1d(np.asarray(sources)), dtype=np.int32)
+        info = capi.TraverseInfo()
+        capi.check(getattr(capi.load(), fn)(self.handle, C.c_void_p(src.ctypes.data), int(src.size), _ptr(out), int(cap), flags, C.byref(info), _stream()))
+        return out, {n: getattr(info, n) for n, _ in capi.TraverseInfo._fields_ if n != "reserved"}
+
+    def sssp(self, sources, max_iterations=0, direction="auto", symmetric=False):
+        """Shortest-path distances from the nearest of `sources` (vertex ids; an int or a sequence) over the edges i → j of row i, weight a_ij
+        (g4s_sssp): (float64 tensor of rows, +inf where unreached; info dict). Exact: the min-plus fixed point, the same bits for every direction
+        ("auto", "push", "pull"). max_iterations=0: rows. symmetric=True declares A == Aᵀ, so no transpose is built. Synchronous."""
+        _traverse_flags(direction, symmetric)
+        return self._traverse("g4s_sssp", sources, torch.empty(self.rows, dtype=torch.float64, device=self.rowptr.device), max_iterations, direction, symmetric)
+
+    def bfs(self, sources, max_depth=0, direction="auto", symmetric=False):
+        """BFS levels from `sources` (g4s_bfs): (int32 tensor of rows, −1 where unreached; info dict). A stored entry is an edge when it is != 0.
+        max_depth=0: no cap. Synchronous."""
+        _traverse_flags(direction, symmetric)
+        return self._traverse("g4s_bfs", sources, torch.empty(self.rows, dtype=torch.int32, device=self.rowptr.device), max_depth, direction, symmetric)
+
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
         X.stride(1) == 1, column-major when X.stride(0) == 1 (k > 1); the leading dimension is the other stride, Y has X's layout. A new Y
@@ -207,6 +234,28 @@ def spmv_semiring_transpose(A, x, y=None, semiring="min_plus", accumulate=False)
     """y := Aᵀ ⊗ x or y ⊕ (Aᵀ ⊗ x) (g4s_spmv_semiring_transpose) — CSR.spmv_semiring_transpose as a function."""
     _spmv_semiring_flags(semiring, accumulate, y)
     return A.spmv_semiring_transpose(x, y, semiring, accumulate)
+
+
+DIRECTIONS = {"auto": 0, "push": capi.TRAVERSE_PUSH, "pull": capi.TRAVERSE_PULL}
+
+
+def _traverse_flags(direction, symmetric):
+    """The flags of g4s_sssp / g4s_bfs; ValueError (before any GPU call) for an unknown direction."""
+    if not isinstance(direction, str) or direction not in DIRECTIONS:
+        raise ValueError(f"unknown direction {direction!r}; expected one of {sorted(DIRECTIONS)}")
+    return DIRECTIONS[direction] | (capi.TRAVERSE_SYMMETRIC if symmetric else 0)
+
+
+def sssp(A, sources, max_iterations=0, direction="auto", symmetric=False):
+    """(dist, info) = shortest paths from `sources` on the graph A stores by out-edges (g4s_sssp) — CSR.sssp as a function."""
+    _traverse_flags(direction, symmetric)
+    return A.sssp(sources, max_iterations, direction, symmetric)
+
+
+def bfs(A, sources, max_depth=0, direction="auto", symmetric=False):
+    """(level, info) = BFS levels from `sources` (g4s_bfs) — CSR.bfs as a function."""
+    _traverse_flags(direction, symmetric)
+    return A.bfs(sources, max_depth, direction, symmetric)
 
 
 def csr_transpose(rowptr, colids, values, rows, cols, with_perm=False):

@@ -385,6 +385,62 @@ g4s_status g4s_csr_transpose_reserve(g4s_csr_t A);
 g4s_status g4s_csr_transpose_info(g4s_csr_t A, g4s_csr_info *info);
 g4s_status g4s_spmv_transpose(g4s_csr_t A, const double *x_dev, double *y_dev, double alpha, double beta, void *stream);
 g4s_status g4s_spmv_semiring_transpose(g4s_csr_t A, const double *x_dev, double *y_dev, unsigned flags, void *stream);
+
+/* ---- Graph traversal on a handle: single- / multi-source shortest paths (g4s_sssp) and BFS levels (g4s_bfs), device-resident, with a per-step choice
+ * between a push from the frontier and the dense pull d := d ⊕ (Aᵀ ⊗ d) — the loops a caller would otherwise write around g4s_spmv_semiring_transpose.
+ * A is square and stored by OUT-edges: row i lists the edges i → j with weight a_ij.
+ *   sources: a HOST array of n_sources >= 1 vertex ids (repeats allowed); all start at distance 0 / level 0, so the result is the distance to the nearest
+ *     source. dist_dev (rows doubles) / level_dev (rows int32) are device arrays that are only written: their old content is never read. Unreached
+ *     vertices get +inf / −1. info may be NULL.
+ *   g4s_sssp computes the min-plus fixed point of d := d ⊕ (Aᵀ ⊗ d) from d[sources] = 0; every stored entry of a row takes part (repeated columns
+ *     included, as in g4s_spmv_semiring). max_iterations == 0 means rows. The result is exact and does not depend on the schedule: IEEE addition is
+ *     monotone (a <= b ⇒ fl(a + w) <= fl(b + w)), so any order of relaxations — the synchronous pull, a push in whatever order its atomics land, any
+ *     mixture — ends at d[v] = min over paths of the path sum rounded left to right. Push, pull and auto therefore agree bit for bit, with each other
+ *     and from run to run. Outside the contract, as for the semiring SpMV: NaN weights, (+inf) + (−inf), the sign of a zero.
+ *     Negative weights are allowed. With a negative cycle reachable from a source there is no fixed point: the call stops at the cap and reports
+ *     converged = 0. Whenever converged == 0, every path of at most `iterations` edges has been relaxed: dist holds upper bounds with
+ *     final <= dist[v] <= (the synchronous result after `iterations` rounds).
+ *   g4s_bfs writes the hop count. A stored entry is an edge under the or-and rule: a_ij != 0 (NaN counts as nonzero), so the levels are those of the
+ *     or-and loop over g4s_spmv_semiring. max_depth == 0 means no cap; with a cap, vertices beyond it stay −1 and converged = 0 if the last frontier
+ *     was not empty. Levels are unique, hence the same in every direction. Whether any stored value is zero is found once (at the reserve, and again
+ *     after g4s_csr_update_values); without one, BFS never reads the values.
+ *   Direction: by default chosen per step — push while the frontier's out-edges are at most nnz / α, pull otherwise; α = 8 for g4s_sssp and 1 for
+ *     g4s_bfs (the measured switch points, DESIGN §4.6 and profiles/traverse.txt; the environment variable G4S_TRAVERSE_ALPHA replaces both).
+ *     G4S_TRAVERSE_PUSH / G4S_TRAVERSE_PULL force one.
+ *   Where it loses: on a graph whose traversal is a handful of dense steps the host loop over g4s_spmv_semiring_transpose is faster — configs[1]
+ *     (10 M R-MAT, 8 steps from the hub): 3.8 ms for the loop against 8.4 ms (SSSP) and 4.0 against 14.0 ms (BFS); every vertex a step changes is
+ *     appended to the next frontier through one tail counter, which bounds a step at about 7 G edges/s. It wins where steps are many and frontiers
+ *     small — the 1000 × 1000 grid, 2053 steps: 80.6 against 112.6 ms (SSSP), 34.8 against 128.7 ms (BFS).
+ *   flags: G4S_TRAVERSE_PUSH, G4S_TRAVERSE_PULL (both together: G4S_ERR_INVALID), G4S_TRAVERSE_SYMMETRIC; any other bit, a NULL handle, sources or
+ *     output, n_sources < 1 and a negative cap return G4S_ERR_INVALID before any HIP call. A non-square handle and a source outside [0, rows) return
+ *     G4S_ERR_INVALID before anything is enqueued. No other entry point accepts these bits.
+ *   Synchronous: the call runs on `stream` and returns when the output is complete. It reads its state back (once per batch of at least
+ *     G4S_TRAVERSE_BATCH push steps, once per pull step: info.host_waits), so it cannot be captured: on a capturing stream it returns G4S_ERR_INVALID
+ *     and enqueues nothing. One traversal or product in flight per handle.
+ *   g4s_csr_traverse_reserve builds what the calls need (NULL stream, synchronous): two frontier queues and a mark per vertex (3·rows ints), the pull
+ *     step's vector (rows doubles), an 80-byte state block, and the handle's transpose through g4s_csr_transpose_reserve — unless the flags hold
+ *     G4S_TRAVERSE_SYMMETRIC or G4S_TRAVERSE_PUSH (which never pulls); a later auto or pull call then reserves the rest. A first call without a
+ *     reserve reserves synchronously; after a reserve a call allocates nothing on the device. g4s_csr_destroy releases all of it,
+ *     g4s_csr_get_info(A).plan_bytes counts the workspace (the transpose is counted by g4s_csr_transpose_info). g4s_csr_update_values needs nothing
+ *     new: push reads the handle's current value array, pull the refreshed Aᵀ. */
+#define G4S_TRAVERSE_PUSH       4096u  /* every step pushes from the frontier                                                          */
+#define G4S_TRAVERSE_PULL       8192u  /* every step is the dense pull d := d ⊕ (Aᵀ ⊗ d)                                              */
+#define G4S_TRAVERSE_SYMMETRIC 16384u  /* the caller declares A == Aᵀ (pattern and values): the pull runs on A itself, no transpose    */
+#define G4S_TRAVERSE_BATCH 16          /* push steps enqueued behind one read of the state, at least (doubles up to 64 within a call)  */
+typedef struct g4s_traverse_info {
+    int32_t iterations;      /* steps run, push + pull                                                  */
+    int32_t converged;       /* 1: fixed point / empty frontier; 0: stopped at the iteration cap        */
+    int32_t push_steps, pull_steps;
+    int32_t host_waits;      /* times the call waited for the device                                    */
+    int32_t reserved;
+    int64_t reached;         /* vertices with a finite distance / a level >= 0                          */
+    int64_t edges_relaxed;   /* edges walked by push steps + nnz per pull step                          */
+} g4s_traverse_info;
+g4s_status g4s_csr_traverse_reserve(g4s_csr_t A, unsigned flags);
+g4s_status g4s_sssp(g4s_csr_t A, const int32_t *sources, int32_t n_sources, double *dist_dev, int32_t max_iterations, unsigned flags,
+                    g4s_traverse_info *info, void *stream);
+g4s_status g4s_bfs(g4s_csr_t A, const int32_t *sources, int32_t n_sources, int32_t *level_dev, int32_t max_depth, unsigned flags,
+                   g4s_traverse_info *info, void *stream);
 g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *acol, const double *aval,
                                   const int32_t *brpt, const int32_t *bcol, const double *bval,
                                   int32_t **crpt, int32_t **ccol, double **cval,

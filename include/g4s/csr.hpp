@@ -195,6 +195,40 @@ void Transpose(const CSR<IT, NT> &a, CSR<IT, NT> &at)
     at.rows = a.cols; at.cols = a.rows; at.nnz = a.nnz; at.zerobased = true;
 }
 
+// Shortest-path distances (dist: a.rows values, +inf where unreached) and BFS levels (level: a.rows values, −1 where unreached) from the nearest of
+// n_sources vertices on the graph `a` stores by out-edges (row i: the edges i → j, weight a_ij), host arrays, synchronous: a handle, one g4s_sssp /
+// g4s_bfs (include/g4s.h has the contract: exact min-plus fixed point; an entry is a BFS edge when it is != 0), the handle destroyed.
+namespace detail {
+template <typename IT, typename NT, typename Out, typename Run>
+void traverse(const CSR<IT, NT> &a, Out *out, const char *what, Run run)
+{
+    static_assert(std::is_same<IT, int32_t>::value && std::is_same<NT, double>::value, "the device traversals work on CSR<int32_t, double>");
+    g4s_csr_t h = nullptr;
+    check(g4s_csr_create(&h, a.rows, a.cols, a.nnz, a.rowptr, a.colids, a.values, G4S_HOST_POINTERS | G4S_SPMV_STREAM), what);
+    void *dev = nullptr;
+    g4s_status st = g4s_dev_alloc(&dev, sizeof(Out) * ((size_t)a.rows + 1));
+    if (st == G4S_OK) st = run(h, (Out *)dev);
+    if (st == G4S_OK) st = g4s_memcpy_d2h(out, dev, sizeof(Out) * (size_t)a.rows);
+    if (dev) g4s_dev_free(dev);
+    g4s_csr_destroy(h);
+    check(st, what);
+}
+} // namespace detail
+template <typename IT, typename NT>
+void SSSP(const CSR<IT, NT> &a, const IT *sources, IT n_sources, NT *dist, g4s_traverse_info *info = nullptr)
+{
+    detail::traverse(a, dist, "SSSP", [&](g4s_csr_t h, NT *d) { return g4s_sssp(h, sources, n_sources, d, 0, 0u, info, nullptr); });
+}
+template <typename IT, typename NT>
+void SSSP(const CSR<IT, NT> &a, IT source, NT *dist) { SSSP(a, &source, (IT)1, dist); }
+template <typename IT, typename NT>
+void BFS(const CSR<IT, NT> &a, const IT *sources, IT n_sources, int32_t *level, g4s_traverse_info *info = nullptr)
+{
+    detail::traverse(a, level, "BFS", [&](g4s_csr_t h, int32_t *l) { return g4s_bfs(h, sources, n_sources, l, 0, 0u, info, nullptr); });
+}
+template <typename IT, typename NT>
+void BFS(const CSR<IT, NT> &a, IT source, int32_t *level) { BFS(a, &source, (IT)1, level); }
+
 // Y = alpha·A·X + beta·Y with host blocks X (cols × k) and Y (rows × k): row-major by default (ld >= k), column-major as in cblas_dxxmm.c's
 // B and C (ld >= cols / rows) with col_major = true.
 template <typename IT, typename NT>
