@@ -40,6 +40,12 @@ class TraverseInfo(C.Structure):
                 ("host_waits", C.c_int32), ("reserved", C.c_int32), ("reached", C.c_int64), ("edges_relaxed", C.c_int64)]
 
 
+class MaskedInfo(C.Structure):
+    """g4s_masked_info: what a g4s_spgemm_masked / g4s_triangle_count call did (which class the rows took)."""
+    _fields_ = [("mask_nnz", C.c_int64), ("products", C.c_int64), ("rows_wave", C.c_int32), ("rows_lds", C.c_int32), ("rows_global", C.c_int32),
+                ("rows_split", C.c_int32)]
+
+
 class DistInfo(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("local_rows", C.c_int32), ("n_ref", C.c_int32), ("nnz_own", C.c_int64), ("nnz_rem", C.c_int64),
                 ("send_bytes", C.c_int64), ("recv_bytes", C.c_int64), ("own_path", C.c_int32), ("rem_path", C.c_int32), ("connected", C.c_int32),
@@ -157,6 +163,8 @@ SIGNATURES = {
                                           C.c_int32, C.c_int32, C.c_int32, i64p, C.POINTER(Timings), C.c_uint]),
     "g4s_spgemm_symbolic": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64p, vp]),
     "g4s_spgemm_numeric": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
+    "g4s_spgemm_masked": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(MaskedInfo), vp]),
+    "g4s_triangle_count": (C.c_int, [C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_register_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY, C.POINTER(PatternDesc)]),
     "g4s_unregister_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY]),
     "g4s_set_host_callback_policy": (C.c_int, [C.c_int32]),

@@ -7,6 +7,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   spmv_semiring  — the same over min-plus, max-plus or or-and (SEMIRINGS): y = A ⊗ x, or y ⊕ (A ⊗ x)
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
   csr_transpose  — Aᵀ as a CSR (the CSC form of A; mm/inc/CSR.h:171-230, mm/inc/convert.h), stable: entries of a column keep their order
+  spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
   spmv_transpose — y = alpha·Aᵀ·x + beta·y on a handle of A (spmv_semiring_transpose: the semiring form), through the handle's own transpose
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
@@ -157,6 +158,10 @@ class CSR:
         max_depth=0: no cap. Synchronous."""
         _traverse_flags(direction, symmetric)
         return self._traverse("g4s_bfs", sources, torch.empty(self.rows, dtype=torch.int32, device=self.rowptr.device), max_depth, direction, symmetric)
+
+    def triangle_count(self, return_info=False):
+        """The triangles of the graph whose symmetric pattern (or lower triangle) this matrix stores — triangle_count(self)."""
+        return triangle_count(self, return_info)
 
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
@@ -401,6 +406,56 @@ def HashSpGEMM(a, b, sortOutput=True, two_phase=False, semiring="plus_times"):
                                       _ptr(b.rowptr), _ptr(b.colids), _ptr(b.values), _ptr(crpt), _ptr(ccol), _ptr(cval),
                                       flags, _stream()))
     return CSR(crpt, ccol, cval, a.rows, b.cols)
+
+
+def _ptr_nn(t):
+    """Like _ptr, but never NULL: an empty array is passed as a pointer that is not read (entry points that take NULL for 'absent')."""
+    if t.numel() > 0:
+        return C.c_void_p(t.data_ptr())
+    if t.device not in _PLACEHOLDER:
+        _PLACEHOLDER[t.device] = torch.zeros(2, dtype=torch.float64, device=t.device)
+    return C.c_void_p(_PLACEHOLDER[t.device].data_ptr())
+
+
+_PLACEHOLDER = {}
+
+
+def _masked_info(info):
+    return {n: getattr(info, n) for n, _ in capi.MaskedInfo._fields_}
+
+
+def spgemm_masked(a, b, mask, semiring="plus_times", pattern_only=False, return_info=False):
+    """C⟨M⟩ = A ⊗ B: the product over `semiring` computed only at the positions of the pattern `mask` (g4s_spgemm_masked) — a CSR, or a
+    (rowptr, colids) pair of int32 device tensors, with strictly ascending rows. The result is a CSR that SHARES the mask's rowptr / colids tensors
+    and owns the new values: the full product's value where it has an entry, the semiring's identity (0.0, +inf, −inf, 0.0) elsewhere.
+    pattern_only=True counts every stored value of a and b as 1.0 and reads no values: plus_times then counts the products of each entry, or_and
+    marks the entries that receive one. mask may be a or b itself (C⟨A⟩ = A·A). Synchronous. return_info=True adds the dict of g4s_masked_info."""
+    if semiring not in SEMIRINGS:
+        raise ValueError(f"unknown semiring {semiring!r}; expected one of {sorted(SEMIRINGS)}")
+    _require_gpu()
+    mrp, mci = (mask.rowptr, mask.colids) if isinstance(mask, CSR) else mask
+    assert a.cols == b.rows
+    assert mrp.dtype == torch.int32 and mci.dtype == torch.int32 and mrp.is_cuda and mci.is_cuda and mrp.numel() == a.rows + 1
+    mrp, mci = mrp.contiguous(), mci.contiguous()
+    cval = torch.empty(mci.numel(), dtype=torch.float64, device=mci.device)
+    info = capi.MaskedInfo()
+    null = C.c_void_p(0)
+    capi.check(capi.load().g4s_spgemm_masked(a.rows, a.cols, b.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), null if pattern_only else _ptr_nn(a.values),
+                                             _ptr_nn(b.rowptr), _ptr_nn(b.colids), null if pattern_only else _ptr_nn(b.values), _ptr_nn(mrp), _ptr_nn(mci),
+                                             _ptr_nn(cval), capi.DEVICE_POINTERS | SEMIRINGS[semiring], C.byref(info), _stream()))
+    c = CSR(mrp, mci, cval, a.rows, b.cols)
+    return (c, _masked_info(info)) if return_info else c
+
+
+def triangle_count(A, return_info=False):
+    """The number of vertex triples i > j > k with (i, j), (i, k) and (j, k) all stored below the diagonal of the square pattern A
+    (g4s_triangle_count): the triangles of a simple undirected graph given as its symmetric pattern or as its lower triangle; entries on and above
+    the diagonal do not count. Rows must be strictly ascending. Synchronous. return_info=True adds the g4s_masked_info of the product L·L⟨L⟩."""
+    _require_gpu()
+    assert A.rows == A.cols
+    count, info = C.c_int64(0), capi.MaskedInfo()
+    capi.check(capi.load().g4s_triangle_count(A.rows, _ptr_nn(A.rowptr), _ptr_nn(A.colids), C.byref(count), capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    return (count.value, _masked_info(info)) if return_info else count.value
 
 
 # ------------------------------------------------------------------------------------------------ synthetic inputs

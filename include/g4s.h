@@ -466,6 +466,67 @@ g4s_status g4s_spgemm_numeric(int32_t M, int32_t K, int32_t N,
                               const int32_t *crpt_dev, int32_t *ccol_dev, double *cval_dev,
                               unsigned flags, void *stream);
 
+/* ---- Masked SpGEMM: C⟨M⟩ = A ⊗ B, the product computed only at the positions of a given pattern M — what g4s_spgemm_csr_i32_f64 followed by a
+ * selection of M's entries gives, without the full product: no symbolic phase, no output allocation, no crpt (the pattern of C is M), so it also works
+ * where the full product exceeds the int32 crpt (G4S_ERR_OVERFLOW). Triangle counting, clustering coefficients, k-truss support, common-neighbour
+ * scores of given pairs and sampled distance products are all of this shape.
+ *   A is M×K, B is K×N, the mask an M×N pattern (mrpt, mcol; no values). cval is caller-allocated, mrpt[M] doubles, only written.
+ *   Values: entry k = (i, j = mcol[k]) gets ⊕ over all products a_ip ⊗ b_pj with a stored a_ip and a stored b_pj (repeated columns in a row of A or B
+ *     each take part, as in g4s_spgemm_*), and the semiring's identity (0.0, +inf, −inf, 0.0) where there is none: the value the full product of the
+ *     same semiring has at (i, j), or the identity where it has no entry. Products whose column is not in the mask row are dropped.
+ *   flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS for all arrays (host: upload, run, copy cval back) and one G4S_SEMIRING_* value. Any other bit
+ *     returns G4S_ERR_INVALID before any HIP call, and so do a NULL arpt, acol, brpt, bcol, mrpt or cval, a negative size, and a NULL mcol unless M == 0.
+ *   Pattern-only: aval == NULL && bval == NULL makes every stored value of A and B count as 1.0, and no value array is read (4 instead of 12 bytes
+ *     per product). Plus-times then counts the products of an entry (exact below 2^53), or-and gives 1.0 exactly where a product exists — the
+ *     structural hit pattern that a plus-times value of 0.0 cannot give. One NULL without the other is G4S_ERR_INVALID.
+ *   Inputs: A and B follow the SpGEMM input contract above (rows in any order, repeated columns, ids range-checked). The rows of the MASK must be
+ *     strictly ascending (sorted, no repeats) with ids in [0, N) and mrpt non-decreasing from 0: checked on the device in the opening pass,
+ *     G4S_ERR_INVALID, cval unspecified afterwards. The mask arrays may be the very arrays of A or B (C⟨A⟩ = A·A is the common call); cval must not
+ *     overlap an input (G4S_ERR_INVALID).
+ *   Exactness: min-plus, max-plus and or-and are exact and deterministic in every row class (min, max and or do not depend on the order of arrival;
+ *     outside the contract, as for the SpGEMM semirings: NaN, (+inf) + (−inf), the sign of a zero). Plus-times is within 1e-10·Σ|a·b| of the entry's
+ *     left-to-right sum and bit-exact whenever every partial sum is representable (integer values, pattern-only).
+ *   Synchronous: runs on `stream` and returns when cval is complete. It classifies rows from counts it reads back, so on a capturing stream it
+ *     returns G4S_ERR_INVALID and enqueues nothing (the rule of g4s_sssp). Scratch (16·M bytes, plus device copies of the arrays with host pointers)
+ *     comes from the library's caching allocator and is released before the call returns. M, nnz(A), nnz(B) or nnz(M) of 0 are valid (cval all identity
+ *     / nothing written). info may be NULL.
+ *   Row classes (g4s_masked_info says which a row took): a mask row of at most 64 entries with at most 4096 products runs on one
+ *     wavefront; up to 8192 entries the mask row is a table in LDS of one workgroup; a longer one is searched in HBM with global atomics; a row of more
+ *     than 2^20 products is divided over up to 128 workgroups (an LDS table each when the mask row has at most 1024 entries, else the HBM search).
+ *     Lookup is a binary search over the sorted mask row after a clip to [min, max] of the row.
+ *   Where it loses: every product is walked even when the mask keeps a handful — a mask much sparser than the product wants the dot-product
+ *     formulation on Bᵀ, which is not built. A split row is divided by entries of A, so a row whose products sit in a few very long rows of B stays
+ *     on few workgroups. Against the full product alone it is level on a dense mask (R-MAT-18, edge factor 16, mask = A: 22.6 against 23.3 ms) and
+ *     ahead where the output dominates (configs[2]: 17.7 against 26.8 ms; 65.3 ms with the selection); pattern-only gains only 4–6 %, the walk is
+ *     bound by the lookups (profiles/spgemm_masked.txt). */
+typedef struct g4s_masked_info {
+    int64_t mask_nnz;        /* mrpt[M]                                                                                          */
+    int64_t products;        /* Σ over rows i with a non-empty mask row of Σ_{p ∈ A(i,:)} nnz(B(p,:)): products looked up           */
+    int32_t rows_wave;       /* rows handled by the wavefront-per-row class                                                       */
+    int32_t rows_lds;        /* rows whose mask row was a table in LDS (split ones included)                                      */
+    int32_t rows_global;     /* rows whose mask row was too long for LDS: searched in HBM, global atomics (split ones included)   */
+    int32_t rows_split;      /* rows whose products were divided over several workgroups                                          */
+} g4s_masked_info;
+g4s_status g4s_spgemm_masked(int32_t M, int32_t K, int32_t N,
+                             const int32_t *arpt, const int32_t *acol, const double *aval,
+                             const int32_t *brpt, const int32_t *bcol, const double *bval,
+                             const int32_t *mrpt, const int32_t *mcol,
+                             double *cval, unsigned flags, g4s_masked_info *info, void *stream);
+
+/* Triangle counting: *triangles (host) = the number of vertex triples i > j > k for which (i, j), (i, k) and (j, k) are all stored in the strictly
+ * lower triangle L of the n×n pattern — for the symmetric pattern of a simple undirected graph, its number of triangles. Entries on and above the
+ * diagonal are ignored, so a full symmetric matrix, its lower triangle alone, and either with self-loops give the same number.
+ *   Rows must be strictly ascending with ids in [0, n) (checked on the device, G4S_ERR_INVALID): L(i) is then a prefix of row i; L is compacted into
+ *     a CSR of its own (4·(n + 1) + 12·nnz(L) bytes of scratch with its values) and the count is Σ cval of the pattern-only plus-times product
+ *     L·L⟨L⟩, summed on the device in int64 in a fixed order (the summands are integers).
+ *   flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS only; any other bit, a NULL rowptr or triangles, a NULL colids with n > 0 and a negative n return
+ *     G4S_ERR_INVALID before any HIP call. Synchronous, not capturable, info as for g4s_spgemm_masked (of the product L·L⟨L⟩).
+ *   Per-vertex and per-edge counts are one g4s_spgemm_masked call on L away. Where it loses: vertices are taken in the order given — no degree
+ *     reordering, so the hub rows of a skewed graph keep their full lower neighbourhoods as mask rows: configs[1] symmetrised (97.9 M edges) takes
+ *     533 ms for 74.9 G products, of which 4 454 hub rows are split (profiles/spgemm_masked.txt). */
+g4s_status g4s_triangle_count(int32_t n, const int32_t *rowptr, const int32_t *colids,
+                              int64_t *triangles, unsigned flags, g4s_masked_info *info, void *stream);
+
 /* ------------------------------------------------------------------ B3: graph gather/apply */
 
 typedef void (*fun_gather)(int, int, const double **, const double *, double *); /* citcoms/lib/global_defs.h:48 */

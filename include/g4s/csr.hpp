@@ -5,6 +5,7 @@
 //   Timings                            mm/inc/Timings.h:4-23, mm/src/Timings.cpp:36-65
 //   SpMV(a,x,y,alpha,beta)             the CSR mat-vec this build defines for mv/ 
 //   SpMVSemiring(a,x,y,multop,addop)   the same over min-plus, max-plus or or-and (y := A ⊗ x, or y ⊕ (A ⊗ x))
+//   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   Transpose(a,at)                    Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
@@ -149,6 +150,39 @@ void HashSpGEMM(const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c, Mul,
 }
 template <typename IT, typename NT>
 void HashSpGEMM(const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c) { HashSpGEMM<false, true>(a, b, c, std::multiplies<NT>(), std::plus<NT>()); }
+
+// c = the product A ⊗ B at the positions of mask's pattern only (g4s_spgemm_masked, host arrays): c receives a copy of the mask's pattern and the new
+// values — the full product's value where it has an entry, the semiring's identity elsewhere. mask's rows must be strictly ascending; its values are
+// not read. The functor pair is checked like HashSpGEMM's. c must not be a, b or mask.
+template <typename IT, typename NT, typename Mul, typename Add>
+void MaskedSpGEMM(const CSR<IT, NT> &a, const CSR<IT, NT> &b, const CSR<IT, NT> &mask, CSR<IT, NT> &c, Mul, Add, g4s_masked_info *info = nullptr)
+{
+    static_assert(semiring_flag<Mul, Add, NT>::supported,
+                  "device SpGEMM implements four (multop, addop) pairs only: (std::multiplies, std::plus), (std::plus, g4s::min_op), "
+                  "(std::plus, g4s::max_op), (std::logical_and, std::logical_or)");
+    c.make_empty();
+    c.rowptr = (IT *)g4s_malloc(sizeof(IT) * ((size_t)mask.rows + 1));
+    c.colids = (IT *)g4s_malloc(sizeof(IT) * ((size_t)mask.nnz + 1));
+    c.values = (NT *)g4s_malloc(sizeof(NT) * ((size_t)mask.nnz + 1));
+    if (!c.rowptr || !c.colids || !c.values) { c.make_empty(); throw std::runtime_error("MaskedSpGEMM: host allocation failed"); }
+    if (mask.rowptr) std::memcpy(c.rowptr, mask.rowptr, sizeof(IT) * ((size_t)mask.rows + 1));
+    else c.rowptr[0] = 0;
+    if (mask.nnz) std::memcpy(c.colids, mask.colids, sizeof(IT) * (size_t)mask.nnz);
+    c.rows = a.rows; c.cols = b.cols; c.nnz = mask.nnz; c.zerobased = true;
+    check(g4s_spgemm_masked(a.rows, a.cols, b.cols, a.rowptr, a.colids, a.values, b.rowptr, b.colids, b.values, c.rowptr, c.colids, c.values,
+                            G4S_HOST_POINTERS | semiring_flag<Mul, Add, NT>::value, info, nullptr), "MaskedSpGEMM");
+}
+template <typename IT, typename NT>
+void MaskedSpGEMM(const CSR<IT, NT> &a, const CSR<IT, NT> &b, const CSR<IT, NT> &mask, CSR<IT, NT> &c) { MaskedSpGEMM(a, b, mask, c, std::multiplies<NT>(), std::plus<NT>()); }
+
+// The triangles of the graph whose symmetric pattern (or lower triangle alone) `a` stores, rows strictly ascending (g4s_triangle_count, host arrays).
+template <typename IT, typename NT>
+int64_t TriangleCount(const CSR<IT, NT> &a, g4s_masked_info *info = nullptr)
+{
+    int64_t count = 0;
+    check(g4s_triangle_count(a.rows, a.rowptr, a.colids, &count, G4S_HOST_POINTERS, info, nullptr), "TriangleCount");
+    return count;
+}
 
 // The wrapper the shipped benchmark calls: mkl(A,B,C,timing) (mm/inc/mkl_mult.h:113-124 ← mm/src/mkl_spgemm.cpp:67,74).
 template <typename IT, typename NT>
