@@ -14,6 +14,7 @@ HOST_POINTERS, DEVICE_POINTERS, SORT_OUTPUT, SPMV_NO_NT, SPMV_BLOCKED, SPMV_STRE
 SPMM_COL_MAJOR = 256
 SPMV_ACCUMULATE = 2048                                                   # semiring SpMV: y := y ⊕ (A ⊗ x) (g4s.h)
 TRAVERSE_PUSH, TRAVERSE_PULL, TRAVERSE_SYMMETRIC, TRAVERSE_BATCH = 4096, 8192, 16384, 16   # g4s_sssp / g4s_bfs (g4s.h)
+CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
 SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM / SpMV value semiring (g4s.h)
 PATTERN_ELEMENT_BLOCK_MATVEC, PATTERN_DENSE_ROW_TIMES_MATRIX, PATTERN_SYM_QUADRATIC_FORM = 1, 2, 3
 DENSE_DGEMM, DENSE_DSYMM, DENSE_DTRMM, DENSE_DGEMV, DENSE_DSYMV, DENSE_DTRMV, DENSE_DSPMV = 1, 2, 3, 4, 5, 6, 7
@@ -44,6 +45,12 @@ class MaskedInfo(C.Structure):
     """g4s_masked_info: what a g4s_spgemm_masked / g4s_triangle_count call did (which class the rows took)."""
     _fields_ = [("mask_nnz", C.c_int64), ("products", C.c_int64), ("rows_wave", C.c_int32), ("rows_lds", C.c_int32), ("rows_global", C.c_int32),
                 ("rows_split", C.c_int32)]
+
+
+class CCInfo(C.Structure):
+    """g4s_cc_info: what a g4s_connected_components call found and did."""
+    _fields_ = [("components", C.c_int64), ("largest", C.c_int64), ("edges_linked", C.c_int64), ("largest_label", C.c_int32),
+                ("sample_rounds", C.c_int32), ("skipped", C.c_int32), ("host_waits", C.c_int32)]
 
 
 class DistInfo(C.Structure):
@@ -165,7 +172,8 @@ SIGNATURES = {
     "g4s_spgemm_numeric": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
     "g4s_spgemm_masked": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_triangle_count": (C.c_int, [C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(MaskedInfo), vp]),
-    "g4s_register_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY, C.POINTER(PatternDesc)]),
+    "g4s_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(CCInfo), vp]),
+    "g4s_register_pattern":(C.c_int, [FUN_GATHER, FUN_APPLY, C.POINTER(PatternDesc)]),
     "g4s_unregister_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY]),
     "g4s_set_host_callback_policy": (C.c_int, [C.c_int32]),
     "g4s_set_host_callback_policy_thread": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),

@@ -1,0 +1,422 @@
+// components.hip — g4s_connected_components (include/g4s.h): the weakly connected components of the graph whose edges are the stored entries of an
+// n × n CSR pattern, as canonical labels (labels[v] = the smallest vertex id of v's component). A concurrent union-find forest in HBM in the shape
+// of Afforest (Sutton, Ben-Nun, Barak 2018), written on this library's own building blocks; `labels` itself is the parent array.
+//
+//   open       cc_open_rows_kernel: rowptr[0] == 0, non-decreasing, parent[v] = v, count[v] = 0. cc_open_ids_kernel (returns at once when the rows
+//              were bad, so no entry outside [0, rowptr[n]) is ever read): every column id in [0, n). From here on every kernel begins with
+//              `if (st->invalid) return`, so an id is never dereferenced before it has been checked. Nothing is read back in between.
+//   sample     round r = 0 … rounds − 1: vertex v links itself to its r-th stored neighbour; a compress after every round (without it the second
+//              round walks the first round's chains: 1000 hops per vertex on the 1000 × 1000 grid).
+//   link(u,v)  a, b = parent[u], parent[v]; while a != b: high / low = max / min; if parent[high] == low, done; if parent[high] == high, one
+//              atomicCAS(parent + high, high, low) — done when it succeeds; otherwise go on from (parent[p], parent[low]) where p is what the load or
+//              the FAILED CAS returned (p < high). parent[x] <= x always holds, so max(a, b) strictly decreases: at most `high` turns, no lane ever
+//              waits for another, nothing spins. The smaller id wins every hook, so the final root is the minimum id: the canonical label.
+//   compress   pointer jumping in passes with a kernel boundary between them: a pass moves every vertex 16 hops up (or to its root), which divides
+//              every depth by 16, so 8 passes flatten any forest of fewer than 2^31 vertices. A pass in which every vertex saw its root leaves the
+//              `pending` word of the next pass at zero and the remaining launches return at once: usually one pass does the work.
+//   pick       one workgroup: the most frequent label among 1024 vertices at a fixed stride (ties: the smaller label) stays in a device word. With
+//              G4S_CC_SYMMETRIC (and without G4S_CC_NO_SKIP) rows that carry it are skipped below; it is always the label counted by reduction.
+//   link rest  entries r >= rounds of every row that is not skipped, balanced over entries as traverse.hip's push is: a workgroup takes 256 rows,
+//              scans their remaining lengths in LDS and its lanes walk the concatenated range; a row above kHubCut entries goes to a hub list and is
+//              walked by all workgroups in chunks of kHubChunk entries (cc_link_hubs_kernel). parent[row] is read once per row; after the compress
+//              most links end at the first compare (one 4-byte gather per entry).
+//   compress, then the statistics: roots, the size of the picked label by reduction, every other label by one atomicAdd per (wave, label), and
+//              the largest component by a max over (size, −label).
+// Memory model: the XCDs' L2s are not coherent for plain loads inside a kernel, so a read of parent[] may be stale. Parents only ever
+// decrease along the tree, so a stale value is a FORMER ancestor: still in the same tree (exits on equality stay sound) and never too small; hooks are
+// decided by the CAS alone, and after a failed CAS the descent goes on from the value it returned. Kernel boundaries are the only ordering between
+// phases. Parent reads are relaxed atomic loads of wavefront scope: plain global loads that the compiler may neither tear nor assume race-free.
+// One host wait per call: no decision is taken on the host between kernels (the picked label, the hub list and the error word stay on the device).
+// Environment switches: G4S_CC_SAMPLE_ROUNDS (0 … 4, default 2), G4S_CC_NO_SKIP=1; every setting gives the same labels.
+#include "common.hpp"
+#include "readback.hpp"
+#include <algorithm>
+#include <climits>
+
+namespace {
+
+constexpr int WG = 256;
+constexpr int kHubCut = 4096;        // a row with more remaining entries goes to the hub list
+constexpr int kHubChunk = 1024;      // entries of a hub per workgroup visit
+constexpr int kHubCap = 1 << 19;     // rows above kHubCut entries: fewer than 2^31 / 4096
+constexpr int kMaxRounds = 4;
+constexpr int kRoundsDefault = 2;
+constexpr int kJumpHops = 16;        // a pass moves a vertex this many hops up
+constexpr int kJumpPasses = 8;       // 16^8 = 2^32 > any depth
+constexpr int kCompressions = kMaxRounds + 1;
+constexpr int kSamples = 1024;       // vertices looked at by the pick
+constexpr size_t kStateBytes = 512;
+
+struct CcState {
+    int invalid;
+    int big_label;                   // the picked label
+    int skip;                        // 1: the link step skips the rows that carry it
+    int n_hubs;
+    unsigned long long edges_linked;
+    unsigned long long components;
+    unsigned long long best;         // (size << 32) | (INT_MAX − label): the maximum is the largest component, ties to the smaller label
+    int pending[kCompressions * (kJumpPasses + 1)];
+};
+static_assert(sizeof(CcState) <= kStateBytes, "state block");
+
+__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+__device__ __forceinline__ void st_(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+
+// Union of the trees of a and b (ancestors, possibly former ones, of the edge's two ends). max(a, b) strictly decreases: bounded, wait-free.
+__device__ __forceinline__ void link_from(int a, int b, int *parent)
+{
+    while (a != b) {
+        const int high = a > b ? a : b, low = a < b ? a : b;
+        int p = ld(parent + high);
+        if (p == low) return;
+        if (p == high) {
+            p = (int)atomicCAS(parent + high, high, low);
+            if (p == high) return;                                 // hooked: high was a root
+        }
+        a = ld(parent + p);                                        // p < high: what the load or the failed CAS returned
+        b = ld(parent + low);
+    }
+}
+
+__global__ __launch_bounds__(WG) void cc_open_rows_kernel(int n, const int *__restrict__ rowptr, int *__restrict__ parent, int *__restrict__ count, CcState *st)
+{
+    int bad = 0;
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
+        const int rb = rowptr[i], re = rowptr[i + 1];
+        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
+        parent[i] = (int)i;
+        count[i] = 0;
+    }
+    if (bad) atomicOr(&st->invalid, 1);
+}
+
+__global__ __launch_bounds__(WG) void cc_open_ids_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ colids, CcState *st)
+{
+    if (st->invalid) return;                                       // rowptr is monotone from 0 beyond this line: [0, rowptr[n]) is the colids array
+    const long long nnz = rowptr[n];
+    int bad = 0;
+    for (long long k = (long long)blockIdx.x * WG + threadIdx.x; k < nnz; k += (long long)gridDim.x * WG) bad |= (unsigned)colids[k] >= (unsigned)n;
+    if (bad) atomicOr(&st->invalid, 2);
+}
+
+__global__ __launch_bounds__(WG) void cc_sample_kernel(int n, int r, const int *__restrict__ rowptr, const int *__restrict__ colids, int *parent, const CcState *st)
+{
+    if (st->invalid) return;
+    for (long long v = (long long)blockIdx.x * WG + threadIdx.x; v < n; v += (long long)gridDim.x * WG) {
+        const int rb = rowptr[v];
+        if (rowptr[v + 1] - rb > r) link_from(ld(parent + v), ld(parent + colids[rb + r]), parent);
+    }
+}
+
+// One pass of pointer jumping. `slot`: this pass's word of st->pending; pass 0 of a compression always runs, a later one only if the pass before
+// left a vertex short of its root. No link runs beside it.
+__global__ __launch_bounds__(WG) void cc_jump_kernel(int n, int *parent, CcState *st, int slot, int first)
+{
+    if (st->invalid || (!first && !st->pending[slot])) return;
+    int more = 0;
+    for (long long v = (long long)blockIdx.x * WG + threadIdx.x; v < n; v += (long long)gridDim.x * WG) {
+        const int p0 = ld(parent + v);
+        int p = p0, g = ld(parent + p);
+        for (int h = 1; h < kJumpHops && g != p; ++h) { p = g; g = ld(parent + p); }
+        if (p != p0) st_(parent + v, p);
+        more |= g != p;
+    }
+    if (more) atomicOr(&st->pending[slot + 1], 1);
+}
+
+__global__ __launch_bounds__(WG) void cc_pick_kernel(int n, const int *__restrict__ parent, CcState *st, int allow_skip)
+{
+    __shared__ int s_lab[kSamples];
+    __shared__ unsigned long long s_red[WG / 64];
+    if (st->invalid) return;
+    const int ns = n < kSamples ? n : kSamples, t = (int)threadIdx.x;
+    for (int i = t; i < ns; i += WG) s_lab[i] = parent[(long long)i * n / ns];
+    __syncthreads();
+    unsigned long long best = 0;
+    for (int i = t; i < ns; i += WG) {
+        const int l = s_lab[i];
+        unsigned c = 0;
+        for (int j = 0; j < ns; ++j) c += s_lab[j] == l;
+        const unsigned long long key = ((unsigned long long)c << 32) | (unsigned)(INT_MAX - l);
+        best = key > best ? key : best;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_down(best, o); best = y > best ? y : best; }
+    if ((t & 63) == 0) s_red[t >> 6] = best;
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < WG / 64; ++w) best = s_red[w] > best ? s_red[w] : best;
+        st->big_label = INT_MAX - (int)(best & 0xffffffffull);
+        st->skip = allow_skip;
+    }
+}
+
+__device__ __forceinline__ void add_linked(long long linked, CcState *st)
+{
+    __shared__ long long s_lk[WG / 64];
+    for (int o = 32; o > 0; o >>= 1) linked += __shfl_down(linked, o);
+    if ((threadIdx.x & 63) == 0) s_lk[threadIdx.x >> 6] = linked;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long sum = 0;
+        for (int w = 0; w < WG / 64; ++w) sum += s_lk[w];
+        if (sum) atomicAdd(&st->edges_linked, (unsigned long long)sum);
+    }
+}
+
+// The entries from `rounds` on of every row that is not skipped, 256 rows per tile, lanes over the concatenated entries.
+__global__ __launch_bounds__(WG) void cc_link_kernel(int n, int rounds, const int *__restrict__ rowptr, const int *__restrict__ colids, int *parent, int *__restrict__ hubs,
+                                                     CcState *st)
+{
+    __shared__ int s_scan[WG + 1];
+    __shared__ int s_start[WG];
+    __shared__ int s_pu[WG];
+    __shared__ int s_wsum[WG / 64];
+    if (st->invalid) return;
+    const int skip = st->skip, big = st->big_label;
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    long long linked = 0;
+    for (long long s0 = (long long)blockIdx.x * WG; s0 < n; s0 += (long long)gridDim.x * WG) {
+        const long long i = s0 + t;
+        int start = 0, deg = 0, pu = 0;
+        if (i < n) {
+            pu = ld(parent + i);
+            if (!(skip && pu == big)) {
+                const int rb = rowptr[i];
+                deg = rowptr[i + 1] - rb - rounds;
+                if (deg > 0) start = rb + rounds;
+                else deg = 0;
+                if (deg > kHubCut) {
+                    const int h = atomicAdd(&st->n_hubs, 1);
+                    if (h < kHubCap) hubs[h] = (int)i;             // fewer than 2^31 / kHubCut such rows exist
+                    deg = 0;
+                }
+            }
+        }
+        linked += deg;
+        int x = deg;                                               // inclusive scan of the 256 lengths: at most 256 · kHubCut
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_wsum[wave] = x;
+        s_start[t] = start;
+        s_pu[t] = pu;
+        __syncthreads();
+        int off = 0;
+        for (int w = 0; w < wave; ++w) off += s_wsum[w];
+        s_scan[t + 1] = off + x;
+        if (t == 0) s_scan[0] = 0;
+        __syncthreads();
+        const int total = s_scan[WG];
+        int lo = 0;                                                // the last entry with s_scan[lo] <= e: never decreases as e grows
+        for (int e = t; e < total; e += WG) {
+            int hi = WG - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (s_scan[mid] <= e) lo = mid;
+                else hi = mid - 1;
+            }
+            const int w = colids[s_start[lo] + (e - s_scan[lo])];
+            link_from(s_pu[lo], ld(parent + w), parent);           // s_pu: an ancestor of the row's vertex, maybe a former one
+        }
+        __syncthreads();
+    }
+    add_linked(linked, st);
+}
+
+// Hub rows: chunk c of hub h belongs to block (c + 4h) mod G.
+__global__ __launch_bounds__(WG) void cc_link_hubs_kernel(int rounds, const int *__restrict__ rowptr, const int *__restrict__ colids, int *parent, const int *__restrict__ hubs,
+                                                          CcState *st)
+{
+    if (st->invalid) return;
+    const int nh = st->n_hubs < kHubCap ? st->n_hubs : kHubCap, G = (int)gridDim.x, t = (int)threadIdx.x;
+    long long linked = 0;
+    for (int h = 0; h < nh; ++h) {
+        const int u = hubs[h];
+        const int start = rowptr[u] + rounds, deg = rowptr[u + 1] - start;   // deg > kHubCut
+        const int chunks = (deg + kHubChunk - 1) / kHubChunk;
+        int first = (int)(((long long)blockIdx.x - 4ll * h) % G);
+        if (first < 0) first += G;
+        for (int c = first; c < chunks; c += G) {
+            const int pu = ld(parent + u);
+            for (int j = 0; j < kHubChunk; j += WG) {
+                const int e = c * kHubChunk + j + t;
+                if (e < deg) {
+                    link_from(pu, ld(parent + colids[start + e]), parent);
+                    linked += 1;
+                }
+            }
+        }
+    }
+    add_linked(linked, st);
+}
+
+// Roots, the size of the picked label (plain reduction) and of every other label (lanes of a wave that share a label issue one add).
+__global__ __launch_bounds__(WG) void cc_count_kernel(int n, const int *__restrict__ labels, int *__restrict__ count, CcState *st)
+{
+    __shared__ long long s_red[2][WG / 64];
+    if (st->invalid) return;
+    const int big = st->big_label, lane = (int)threadIdx.x & 63;
+    long long roots = 0, bigc = 0;
+    for (long long v0 = (long long)blockIdx.x * WG; v0 < n; v0 += (long long)gridDim.x * WG) {
+        const long long v = v0 + threadIdx.x;
+        const bool valid = v < n;
+        const int l = valid ? labels[v] : -1;
+        roots += valid && l == v;
+        bigc += valid && l == big;
+        const bool act = valid && l != big;
+        unsigned long long m = __ballot(act);                      // the same for every lane: the loop below is uniform
+        while (m) {
+            const int leader = __ffsll((long long)m) - 1;
+            const int lbl = __shfl(l, leader);
+            const unsigned long long same = __ballot(act && l == lbl);
+            if (lane == leader) atomicAdd(count + lbl, __popcll(same));
+            m &= ~same;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { roots += __shfl_down(roots, o); bigc += __shfl_down(bigc, o); }
+    if (lane == 0) { s_red[0][threadIdx.x >> 6] = roots; s_red[1][threadIdx.x >> 6] = bigc; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long r = 0, b = 0;
+        for (int w = 0; w < WG / 64; ++w) { r += s_red[0][w]; b += s_red[1][w]; }
+        if (r) atomicAdd(&st->components, (unsigned long long)r);
+        if (b) atomicAdd(count + big, (int)b);
+    }
+}
+
+__global__ __launch_bounds__(WG) void cc_largest_kernel(int n, const int *__restrict__ labels, const int *__restrict__ count, CcState *st)
+{
+    __shared__ unsigned long long s_red[WG / 64];
+    if (st->invalid) return;
+    unsigned long long best = 0;
+    for (long long v = (long long)blockIdx.x * WG + threadIdx.x; v < n; v += (long long)gridDim.x * WG) {
+        if (labels[v] != v) continue;
+        const unsigned long long key = ((unsigned long long)(unsigned)count[v] << 32) | (unsigned)(INT_MAX - (int)v);
+        best = key > best ? key : best;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_down(best, o); best = y > best ? y : best; }
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < WG / 64; ++w) best = s_red[w] > best ? s_red[w] : best;
+        if (best) atomicMax(&st->best, best);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+// A block of the library's caching allocator, handed back on every path. `idle`: the stream that used it has been synchronised.
+struct BigBuf {
+    void *p = nullptr;
+    bool idle = false;
+    BigBuf() = default;
+    BigBuf(const BigBuf &) = delete;
+    BigBuf &operator=(const BigBuf &) = delete;
+    ~BigBuf() { if (p) (void)g4s::big_free(p, idle); }
+    int alloc(size_t bytes) { return g4s::big_alloc(&p, bytes); }
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+int env_int(const char *name, int dflt, int lo, int hi)
+{
+    const char *e = getenv(name);
+    if (!e || !*e) return dflt;
+    return std::max(lo, std::min(hi, atoi(e)));
+}
+
+int grid_for(long long n, long long cap) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, cap)); }
+
+// Enqueues the whole labelling on device arrays. `st` has room for kStateBytes, `count` for n ints, `hubs` for min(n, kHubCap).
+int enqueue(int n, const int *rowptr, const int *colids, int *labels, bool symmetric, int rounds, bool no_skip, CcState *st, int *count, int *hubs, hipStream_t s)
+{
+    const int g = grid_for(n, 8192), g_edges = grid_for(n, 2048);
+    int compression = 0;
+    auto compress = [&]() {
+        const int base = compression++ * (kJumpPasses + 1);
+        for (int k = 0; k < kJumpPasses; ++k) hipLaunchKernelGGL(cc_jump_kernel, dim3(g), dim3(WG), 0, s, n, labels, st, base + k, k == 0);
+    };
+    G4S_HIP_TRY(hipMemsetAsync(st, 0, kStateBytes, s));
+    hipLaunchKernelGGL(cc_open_rows_kernel, dim3(g), dim3(WG), 0, s, n, rowptr, labels, count, st);
+    hipLaunchKernelGGL(cc_open_ids_kernel, dim3(8192), dim3(WG), 0, s, n, rowptr, colids, st);
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(cc_sample_kernel, dim3(g), dim3(WG), 0, s, n, r, rowptr, colids, labels, st);
+        compress();
+    }
+    hipLaunchKernelGGL(cc_pick_kernel, dim3(1), dim3(WG), 0, s, n, labels, st, symmetric && !no_skip ? 1 : 0);
+    hipLaunchKernelGGL(cc_link_kernel, dim3(g_edges), dim3(WG), 0, s, n, rounds, rowptr, colids, labels, hubs, st);
+    hipLaunchKernelGGL(cc_link_hubs_kernel, dim3(1024), dim3(WG), 0, s, rounds, rowptr, colids, labels, hubs, st);
+    compress();
+    hipLaunchKernelGGL(cc_count_kernel, dim3(g), dim3(WG), 0, s, n, labels, count, st);
+    hipLaunchKernelGGL(cc_largest_kernel, dim3(g), dim3(WG), 0, s, n, labels, count, st);
+    G4S_HIP_TRY(hipGetLastError());
+    return G4S_OK;
+}
+
+int upload(BigBuf &b, const void *src, size_t bytes, hipStream_t s)
+{
+    G4S_TRY(b.alloc(bytes ? bytes : 4));
+    if (bytes) G4S_HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    return G4S_OK;
+}
+
+} // namespace
+
+G4S_API g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, const int32_t *colids, int32_t *labels, unsigned flags, g4s_cc_info *info,
+                                            void *stream)
+{
+    G4S_REQUIRE((flags & ~(G4S_DEVICE_POINTERS | G4S_CC_SYMMETRIC)) == 0u, "flags other than G4S_HOST_POINTERS / G4S_DEVICE_POINTERS and G4S_CC_SYMMETRIC");
+    G4S_REQUIRE(n >= 0, "negative dimension");
+    G4S_REQUIRE(rowptr && labels, "rowptr or labels is NULL");
+    G4S_REQUIRE(colids || n == 0, "colids is NULL");
+    const hipStream_t s = g4s::as_stream(stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its result back and cannot be captured", __func__);
+    if (info) *info = g4s_cc_info{};
+    if (n == 0) return G4S_OK;
+
+    const int rounds = env_int("G4S_CC_SAMPLE_ROUNDS", kRoundsDefault, 0, kMaxRounds);
+    const bool no_skip = env_int("G4S_CC_NO_SKIP", 0, 0, 1) != 0, symmetric = (flags & G4S_CC_SYMMETRIC) != 0, device = (flags & G4S_DEVICE_POINTERS) != 0;
+    long long nnz = 0;
+    if (!device) {
+        nnz = rowptr[n];
+        G4S_REQUIRE(nnz >= 0, "rowptr[n] is negative");
+    }
+    BigBuf work, d_rp, d_ci, d_lab;                                // the state, the size count (n ints), the hub list
+    const size_t n4 = (sizeof(int) * (size_t)n + 255) / 256 * 256, hub4 = sizeof(int) * (size_t)std::min(n, kHubCap);
+    CcState h{};
+    auto run = [&]() -> int {
+        G4S_TRY(work.alloc(kStateBytes + n4 + hub4));
+        CcState *st = work.as<CcState>();
+        int *count = reinterpret_cast<int *>(work.as<char>() + kStateBytes), *hubs = reinterpret_cast<int *>(work.as<char>() + kStateBytes + n4);
+        const int *rp = rowptr, *ci = colids;
+        int *lab = labels;
+        if (!device) {
+            G4S_TRY(upload(d_rp, rowptr, sizeof(int) * ((size_t)n + 1), s));
+            G4S_TRY(upload(d_ci, colids, sizeof(int) * (size_t)nnz, s));
+            G4S_TRY(d_lab.alloc(sizeof(int) * (size_t)n));
+            rp = d_rp.as<int>(); ci = d_ci.as<int>(); lab = d_lab.as<int>();
+        }
+        G4S_TRY(enqueue(n, rp, ci, lab, symmetric, rounds, no_skip, st, count, hubs, s));
+        G4S_HIP_TRY(g4s::read_small(&h, st, sizeof(CcState), s));
+        if (!device) G4S_HIP_TRY(hipMemcpyAsync(labels, lab, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+        G4S_HIP_TRY(g4s::reads_sync(s));                           // the call's one wait
+        return G4S_OK;
+    };
+    int status = run();
+    if (status != G4S_OK) { (void)g4s::reads_sync(s); (void)hipStreamSynchronize(s); }
+    work.idle = d_rp.idle = d_ci.idle = d_lab.idle = true;
+    if (status == G4S_OK && h.invalid)
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_connected_components: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"
+                                                                                                  : "a column id is outside [0, n)");
+    if (status == G4S_OK && info) {
+        info->components = (int64_t)h.components;
+        info->largest = (int64_t)(h.best >> 32);
+        info->edges_linked = (int64_t)h.edges_linked;
+        info->largest_label = INT_MAX - (int32_t)(h.best & 0xffffffffull);
+        info->sample_rounds = rounds;
+        info->skipped = h.skip;
+        info->host_waits = 1;
+    }
+    return status;
+}

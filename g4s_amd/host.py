@@ -8,6 +8,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
   csr_transpose  — Aᵀ as a CSR (the CSC form of A; mm/inc/CSR.h:171-230, mm/inc/convert.h), stable: entries of a column keep their order
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
+  connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
   spmv_transpose — y = alpha·Aᵀ·x + beta·y on a handle of A (spmv_semiring_transpose: the semiring form), through the handle's own transpose
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
@@ -162,6 +163,11 @@ class CSR:
     def triangle_count(self, return_info=False):
         """The triangles of the graph whose symmetric pattern (or lower triangle) this matrix stores — triangle_count(self)."""
         return triangle_count(self, return_info)
+
+    def connected_components(self, symmetric=False, return_info=False):
+        """Canonical labels of the weakly connected components of this square pattern — connected_components(self). Needs no plan: the handle
+        is not touched."""
+        return connected_components(self, symmetric, return_info)
 
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
@@ -456,6 +462,45 @@ def triangle_count(A, return_info=False):
     count, info = C.c_int64(0), capi.MaskedInfo()
     capi.check(capi.load().g4s_triangle_count(A.rows, _ptr_nn(A.rowptr), _ptr_nn(A.colids), C.byref(count), capi.DEVICE_POINTERS, C.byref(info), _stream()))
     return (count.value, _masked_info(info)) if return_info else count.value
+
+
+def connected_components(A, symmetric=False, return_info=False):
+    """labels (int32 device tensor of n) = the smallest vertex id of each vertex's weakly connected component (g4s_connected_components): every
+    stored entry of the square pattern is an undirected edge, whatever its value. A is a CSR, or a (rowptr, colids) pair of int32 device tensors or
+    of numpy arrays (host pointers; the labels come back on the device all the same). symmetric=True declares the PATTERN symmetric, which lets the
+    call skip the rows of the largest sampled component; on a pattern that is not, components may come out split. Synchronous; no plan is built.
+    return_info=True adds the dict of g4s_cc_info. ValueError (before any GPU call) for a non-square CSR or a `symmetric` that is not a bool."""
+    if not isinstance(symmetric, (bool, np.bool_)):
+        raise ValueError(f"symmetric must be a bool, not {symmetric!r}")
+    if isinstance(A, (tuple, list)):
+        if len(A) != 2:
+            raise ValueError("expected a CSR or a (rowptr, colids) pair")
+        rowptr, colids = A
+        n = int(rowptr.numel() if isinstance(rowptr, torch.Tensor) else np.asarray(rowptr).size) - 1
+        if n < 0:
+            raise ValueError("rowptr is empty: a pattern of n rows has n + 1 row pointers")
+    else:
+        if A.rows != A.cols:
+            raise ValueError(f"connected components need a square pattern, not {A.rows} x {A.cols}")
+        rowptr, colids, n = A.rowptr, A.colids, int(A.rows)
+    _require_gpu()
+    flags = capi.CC_SYMMETRIC if symmetric else 0
+    info = capi.CCInfo()
+    if isinstance(rowptr, torch.Tensor):
+        assert rowptr.is_cuda and colids.is_cuda and rowptr.dtype == torch.int32 and colids.dtype == torch.int32
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        labels = torch.empty(n, dtype=torch.int32, device=rowptr.device)
+        capi.check(capi.load().g4s_connected_components(n, _ptr_nn(rowptr), _ptr_nn(colids), _ptr_nn(labels), flags | capi.DEVICE_POINTERS, C.byref(info),
+                                                        _stream()))
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        out = np.empty(max(n, 1), np.int32)
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        capi.check(capi.load().g4s_connected_components(n, P(rowptr), P(colids if colids.size else out), P(out), flags | capi.HOST_POINTERS, C.byref(info),
+                                                        _stream()))
+        labels = torch.from_numpy(out[:n]).cuda()
+    inf = {n_: getattr(info, n_) for n_, _ in capi.CCInfo._fields_}
+    return (labels, inf) if return_info else labels
 
 
 # ------------------------------------------------------------------------------------------------ synthetic inputs

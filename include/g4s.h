@@ -527,6 +527,48 @@ g4s_status g4s_spgemm_masked(int32_t M, int32_t K, int32_t N,
 g4s_status g4s_triangle_count(int32_t n, const int32_t *rowptr, const int32_t *colids,
                               int64_t *triangles, unsigned flags, g4s_masked_info *info, void *stream);
 
+/* Connected components: labels[v] (n int32, device or host like the other arrays, only written — its old content is never read) = the smallest vertex
+ * id in v's component, for the WEAKLY connected components of the graph on vertices 0 … n−1 whose edges are the stored entries of the n×n pattern,
+ * direction ignored. Raw arrays, no handle and no plan: the call reads the pattern only.
+ *   Every stored entry is an edge, whatever its value (no value array is passed: g4s_triangle_count's rule, and what
+ *     scipy.sparse.csgraph.connected_components does with an explicitly stored zero). Self-loops, repeated columns, unsorted rows and empty rows are
+ *     valid and change nothing; an isolated vertex is a component of its own.
+ *   Labels are canonical: labels[v] <= v, labels[labels[v]] == labels[v], a component's root is its vertex with labels[v] == v. The result is the
+ *     same on every run, for every schedule and every tuning switch, and is compared with ==, never up to a relabelling.
+ *   G4S_CC_SYMMETRIC: the caller declares the PATTERN symmetric ((i,j) stored ⇔ (j,i) stored). It allows the one optimisation that needs it: after the
+ *     sampling rounds the rows of the most frequent sampled label are not walked again (info.skipped), which is only sound when every edge is also
+ *     stored from its other end. Without the flag the pattern may be anything — a directed graph, an upper triangle alone — and the result is that of
+ *     the symmetrised pattern. With the flag on a pattern that is NOT symmetric the call still terminates and writes ids in [0, n) with
+ *     labels[v] <= v, but components may come out split: outside the contract.
+ *   Algorithm: a union-find forest in `labels` itself, "smaller id wins", in the shape of Afforest — two sampling rounds (vertex v hooks
+ *     to its r-th neighbour), pointer-jumping compress, the remaining entries balanced over edges (rows above 4096 entries in chunks of 1024 over all
+ *     workgroups), compress. Hooks are one compare-and-swap on a root; a failed one continues from the value it returned towards strictly smaller
+ *     ids, so every loop is bounded and nothing waits on another workgroup.
+ *   Checks: any flag bit other than G4S_DEVICE_POINTERS and G4S_CC_SYMMETRIC, a NULL rowptr or labels, a NULL colids with n > 0 and a negative n
+ *     return G4S_ERR_INVALID before any HIP call. On the device, before any id is dereferenced: rowptr[0] == 0, rowptr non-decreasing (so
+ *     rowptr[n] <= INT32_MAX entries), ids in [0, n) — G4S_ERR_INVALID, labels unspecified afterwards. n == 0 (nothing written) and nnz == 0
+ *     (labels[v] = v) are valid. labels must not overlap rowptr or colids. info may be NULL.
+ *   Synchronous: runs on `stream` and returns when labels and info are complete; no decision is taken on the host between kernels, so the call
+ *     waits for the device once (info.host_waits). On a capturing stream it returns G4S_ERR_INVALID and enqueues nothing. Scratch — a 512-byte
+ *     state block, 4·n bytes for the component sizes, 4·min(n, 2^19) bytes for the list of long rows, plus device copies of rowptr, colids and labels
+ *     with host pointers — comes from the library's caching allocator and is released before the call returns.
+ *   Environment: G4S_CC_SAMPLE_ROUNDS = 0 … 4 (default 2), G4S_CC_NO_SKIP=1 (never skip, flag or not). Labels do not depend on them.
+ *   Where it loses: not known yet — the comparison with the min-plus label-propagation loop over g4s_spmv_semiring / g4s_spmv_semiring_transpose
+ *     and with scipy on the host (tools/bench_components.py) has not been recorded; profiles/components.txt holds the protocol and DESIGN §4.8 the
+ *     expectation (the loop needs diameter-many rounds, so it should lose on a grid; on a graph of small diameter such as configs[1] it may not). */
+#define G4S_CC_SYMMETRIC 32768u   /* the caller declares the PATTERN symmetric: (i,j) stored ⇔ (j,i) stored */
+typedef struct g4s_cc_info {
+    int64_t components;      /* number of distinct labels (isolated vertices and empty rows count)              */
+    int64_t largest;         /* vertices in the largest component                                                */
+    int64_t edges_linked;    /* stored entries that went through the link step after the sampling rounds          */
+    int32_t largest_label;   /* its label (the smallest one among components of that size)                        */
+    int32_t sample_rounds;   /* neighbour-sampling rounds run                                                     */
+    int32_t skipped;         /* 1: vertices of the sampled largest component were skipped in the link step        */
+    int32_t host_waits;      /* times the call waited for the device                                              */
+} g4s_cc_info;               /* 40 bytes */
+g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, const int32_t *colids,
+                                    int32_t *labels, unsigned flags, g4s_cc_info *info, void *stream);
+
 /* ------------------------------------------------------------------ B3: graph gather/apply */
 
 typedef void (*fun_gather)(int, int, const double **, const double *, double *); /* citcoms/lib/global_defs.h:48 */

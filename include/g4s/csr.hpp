@@ -6,7 +6,8 @@
 //   SpMV(a,x,y,alpha,beta)             the CSR mat-vec this build defines for mv/ 
 //   SpMVSemiring(a,x,y,multop,addop)   the same over min-plus, max-plus or or-and (y := A ⊗ x, or y ⊕ (A ⊗ x))
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
-//   Transpose(a,at)                    Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
+//   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
+//   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
 #pragma once
@@ -182,6 +183,18 @@ int64_t TriangleCount(const CSR<IT, NT> &a, g4s_masked_info *info = nullptr)
     int64_t count = 0;
     check(g4s_triangle_count(a.rows, a.rowptr, a.colids, &count, G4S_HOST_POINTERS, info, nullptr), "TriangleCount");
     return count;
+}
+
+// labels[v] (a.rows values) = the smallest vertex id in v's weakly connected component of the square pattern `a` — every stored entry an undirected
+// edge, whatever its value (g4s_connected_components, host arrays). symmetric: the caller declares the pattern symmetric (G4S_CC_SYMMETRIC).
+template <typename IT, typename NT>
+void ConnectedComponents(const CSR<IT, NT> &a, int32_t *labels, bool symmetric = false, g4s_cc_info *info = nullptr)
+{
+    if (a.rows != a.cols) throw std::runtime_error("ConnectedComponents: the pattern is not square");
+    const IT zero = 0;                                      // an empty CSR holds no arrays: nothing is read or written for rows == 0
+    int32_t none = 0;
+    check(g4s_connected_components(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, a.rows ? labels : &none,
+                                   G4S_HOST_POINTERS | (symmetric ? G4S_CC_SYMMETRIC : 0u), info, nullptr), "ConnectedComponents");
 }
 
 // The wrapper the shipped benchmark calls: mkl(A,B,C,timing) (mm/inc/mkl_mult.h:113-124 ← mm/src/mkl_spgemm.cpp:67,74).
