@@ -2743,7 +2743,11 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         size_t free_b = 0, total_b = 0;
         G4S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         int *cols = nullptr;
-        if (total_cols > 0 && ((size_t)total_cols * sizeof(int) <= free_b / 4 || (size_t)total_cols * sizeof(int) <= g_col_cache.bytes))
+        // (g_col_cache.bytes is read here without its lock, beside other threads' products: only a hint for whether to ask at all — acquire_column_scratch
+        // decides under the lock, and a stale size costs at most one product the scratch)
+        // G4S_SPGEMM_NO_COLSCRATCH=1: the product runs as it does while another call holds the scratch (the numeric phase marks and emits its rows itself)
+        if (total_cols > 0 && !getenv("G4S_SPGEMM_NO_COLSCRATCH") &&
+            ((size_t)total_cols * sizeof(int) <= free_b / 4 || (size_t)total_cols * sizeof(int) <= g_col_cache.bytes))
             cols = acquire_column_scratch(sizeof(int) * (size_t)total_cols);
         if (cols) {
             pre->holds_cache = true;

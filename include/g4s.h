@@ -112,6 +112,21 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
+ * Threads and streams (what tests/test_concurrency_gpu.py pins, every result compared bit for bit):
+ *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
+ *     g4s_connected_components, g4s_csr_transpose, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
+ *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
+ *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
+ *   Different streams from one thread: g4s_spmv, g4s_spmm, g4s_spmv_semiring and g4s_spmv_transpose (after the reserves) on DIFFERENT handles may be
+ *     enqueued on different streams with nothing between them; each result is that of the call made alone. One handle stays one product at a time.
+ *   g4s_last_error() belongs to the calling thread: a refusal in one thread never shows in another, and leaves nothing behind in its own — the
+ *     next valid call there is exact.
+ *   The state g4s_spgemm_symbolic keeps for g4s_spgemm_numeric is ONE per process, whichever thread made it. Any thread's next g4s_spgemm_symbolic
+ *     or one-call product, g4s_trim and g4s_shutdown drop it; a numeric call that is using it at that moment finishes with it, the next one works
+ *     everything out again — the result is the same either way. The column scratch is one per process too: a product that starts while another
+ *     call or the kept state holds it runs without (G4S_SPGEMM_NO_COLSCRATCH=1 takes that path on purpose), with the same result.
+ *   g4s_shutdown must not run beside other calls: it destroys the scratch pools they allocate from.
  * Stream order of create: g4s_csr_create reads the arrays and builds the plan on the NULL (legacy default) stream and returns after it
  * has synchronised; with G4S_DEVICE_POINTERS the arrays must be complete with respect to that stream — a caller that filled them on a
  * non-blocking stream synchronises it first. */

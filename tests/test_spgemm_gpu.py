@@ -169,6 +169,41 @@ def test_spgemm_three_windows(oracle, column_map, two_phase):
     _three_window_case(oracle, two_phase)
 
 
+@pytest.mark.parametrize("semiring", ["plus_times", "min_plus"])
+@pytest.mark.parametrize("two_phase", [False, True])
+def test_spgemm_without_column_scratch(oracle, monkeypatch, capfd, semiring, two_phase):
+    """The process-wide column scratch goes to one call at a time; a product that starts while another holds it runs without (its numeric phase marks and
+    emits the rows itself). G4S_SPGEMM_NO_COLSCRATCH takes that path on purpose: the same inputs with and without the switch give the same bits, and the
+    reference's. Integer values (test_spgemm_masked_gpu._ints), so that the plus-times sums are exact in any order and == is the comparison for both
+    semirings. That the default run did take the scratch, and the other did not, is read off the library's G4S_DEBUG line."""
+    from g4s_amd import host
+    from tests import semiring_ref
+    from tests.test_spgemm_semiring_gpu import _all_row_classes_case
+    A, B, M, K, N = _all_row_classes_case()
+    ints = lambda X, seed: (X[0], X[1], np.random.default_rng(seed).integers(-4, 5, len(X[1])).astype(np.float64))
+    A, B = ints(A, 1), ints(B, 2)
+    monkeypatch.setenv("G4S_DEBUG", "1")
+
+    def run():
+        capfd.readouterr()
+        a, b = host.CSR.from_host(*A, M, K), host.CSR.from_host(*B, K, N)
+        c = host.HashSpGEMM(a, b, two_phase=two_phase, semiring=semiring).to_host()
+        return c, "scratch for pre-sorted columns" in capfd.readouterr().err
+
+    with_scratch, took = run()
+    assert took, "the default run of this case no longer takes the column scratch: the comparison below would compare a path with itself"
+    monkeypatch.setenv("G4S_SPGEMM_NO_COLSCRATCH", "1")
+    without, took = run()
+    assert not took
+    want = semiring_ref.spgemm(A, B, M, semiring)
+    orpt, ocol, _ = oracle.spgemm(A, B, N, sort_output=True)
+    assert np.array_equal(want[0], orpt) and np.array_equal(want[1], ocol)
+    for got in (with_scratch, without):
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        assert np.array_equal(got[2] + 0.0, want[2] + 0.0)
+    assert np.array_equal(with_scratch[2] + 0.0, without[2] + 0.0)                # (the sign of a zero is outside the contract)
+
+
 @pytest.mark.parametrize("shape", ["256", "512", "1024"])
 @pytest.mark.parametrize("static_rows", [False, True])
 def test_spgemm_workgroup_shapes(oracle, monkeypatch, shape, static_rows):
