@@ -1,5 +1,5 @@
 // csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip,
-// traverse.hip.
+// traverse.hip, pagerank.hip.
 #pragma once
 #include "common.hpp"
 #include "spmv_stream.hpp"
@@ -29,6 +29,12 @@ void traverse_work_destroy(TraverseWork *w);
 long long traverse_work_bytes(const TraverseWork *w);
 void traverse_values_changed(TraverseWork *w);   // g4s_csr_update_values: whether a stored value is zero has to be found out again
 
+// pagerank.hip: the workspace of g4s_pagerank (1 / out-strength, x, y, the normalised teleport vector, per-workgroup partials, the state block)
+struct PagerankWork;
+void pagerank_work_destroy(PagerankWork *w);
+long long pagerank_work_bytes(const PagerankWork *w);
+void pagerank_values_changed(PagerankWork *w);   // g4s_csr_update_values: the strength pass has to run again
+
 } // namespace g4s
 
 struct g4s_csr_s {
@@ -49,6 +55,7 @@ struct g4s_csr_s {
     g4s::SpmmWork *spmm = nullptr;      // g4s_spmm's workspace (spmm.hip), built by g4s_csr_spmm_reserve or a first g4s_spmm
     g4s::TransposeWork *tr = nullptr;   // Aᵀ and its handle (transpose.hip), built by g4s_csr_transpose_reserve or a first transposed product
     g4s::TraverseWork *trv = nullptr;   // g4s_sssp / g4s_bfs workspace (traverse.hip), built by g4s_csr_traverse_reserve or a first traversal
+    g4s::PagerankWork *prk = nullptr;   // g4s_pagerank workspace (pagerank.hip), built by g4s_csr_pagerank_reserve or a first g4s_pagerank
 };
 
 namespace g4s {

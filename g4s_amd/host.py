@@ -10,6 +10,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
+  pagerank       — PageRank of a graph stored by out-edges (g4s_pagerank): one call, the loop, the dangling mass and the stop test on the device
   spmv_transpose — y = alpha·Aᵀ·x + beta·y on a handle of A (spmv_semiring_transpose: the semiring form), through the handle's own transpose
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
 """
@@ -160,6 +161,27 @@ class CSR:
         _traverse_flags(direction, symmetric)
         return self._traverse("g4s_bfs", sources, torch.empty(self.rows, dtype=torch.int32, device=self.rowptr.device), max_depth, direction, symmetric)
 
+    def pagerank_reserve(self, symmetric=False):
+        """Build now what pagerank needs (g4s_csr_pagerank_reserve; synchronous): the workspace, the out-strengths and — unless symmetric — Aᵀ."""
+        flags = _pagerank_args(0.85, 1e-10, 0, None, None, symmetric, self)
+        torch.cuda.current_stream().synchronize()
+        capi.check(capi.load().g4s_csr_pagerank_reserve(self.handle, flags & capi.PAGERANK_SYMMETRIC))
+
+    def pagerank(self, damping=0.85, tol=1e-10, max_iterations=0, personalization=None, start=None, symmetric=False):
+        """PageRank of the graph this matrix stores by out-edges (row u: the edges u → v, weight a_uv >= 0; g4s_pagerank): (float64 tensor of rows
+        that sums to 1; info dict). networkx's pagerank with dangling = personalization: r' = damping·(Aᵀ(r / s) + m·p) + (1 − damping)·p with s the
+        out-strengths, m the rank of the dangling vertices and p = personalization / Σ (float64 device tensor of rows, >= 0; None: uniform). Stops
+        after the first iteration with Σ|r' − r| < tol, or at max_iterations (0: 100). start: a float64 device tensor to iterate from (normalised
+        inside; it is not modified); None: p. symmetric=True declares A == Aᵀ, so no transpose is built. Synchronous. ValueError before any GPU
+        call for bad arguments."""
+        flags = _pagerank_args(damping, tol, max_iterations, personalization, start, symmetric, self)
+        rank = torch.empty(self.rows, dtype=torch.float64, device=self.rowptr.device) if start is None else start.clone()
+        pers = None if personalization is None else personalization.contiguous()
+        info = capi.PagerankInfo()
+        capi.check(capi.load().g4s_pagerank(self.handle, float(damping), float(tol), int(max_iterations), _ptr(pers), _ptr_nn(rank), flags, C.byref(info),
+                                            _stream()))
+        return rank, {n: getattr(info, n) for n, _ in capi.PagerankInfo._fields_}
+
     def triangle_count(self, return_info=False):
         """The triangles of the graph whose symmetric pattern (or lower triangle) this matrix stores — triangle_count(self)."""
         return triangle_count(self, return_info)
@@ -267,6 +289,36 @@ def bfs(A, sources, max_depth=0, direction="auto", symmetric=False):
     """(level, info) = BFS levels from `sources` (g4s_bfs) — CSR.bfs as a function."""
     _traverse_flags(direction, symmetric)
     return A.bfs(sources, max_depth, direction, symmetric)
+
+
+def _pagerank_args(damping, tol, max_iterations, personalization, start, symmetric, A=None):
+    """The flags of g4s_pagerank; ValueError (before any GPU call) for an argument the call would refuse."""
+    if isinstance(damping, bool) or not isinstance(damping, (int, float, np.floating)) or not (0.0 <= damping < 1.0):
+        raise ValueError(f"damping must be a number in [0, 1), not {damping!r}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not (tol >= 0.0):
+        raise ValueError(f"tol must be a number >= 0, not {tol!r}")
+    if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or not (0 <= max_iterations < 2 ** 31):
+        raise ValueError(f"max_iterations must be an int >= 0 (0: 100), not {max_iterations!r}")
+    if not isinstance(symmetric, (bool, np.bool_)):
+        raise ValueError(f"symmetric must be a bool, not {symmetric!r}")
+    for name, v in (("personalization", personalization), ("start", start)):
+        if v is None:
+            continue
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D float64 tensor or None")
+        if A is not None and v.numel() != A.rows:
+            raise ValueError(f"{name} has {v.numel()} entries, the graph has {A.rows} vertices")
+        if not v.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+    if A is not None and A.rows != A.cols:
+        raise ValueError(f"PageRank needs a square matrix, not {A.rows} x {A.cols}")
+    return (capi.PAGERANK_SYMMETRIC if symmetric else 0) | (capi.PAGERANK_WARM_START if start is not None else 0)
+
+
+def pagerank(A, damping=0.85, tol=1e-10, max_iterations=0, personalization=None, start=None, symmetric=False):
+    """(rank, info) = PageRank of the graph A stores by out-edges (g4s_pagerank) — CSR.pagerank as a function."""
+    _pagerank_args(damping, tol, max_iterations, personalization, start, symmetric)
+    return A.pagerank(damping, tol, max_iterations, personalization, start, symmetric)
 
 
 def csr_transpose(rowptr, colids, values, rows, cols, with_perm=False):

@@ -456,6 +456,52 @@ g4s_status g4s_sssp(g4s_csr_t A, const int32_t *sources, int32_t n_sources, doub
                     g4s_traverse_info *info, void *stream);
 g4s_status g4s_bfs(g4s_csr_t A, const int32_t *sources, int32_t n_sources, int32_t *level_dev, int32_t max_depth, unsigned flags,
                    g4s_traverse_info *info, void *stream);
+
+/* ---- PageRank on a handle (g4s_pagerank): power iteration, device-resident — the loop a caller would otherwise write around g4s_spmv_transpose and
+ * four or five vector operations, with a host read of the residual per iteration. The result is networkx's `pagerank` with dangling = personalization.
+ * A is square and stored by OUT-edges: row u lists the edges u → v with weight a_uv; repeated columns add. An unweighted graph is a handle whose
+ * values are all 1.
+ *   Out-strength s_u = Σ_v a_uv; a vertex with s_u == 0 is dangling (an empty row, or a row whose weights are all zero). Weights must be finite and
+ *     >= 0: the call checks this on the device in its strength pass; a violation returns G4S_ERR_INVALID and leaves rank_dev unspecified.
+ *   Teleport vector p = personalization_dev / Σ personalization_dev: n doubles on the device, read only, finite and >= 0 with a sum > 0 (otherwise
+ *     G4S_ERR_INVALID); NULL: p_v = 1.0 / n.
+ *   One iteration, in this order of operations (the library is built with -ffp-contract=off):
+ *       x_u = r_u · (1 / s_u), or 0 for a dangling u;   y = Aᵀ·x;   m = Σ_{u dangling} r_u;
+ *       r'_v = damping · (y_v + m · p_v) + (1 − damping) · p_v;   residual = Σ_v |r'_v − r_v|.
+ *   Stop: after the first iteration with residual < tol (strict: tol == 0 runs exactly max_iterations), or at the cap; max_iterations == 0 means 100.
+ *   Start: r_0 = p; with G4S_PAGERANK_WARM_START r_0 = rank_dev / Σ rank_dev (the rules of p). rank_dev (n doubles, device) receives the ranks.
+ *   Accuracy: every quantity is non-negative and the iteration contracts in L1 by `damping`, so after the same number of iterations the result is
+ *     within γ / (1 − damping) in L1 of the exact iteration, γ = (max in-degree + max out-degree + ⌈log₂ n⌉ + 16) · 2⁻⁵³, whatever the order of the
+ *     sums (tests/test_pagerank_gpu.py has the derivation). residual and the dangling mass are summed in a fixed order on a grid that depends on n
+ *     only: the same bits on every run; the ranks too wherever the product is reproducible (every path but the blocked one).
+ *   Checked before any HIP call (G4S_ERR_INVALID): a NULL handle or rank_dev, damping outside [0, 1) or NaN, tol < 0 or NaN, a negative cap, a flag
+ *     bit other than the two below. A non-square handle returns G4S_ERR_INVALID before anything is enqueued. No other entry point accepts these bits.
+ *   Synchronous: the call runs on `stream` and returns when rank_dev is complete. It reads its state back once per batch of at least
+ *     G4S_PAGERANK_BATCH iterations (info.host_waits; later batches are sized from the geometric decay of the residual), so it cannot be captured: on
+ *     a capturing stream it returns G4S_ERR_INVALID and enqueues nothing. Iterations enqueued behind the stop cost their product (info.products) and
+ *     change nothing. One product, traversal or PageRank in flight per handle.
+ *   g4s_csr_pagerank_reserve builds what the calls need (NULL stream, synchronous): 1 / s, x, y and the normalised p (4·n doubles), 16 KiB of
+ *     per-workgroup partial sums, a 64-byte state block, the strength pass, and the handle's transpose through g4s_csr_transpose_reserve — unless
+ *     the flags hold G4S_PAGERANK_SYMMETRIC. A first call without a reserve reserves synchronously; after a reserve a call allocates nothing on the
+ *     device. g4s_csr_get_info(A).plan_bytes counts the workspace (the transpose is counted by g4s_csr_transpose_info); g4s_csr_destroy releases it.
+ *     After g4s_csr_update_values the next call runs the strength pass again, on its stream.
+ *   Out of scope: several teleport vectors at once through g4s_spmm, a pattern-only mode on a handle with arbitrary values, a capturable form, the
+ *     distributed handle. */
+#define G4S_PAGERANK_SYMMETRIC   65536u  /* the caller declares A == Aᵀ (pattern and values): products run on A itself, no transpose */
+#define G4S_PAGERANK_WARM_START 131072u  /* rank_dev holds the starting vector (normalised inside); default start: the teleport vector */
+#define G4S_PAGERANK_BATCH 8             /* iterations enqueued behind one read of the state, at least */
+typedef struct g4s_pagerank_info {
+    int32_t iterations;   /* iterations that changed rank */
+    int32_t converged;    /* 1: residual < tol; 0: stopped at the cap */
+    int32_t host_waits;   /* times the call waited for the device */
+    int32_t products;     /* products enqueued, those behind the stop included */
+    int64_t dangling;     /* vertices of zero out-strength */
+    double  residual;     /* ‖r_k − r_{k−1}‖₁ of the last iteration */
+} g4s_pagerank_info;
+g4s_status g4s_csr_pagerank_reserve(g4s_csr_t A, unsigned flags);
+g4s_status g4s_pagerank(g4s_csr_t A, double damping, double tol, int32_t max_iterations,
+                        const double *personalization_dev, double *rank_dev, unsigned flags,
+                        g4s_pagerank_info *info, void *stream);
 g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *acol, const double *aval,
                                   const int32_t *brpt, const int32_t *bcol, const double *bval,
                                   int32_t **crpt, int32_t **ccol, double **cval,

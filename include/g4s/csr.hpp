@@ -276,6 +276,26 @@ void BFS(const CSR<IT, NT> &a, const IT *sources, IT n_sources, int32_t *level, 
 template <typename IT, typename NT>
 void BFS(const CSR<IT, NT> &a, IT source, int32_t *level) { BFS(a, &source, (IT)1, level); }
 
+// PageRank of the graph `a` stores by out-edges (g4s_pagerank; include/g4s.h has the contract: networkx's pagerank with dangling = personalization,
+// weights finite and >= 0), host arrays, synchronous: rank receives a.rows values; personalization (a.rows values, or nullptr for the uniform
+// teleport vector) is staged on the device; max_iterations == 0 means 100. A handle, one call, the handle destroyed.
+template <typename IT, typename NT>
+void PageRank(const CSR<IT, NT> &a, NT *rank, double damping = 0.85, double tol = 1e-10, int32_t max_iterations = 0, const NT *personalization = nullptr,
+              g4s_pagerank_info *info = nullptr)
+{
+    detail::traverse(a, rank, "PageRank", [&](g4s_csr_t h, NT *r) {
+        void *p = nullptr;
+        g4s_status st = G4S_OK;
+        if (personalization) {
+            st = g4s_dev_alloc(&p, sizeof(NT) * ((size_t)a.rows + 1));
+            if (st == G4S_OK) st = g4s_memcpy_h2d(p, personalization, sizeof(NT) * (size_t)a.rows);
+        }
+        if (st == G4S_OK) st = g4s_pagerank(h, damping, tol, max_iterations, (const NT *)p, r, 0u, info, nullptr);
+        if (p) g4s_dev_free(p);
+        return st;
+    });
+}
+
 // Y = alpha·A·X + beta·Y with host blocks X (cols × k) and Y (rows × k): row-major by default (ld >= k), column-major as in cblas_dxxmm.c's
 // B and C (ld >= cols / rows) with col_major = true.
 template <typename IT, typename NT>
