@@ -15,6 +15,7 @@ SPMM_COL_MAJOR = 256
 SPMV_ACCUMULATE = 2048                                                   # semiring SpMV: y := y ⊕ (A ⊗ x) (g4s.h)
 TRAVERSE_PUSH, TRAVERSE_PULL, TRAVERSE_SYMMETRIC, TRAVERSE_BATCH = 4096, 8192, 16384, 16   # g4s_sssp / g4s_bfs (g4s.h)
 PAGERANK_SYMMETRIC, PAGERANK_WARM_START, PAGERANK_BATCH = 65536, 131072, 8                 # g4s_pagerank (g4s.h)
+BC_ACCUMULATE, BC_BATCH = 262144, 16                                     # g4s_betweenness (g4s.h)
 CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
 SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM / SpMV value semiring (g4s.h)
 PATTERN_ELEMENT_BLOCK_MATVEC, PATTERN_DENSE_ROW_TIMES_MATRIX, PATTERN_SYM_QUADRATIC_FORM = 1, 2, 3
@@ -46,6 +47,12 @@ class PagerankInfo(C.Structure):
     """g4s_pagerank_info: what a g4s_pagerank call did."""
     _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("host_waits", C.c_int32), ("products", C.c_int32),
                 ("dangling", C.c_int64), ("residual", C.c_double)]
+
+
+class BcInfo(C.Structure):
+    """g4s_bc_info: what a g4s_betweenness call did."""
+    _fields_ = [("sources", C.c_int32), ("max_depth", C.c_int32), ("host_waits", C.c_int32), ("sigma_exact", C.c_int32),
+                ("levels", C.c_int64), ("reached", C.c_int64), ("edges_walked", C.c_int64), ("sigma_max", C.c_double)]
 
 
 class MaskedInfo(C.Structure):
@@ -144,6 +151,8 @@ SIGNATURES = {
     "g4s_bfs": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint, C.POINTER(TraverseInfo), vp]),
     "g4s_csr_pagerank_reserve": (C.c_int, [vp, C.c_uint]),
     "g4s_pagerank": (C.c_int, [vp, C.c_double, C.c_double, C.c_int32, vp, vp, C.c_uint, C.POINTER(PagerankInfo), vp]),
+    "g4s_csr_betweenness_reserve": (C.c_int, [vp, C.c_uint]),
+    "g4s_betweenness": (C.c_int, [vp, vp, C.c_int32, C.c_double, vp, C.c_uint, C.POINTER(BcInfo), vp]),
     "g4s_spmm": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint, vp]),
     "g4s_csr_spmm_reserve": (C.c_int, [vp, C.c_int32]),
     "g4s_spmm_csr_i32_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_uint]),

@@ -1,0 +1,590 @@
+// betweenness.hip — g4s_betweenness (include/g4s.h): Brandes' betweenness centrality on a CSR handle stored by out-edges, one source after the other,
+// both halves of every traversal on the device.
+//
+// Forward half: a BFS that counts shortest paths, ONE kernel per level, shaped like push_kernel of traverse.hip. `order` holds every frontier of the
+// traversal one behind the other (a vertex joins once, so rows entries suffice); level d is order[level_start[d] .. level_start[d + 1]). A workgroup
+// takes 256 frontier vertices, scans their degrees in LDS and its lanes walk the concatenated edge range; a vertex above kHubCut edges is also kept
+// in a hub list of its own (two of them, ping-pong: `order` has no free back end) and walked by all workgroups in kHubChunk-edge chunks. Per edge
+// u → v: compare-and-swap of level[v] from −1 to d + 1 — the winner appends v, one atomicAdd per wave — then, if level[v] == d + 1, σ[v] += σ[u] by
+// an fp64 global atomic. σ[u] is final: level d was completed behind the previous kernel boundary, and nobody reads σ[v] before the next one.
+// The workgroup that finishes last (a ticket, no waiting) records level_start[d + 2], the lane count of the new level for the way back, the
+// counters and `stop`: 1 nothing new was found, 4 the frontier outgrew the launch grid. A kernel that finds stop != 0 returns at once, so the host
+// enqueues kBatch (doubling to kBatchMax) launches blind and reads the 104-byte state once per batch. Each frontier vertex's σ goes into one max
+// per source (sigma_max_bits): a non-finite one is G4S_ERR_OVERFLOW, one above 2^53 clears sigma_exact.
+//
+// Backward half: D known from that read, one kernel per level d = D − 1 … 1 without further reads (level 0 is the source, whose δ is 0 by
+// definition). Vertex u of level d is OWNED by a group of LPR ∈ {1, 4, 16, 64} lanes — chosen per level from its mean degree by the forward step
+// that built it — which walks row u of A (no transpose: the successors of u are among its out-edges) and sums σ[u] / σ[v] · (1 + δ[v]) over the
+// edges into level d + 1: lane j takes entries j, j + LPR, … in order, then a butterfly over the group. The owner writes δ[u] and acc[u] += δ[u].
+// Rows above kHubCut are skipped there and summed by a whole workgroup each (back_long_kernel: 256 strided partial sums, a shuffle tree per
+// wave, the waves in index order); that kernel is launched only when the handle has such a row. No atomics on this side, so δ and acc are the
+// same bits whatever the grid. An epilogue writes bc = (old bc) + scale · acc.
+//
+// Determinism: while every σ <= 2^53 the forward atomics add integers exactly, in any order; everything else is summed in an order fixed by the
+// graph and the source list. Where it loses: one level is one launch in each direction — a deep graph is launch-bound.
+#include "common.hpp"
+#include "csr_handle.hpp"
+#include "readback.hpp"
+#include "betweenness.hpp"
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <new>
+
+namespace {
+
+using g4s::BcState;
+
+constexpr int WG = 256;
+constexpr int kHubCut = 4096;     // a vertex with more out-edges is a hub: walked by all workgroups (forward), summed by a whole one (backward)
+constexpr int kHubChunk = 1024;   // edges of a hub per workgroup visit
+constexpr int kBatch = G4S_BC_BATCH;
+constexpr int kBatchMax = 64;
+constexpr long long kEdgesPerWg = 2048;   // the launch grid of a batch: one workgroup per 2048 frontier edges
+constexpr long long kGridGrowth = 8;      // stop = 4 once the frontier has 8 times the edges the grid was sized for
+
+static_assert(sizeof(BcState) == 104, "the host reads BcState as one small block");
+
+struct StepArgs {
+    long long grid_cap;   // more out-edges than this ask for a larger grid
+    int resume;           // the first launch of a batch goes on from stop == 4
+};
+
+struct Arrays {           // the workspace and the matrix, as the kernels see them
+    int rows, hub_cap;
+    const int *rowptr, *colids;
+    const double *values;
+    int *level, *order, *level_start, *hub0, *hub1;
+    unsigned char *lpr;
+    double *sigma, *delta, *acc;
+    BcState *st;
+};
+
+__device__ __forceinline__ int lanes_for(long long edges, int n) { return edges <= 2ll * n ? 1 : edges <= 8ll * n ? 4 : edges <= 32ll * n ? 16 : 64; }
+
+// The fills of one traversal, fused: level = −1, σ = δ = 0 (acc too for the first source of a call), the source at level 0 with σ = 1, the state.
+__global__ __launch_bounds__(WG) void init_kernel(const Arrays w, int src, int first)
+{
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < w.rows; i += (long long)gridDim.x * WG) {
+        const bool is = i == src;
+        w.level[i] = is ? 0 : -1;
+        w.sigma[i] = is ? 1.0 : 0.0;
+        w.delta[i] = 0.0;
+        if (first) w.acc[i] = 0.0;
+    }
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    BcState *st = w.st;
+    const int deg = w.rowptr[src + 1] - w.rowptr[src], hub = deg > kHubCut;
+    w.order[0] = src;
+    w.level_start[0] = 0;
+    w.level_start[1] = 1;
+    if (hub) w.hub0[0] = src;
+    st->edges_cur = deg; st->edges_next = 0; st->edges_level_max = deg;
+    st->n_cur = 1; st->width_max = 1; st->n_hub_cur = hub; st->n_hub_next = 0;
+    st->tail = 1; st->depth = 0; st->stop = 0; st->cur = 0; st->tickets = 0;
+    if (first) { st->max_depth = 0; st->levels = 0; st->reached = 0; st->edges_walked = 0; st->sigma_max_bits = 0ull; }
+    st->reached += 1;
+}
+
+// One atomicAdd per wave for the vertices its lanes discovered; a hub goes to the next hub list as well.
+__device__ __forceinline__ void append(bool want, int v, int deg, const Arrays &w, int *hubs_next, long long &deg_sum)
+{
+    const unsigned long long m = __ballot(want);
+    if (!want) return;
+    const int lane = __lane_id();
+    const int leader = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&w.st->tail, __popcll(m));
+    base = __shfl(base, leader);
+    const int idx = base + __popcll(m & ((1ull << lane) - 1ull));
+    if ((unsigned)idx < (unsigned)w.rows) w.order[idx] = v;            // a vertex is appended once per traversal: idx < rows by construction
+    if (deg > kHubCut) {
+        const int h = atomicAdd(&w.st->n_hub_next, 1);
+        if ((unsigned)h < (unsigned)w.hub_cap) hubs_next[h] = v;       // at most nnz / (kHubCut + 1) such rows exist
+    }
+    deg_sum += deg;
+}
+
+// The edge u → v (entry k) seen from level d: claim v for level d + 1 if nobody has, then hand σ[u] on if v is in level d + 1.
+template <bool VALUES>
+__device__ __forceinline__ bool relax(int k, int v, double su, int d, const Arrays &w)
+{
+    if constexpr (VALUES) {
+        if (!(w.values[k] != 0.0)) return false;                      // or-and: a stored 0.0 is no edge (NaN counts as one)
+    }
+    int lv = w.level[v];                                               // a stale read is −1: the compare-and-swap below decides
+    bool won = false;
+    if (lv == -1) {
+        const int old = atomicCAS(w.level + v, -1, d + 1);
+        won = old == -1;
+        lv = won ? d + 1 : old;
+    }
+    if (lv == d + 1) atomicAdd(w.sigma + v, su);
+    return won;
+}
+
+// The end of a forward step: the block's share of the next frontier's out-edges and of the σ maximum, then the ticket; the last block turns the page.
+__device__ __forceinline__ void finish(const Arrays &w, long long deg_sum, double smax, int d, int end, const StepArgs a)
+{
+    __shared__ long long s_red[WG / 64];
+    __shared__ double s_max[WG / 64];
+    __shared__ int s_last;
+    BcState *st = w.st;
+    for (int o = 32; o > 0; o >>= 1) {
+        deg_sum += __shfl_down(deg_sum, o);
+        smax = fmax(smax, __shfl_down(smax, o));
+    }
+    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = deg_sum; s_max[threadIdx.x >> 6] = smax; }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long sum = 0;
+        double mx = 0.0;
+        for (int i = 0; i < WG / 64; ++i) { sum += s_red[i]; mx = fmax(mx, s_max[i]); }
+        if (sum) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)sum);
+        if (mx > 0.0) atomicMax(&st->sigma_max_bits, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order as their bits
+        __threadfence();
+        s_last = atomicAdd(&st->tickets, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last || threadIdx.x != 0) return;
+    __threadfence();
+    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0);
+    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
+    const int n_new = tail - end;
+    st->levels += 1;
+    st->edges_walked += st->edges_cur * (n_new > 0 ? 2 : 1);           // level d is walked again on the way back unless it is the deepest
+    w.level_start[d + 2] = tail;                                       // d <= rows − 1 and level_start has rows + 2 entries
+    if (n_new > 0) {
+        w.lpr[d + 1] = (unsigned char)lanes_for(e, n_new);
+        st->depth = d + 1;
+        st->reached += n_new;
+        if (d + 1 > st->max_depth) st->max_depth = d + 1;
+        if (n_new > st->width_max) st->width_max = n_new;
+        if (e > st->edges_level_max) st->edges_level_max = e;
+    }
+    st->n_cur = n_new; st->n_hub_cur = nh; st->edges_cur = e;
+    st->n_hub_next = 0; st->edges_next = 0;
+    st->cur ^= 1;
+    st->tickets = 0;
+    st->stop = n_new == 0 ? 1 : (e > a.grid_cap ? 4 : 0);
+}
+
+template <bool VALUES>
+__global__ __launch_bounds__(WG) void forward_kernel(const Arrays w, const StepArgs a)
+{
+    __shared__ int s_scan[WG + 1];
+    __shared__ int s_start[WG];
+    __shared__ double s_su[WG];
+    __shared__ int s_wsum[WG / 64];
+    BcState *st = w.st;
+    if (st->stop != 0 && !(st->stop == 4 && a.resume)) return;        // the same word for every block: it changes only after the last ticket
+    const int d = st->depth, nh = st->n_hub_cur, cur = st->cur;
+    const int begin = w.level_start[d], end = w.level_start[d + 1], n = end - begin;
+    const int *hubs = cur ? w.hub1 : w.hub0;
+    int *hubs_next = cur ? w.hub0 : w.hub1;
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, G = (int)gridDim.x;
+    long long deg_sum = 0;
+    double smax = 0.0;
+
+    for (int s0 = (int)blockIdx.x * WG; s0 < n; s0 += G * WG) {
+        const int i = s0 + t;
+        int start = 0, deg = 0;
+        double su = 0.0;
+        if (i < n) {
+            const int u = w.order[begin + i];
+            start = w.rowptr[u];
+            deg = w.rowptr[u + 1] - start;
+            if (deg > kHubCut) deg = 0;                                // a hub: walked below, out of the hub list
+            su = w.sigma[u];
+            smax = fmax(smax, su);                                     // fmax drops a NaN; +inf is what an overflow leaves
+        }
+        int x = deg;                                                   // inclusive scan of the 256 degrees
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_wsum[wave] = x;
+        s_start[t] = start;
+        s_su[t] = su;
+        __syncthreads();
+        int off = 0;
+        for (int i2 = 0; i2 < wave; ++i2) off += s_wsum[i2];
+        s_scan[t + 1] = off + x;
+        if (t == 0) s_scan[0] = 0;
+        __syncthreads();
+        const int total = s_scan[WG];                                  // 256 rows of at most kHubCut entries: no overflow
+        int lo = 0;                                                    // the last entry with s_scan[lo] <= e: never decreases as e grows
+        for (int e0 = 0; e0 < total; e0 += WG) {
+            const int e = e0 + t;
+            bool want = false;
+            int v = 0, vdeg = 0;
+            if (e < total) {
+                int hi = WG - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (s_scan[mid] <= e) lo = mid;
+                    else hi = mid - 1;
+                }
+                const int k = s_start[lo] + (e - s_scan[lo]);
+                v = w.colids[k];
+                want = relax<VALUES>(k, v, s_su[lo], d, w);
+                if (want) vdeg = w.rowptr[v + 1] - w.rowptr[v];
+            }
+            append(want, v, vdeg, w, hubs_next, deg_sum);
+        }
+        __syncthreads();
+    }
+
+    for (int h = 0; h < nh; ++h) {                                     // hubs: chunk c of hub h belongs to block (c + 4h) mod G
+        const int u = hubs[h];
+        const int start = w.rowptr[u], deg = w.rowptr[u + 1] - start;
+        const double su = w.sigma[u];
+        const int chunks = (deg + kHubChunk - 1) / kHubChunk;
+        int first = (int)(((long long)blockIdx.x - 4ll * h) % G);
+        if (first < 0) first += G;
+        for (int c = first; c < chunks; c += G) {
+            for (int j = 0; j < kHubChunk; j += WG) {
+                const int e = c * kHubChunk + j + t;
+                bool want = false;
+                int v = 0, vdeg = 0;
+                if (e < deg) {
+                    const int k = start + e;
+                    v = w.colids[k];
+                    want = relax<VALUES>(k, v, su, d, w);
+                    if (want) vdeg = w.rowptr[v + 1] - w.rowptr[v];
+                }
+                append(want, v, vdeg, w, hubs_next, deg_sum);
+            }
+        }
+    }
+    finish(w, deg_sum, smax, d, end, a);
+}
+
+// The term of the edge u → v (entry k) in δ[u], for u in level d.
+template <bool VALUES>
+__device__ __forceinline__ double term(int k, double su, int d, const Arrays &w)
+{
+    if constexpr (VALUES) {
+        if (!(w.values[k] != 0.0)) return 0.0;
+    }
+    const int v = w.colids[k];
+    if (w.level[v] != d + 1) return 0.0;
+    return su / w.sigma[v] * (1.0 + w.delta[v]);
+}
+
+// Level [begin, end) of `order`, LPR lanes per vertex: lane j sums entries j, j + LPR, … of the row in order, then a butterfly over the group.
+template <int LPR, bool VALUES>
+__device__ __forceinline__ void back_rows(const Arrays &w, int begin, int end, int d, int src)
+{
+    constexpr int GPB = WG / LPR;
+    const int t = (int)threadIdx.x, lig = t % LPR;
+    for (long long r0 = (long long)begin + (long long)blockIdx.x * GPB; r0 < end; r0 += (long long)gridDim.x * GPB) {
+        const long long i = r0 + t / LPR;
+        double sum = 0.0;
+        bool mine = false;
+        int u = 0;
+        if (i < end) {
+            u = w.order[i];
+            const int b = w.rowptr[u], e = w.rowptr[u + 1];
+            if (e - b <= kHubCut) {
+                mine = true;
+                const double su = w.sigma[u];
+                for (int k = b + lig; k < e; k += LPR) sum += term<VALUES>(k, su, d, w);
+            }
+        }
+        if constexpr (LPR > 1) {
+            for (int o = LPR / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        }
+        if (mine && lig == 0) {
+            w.delta[u] = sum;
+            if (u != src) w.acc[u] += sum;
+        }
+    }
+}
+
+template <bool VALUES>
+__global__ __launch_bounds__(WG) void backward_kernel(const Arrays w, int d, int src)
+{
+    const int begin = w.level_start[d], end = w.level_start[d + 1];
+    switch (w.lpr[d]) {                                                // written by the forward step that built level d: the same for every block
+    case 1: back_rows<1, VALUES>(w, begin, end, d, src); break;
+    case 4: back_rows<4, VALUES>(w, begin, end, d, src); break;
+    case 16: back_rows<16, VALUES>(w, begin, end, d, src); break;
+    default: back_rows<64, VALUES>(w, begin, end, d, src); break;
+    }
+}
+
+// The hubs of level d: a workgroup looks at 256 entries of the level and sums each long row among them with all its threads, in a fixed tree.
+template <bool VALUES>
+__global__ __launch_bounds__(WG) void back_long_kernel(const Arrays w, int d, int src)
+{
+    __shared__ unsigned long long s_mask[WG / 64];
+    __shared__ double s_red[WG / 64];
+    const int begin = w.level_start[d], end = w.level_start[d + 1];
+    const int t = (int)threadIdx.x;
+    for (long long base = (long long)begin + (long long)blockIdx.x * WG; base < end; base += (long long)gridDim.x * WG) {
+        const long long i = base + t;
+        bool is_long = false;
+        if (i < end) {
+            const int u = w.order[i];
+            is_long = w.rowptr[u + 1] - w.rowptr[u] > kHubCut;
+        }
+        const unsigned long long m = __ballot(is_long);
+        if ((t & 63) == 0) s_mask[t >> 6] = m;
+        __syncthreads();
+        for (int wv = 0; wv < WG / 64; ++wv) {
+            unsigned long long mm = s_mask[wv];                        // the same word for every thread: the loop below is uniform
+            while (mm) {
+                const int u = w.order[base + wv * 64 + (__ffsll((long long)mm) - 1)];
+                mm &= mm - 1;
+                const int b = w.rowptr[u], e = w.rowptr[u + 1];
+                const double su = w.sigma[u];
+                double s = 0.0;
+                for (int k = b + t; k < e; k += WG) s += term<VALUES>(k, su, d, w);
+                for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+                if ((t & 63) == 0) s_red[t >> 6] = s;
+                __syncthreads();
+                if (t == 0) {
+                    double sum = 0.0;
+                    for (int i2 = 0; i2 < WG / 64; ++i2) sum += s_red[i2];
+                    w.delta[u] = sum;
+                    if (u != src) w.acc[u] += sum;
+                }
+                __syncthreads();
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(WG) void epilogue_kernel(int rows, double scale, int accumulate, const double *__restrict__ acc, double *__restrict__ bc)
+{
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) bc[i] = (accumulate ? bc[i] : 0.0) + scale * acc[i];
+}
+
+// zero_values |= 1 when a stored value is 0.0 (or-and: a stored zero is no edge, so the kernels then read the values)
+__global__ __launch_bounds__(WG) void any_zero_kernel(long long nnz, const double *__restrict__ values, BcState *st)
+{
+    int z = 0;
+    for (long long k = (long long)blockIdx.x * WG + threadIdx.x; k < nnz; k += (long long)gridDim.x * WG) z |= values[k] == 0.0;
+    if (z) atomicOr(&st->zero_values, 1);
+}
+
+__global__ __launch_bounds__(WG) void max_degree_kernel(int rows, const int *__restrict__ rowptr, BcState *st)
+{
+    int m = 0;
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) m = max(m, rowptr[i + 1] - rowptr[i]);
+    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_down(m, o));
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&st->max_degree, m);
+}
+
+inline int grid_rows(long long n, int cus) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, 8LL * cus)); }
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------ the handle's workspace
+namespace g4s {
+
+struct BcWork {
+    int32_t *ints = nullptr;      // level (n) | order (n) | level_start (n + 2) | hub list 0 | hub list 1 (hub_cap each)
+    unsigned char *lpr = nullptr; // lanes per vertex of every level's backward step (n + 2 bytes)
+    double *vec = nullptr;        // sigma | delta | acc, n doubles each
+    BcState *state = nullptr;
+    int cus = 1;
+    int hub_cap = 1;
+    int max_degree = 0;
+    int values_state = 0;         // 0 unknown, 1 no stored value is zero, 2 some are
+    int64_t n = 0;
+    int64_t bytes = 0;
+};
+
+void betweenness_work_destroy(BcWork *w)
+{
+    if (!w) return;
+    (void)hipFree(w->ints);
+    (void)hipFree(w->lpr);
+    (void)hipFree(w->vec);
+    (void)hipFree(w->state);
+    delete w;
+}
+
+long long betweenness_work_bytes(const BcWork *w) { return w ? w->bytes : 0; }
+
+void betweenness_values_changed(BcWork *w) { if (w) w->values_state = 0; }
+
+} // namespace g4s
+
+namespace {
+
+// The workspace (once), the longest row and whether a stored value is zero. NULL stream, synchronous.
+int reserve(g4s_csr_s *A)
+{
+    if (!A->bc) {
+        g4s::BcWork *w = new (std::nothrow) g4s::BcWork();
+        if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
+        const size_t n = (size_t)std::max(A->rows, 1);
+        w->n = (int64_t)n;
+        w->hub_cap = (int)std::min<int64_t>((int64_t)n, A->nnz / (kHubCut + 1)) + 1;
+        const size_t n_ints = 3 * n + 2 + 2 * (size_t)w->hub_cap;
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->ints, sizeof(int32_t) * n_ints);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->lpr, n + 2);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->vec, sizeof(double) * 3 * n);
+        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->state, sizeof(BcState));
+        if (e == hipSuccess) e = hipMemset(w->state, 0, sizeof(BcState));
+        if (e == hipSuccess && A->rows > 0) {
+            hipLaunchKernelGGL(max_degree_kernel, dim3(grid_rows(A->rows, std::max(w->cus, 1))), dim3(WG), 0, nullptr, A->rows, A->d_rowptr, w->state);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpy(&w->max_degree, &w->state->max_degree, sizeof(int), hipMemcpyDeviceToHost);
+        }
+        if (e != hipSuccess) {
+            g4s::betweenness_work_destroy(w);
+            return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "g4s_csr_betweenness_reserve: %s", hipGetErrorString(e));
+        }
+        w->cus = std::max(w->cus, 1);
+        w->bytes = (int64_t)sizeof(int32_t) * (int64_t)n_ints + (int64_t)(n + 2) + (int64_t)sizeof(double) * 3 * (int64_t)n + (int64_t)sizeof(BcState);
+        A->bc = w;
+    }
+    g4s::BcWork *w = A->bc;
+    if (w->values_state == 0) {
+        int h = 0;
+        if (A->nnz > 0) {
+            G4S_HIP_TRY(hipMemset(&w->state->zero_values, 0, sizeof(int)));
+            hipLaunchKernelGGL(any_zero_kernel, dim3(grid_rows(A->nnz, w->cus)), dim3(WG), 0, nullptr, (long long)A->nnz, A->d_values, w->state);
+            G4S_HIP_TRY(hipGetLastError());
+            G4S_HIP_TRY(hipMemcpy(&h, &w->state->zero_values, sizeof(int), hipMemcpyDeviceToHost));
+        }
+        w->values_state = h ? 2 : 1;
+    }
+    return G4S_OK;
+}
+
+int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double scale, double *bc, unsigned flags, g4s_bc_info *info, hipStream_t s)
+{
+    const char *fn = "g4s_betweenness";
+    if (A->rows != A->cols) return g4s::set_error(G4S_ERR_INVALID, "%s: the handle is %d x %d, betweenness needs a square matrix", fn, A->rows, A->cols);
+    for (int32_t i = 0; i < n_sources; ++i)
+        if (sources[i] < 0 || sources[i] >= A->rows) return g4s::set_error(G4S_ERR_INVALID, "%s: sources[%d] = %d is outside [0, %d)", fn, i, sources[i], A->rows);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its state back and cannot be captured", fn);
+    if (info) *info = g4s_bc_info{};
+    if (!A->bc) G4S_TRY(reserve(A));
+    g4s::BcWork *wk = A->bc;
+
+    const int rows = A->rows;
+    const size_t n = (size_t)wk->n;
+    Arrays w;
+    w.rows = rows; w.hub_cap = wk->hub_cap;
+    w.rowptr = A->d_rowptr; w.colids = A->d_colids; w.values = A->d_values;
+    w.level = wk->ints; w.order = wk->ints + n; w.level_start = wk->ints + 2 * n; w.hub0 = wk->ints + 3 * n + 2; w.hub1 = w.hub0 + wk->hub_cap;
+    w.lpr = wk->lpr;
+    w.sigma = wk->vec; w.delta = wk->vec + n; w.acc = wk->vec + 2 * n;
+    w.st = wk->state;
+    BcState *st = wk->state;
+
+    auto fail = [&](int code) { (void)g4s::reads_sync(s); return code; };   // also settles a noted read of h
+#define BC_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(g4s::set_error(G4S_ERR_HIP, "%s: %s: %s", fn, #expr, hipGetErrorString(e_))); } while (0)
+    // New values since the last verdict: the scan runs in front of the first traversal, which reads the values whatever it will say; the verdict
+    // comes back with the first state read, so it costs no wait of its own.
+    const bool rescan = wk->values_state == 0;
+    if (rescan && A->nnz > 0) {
+        BC_HIP(hipMemsetAsync(&st->zero_values, 0, sizeof(int), s));
+        hipLaunchKernelGGL(any_zero_kernel, dim3(grid_rows(A->nnz, wk->cus)), dim3(WG), 0, s, (long long)A->nnz, A->d_values, st);
+        BC_HIP(hipGetLastError());
+    }
+    const bool values = wk->values_state != 1;
+    const bool has_hubs = wk->max_degree > kHubCut;
+    const int min_grid = 8;
+    const int max_grid = (int)std::max<long long>(min_grid, std::min<long long>(2LL * wk->cus, (A->nnz + rows + kEdgesPerWg - 1) / kEdgesPerWg));
+
+    BcState h{};
+    int waits = 0;
+    for (int32_t i = 0; i < n_sources; ++i) {
+        const int src = sources[i];
+        hipLaunchKernelGGL(init_kernel, dim3(grid_rows(rows, wk->cus)), dim3(WG), 0, s, w, src, (int)(i == 0));
+        BC_HIP(hipGetLastError());
+        bool know = false, outgrown = false;                               // h is this traversal's state; a frontier outgrew a sized grid once
+        int batch = kBatch;
+        for (;;) {
+            int grid = max_grid;
+            if (know && !outgrown) grid = (int)std::max((long long)min_grid, std::min((long long)max_grid, (h.edges_cur + h.n_cur) / kEdgesPerWg));
+            StepArgs a;
+            a.grid_cap = grid == max_grid ? LLONG_MAX : (long long)grid * kEdgesPerWg * kGridGrowth;
+            for (int b = 0; b < batch; ++b) {
+                a.resume = b == 0;
+                if (values) hipLaunchKernelGGL(forward_kernel<true>, dim3(grid), dim3(WG), 0, s, w, a);
+                else hipLaunchKernelGGL(forward_kernel<false>, dim3(grid), dim3(WG), 0, s, w, a);
+            }
+            BC_HIP(hipGetLastError());
+            BC_HIP(g4s::read_small(&h, st, sizeof(BcState), s));
+            BC_HIP(g4s::reads_sync(s));
+            ++waits;
+            if (rescan) wk->values_state = h.zero_values ? 2 : 1;
+            if (h.stop == 1) break;
+            if (h.stop == 4) outgrown = true;                              // the rest of this traversal runs on the full grid: one resume per source
+            if (know) batch = std::min(kBatchMax, batch * 2);
+            know = true;
+        }
+        double smax;
+        memcpy(&smax, &h.sigma_max_bits, sizeof smax);
+        if (!(smax < (double)INFINITY))
+            return g4s::set_error(G4S_ERR_OVERFLOW, "%s: the number of shortest paths from sources[%d] = %d exceeds the range of a double", fn, i, src);
+        const int D = h.depth;
+        const int gb = (int)std::max(1LL, std::min(4LL * wk->cus, (h.edges_level_max + h.width_max + kEdgesPerWg - 1) / kEdgesPerWg));
+        const int gl = (int)std::max(1LL, std::min(4LL * wk->cus, ((long long)h.width_max + WG - 1) / WG));
+        for (int d = D - 1; d >= 1; --d) {
+            if (values) hipLaunchKernelGGL(backward_kernel<true>, dim3(gb), dim3(WG), 0, s, w, d, src);
+            else hipLaunchKernelGGL(backward_kernel<false>, dim3(gb), dim3(WG), 0, s, w, d, src);
+            if (has_hubs) {
+                if (values) hipLaunchKernelGGL(back_long_kernel<true>, dim3(gl), dim3(WG), 0, s, w, d, src);
+                else hipLaunchKernelGGL(back_long_kernel<false>, dim3(gl), dim3(WG), 0, s, w, d, src);
+            }
+        }
+        BC_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(epilogue_kernel, dim3(grid_rows(rows, wk->cus)), dim3(WG), 0, s, rows, scale, (int)((flags & G4S_BC_ACCUMULATE) != 0), (const double *)w.acc, bc);
+    BC_HIP(hipGetLastError());
+    BC_HIP(g4s::reads_sync(s));
+    ++waits;
+#undef BC_HIP
+    if (info) {
+        double smax;
+        memcpy(&smax, &h.sigma_max_bits, sizeof smax);
+        info->sources = n_sources;
+        info->max_depth = h.max_depth;
+        info->host_waits = waits;
+        info->sigma_exact = smax <= 9007199254740992.0;
+        info->levels = h.levels;
+        info->reached = h.reached;
+        info->edges_walked = h.edges_walked;
+        info->sigma_max = smax;
+    }
+    return G4S_OK;
+}
+
+} // namespace
+
+G4S_API g4s_status g4s_csr_betweenness_reserve(g4s_csr_t A, unsigned flags)
+{
+    G4S_REQUIRE(flags == 0u, "flags must be 0");
+    G4S_REQUIRE(A, "NULL handle");
+    G4S_REQUIRE(A->rows == A->cols, "betweenness needs a square matrix");
+    G4S_HIP_TRY(hipDeviceSynchronize());
+    return reserve(A);
+}
+
+G4S_API g4s_status g4s_betweenness(g4s_csr_t A, const int32_t *sources, int32_t n_sources, double scale, double *bc_dev, unsigned flags, g4s_bc_info *info,
+                                   void *stream)
+{
+    G4S_REQUIRE((flags & ~G4S_BC_ACCUMULATE) == 0u, "flags other than G4S_BC_ACCUMULATE");
+    G4S_REQUIRE(A, "NULL handle");
+    G4S_REQUIRE(sources, "sources is NULL");
+    G4S_REQUIRE(bc_dev, "bc_dev is NULL");
+    G4S_REQUIRE(n_sources >= 1, "n_sources < 1 (sources is empty)");
+    G4S_REQUIRE(std::isfinite(scale), "scale is not finite");
+    return betweenness(A, sources, n_sources, scale, bc_dev, flags, info, g4s::as_stream(stream));
+}

@@ -2,7 +2,7 @@
 //
 // A handle holds the matrix on the device and the plan of one of four SpMV paths, each a module of its own with the same interface (build, update_values,
 // destroy, bytes, spmv): row-streaming (spmv.hip, spmv_stream.hpp), propagation-blocked (spmv_pb.hip), diagonal (spmv_dia.hip), block-row (spmv_bcsr.hip).
-// g4s_spmm (spmm.hip), the transposed products (transpose.hip), the traversals (traverse.hip) and PageRank (pagerank.hip) work on the same handle through csr_handle.hpp. Nothing device-side lives here but the
+// g4s_spmm (spmm.hip), the transposed products (transpose.hip), the traversals (traverse.hip), PageRank (pagerank.hip) and betweenness centrality (betweenness.hip) work on the same handle through csr_handle.hpp. Nothing device-side lives here but the
 // column range check of g4s_csr_create.
 #include "csr_handle.hpp"
 #include <new>
@@ -36,6 +36,7 @@ void release(g4s_csr_s *A)
     g4s::transpose_work_destroy(A->tr);
     g4s::traverse_work_destroy(A->trv);
     g4s::pagerank_work_destroy(A->prk);
+    g4s::betweenness_work_destroy(A->bc);
     delete A;                                                       // the row-streaming plan frees its own buffers
 }
 
@@ -197,6 +198,7 @@ G4S_API g4s_status g4s_csr_update_values(g4s_csr_t A, const double *values, unsi
     int st = update_values(A, values, flags, stream);
     g4s::traverse_values_changed(A->trv);
     g4s::pagerank_values_changed(A->prk);
+    g4s::betweenness_values_changed(A->bc);
     if (A->tr) {
         const int st2 = g4s::transpose_update_values(A->tr, A->d_values, g4s::as_stream(stream));
         if (st == G4S_OK) st = st2;
@@ -219,7 +221,7 @@ G4S_API g4s_status g4s_csr_get_info(g4s_csr_t A, g4s_csr_info *info)
     info->algorithmic_bytes = 12 * A->nnz + 4 * ((int64_t)A->rows + 1) + 8 * (int64_t)A->rows + 8 * (int64_t)A->cols;
     // every part knows its own size; a transpose's bytes are added by g4s_csr_transpose_info
     info->plan_bytes = A->stream.bytes() + g4s::pb_bytes(A->pb) + g4s::dia_bytes(A->dia) + g4s::bcsr_bytes(A->bcsr) + g4s::spmm_work_bytes(A->spmm) +
-                       g4s::traverse_work_bytes(A->trv) + g4s::pagerank_work_bytes(A->prk);
+                       g4s::traverse_work_bytes(A->trv) + g4s::pagerank_work_bytes(A->prk) + g4s::betweenness_work_bytes(A->bc);
     info->spmv_path = g4s::csr_spmv_path(A);
     return G4S_OK;
 }

@@ -1,5 +1,5 @@
 // csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip,
-// traverse.hip, pagerank.hip.
+// traverse.hip, pagerank.hip, betweenness.hip.
 #pragma once
 #include "common.hpp"
 #include "spmv_stream.hpp"
@@ -35,6 +35,12 @@ void pagerank_work_destroy(PagerankWork *w);
 long long pagerank_work_bytes(const PagerankWork *w);
 void pagerank_values_changed(PagerankWork *w);   // g4s_csr_update_values: the strength pass has to run again
 
+// betweenness.hip: the workspace of g4s_betweenness (levels, the concatenated frontiers and their starts, hub lists, σ, δ, the sum over sources, the state block)
+struct BcWork;
+void betweenness_work_destroy(BcWork *w);
+long long betweenness_work_bytes(const BcWork *w);
+void betweenness_values_changed(BcWork *w);   // g4s_csr_update_values: whether a stored value is zero has to be found out again
+
 } // namespace g4s
 
 struct g4s_csr_s {
@@ -56,6 +62,7 @@ struct g4s_csr_s {
     g4s::TransposeWork *tr = nullptr;   // Aᵀ and its handle (transpose.hip), built by g4s_csr_transpose_reserve or a first transposed product
     g4s::TraverseWork *trv = nullptr;   // g4s_sssp / g4s_bfs workspace (traverse.hip), built by g4s_csr_traverse_reserve or a first traversal
     g4s::PagerankWork *prk = nullptr;   // g4s_pagerank workspace (pagerank.hip), built by g4s_csr_pagerank_reserve or a first g4s_pagerank
+    g4s::BcWork *bc = nullptr;          // g4s_betweenness workspace (betweenness.hip), built by g4s_csr_betweenness_reserve or a first g4s_betweenness
 };
 
 namespace g4s {

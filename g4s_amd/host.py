@@ -11,6 +11,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
   pagerank       — PageRank of a graph stored by out-edges (g4s_pagerank): one call, the loop, the dangling mass and the stop test on the device
+  betweenness    — betweenness centrality from a list of sources (g4s_betweenness): Brandes' two sweeps per source, both on the device
   spmv_transpose — y = alpha·Aᵀ·x + beta·y on a handle of A (spmv_semiring_transpose: the semiring form), through the handle's own transpose
 Everything here calls the C-ABI (libg4s_hip.so); torch tensors only hold device memory. No CPU fallback.
 """
@@ -182,6 +183,26 @@ class CSR:
                                             _stream()))
         return rank, {n: getattr(info, n) for n, _ in capi.PagerankInfo._fields_}
 
+    def betweenness_reserve(self):
+        """Build now what betweenness needs (g4s_csr_betweenness_reserve; synchronous): the workspace and the verdict on stored zeros. No transpose."""
+        if self.rows != self.cols:
+            raise ValueError(f"betweenness needs a square matrix, not {self.rows} x {self.cols}")
+        torch.cuda.current_stream().synchronize()
+        capi.check(capi.load().g4s_csr_betweenness_reserve(self.handle, 0))
+
+    def betweenness(self, sources, scale=1.0, out=None, accumulate=False):
+        """Betweenness centrality of the graph this matrix stores by out-edges, from `sources` (vertex ids; an int or a sequence — each one is a
+        traversal, a repeated one counts twice; g4s_betweenness): (float64 tensor of rows; info dict). bc[v] = scale · Σ_s δ_s(v) with Brandes'
+        dependencies δ_s: the sum over s of networkx's betweenness_centrality_subset(G, [s], G, normalized=False). An entry is an edge when it is
+        != 0, repeated columns are parallel edges. accumulate=True adds to `out` (a float64 device tensor of rows, required then) instead of
+        overwriting it. Bit-for-bit reproducible while info["sigma_exact"] == 1. Synchronous. ValueError before any GPU call for bad arguments; a
+        path count beyond the range of a double raises G4SError with status ERR_OVERFLOW."""
+        src, flags = _betweenness_args(sources, scale, out, accumulate, self)
+        bc = torch.empty(self.rows, dtype=torch.float64, device=self.rowptr.device) if out is None else out
+        info = capi.BcInfo()
+        capi.check(capi.load().g4s_betweenness(self.handle, C.c_void_p(src.ctypes.data), int(src.size), float(scale), _ptr_nn(bc), flags, C.byref(info), _stream()))
+        return bc, {n: getattr(info, n) for n, _ in capi.BcInfo._fields_}
+
     def triangle_count(self, return_info=False):
         """The triangles of the graph whose symmetric pattern (or lower triangle) this matrix stores — triangle_count(self)."""
         return triangle_count(self, return_info)
@@ -319,6 +340,43 @@ def pagerank(A, damping=0.85, tol=1e-10, max_iterations=0, personalization=None,
     """(rank, info) = PageRank of the graph A stores by out-edges (g4s_pagerank) — CSR.pagerank as a function."""
     _pagerank_args(damping, tol, max_iterations, personalization, start, symmetric)
     return A.pagerank(damping, tol, max_iterations, personalization, start, symmetric)
+
+
+def _betweenness_args(sources, scale, out, accumulate, A=None):
+    """(sources as a contiguous int32 array, the flags of g4s_betweenness); ValueError (before any GPU call) for an argument the call would refuse."""
+    if isinstance(sources, (str, bytes)) or sources is None:
+        raise ValueError(f"sources must be a vertex id or a sequence of vertex ids, not {sources!r}")
+    try:
+        arr = np.atleast_1d(np.asarray(sources))
+    except Exception as e:
+        raise ValueError(f"sources must be a vertex id or a sequence of vertex ids: {e}") from None
+    if arr.ndim != 1 or arr.size < 1 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"sources must be a non-empty 1-D sequence of integers, not {sources!r}")
+    if arr.min() < 0 or arr.max() >= (A.rows if A is not None else 2 ** 31):
+        raise ValueError(f"sources holds a vertex id outside [0, {A.rows if A is not None else 2 ** 31})")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating, np.integer)) or not np.isfinite(scale):
+        raise ValueError(f"scale must be a finite number, not {scale!r}")
+    if not isinstance(accumulate, (bool, np.bool_)):
+        raise ValueError(f"accumulate must be a bool, not {accumulate!r}")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the out to add to (out is None)")
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 1 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous 1-D float64 tensor or None")
+        if A is not None and out.numel() != A.rows:
+            raise ValueError(f"out has {out.numel()} entries, the graph has {A.rows} vertices")
+        if not out.is_cuda:
+            raise ValueError("out must be a device tensor")
+    if A is not None and A.rows != A.cols:
+        raise ValueError(f"betweenness needs a square matrix, not {A.rows} x {A.cols}")
+    return np.ascontiguousarray(arr, dtype=np.int32), (capi.BC_ACCUMULATE if accumulate else 0)
+
+
+def betweenness(A, sources, scale=1.0, out=None, accumulate=False):
+    """(bc, info) = betweenness centrality of the graph A stores by out-edges, from `sources` (g4s_betweenness) — CSR.betweenness as a function."""
+    _betweenness_args(sources, scale, out, accumulate)
+    return A.betweenness(sources, scale, out, accumulate)
 
 
 def csr_transpose(rowptr, colids, values, rows, cols, with_perm=False):

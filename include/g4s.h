@@ -502,6 +502,60 @@ g4s_status g4s_csr_pagerank_reserve(g4s_csr_t A, unsigned flags);
 g4s_status g4s_pagerank(g4s_csr_t A, double damping, double tol, int32_t max_iterations,
                         const double *personalization_dev, double *rank_dev, unsigned flags,
                         g4s_pagerank_info *info, void *stream);
+
+/* ---- Betweenness centrality on a handle (g4s_betweenness): Brandes' algorithm, one BFS that counts shortest paths and one dependency sweep per
+ * source, both device-resident — what neither g4s_bfs (it keeps no path counts and forgets its frontiers) nor a host loop over g4s_spmv_semiring
+ * (no semiring expresses the σ_u / σ_v · (1 + δ_v) recurrence) can give. A is square and stored by OUT-edges: row u lists the edges u → v.
+ *   Edges: a stored entry is an edge under g4s_bfs's or-and rule, a_uv != 0 (NaN counts as an edge); the weight itself is not used. Values are read
+ *     only when a stored zero exists; that verdict is taken at the reserve and again after g4s_csr_update_values. Repeated columns are PARALLEL
+ *     edges: each carries its own shortest paths.
+ *   sources: a HOST array of n_sources >= 1 vertex ids, as for g4s_bfs. Each listed source is one traversal, in the order given; a repeated source
+ *     counts twice.
+ *   For a source s: level = BFS depth; σ[s] = 1, σ[v] = Σ σ[u] over the edges u → v with level[u] = level[v] − 1 (the number of shortest paths);
+ *     from the deepest level upwards δ[u] = Σ over the edges u → v with level[v] = level[u] + 1 of (σ[u] / σ[v]) · (1 + δ[v]); δ[s] = 0, and an
+ *     unreached vertex has δ = 0.
+ *   Result: bc_dev[v] = scale · Σ_s δ_s(v) (rows doubles on the device, only written) — with G4S_BC_ACCUMULATE bc_dev[v] + scale · Σ_s δ_s(v), so a
+ *     long source list may be split over calls. This is the sum over s of networkx's betweenness_centrality_subset(G, [s], all nodes,
+ *     normalized=False) on a DiGraph without parallel edges; scale = 0.5 with every vertex as a source gives networkx's undirected value on a
+ *     symmetric A, 1 / ((n − 1)(n − 2)) the normalised directed one.
+ *   Exactness: σ is fp64. While every σ <= 2^53 the path counts are integers and their sums exact in whatever order the atomics of the forward step
+ *     land; δ and the sum over sources are formed without atomics in an order that depends on the graph and the source list only (fixed lanes per
+ *     row, fixed shuffle trees, sources one after the other). The result is then the same bits on every run, stream and launch grid, and
+ *     info.sigma_exact = 1. Above 2^53 (sigma_exact = 0) σ carries rounding that depends on the order of arrival: the result stays within 1e-10
+ *     relative of the exact one but need not repeat bit for bit. A σ that overflows to infinity returns G4S_ERR_OVERFLOW with bc_dev unspecified
+ *     (a 1000 × 1000 grid from a corner reaches about 2^1994); it is detected on the device, one maximum per source read with the state, and the
+ *     handle stays usable.
+ *   Checked before any HIP call (G4S_ERR_INVALID, g4s_last_error names the argument): a NULL handle, sources or bc_dev, n_sources < 1, a scale
+ *     that is not finite, a flag bit other than G4S_BC_ACCUMULATE (the reserve accepts no bit). Before anything is enqueued: a non-square handle, a
+ *     source outside [0, rows), a capturing stream. No other entry point accepts the bit.
+ *   Synchronous: the call runs on `stream` and returns when bc_dev is complete. The forward half is one kernel per level, enqueued blind in batches
+ *     of at least G4S_BC_BATCH (doubling to 64 within a traversal) with one read of the 104-byte state per batch; the backward half is one kernel
+ *     per level (two on a handle with a row above 4096 entries) without reads. info.host_waits <= ⌈levels / G4S_BC_BATCH⌉ + 2·sources. One product,
+ *     traversal, PageRank or betweenness call in flight per handle.
+ *   g4s_csr_betweenness_reserve builds what the calls need (NULL stream, synchronous): level, order — all frontiers of a traversal one behind the
+ *     other — and level_start (3·rows + 2 ints), two hub lists of min(rows, nnz / 4097) + 1 ints, rows + 2 bytes of lanes-per-level, σ, δ and the
+ *     sum over sources (3·rows doubles) and the state block: 4·(3·rows + 2 + 2·hub) + (rows + 2) + 24·rows + 104 bytes. No transpose: forward
+ *     pushes along A, backward pulls along the out-edges of A. A first call without a reserve reserves synchronously; after a reserve a call
+ *     allocates nothing on the device. g4s_csr_get_info(A).plan_bytes counts the workspace, g4s_csr_destroy releases it.
+ *   Where it loses: one level is one launch in each direction, about 2·depth launches per source, so a deep graph (a grid, a road network) is
+ *     launch-bound; the sources run one after the other, so a small graph never fills the device (profiles/betweenness.txt).
+ *   Out of scope: several sources at once, direction switching (a bottom-up forward step), a weighted (Dijkstra) form, edge betweenness, a
+ *     capturable form, the distributed handle. */
+#define G4S_BC_ACCUMULATE 262144u   /* bc_dev holds earlier results: bc := bc + scale·Σ_s δ_s instead of bc := scale·Σ_s δ_s */
+#define G4S_BC_BATCH 16             /* forward steps enqueued behind one read of the state, at least */
+typedef struct g4s_bc_info {
+    int32_t sources;       /* traversals run (= n_sources) */
+    int32_t max_depth;     /* deepest BFS level over all sources */
+    int32_t host_waits;    /* times the call waited for the device */
+    int32_t sigma_exact;   /* 1: every path count stayed <= 2^53, so all σ are exact integers and the result is schedule-independent */
+    int64_t levels;        /* forward steps, summed over sources (deepest level + 1 per source) */
+    int64_t reached;       /* vertices reached, summed over sources */
+    int64_t edges_walked;  /* forward + backward */
+    double  sigma_max;     /* largest path count met */
+} g4s_bc_info;             /* 48 bytes */
+g4s_status g4s_csr_betweenness_reserve(g4s_csr_t A, unsigned flags);
+g4s_status g4s_betweenness(g4s_csr_t A, const int32_t *sources, int32_t n_sources, double scale,
+                           double *bc_dev, unsigned flags, g4s_bc_info *info, void *stream);
 g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *acol, const double *aval,
                                   const int32_t *brpt, const int32_t *bcol, const double *bval,
                                   int32_t **crpt, int32_t **ccol, double **cval,

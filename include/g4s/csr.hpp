@@ -296,6 +296,15 @@ void PageRank(const CSR<IT, NT> &a, NT *rank, double damping = 0.85, double tol 
     });
 }
 
+// Betweenness centrality of the graph `a` stores by out-edges, from n_sources vertices (g4s_betweenness; include/g4s.h has the contract: Brandes'
+// dependencies summed over the listed sources, an entry is an edge when it is != 0, repeated columns are parallel edges), host arrays, synchronous:
+// bc receives a.rows values, scale · Σ_s δ_s. A handle, one call, the handle destroyed.
+template <typename IT, typename NT>
+void BetweennessCentrality(const CSR<IT, NT> &a, NT *bc, const IT *sources, IT n_sources, double scale = 1.0, g4s_bc_info *info = nullptr)
+{
+    detail::traverse(a, bc, "BetweennessCentrality", [&](g4s_csr_t h, NT *b) { return g4s_betweenness(h, sources, n_sources, scale, b, 0u, info, nullptr); });
+}
+
 // Y = alpha·A·X + beta·Y with host blocks X (cols × k) and Y (rows × k): row-major by default (ld >= k), column-major as in cblas_dxxmm.c's
 // B and C (ld >= cols / rows) with col_major = true.
 template <typename IT, typename NT>
