@@ -1,10 +1,9 @@
 // betweenness.hip — g4s_betweenness (include/g4s.h): Brandes' betweenness centrality on a CSR handle stored by out-edges, one source after the other,
 // both halves of every traversal on the device.
 //
-// Forward half: a BFS that counts shortest paths, ONE kernel per level, shaped like push_kernel of traverse.hip. `order` holds every frontier of the
-// traversal one behind the other (a vertex joins once, so rows entries suffice); level d is order[level_start[d] .. level_start[d + 1]). A workgroup
-// takes 256 frontier vertices, scans their degrees in LDS and its lanes walk the concatenated edge range; a vertex above kHubCut edges is also kept
-// in a hub list of its own (two of them, ping-pong: `order` has no free back end) and walked by all workgroups in kHubChunk-edge chunks. Per edge
+// Forward half: a BFS that counts shortest paths, ONE kernel per level, on the frontier walk of frontier.hpp. `order` holds every frontier of the
+// traversal one behind the other (a vertex joins once, so rows entries suffice); level d is order[level_start[d] .. level_start[d + 1]). A vertex
+// above kHubCut edges is also kept in a hub list of its own (two of them, ping-pong: `order` has no free back end). Per edge
 // u → v: compare-and-swap of level[v] from −1 to d + 1 — the winner appends v, one atomicAdd per wave — then, if level[v] == d + 1, σ[v] += σ[u] by
 // an fp64 global atomic. σ[u] is final: level d was completed behind the previous kernel boundary, and nobody reads σ[v] before the next one.
 // The workgroup that finishes last (a ticket, no waiting) records level_start[d + 2], the lane count of the new level for the way back, the
@@ -24,7 +23,7 @@
 // graph and the source list. Where it loses: one level is one launch in each direction — a deep graph is launch-bound.
 #include "common.hpp"
 #include "csr_handle.hpp"
-#include "readback.hpp"
+#include "frontier.hpp"
 #include "betweenness.hpp"
 #include <algorithm>
 #include <climits>
@@ -35,9 +34,6 @@ namespace {
 
 using g4s::BcState;
 
-constexpr int WG = 256;
-constexpr int kHubCut = 4096;     // a vertex with more out-edges is a hub: walked by all workgroups (forward), summed by a whole one (backward)
-constexpr int kHubChunk = 1024;   // edges of a hub per workgroup visit
 constexpr int kBatch = G4S_BC_BATCH;
 constexpr int kBatchMax = 64;
 constexpr long long kEdgesPerWg = 2048;   // the launch grid of a batch: one workgroup per 2048 frontier edges
@@ -89,14 +85,8 @@ __global__ __launch_bounds__(WG) void init_kernel(const Arrays w, int src, int f
 // One atomicAdd per wave for the vertices its lanes discovered; a hub goes to the next hub list as well.
 __device__ __forceinline__ void append(bool want, int v, int deg, const Arrays &w, int *hubs_next, long long &deg_sum)
 {
-    const unsigned long long m = __ballot(want);
+    const int idx = wave_append(want, &w.st->tail);
     if (!want) return;
-    const int lane = __lane_id();
-    const int leader = __ffsll((long long)m) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(&w.st->tail, __popcll(m));
-    base = __shfl(base, leader);
-    const int idx = base + __popcll(m & ((1ull << lane) - 1ull));
     if ((unsigned)idx < (unsigned)w.rows) w.order[idx] = v;            // a vertex is appended once per traversal: idx < rows by construction
     if (deg > kHubCut) {
         const int h = atomicAdd(&w.st->n_hub_next, 1);
@@ -173,91 +163,35 @@ __device__ __forceinline__ void finish(const Arrays &w, long long deg_sum, doubl
 template <bool VALUES>
 __global__ __launch_bounds__(WG) void forward_kernel(const Arrays w, const StepArgs a)
 {
-    __shared__ int s_scan[WG + 1];
-    __shared__ int s_start[WG];
-    __shared__ double s_su[WG];
-    __shared__ int s_wsum[WG / 64];
     BcState *st = w.st;
     if (st->stop != 0 && !(st->stop == 4 && a.resume)) return;        // the same word for every block: it changes only after the last ticket
-    const int d = st->depth, nh = st->n_hub_cur, cur = st->cur;
-    const int begin = w.level_start[d], end = w.level_start[d + 1], n = end - begin;
+    const int d = st->depth, cur = st->cur;
+    const int begin = w.level_start[d], end = w.level_start[d + 1];
     const int *hubs = cur ? w.hub1 : w.hub0;
     int *hubs_next = cur ? w.hub0 : w.hub1;
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, G = (int)gridDim.x;
     long long deg_sum = 0;
     double smax = 0.0;
-
-    for (int s0 = (int)blockIdx.x * WG; s0 < n; s0 += G * WG) {
-        const int i = s0 + t;
-        int start = 0, deg = 0;
-        double su = 0.0;
-        if (i < n) {
-            const int u = w.order[begin + i];
-            start = w.rowptr[u];
-            deg = w.rowptr[u + 1] - start;
-            if (deg > kHubCut) deg = 0;                                // a hub: walked below, out of the hub list
-            su = w.sigma[u];
-            smax = fmax(smax, su);                                     // fmax drops a NaN; +inf is what an overflow leaves
+    auto vertex = [&](int u, int &start, int &deg, double &su) {
+        start = w.rowptr[u];
+        deg = w.rowptr[u + 1] - start;
+        su = w.sigma[u];
+    };
+    auto entry = [&](bool valid, int k, double su) {
+        bool want = false;
+        int v = 0, vdeg = 0;
+        if (valid) {
+            v = w.colids[k];
+            want = relax<VALUES>(k, v, su, d, w);
+            if (want) vdeg = w.rowptr[v + 1] - w.rowptr[v];
         }
-        int x = deg;                                                   // inclusive scan of the 256 degrees
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_wsum[wave] = x;
-        s_start[t] = start;
-        s_su[t] = su;
-        __syncthreads();
-        int off = 0;
-        for (int i2 = 0; i2 < wave; ++i2) off += s_wsum[i2];
-        s_scan[t + 1] = off + x;
-        if (t == 0) s_scan[0] = 0;
-        __syncthreads();
-        const int total = s_scan[WG];                                  // 256 rows of at most kHubCut entries: no overflow
-        int lo = 0;                                                    // the last entry with s_scan[lo] <= e: never decreases as e grows
-        for (int e0 = 0; e0 < total; e0 += WG) {
-            const int e = e0 + t;
-            bool want = false;
-            int v = 0, vdeg = 0;
-            if (e < total) {
-                int hi = WG - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (s_scan[mid] <= e) lo = mid;
-                    else hi = mid - 1;
-                }
-                const int k = s_start[lo] + (e - s_scan[lo]);
-                v = w.colids[k];
-                want = relax<VALUES>(k, v, s_su[lo], d, w);
-                if (want) vdeg = w.rowptr[v + 1] - w.rowptr[v];
-            }
-            append(want, v, vdeg, w, hubs_next, deg_sum);
-        }
-        __syncthreads();
-    }
-
-    for (int h = 0; h < nh; ++h) {                                     // hubs: chunk c of hub h belongs to block (c + 4h) mod G
-        const int u = hubs[h];
-        const int start = w.rowptr[u], deg = w.rowptr[u + 1] - start;
-        const double su = w.sigma[u];
-        const int chunks = (deg + kHubChunk - 1) / kHubChunk;
-        int first = (int)(((long long)blockIdx.x - 4ll * h) % G);
-        if (first < 0) first += G;
-        for (int c = first; c < chunks; c += G) {
-            for (int j = 0; j < kHubChunk; j += WG) {
-                const int e = c * kHubChunk + j + t;
-                bool want = false;
-                int v = 0, vdeg = 0;
-                if (e < deg) {
-                    const int k = start + e;
-                    v = w.colids[k];
-                    want = relax<VALUES>(k, v, su, d, w);
-                    if (want) vdeg = w.rowptr[v + 1] - w.rowptr[v];
-                }
-                append(want, v, vdeg, w, hubs_next, deg_sum);
-            }
-        }
-    }
+        append(want, v, vdeg, w, hubs_next, deg_sum);
+    };
+    walk_tiles<double>(end - begin, [&](int i, int &start, int &deg, double &su) {
+        vertex(w.order[begin + i], start, deg, su);
+        if (deg > kHubCut) deg = 0;                                    // a hub: walked below, out of the hub list
+        smax = fmax(smax, su);                                         // fmax drops a NaN; +inf is what an overflow leaves
+    }, entry);
+    walk_hubs<double>(st->n_hub_cur, [&](int h, int &start, int &deg, double &su) { vertex(hubs[h], start, deg, su); }, entry);
     finish(w, deg_sum, smax, d, end, a);
 }
 
@@ -363,14 +297,6 @@ __global__ __launch_bounds__(WG) void epilogue_kernel(int rows, double scale, in
     for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) bc[i] = (accumulate ? bc[i] : 0.0) + scale * acc[i];
 }
 
-// zero_values |= 1 when a stored value is 0.0 (or-and: a stored zero is no edge, so the kernels then read the values)
-__global__ __launch_bounds__(WG) void any_zero_kernel(long long nnz, const double *__restrict__ values, BcState *st)
-{
-    int z = 0;
-    for (long long k = (long long)blockIdx.x * WG + threadIdx.x; k < nnz; k += (long long)gridDim.x * WG) z |= values[k] == 0.0;
-    if (z) atomicOr(&st->zero_values, 1);
-}
-
 __global__ __launch_bounds__(WG) void max_degree_kernel(int rows, const int *__restrict__ rowptr, BcState *st)
 {
     int m = 0;
@@ -378,8 +304,6 @@ __global__ __launch_bounds__(WG) void max_degree_kernel(int rows, const int *__r
     for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_down(m, o));
     if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&st->max_degree, m);
 }
-
-inline int grid_rows(long long n, int cus) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, 8LL * cus)); }
 
 } // namespace
 
@@ -394,7 +318,7 @@ struct BcWork {
     int cus = 1;
     int hub_cap = 1;
     int max_degree = 0;
-    int values_state = 0;         // 0 unknown, 1 no stored value is zero, 2 some are
+    ZeroScan zeros;               // is a stored value 0.0? the kernels then have to read the values
     int64_t n = 0;
     int64_t bytes = 0;
 };
@@ -411,7 +335,7 @@ void betweenness_work_destroy(BcWork *w)
 
 long long betweenness_work_bytes(const BcWork *w) { return w ? w->bytes : 0; }
 
-void betweenness_values_changed(BcWork *w) { if (w) w->values_state = 0; }
+void betweenness_values_changed(BcWork *w) { if (w) w->zeros.changed(); }
 
 } // namespace g4s
 
@@ -449,17 +373,7 @@ int reserve(g4s_csr_s *A)
         A->bc = w;
     }
     g4s::BcWork *w = A->bc;
-    if (w->values_state == 0) {
-        int h = 0;
-        if (A->nnz > 0) {
-            G4S_HIP_TRY(hipMemset(&w->state->zero_values, 0, sizeof(int)));
-            hipLaunchKernelGGL(any_zero_kernel, dim3(grid_rows(A->nnz, w->cus)), dim3(WG), 0, nullptr, (long long)A->nnz, A->d_values, w->state);
-            G4S_HIP_TRY(hipGetLastError());
-            G4S_HIP_TRY(hipMemcpy(&h, &w->state->zero_values, sizeof(int), hipMemcpyDeviceToHost));
-        }
-        w->values_state = h ? 2 : 1;
-    }
-    return G4S_OK;
+    return w->zeros.scan(A->nnz, A->d_values, w->cus, &w->state->zero_values, nullptr, nullptr);
 }
 
 int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double scale, double *bc, unsigned flags, g4s_bc_info *info, hipStream_t s)
@@ -490,13 +404,9 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
 #define BC_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(g4s::set_error(G4S_ERR_HIP, "%s: %s: %s", fn, #expr, hipGetErrorString(e_))); } while (0)
     // New values since the last verdict: the scan runs in front of the first traversal, which reads the values whatever it will say; the verdict
     // comes back with the first state read, so it costs no wait of its own.
-    const bool rescan = wk->values_state == 0;
-    if (rescan && A->nnz > 0) {
-        BC_HIP(hipMemsetAsync(&st->zero_values, 0, sizeof(int), s));
-        hipLaunchKernelGGL(any_zero_kernel, dim3(grid_rows(A->nnz, wk->cus)), dim3(WG), 0, s, (long long)A->nnz, A->d_values, st);
-        BC_HIP(hipGetLastError());
-    }
-    const bool values = wk->values_state != 1;
+    const bool rescan = wk->zeros.state == 0;
+    if (rescan && A->nnz > 0) BC_HIP(wk->zeros.enqueue(A->nnz, A->d_values, wk->cus, &st->zero_values, s));
+    const bool values = wk->zeros.state != 1;
     const bool has_hubs = wk->max_degree > kHubCut;
     const int min_grid = 8;
     const int max_grid = (int)std::max<long long>(min_grid, std::min<long long>(2LL * wk->cus, (A->nnz + rows + kEdgesPerWg - 1) / kEdgesPerWg));
@@ -523,7 +433,7 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
             BC_HIP(g4s::read_small(&h, st, sizeof(BcState), s));
             BC_HIP(g4s::reads_sync(s));
             ++waits;
-            if (rescan) wk->values_state = h.zero_values ? 2 : 1;
+            if (rescan) wk->zeros.state = h.zero_values ? 2 : 1;
             if (h.stop == 1) break;
             if (h.stop == 4) outgrown = true;                              // the rest of this traversal runs on the full grid: one resume per source
             if (know) batch = std::min(kBatchMax, batch * 2);

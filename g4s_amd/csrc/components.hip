@@ -16,9 +16,8 @@
 //              `pending` word of the next pass at zero and the remaining launches return at once: usually one pass does the work.
 //   pick       one workgroup: the most frequent label among 1024 vertices at a fixed stride (ties: the smaller label) stays in a device word. With
 //              G4S_CC_SYMMETRIC (and without G4S_CC_NO_SKIP) rows that carry it are skipped below; it is always the label counted by reduction.
-//   link rest  entries r >= rounds of every row that is not skipped, balanced over entries as traverse.hip's push is: a workgroup takes 256 rows,
-//              scans their remaining lengths in LDS and its lanes walk the concatenated range; a row above kHubCut entries goes to a hub list and is
-//              walked by all workgroups in chunks of kHubChunk entries (cc_link_hubs_kernel). parent[row] is read once per row; after the compress
+//   link rest  entries r >= rounds of every row that is not skipped, on the frontier walk of frontier.hpp: a row above kHubCut remaining entries
+//              goes to a hub list (cc_link_hubs_kernel). parent[row] is read once per row, once per chunk of a hub; after the compress
 //              most links end at the first compare (one 4-byte gather per entry).
 //   compress, then the statistics: roots, the size of the picked label by reduction, every other label by one atomicAdd per (wave, label), and
 //              the largest component by a max over (size, −label).
@@ -29,15 +28,12 @@
 // One host wait per call: no decision is taken on the host between kernels (the picked label, the hub list and the error word stay on the device).
 // Environment switches: G4S_CC_SAMPLE_ROUNDS (0 … 4, default 2), G4S_CC_NO_SKIP=1; every setting gives the same labels.
 #include "common.hpp"
-#include "readback.hpp"
+#include "frontier.hpp"
 #include <algorithm>
 #include <climits>
 
 namespace {
 
-constexpr int WG = 256;
-constexpr int kHubCut = 4096;        // a row with more remaining entries goes to the hub list
-constexpr int kHubChunk = 1024;      // entries of a hub per workgroup visit
 constexpr int kHubCap = 1 << 19;     // rows above kHubCut entries: fewer than 2^31 / 4096
 constexpr int kMaxRounds = 4;
 constexpr int kRoundsDefault = 2;
@@ -167,87 +163,44 @@ __device__ __forceinline__ void add_linked(long long linked, CcState *st)
 __global__ __launch_bounds__(WG) void cc_link_kernel(int n, int rounds, const int *__restrict__ rowptr, const int *__restrict__ colids, int *parent, int *__restrict__ hubs,
                                                      CcState *st)
 {
-    __shared__ int s_scan[WG + 1];
-    __shared__ int s_start[WG];
-    __shared__ int s_pu[WG];
-    __shared__ int s_wsum[WG / 64];
     if (st->invalid) return;
     const int skip = st->skip, big = st->big_label;
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     long long linked = 0;
-    for (long long s0 = (long long)blockIdx.x * WG; s0 < n; s0 += (long long)gridDim.x * WG) {
-        const long long i = s0 + t;
-        int start = 0, deg = 0, pu = 0;
-        if (i < n) {
-            pu = ld(parent + i);
-            if (!(skip && pu == big)) {
-                const int rb = rowptr[i];
-                deg = rowptr[i + 1] - rb - rounds;
-                if (deg > 0) start = rb + rounds;
-                else deg = 0;
-                if (deg > kHubCut) {
-                    const int h = atomicAdd(&st->n_hubs, 1);
-                    if (h < kHubCap) hubs[h] = (int)i;             // fewer than 2^31 / kHubCut such rows exist
-                    deg = 0;
-                }
-            }
+    walk_tiles<int>(n, [&](int i, int &start, int &len, int &pu) {
+        pu = ld(parent + i);
+        if (skip && pu == big) return;
+        const int rb = rowptr[i], rest = rowptr[i + 1] - rb - rounds;
+        if (rest <= 0) return;
+        if (rest > kHubCut) {
+            const int h = atomicAdd(&st->n_hubs, 1);
+            if (h < kHubCap) hubs[h] = i;                          // fewer than 2^31 / kHubCut such rows exist
+            return;
         }
-        linked += deg;
-        int x = deg;                                               // inclusive scan of the 256 lengths: at most 256 · kHubCut
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_wsum[wave] = x;
-        s_start[t] = start;
-        s_pu[t] = pu;
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wave; ++w) off += s_wsum[w];
-        s_scan[t + 1] = off + x;
-        if (t == 0) s_scan[0] = 0;
-        __syncthreads();
-        const int total = s_scan[WG];
-        int lo = 0;                                                // the last entry with s_scan[lo] <= e: never decreases as e grows
-        for (int e = t; e < total; e += WG) {
-            int hi = WG - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (s_scan[mid] <= e) lo = mid;
-                else hi = mid - 1;
-            }
-            const int w = colids[s_start[lo] + (e - s_scan[lo])];
-            link_from(s_pu[lo], ld(parent + w), parent);           // s_pu: an ancestor of the row's vertex, maybe a former one
-        }
-        __syncthreads();
-    }
+        start = rb + rounds;
+        len = rest;
+        linked += rest;
+    }, [&](bool valid, int k, int pu) {
+        if (valid) link_from(pu, ld(parent + colids[k]), parent);  // pu: an ancestor of the row's vertex, maybe a former one
+    });
     add_linked(linked, st);
 }
 
-// Hub rows: chunk c of hub h belongs to block (c + 4h) mod G.
+// Hub rows, by all workgroups; parent[u] is read again for every chunk.
 __global__ __launch_bounds__(WG) void cc_link_hubs_kernel(int rounds, const int *__restrict__ rowptr, const int *__restrict__ colids, int *parent, const int *__restrict__ hubs,
                                                           CcState *st)
 {
     if (st->invalid) return;
-    const int nh = st->n_hubs < kHubCap ? st->n_hubs : kHubCap, G = (int)gridDim.x, t = (int)threadIdx.x;
     long long linked = 0;
-    for (int h = 0; h < nh; ++h) {
+    walk_hubs<int>(st->n_hubs < kHubCap ? st->n_hubs : kHubCap, [&](int h, int &start, int &len, int &pu) {
         const int u = hubs[h];
-        const int start = rowptr[u] + rounds, deg = rowptr[u + 1] - start;   // deg > kHubCut
-        const int chunks = (deg + kHubChunk - 1) / kHubChunk;
-        int first = (int)(((long long)blockIdx.x - 4ll * h) % G);
-        if (first < 0) first += G;
-        for (int c = first; c < chunks; c += G) {
-            const int pu = ld(parent + u);
-            for (int j = 0; j < kHubChunk; j += WG) {
-                const int e = c * kHubChunk + j + t;
-                if (e < deg) {
-                    link_from(pu, ld(parent + colids[start + e]), parent);
-                    linked += 1;
-                }
-            }
-        }
-    }
+        start = rowptr[u] + rounds;
+        len = rowptr[u + 1] - start;                               // > kHubCut
+        pu = ld(parent + u);
+    }, [&](bool valid, int k, int pu) {
+        if (!valid) return;
+        link_from(pu, ld(parent + colids[k]), parent);
+        linked += 1;
+    });
     add_linked(linked, st);
 }
 

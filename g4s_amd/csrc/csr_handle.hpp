@@ -1,5 +1,5 @@
 // csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip,
-// traverse.hip, pagerank.hip, betweenness.hip.
+// traverse.hip, pagerank.hip, betweenness.hip. The device code that traverse.hip and betweenness.hip share (and components.hip, which has no handle) is frontier.hpp.
 #pragma once
 #include "common.hpp"
 #include "spmv_stream.hpp"

@@ -8,9 +8,8 @@
 // g4s_conj_grad does. Kernel boundaries are the only ordering between workgroups; nothing spins and every loop is bounded by
 // the queue length (<= rows) or a row length.
 //
-//   push    a workgroup takes 256 queue entries, scans their degrees in LDS and its lanes walk the concatenated edge range (binary search in
-//           the scan, monotone per lane). Vertices above kHubCut edges sit at the BACK of the queue and are walked by all workgroups in
-//           chunks of kHubChunk edges. SSSP: cand = d[u] + w; plain load of d[v]; global_atomic_min_f64 only when cand < d[v]; the vertex is
+//   push    the frontier walk of frontier.hpp over the queue: rows at most kHubCut long from the front, hubs from the BACK of the same array.
+//           SSSP: cand = d[u] + w; plain load of d[v]; global_atomic_min_f64 only when cand < d[v]; the vertex is
 //           appended when the atomic returned a larger value and its step stamp (atomicMax on mark[v]) shows it is not queued yet.
 //           BFS: compare-and-swap of level[v] from −1. Appends are one atomicAdd per wave.
 //   pull    SSSP: y := Aᵀ ⊗ d by the inner handle's semiring kernels (any path), then sssp_combine_kernel: d := min(d, y), the changed vertices
@@ -22,7 +21,7 @@
 // min is order-independent and IEEE addition is monotone, so every schedule ends at the same bits (g4s.h has the argument).
 #include "common.hpp"
 #include "csr_handle.hpp"
-#include "readback.hpp"
+#include "frontier.hpp"
 #include "traverse.hpp"
 #include <algorithm>
 #include <climits>
@@ -33,9 +32,6 @@ namespace {
 
 using g4s::TravState;
 
-constexpr int WG = 256;
-constexpr int kHubCut = 4096;     // a queued vertex with more out-edges goes to the hub end of the queue
-constexpr int kHubChunk = 1024;   // edges of a hub per workgroup visit
 constexpr int kBatch = G4S_TRAVERSE_BATCH;   // push launches behind one state read, at least; doubles up to kBatchMax
 constexpr int kBatchMax = 64;
 constexpr long long kEdgesPerWg = 2048;      // the launch grid of a batch: one workgroup per 2048 frontier edges, 8..2 per CU
@@ -51,21 +47,13 @@ struct StepArgs {
     int resume;            // push only: the first launch of a batch goes on from stop == 4
 };
 
-// One atomicAdd per wave for the vertices its lanes append. Called by every lane that is active at the call site.
+// A vertex for the next queue: at most kHubCut out-edges to the front (one atomicAdd per wave), more to the hub end. Called by every lane that is
+// active at the call site.
 __device__ __forceinline__ void append(bool want, int v, int deg, int rows, int *__restrict__ q, TravState *st, long long &deg_sum)
 {
     const bool hub = want && deg > kHubCut;
-    const bool nor = want && !hub;
-    const unsigned long long m = __ballot(nor);
-    if (nor) {
-        const int lane = __lane_id();
-        const int leader = __ffsll((long long)m) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&st->n_next, __popcll(m));
-        base = __shfl(base, leader);
-        const int idx = base + __popcll(m & ((1ull << lane) - 1ull));
-        if ((unsigned)idx < (unsigned)rows) q[idx] = v;            // a vertex is appended once per step: idx < rows by construction
-    }
+    const int idx = wave_append(want && !hub, &st->n_next);
+    if ((unsigned)idx < (unsigned)rows) q[idx] = v;                // a vertex is appended once per step: idx < rows by construction
     if (hub) {
         const int h = atomicAdd(&st->n_hub_next, 1);
         if ((unsigned)h < (unsigned)rows) q[rows - 1 - h] = v;
@@ -163,86 +151,28 @@ template <bool BFS, bool VALUES>
 __global__ __launch_bounds__(WG) void push_kernel(int rows, const int *__restrict__ rowptr, const int *__restrict__ colids, const double *__restrict__ values,
                                                   double *dist, int *level, int *mark, int *q0, int *q1, TravState *st, const StepArgs a)
 {
-    __shared__ int s_scan[WG + 1];
-    __shared__ int s_start[WG];
-    __shared__ double s_du[WG];
-    __shared__ int s_wsum[WG / 64];
     if (st->stop != 0 && !(st->stop == 4 && a.resume)) return;     // the same word for every block: it changes only after the last ticket
-    const int cur = st->cur, n = st->n_cur, nh = st->n_hub_cur, stamp = st->iter + 1;
+    const int cur = st->cur, stamp = st->iter + 1;
     const int *q = cur ? q1 : q0;
     int *qn = cur ? q0 : q1;
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, G = (int)gridDim.x;
     long long deg_sum = 0;
-
-    for (int s0 = (int)blockIdx.x * WG; s0 < n; s0 += G * WG) {
-        const int i = s0 + t;
-        int start = 0, deg = 0;
-        double du = 0.0;
-        if (i < n) {
-            const int u = q[i];
-            start = rowptr[u];
-            deg = rowptr[u + 1] - start;
-            if constexpr (!BFS) du = dist[u];
+    auto vertex = [&](int u, int &start, int &deg, double &du) {
+        start = rowptr[u];
+        deg = rowptr[u + 1] - start;
+        if constexpr (!BFS) du = dist[u];                          // BFS carries nothing: its payload is never read and takes no LDS
+    };
+    auto entry = [&](bool valid, int k, double du) {
+        bool want = false;
+        int v = 0, vdeg = 0;
+        if (valid) {
+            v = colids[k];
+            want = relax<BFS, VALUES>(k, v, du, stamp, values, dist, level, mark);
+            if (want) vdeg = rowptr[v + 1] - rowptr[v];
         }
-        int x = deg;                                               // inclusive scan of the 256 degrees
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_wsum[wave] = x;
-        s_start[t] = start;
-        s_du[t] = du;
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wave; ++w) off += s_wsum[w];
-        s_scan[t + 1] = off + x;
-        if (t == 0) s_scan[0] = 0;
-        __syncthreads();
-        const int total = s_scan[WG];                              // distinct vertices: at most nnz <= INT32_MAX
-        int lo = 0;                                                // the last entry with s_scan[lo] <= e: never decreases as e grows
-        for (int e0 = 0; e0 < total; e0 += WG) {
-            const int e = e0 + t;
-            bool want = false;
-            int v = 0, vdeg = 0;
-            if (e < total) {
-                int hi = WG - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (s_scan[mid] <= e) lo = mid;
-                    else hi = mid - 1;
-                }
-                const int k = s_start[lo] + (e - s_scan[lo]);
-                v = colids[k];
-                want = relax<BFS, VALUES>(k, v, s_du[lo], stamp, values, dist, level, mark);
-                if (want) vdeg = rowptr[v + 1] - rowptr[v];
-            }
-            append(want, v, vdeg, rows, qn, st, deg_sum);
-        }
-        __syncthreads();
-    }
-
-    for (int h = 0; h < nh; ++h) {                                 // hubs: chunk c of hub h belongs to block (c + 4h) mod G
-        const int u = q[rows - 1 - h];
-        const int start = rowptr[u], deg = rowptr[u + 1] - start;
-        const double du = BFS ? 0.0 : dist[u];
-        const int chunks = (deg + kHubChunk - 1) / kHubChunk;
-        int first = (int)(((long long)blockIdx.x - 4ll * h) % G);
-        if (first < 0) first += G;
-        for (int c = first; c < chunks; c += G) {
-            for (int j = 0; j < kHubChunk; j += WG) {
-                const int e = c * kHubChunk + j + t;
-                bool want = false;
-                int v = 0, vdeg = 0;
-                if (e < deg) {
-                    const int k = start + e;
-                    v = colids[k];
-                    want = relax<BFS, VALUES>(k, v, du, stamp, values, dist, level, mark);
-                    if (want) vdeg = rowptr[v + 1] - rowptr[v];
-                }
-                append(want, v, vdeg, rows, qn, st, deg_sum);
-            }
-        }
-    }
+        append(want, v, vdeg, rows, qn, st, deg_sum);
+    };
+    walk_tiles<double>(st->n_cur, [&](int i, int &start, int &deg, double &du) { vertex(q[i], start, deg, du); }, entry);
+    walk_hubs<double>(st->n_hub_cur, [&](int h, int &start, int &deg, double &du) { vertex(q[rows - 1 - h], start, deg, du); }, entry);
     finish(st, deg_sum, KIND_PUSH, a);
 }
 
@@ -325,16 +255,6 @@ __global__ __launch_bounds__(WG) void count_kernel(int rows, const double *__res
     }
 }
 
-// zero_values |= 1 when a stored value is 0.0: BFS then has to read the values (or-and: a stored zero is no edge)
-__global__ __launch_bounds__(WG) void any_zero_kernel(long long nnz, const double *__restrict__ values, TravState *st)
-{
-    int z = 0;
-    for (long long k = (long long)blockIdx.x * WG + threadIdx.x; k < nnz; k += (long long)gridDim.x * WG) z |= values[k] == 0.0;
-    if (z) atomicOr(&st->zero_values, 1);
-}
-
-inline int grid_rows(long long n, int cus) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, 8LL * cus)); }
-
 } // namespace
 
 // ------------------------------------------------------------------------------------------------ the handle's workspace
@@ -346,7 +266,7 @@ struct TraverseWork {
     double *dist2 = nullptr;                  // rows doubles: y of the pull step
     TravState *state = nullptr;
     int cus = 1;
-    int values_state = 0;                     // 0 unknown, 1 no stored value is zero, 2 some are
+    ZeroScan zeros;                           // is a stored value 0.0? BFS then has to read the values
     int64_t bytes = 0;
 };
 
@@ -363,7 +283,7 @@ void traverse_work_destroy(TraverseWork *w)
 
 long long traverse_work_bytes(const TraverseWork *w) { return w ? w->bytes : 0; }
 
-void traverse_values_changed(TraverseWork *w) { if (w) w->values_state = 0; }
+void traverse_values_changed(TraverseWork *w) { if (w) w->zeros.changed(); }
 
 } // namespace g4s
 
@@ -376,18 +296,7 @@ constexpr unsigned kAllFlags = kDirFlags | G4S_TRAVERSE_SYMMETRIC;
 int scan_values(g4s_csr_s *A, hipStream_t s, int *waits)
 {
     g4s::TraverseWork *w = A->trv;
-    if (w->values_state != 0) return G4S_OK;
-    int h = 0;
-    if (A->nnz > 0) {
-        G4S_HIP_TRY(hipMemsetAsync(&w->state->zero_values, 0, sizeof(int), s));
-        hipLaunchKernelGGL(any_zero_kernel, dim3(grid_rows(A->nnz, w->cus)), dim3(WG), 0, s, (long long)A->nnz, A->d_values, w->state);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::read_small(&h, &w->state->zero_values, sizeof(int), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        if (waits) *waits += 1;
-    }
-    w->values_state = h ? 2 : 1;
-    return G4S_OK;
+    return w->zeros.scan(A->nnz, A->d_values, w->cus, &w->state->zero_values, s, waits);
 }
 
 // The workspace (once) and, unless the flags rule a pull out or declare A symmetric, the handle's transpose. NULL stream, synchronous.
@@ -451,7 +360,7 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
     g4s::TraverseWork *w = A->trv;
     int waits = 0;
     if (BFS) G4S_TRY(scan_values(A, s, &waits));
-    const bool values = w->values_state == 2;
+    const bool values = w->zeros.state == 2;
 
     // the pull side: Aᵀ (its inner handle and arrays), or A itself when the caller declares it symmetric
     g4s_csr_t pull_handle = A;
