@@ -134,7 +134,7 @@ int bcsr_try_build(BcsrPlan **out, int rows, int cols, long long nnz, const int3
 {
     *out = nullptr;
     if (rows < 64 || nnz <= 0) return G4S_OK;
-    for (int b : {3, 2, 4}) {
+    for (int b : {3, 2}) {   // aligned 4×4 blocks are aligned 2×2 blocks (twice as many, inside the 2×2 tile whenever they fit a 4×4 one): b = 4 after 2 was never taken
         const int bb = b * b;
         if (rows % b || cols % b || nnz % bb || nnz < 2ll * b * rows) continue;   // at least two blocks per block-row on average: otherwise the CSR kernel is as good
         const int nbr = rows / b;
@@ -199,8 +199,7 @@ static int bcsr_launch(BcsrPlan *P, const double *x, double *y, double alpha, do
         else hipLaunchKernelGGL((spmv_bcsr_kernel<B, false, S>), dim3(P->n_items), dim3(kWG), 0, s, P->items.as<Item>(), P->d_rowptr, P->bcol.as<int32_t>(), P->bval.as<double>(), x, y, alpha, beta);         \
     } while (0)
     if (P->b == 3) G4S_BCSR_LAUNCH(3);
-    else if (P->b == 2) G4S_BCSR_LAUNCH(2);
-    else G4S_BCSR_LAUNCH(4);
+    else G4S_BCSR_LAUNCH(2);
 #undef G4S_BCSR_LAUNCH
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;

@@ -136,7 +136,8 @@ __global__ __launch_bounds__(256) void dia_refill_kernel(int rows, int nd, long 
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= rows) return;
     const unsigned m = mask[row];
-    const int k0 = rowptr[row], last = max(rowptr[row + 1] - 1, k0);
+    if (!m) return;                                                // an empty row stores nothing, and its k0 may be nnz: one past the caller's array
+    const int k0 = rowptr[row], last = rowptr[row + 1] - 1;        // m != 0: the row has an entry, so k0 <= last <= nnz − 1
     double v[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) v[d] = values[min(k0 + (int)__popc(m & ((1u << d) - 1u)), last)];   // (absent diagonals read a neighbour: not stored)
