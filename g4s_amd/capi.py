@@ -17,6 +17,9 @@ TRAVERSE_PUSH, TRAVERSE_PULL, TRAVERSE_SYMMETRIC, TRAVERSE_BATCH = 4096, 8192, 1
 PAGERANK_SYMMETRIC, PAGERANK_WARM_START, PAGERANK_BATCH = 65536, 131072, 8                 # g4s_pagerank (g4s.h)
 BC_ACCUMULATE, BC_BATCH = 262144, 16                                     # g4s_betweenness (g4s.h)
 CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
+EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
+COMBINE_PLUS, COMBINE_TIMES, COMBINE_MIN, COMBINE_MAX, COMBINE_FIRST, COMBINE_SECOND = 0, 1, 2, 3, 4, 5
+SELECT_TRIL, SELECT_TRIU, SELECT_OFFDIAG, SELECT_DIAG, SELECT_NONZERO, SELECT_GT, SELECT_GE, SELECT_LT, SELECT_LE = 0, 1, 2, 3, 4, 5, 6, 7, 8   # g4s_csr_select_*: pred
 SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM / SpMV value semiring (g4s.h)
 PATTERN_ELEMENT_BLOCK_MATVEC, PATTERN_DENSE_ROW_TIMES_MATRIX, PATTERN_SYM_QUADRATIC_FORM = 1, 2, 3
 DENSE_DGEMM, DENSE_DSYMM, DENSE_DTRMM, DENSE_DGEMV, DENSE_DSYMV, DENSE_DTRMV, DENSE_DSPMV = 1, 2, 3, 4, 5, 6, 7
@@ -65,6 +68,12 @@ class CCInfo(C.Structure):
     """g4s_cc_info: what a g4s_connected_components call found and did."""
     _fields_ = [("components", C.c_int64), ("largest", C.c_int64), ("edges_linked", C.c_int64), ("largest_label", C.c_int32),
                 ("sample_rounds", C.c_int32), ("skipped", C.c_int32), ("host_waits", C.c_int32)]
+
+
+class EwiseInfo(C.Structure):
+    """g4s_ewise_info: what a g4s_csr_ewise_symbolic call found (entry counts, work units)."""
+    _fields_ = [("nnz_a", C.c_int64), ("nnz_b", C.c_int64), ("nnz_c", C.c_int64), ("units", C.c_int64), ("unit_entries", C.c_int32),
+                ("rows_split", C.c_int32), ("host_waits", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DistInfo(C.Structure):
@@ -191,6 +200,10 @@ SIGNATURES = {
     "g4s_spgemm_masked": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_triangle_count": (C.c_int, [C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(CCInfo), vp]),
+    "g4s_csr_ewise_symbolic": (C.c_int, [C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64p, C.c_uint, C.POINTER(EwiseInfo), vp]),
+    "g4s_csr_ewise_numeric": (C.c_int, [C.c_int, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
+    "g4s_csr_select_symbolic": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, i64p, C.c_uint, vp]),
+    "g4s_csr_select_numeric": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
     "g4s_register_pattern":(C.c_int, [FUN_GATHER, FUN_APPLY, C.POINTER(PatternDesc)]),
     "g4s_unregister_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY]),
     "g4s_set_host_callback_policy": (C.c_int, [C.c_int32]),

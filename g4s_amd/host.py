@@ -212,6 +212,18 @@ class CSR:
         is not touched."""
         return connected_components(self, symmetric, return_info)
 
+    def ewise(self, other, op="union", combine="plus", pattern_only=False, return_info=False):
+        """self ∪ other, self ∩ other or self ∖ other as a new device CSR — csr_ewise(self, other, …)."""
+        return csr_ewise(self, other, op, combine, pattern_only, return_info)
+
+    def select(self, pred, k=0, thr=0.0):
+        """The entries of this matrix that satisfy `pred`, in their stored order, as a new device CSR — csr_select(self, …)."""
+        return csr_select(self, pred, k, thr)
+
+    def symmetrise(self, combine="max", drop_diagonal=False):
+        """A ∪ Aᵀ of this square matrix as a new device CSR — csr_symmetrise(self, …)."""
+        return csr_symmetrise(self, combine, drop_diagonal)
+
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
         X.stride(1) == 1, column-major when X.stride(0) == 1 (k > 1); the leading dimension is the other stride, Y has X's layout. A new Y
@@ -611,6 +623,83 @@ def connected_components(A, symmetric=False, return_info=False):
         labels = torch.from_numpy(out[:n]).cuda()
     inf = {n_: getattr(info, n_) for n_, _ in capi.CCInfo._fields_}
     return (labels, inf) if return_info else labels
+
+
+# ------------------------------------------------------------------------------------------------ element-wise combination and select
+EWISE_OPS = {"union": capi.EWISE_UNION, "intersect": capi.EWISE_INTERSECT, "difference": capi.EWISE_DIFFERENCE}
+COMBINERS = {"plus": capi.COMBINE_PLUS, "times": capi.COMBINE_TIMES, "min": capi.COMBINE_MIN, "max": capi.COMBINE_MAX, "first": capi.COMBINE_FIRST,
+             "second": capi.COMBINE_SECOND}
+SELECT_PREDICATES = {"tril": capi.SELECT_TRIL, "triu": capi.SELECT_TRIU, "offdiag": capi.SELECT_OFFDIAG, "diag": capi.SELECT_DIAG,
+                     "nonzero": capi.SELECT_NONZERO, "gt": capi.SELECT_GT, "ge": capi.SELECT_GE, "lt": capi.SELECT_LT, "le": capi.SELECT_LE}
+
+
+def _name(table, value, what):
+    if not isinstance(value, str) or value not in table:
+        raise ValueError(f"unknown {what} {value!r}; expected one of {sorted(table)}")
+    return table[value]
+
+
+def csr_ewise(a, b, op="union", combine="plus", pattern_only=False, return_info=False):
+    """A ∪ B ("union"), A ∩ B ("intersect") or A ∖ B ("difference": the entries of A whose position B does not store, with A's values) of two device
+    CSRs of one shape, as a new device CSR (g4s_csr_ewise_symbolic / g4s_csr_ewise_numeric). combine — "plus", "times", "min", "max", "first",
+    "second" — gives the value where both store a position; under union an entry of one matrix alone is copied. Rows of a and b must be strictly
+    ascending; the result's are. A stored position is an entry whatever its value: explicit zeros and sums equal to 0.0 stay stored. b may be a.
+    pattern_only=True reads no values: the result's values are all 1.0. Synchronous. return_info=True adds the dict of g4s_ewise_info.
+    ValueError (before any GPU call) for an unknown op or combine and for shapes that differ."""
+    opv, cv = _name(EWISE_OPS, op, "op"), _name(COMBINERS, combine, "combine")
+    if (a.rows, a.cols) != (b.rows, b.cols):
+        raise ValueError(f"element-wise {op} needs one shape, not {a.rows} x {a.cols} and {b.rows} x {b.cols}")
+    _require_gpu()
+    lib, dev = capi.load(), a.rowptr.device
+    crp = torch.empty(a.rows + 1, dtype=torch.int32, device=dev)
+    cnnz, info = C.c_int64(0), capi.EwiseInfo()
+    capi.check(lib.g4s_csr_ewise_symbolic(opv, a.rows, a.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), _ptr_nn(b.rowptr), _ptr_nn(b.colids), _ptr_nn(crp),
+                                          C.byref(cnnz), capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    cci = torch.empty(cnnz.value, dtype=torch.int32, device=dev)
+    cva = torch.ones(cnnz.value, dtype=torch.float64, device=dev) if pattern_only else torch.empty(cnnz.value, dtype=torch.float64, device=dev)
+    null = C.c_void_p(0)
+    capi.check(lib.g4s_csr_ewise_numeric(opv, cv, a.rows, a.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), null if pattern_only else _ptr_nn(a.values),
+                                         _ptr_nn(b.rowptr), _ptr_nn(b.colids), null if pattern_only else _ptr_nn(b.values), _ptr_nn(crp), _ptr_nn(cci),
+                                         null if pattern_only else _ptr_nn(cva), capi.DEVICE_POINTERS, _stream()))
+    c = CSR(crp, cci, cva, a.rows, a.cols)
+    return (c, {n: getattr(info, n) for n, _ in capi.EwiseInfo._fields_}) if return_info else c
+
+
+def csr_select(a, pred, k=0, thr=0.0):
+    """The entries of the device CSR a that satisfy pred, in their stored order and with their bits, as a new device CSR (g4s_csr_select_symbolic /
+    g4s_csr_select_numeric): "tril" col − row <= k, "triu" col − row >= k, "offdiag", "diag", "nonzero" value != 0, "gt" / "ge" / "lt" / "le" value
+    against thr (NaN fails all four and passes "nonzero"). Rows may be in any order, with repeats. Synchronous. ValueError (before any GPU call) for
+    an unknown pred, a k that is not an integer and a thr that is not a number."""
+    pv = _name(SELECT_PREDICATES, pred, "pred")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k must be an integer, not {k!r}")
+    if isinstance(thr, (bool, np.bool_)) or not isinstance(thr, (int, float, np.integer, np.floating)):
+        raise ValueError(f"thr must be a number, not {thr!r}")
+    _require_gpu()
+    lib, dev = capi.load(), a.rowptr.device
+    crp = torch.empty(a.rows + 1, dtype=torch.int32, device=dev)
+    cnnz = C.c_int64(0)
+    capi.check(lib.g4s_csr_select_symbolic(pv, int(k), float(thr), a.rows, a.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), _ptr_nn(a.values), _ptr_nn(crp),
+                                           C.byref(cnnz), capi.DEVICE_POINTERS, _stream()))
+    cci = torch.empty(cnnz.value, dtype=torch.int32, device=dev)
+    cva = torch.empty(cnnz.value, dtype=torch.float64, device=dev)
+    capi.check(lib.g4s_csr_select_numeric(pv, int(k), float(thr), a.rows, a.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), _ptr_nn(a.values), _ptr_nn(crp),
+                                          _ptr_nn(cci), _ptr_nn(cva), capi.DEVICE_POINTERS, _stream()))
+    return CSR(crp, cci, cva, a.rows, a.cols)
+
+
+def csr_symmetrise(a, combine="max", drop_diagonal=False):
+    """A ∪ Aᵀ of a square device CSR with strictly ascending rows, as a new device CSR whose pattern is symmetric — what G4S_CC_SYMMETRIC,
+    G4S_PAGERANK_SYMMETRIC, G4S_TRAVERSE_SYMMETRIC and g4s_triangle_count ask for. A composition: g4s_csr_transpose, a union with `combine` where
+    both (i, j) and (j, i) are stored ("max" and "plus" give a symmetric matrix; "first" keeps A's value), then an "offdiag" select with
+    drop_diagonal=True. ValueError (before any GPU call) for a matrix that is not square, an unknown combine and a drop_diagonal that is not a bool."""
+    _name(COMBINERS, combine, "combine")
+    if not isinstance(drop_diagonal, (bool, np.bool_)):
+        raise ValueError(f"drop_diagonal must be a bool, not {drop_diagonal!r}")
+    if a.rows != a.cols:
+        raise ValueError(f"symmetrise needs a square matrix, not {a.rows} x {a.cols}")
+    s = csr_ewise(a, a.transpose(), "union", combine)
+    return csr_select(s, "offdiag") if drop_diagonal else s
 
 
 # ------------------------------------------------------------------------------------------------ synthetic inputs

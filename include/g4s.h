@@ -114,7 +114,7 @@ typedef struct g4s_csr_info {
  * handle must be ordered (same stream, or an event between them); different handles are independent.
  * Threads and streams (what tests/test_concurrency_gpu.py pins, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_csr_transpose, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -683,6 +683,81 @@ typedef struct g4s_cc_info {
 } g4s_cc_info;               /* 40 bytes */
 g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, const int32_t *colids,
                                     int32_t *labels, unsigned flags, g4s_cc_info *info, void *stream);
+
+/* Element-wise combination of two CSR matrices of the same shape, and filtering of one, on the device. Two calls each, on the model of
+ * g4s_spgemm_symbolic / g4s_spgemm_numeric, with caller-allocated outputs: the symbolic call writes crpt (rows + 1) and *cnnz, the caller allocates
+ * ccol (and cval) of *cnnz entries, the numeric call fills them. Nothing is kept between the two calls — no process-wide state, so different host
+ * threads may call at the same time; the numeric call works the row split out again from the inputs and refuses a crpt whose last element is not
+ * the entry count it arrives at itself.
+ *   op: G4S_EWISE_UNION (every position stored in A or in B), G4S_EWISE_INTERSECT (stored in both), G4S_EWISE_DIFFERENCE (the entries of A whose
+ *     position is not stored in B, with A's values). combine: G4S_COMBINE_PLUS, TIMES, MIN, MAX, FIRST (A's value), SECOND (B's), applied where
+ *     both matrices store the position; under union an entry stored in only one matrix is copied bit for bit. op, combine and pred are plain ints,
+ *     not flag bits.
+ *   Input contract: the rows of A and B are strictly ascending with ids in [0, cols); rowptr is non-decreasing from 0. The symbolic call checks all
+ *     of it on the device, the row pointers before any of them is used as an index; a violation returns G4S_ERR_INVALID and leaves the outputs
+ *     unspecified (the mask rule of g4s_spgemm_masked). Column ids are only ever compared, never used as an index. Unsorted rows are sorted by a
+ *     stable double g4s_csr_transpose ((Aᵀ)ᵀ has ascending rows, repeats in their stored order); duplicates must be merged by the caller. A and B
+ *     may be the very same arrays. The numeric call repeats the row-pointer check, not the one on the ids.
+ *   Output: rows strictly ascending. A stored position is an entry whatever its value: explicit zeros are kept, and a sum that is 0.0 stays stored.
+ *     Every value is one IEEE operation on two doubles or a copy, so the result is the same bits on every run. NaN and the sign of zero under
+ *     MIN / MAX are outside the contract, as for the semirings (MIN is b < a ? b : a, MAX is a < b ? b : a).
+ *   Pattern-only: aval == bval == cval == NULL writes ccol only. Any other mix of NULL value arrays is G4S_ERR_INVALID.
+ *   Select keeps the entries that satisfy pred, in their stored order and with their bits (stable), so rows may be in any order, with repeats, and
+ *     ids are not range-checked (they are never an index): G4S_SELECT_TRIL col − row <= k, TRIU col − row >= k (in 64 bits), OFFDIAG col != row,
+ *     DIAG col == row, NONZERO val != 0, GT / GE / LT / LE val against thr with the plain C comparison — NaN fails all four and passes NONZERO.
+ *     k and thr are ignored by the predicates that do not name them. A value predicate needs val (NULL: G4S_ERR_INVALID); a positional one accepts
+ *     val == NULL. cval may be NULL (ccol only); cval without val is G4S_ERR_INVALID.
+ *   flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS for all arrays (cnnz and info are always host memory); any other bit returns G4S_ERR_INVALID.
+ *     Checked before any HIP call (G4S_ERR_INVALID): flag bits, op / combine / pred, negative rows or cols, a NULL row pointer, crpt or cnnz, a
+ *     NULL column array unless rows == 0, the NULL rules of the value arrays, and — with host pointers, where every length is known — an output
+ *     that overlaps an input or another output. With device pointers the lengths of the column arrays are on the device: the symbolic call checks
+ *     crpt against the row pointers before any HIP call and against the column arrays after its one wait (G4S_ERR_INVALID, the arrays involved
+ *     unspecified); the numeric call reads the three counts first and checks before it enqueues anything.
+ *   cnnz is summed in 64 bits; more than INT32_MAX entries return G4S_ERR_OVERFLOW from the symbolic call (crpt unspecified). rows, cols or an
+ *     entry count of 0 are valid.
+ *   Synchronous on `stream`: the symbolic calls wait for the device once (info.host_waits), the numeric ones twice with device pointers (the counts,
+ *     the end) and once with host pointers. On a capturing stream all four return G4S_ERR_INVALID and enqueue nothing. Scratch — 12·rows bytes, in
+ *     the numeric calls 8 more per unit, plus device copies of the arrays with host pointers — comes from the library's caching allocator and is
+ *     released before return.
+ *   Work units (info): every row's merged sequence of la + lb positions (select: its la entries) is cut into units of unit_entries = 64; 16 lanes
+ *     take a unit, so short rows share a wave and a hub row spreads over the whole grid. Where it loses: rows much shorter than 64 positions leave
+ *     most of a unit's lanes idle, and the numeric call reads the column ids twice (profiles/ewise.txt). */
+#define G4S_EWISE_UNION       0
+#define G4S_EWISE_INTERSECT   1
+#define G4S_EWISE_DIFFERENCE  2
+#define G4S_COMBINE_PLUS      0
+#define G4S_COMBINE_TIMES     1
+#define G4S_COMBINE_MIN       2
+#define G4S_COMBINE_MAX       3
+#define G4S_COMBINE_FIRST     4
+#define G4S_COMBINE_SECOND    5
+#define G4S_SELECT_TRIL       0
+#define G4S_SELECT_TRIU       1
+#define G4S_SELECT_OFFDIAG    2
+#define G4S_SELECT_DIAG       3
+#define G4S_SELECT_NONZERO    4
+#define G4S_SELECT_GT         5
+#define G4S_SELECT_GE         6
+#define G4S_SELECT_LT         7
+#define G4S_SELECT_LE         8
+typedef struct g4s_ewise_info {
+    int64_t nnz_a, nnz_b;    /* stored entries of A and of B                                                     */
+    int64_t nnz_c;           /* entries of the result (what *cnnz receives)                                      */
+    int64_t units;           /* work units: Σ over rows of ceil((la + lb) / unit_entries)                        */
+    int32_t unit_entries;    /* merged positions per unit (a constant of the build)                              */
+    int32_t rows_split;      /* rows cut into more than one unit                                                 */
+    int32_t host_waits;      /* times the call waited for the device                                             */
+    int32_t reserved;
+} g4s_ewise_info;            /* 48 bytes */
+g4s_status g4s_csr_ewise_symbolic(int op, int32_t rows, int32_t cols, const int32_t *arpt, const int32_t *acol, const int32_t *brpt,
+                                  const int32_t *bcol, int32_t *crpt, int64_t *cnnz, unsigned flags, g4s_ewise_info *info, void *stream);
+g4s_status g4s_csr_ewise_numeric(int op, int combine, int32_t rows, int32_t cols, const int32_t *arpt, const int32_t *acol, const double *aval,
+                                 const int32_t *brpt, const int32_t *bcol, const double *bval, const int32_t *crpt, int32_t *ccol, double *cval,
+                                 unsigned flags, void *stream);
+g4s_status g4s_csr_select_symbolic(int pred, int64_t k, double thr, int32_t rows, int32_t cols, const int32_t *rpt, const int32_t *col,
+                                   const double *val, int32_t *crpt, int64_t *cnnz, unsigned flags, void *stream);
+g4s_status g4s_csr_select_numeric(int pred, int64_t k, double thr, int32_t rows, int32_t cols, const int32_t *rpt, const int32_t *col,
+                                  const double *val, const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream);
 
 /* ------------------------------------------------------------------ B3: graph gather/apply */
 

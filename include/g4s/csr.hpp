@@ -8,6 +8,7 @@
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
+//   EWiseAdd / EWiseMult / EWiseDifference(a,b,c), Select(a,c,pred,k,thr), Symmetrise(a,c)   A ∪ B, A ∩ B, A ∖ B, a filter, A ∪ Aᵀ (g4s_csr_ewise_*, g4s_csr_select_*)
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
 #pragma once
@@ -240,6 +241,87 @@ void Transpose(const CSR<IT, NT> &a, CSR<IT, NT> &at)
     check(g4s_csr_transpose(a.rows, a.cols, a.nnz, a.rowptr, a.colids, a.values, at.rowptr, at.colids, a.values ? at.values : nullptr, nullptr, G4S_HOST_POINTERS, nullptr),
           "Transpose");
     at.rows = a.cols; at.cols = a.rows; at.nnz = a.nnz; at.zerobased = true;
+}
+
+// Element-wise combination and filtering on the device (g4s_csr_ewise_* / g4s_csr_select_*, host arrays; include/g4s.h has the contract): rows of a
+// and b strictly ascending, the result's too; a stored position is an entry whatever its value. c's old arrays are released first; c must not be a or b.
+//   EWiseAdd(a, b, c, combine)     every position of a or b; combine (G4S_COMBINE_*, default PLUS) where both store it, a copy elsewhere
+//   EWiseMult(a, b, c, combine)    the positions both store (default TIMES)
+//   EWiseDifference(a, b, c)       the entries of a whose position b does not store
+//   Select(a, c, pred, k, thr)     the entries of a that satisfy G4S_SELECT_* pred, in stored order (rows in any order)
+//   Symmetrise(a, c, combine, drop_diagonal)   a ∪ aᵀ of a square matrix (default MAX), optionally without its diagonal
+namespace detail {
+template <typename IT, typename NT>
+void adopt(CSR<IT, NT> &c, IT rows, IT cols, int64_t nnz, const char *what)
+{
+    c.colids = (IT *)g4s_malloc(sizeof(IT) * ((size_t)nnz + 1));
+    c.values = (NT *)g4s_malloc(sizeof(NT) * ((size_t)nnz + 1));
+    if (!c.colids || !c.values) { c.make_empty(); throw std::runtime_error(std::string(what) + ": host allocation failed"); }
+    c.rows = rows; c.cols = cols; c.nnz = (IT)nnz; c.zerobased = true;
+}
+template <typename IT, typename NT>
+void ewise(int op, int combine, const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c, g4s_ewise_info *info, const char *what)
+{
+    static_assert(std::is_same<IT, int32_t>::value && std::is_same<NT, double>::value, "the device works on CSR<int32_t, double>");
+    if (a.rows != b.rows || a.cols != b.cols) throw std::runtime_error(std::string(what) + ": the shapes differ");
+    c.make_empty();
+    const IT zero = 0;                                      // an empty CSR holds no arrays
+    const IT *arp = a.rowptr ? a.rowptr : &zero, *brp = b.rowptr ? b.rowptr : &zero;
+    const IT rows = a.rowptr && b.rowptr ? a.rows : 0;
+    c.rowptr = (IT *)g4s_malloc(sizeof(IT) * ((size_t)a.rows + 1));
+    if (!c.rowptr) throw std::runtime_error(std::string(what) + ": host allocation failed");
+    int64_t cnnz = 0;
+    g4s_status st = g4s_csr_ewise_symbolic(op, rows, a.cols, arp, a.colids, brp, b.colids, c.rowptr, &cnnz, G4S_HOST_POINTERS, info, nullptr);
+    if (st != G4S_OK) { c.make_empty(); check(st, what); }
+    for (IT r = rows; r < a.rows; ++r) c.rowptr[r + 1] = 0;
+    adopt(c, a.rows, a.cols, cnnz, what);
+    st = g4s_csr_ewise_numeric(op, combine, rows, a.cols, arp, a.colids, a.values, brp, b.colids, b.values, c.rowptr, c.colids, c.values, G4S_HOST_POINTERS, nullptr);
+    if (st != G4S_OK) { c.make_empty(); check(st, what); }
+}
+} // namespace detail
+template <typename IT, typename NT>
+void EWiseAdd(const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c, int combine = G4S_COMBINE_PLUS, g4s_ewise_info *info = nullptr)
+{
+    detail::ewise(G4S_EWISE_UNION, combine, a, b, c, info, "EWiseAdd");
+}
+template <typename IT, typename NT>
+void EWiseMult(const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c, int combine = G4S_COMBINE_TIMES, g4s_ewise_info *info = nullptr)
+{
+    detail::ewise(G4S_EWISE_INTERSECT, combine, a, b, c, info, "EWiseMult");
+}
+template <typename IT, typename NT>
+void EWiseDifference(const CSR<IT, NT> &a, const CSR<IT, NT> &b, CSR<IT, NT> &c, g4s_ewise_info *info = nullptr)
+{
+    detail::ewise(G4S_EWISE_DIFFERENCE, G4S_COMBINE_FIRST, a, b, c, info, "EWiseDifference");
+}
+template <typename IT, typename NT>
+void Select(const CSR<IT, NT> &a, CSR<IT, NT> &c, int pred, int64_t k = 0, double thr = 0.0)
+{
+    static_assert(std::is_same<IT, int32_t>::value && std::is_same<NT, double>::value, "the device works on CSR<int32_t, double>");
+    c.make_empty();
+    const IT zero = 0;
+    const IT *rp = a.rowptr ? a.rowptr : &zero;
+    const IT rows = a.rowptr ? a.rows : 0;
+    c.rowptr = (IT *)g4s_malloc(sizeof(IT) * ((size_t)a.rows + 1));
+    if (!c.rowptr) throw std::runtime_error("Select: host allocation failed");
+    int64_t cnnz = 0;
+    g4s_status st = g4s_csr_select_symbolic(pred, k, thr, rows, a.cols, rp, a.colids, a.values, c.rowptr, &cnnz, G4S_HOST_POINTERS, nullptr);
+    if (st != G4S_OK) { c.make_empty(); check(st, "Select"); }
+    for (IT r = rows; r < a.rows; ++r) c.rowptr[r + 1] = 0;
+    detail::adopt(c, a.rows, a.cols, cnnz, "Select");
+    st = g4s_csr_select_numeric(pred, k, thr, rows, a.cols, rp, a.colids, a.values, c.rowptr, c.colids, c.values, G4S_HOST_POINTERS, nullptr);
+    if (st != G4S_OK) { c.make_empty(); check(st, "Select"); }
+}
+template <typename IT, typename NT>
+void Symmetrise(const CSR<IT, NT> &a, CSR<IT, NT> &c, int combine = G4S_COMBINE_MAX, bool drop_diagonal = false)
+{
+    if (a.rows != a.cols) throw std::runtime_error("Symmetrise: the matrix is not square");
+    CSR<IT, NT> at;
+    Transpose(a, at);
+    if (!drop_diagonal) { EWiseAdd(a, at, c, combine); return; }
+    CSR<IT, NT> u;
+    EWiseAdd(a, at, u, combine);
+    Select(u, c, G4S_SELECT_OFFDIAG);
 }
 
 // Shortest-path distances (dist: a.rows values, +inf where unreached) and BFS levels (level: a.rows values, −1 where unreached) from the nearest of
