@@ -161,6 +161,7 @@ __global__ __launch_bounds__(256) void elem_matvec_fixed_kernel(int nno, const i
 struct g4s_elem_op_s {
     int nel = 0, npe = 0, dof = 0, nno = 0, neq = 0;
     DevBuf node_ptr, node_terms, elem_eq, node_eq, terms8;
+    int max_terms = 0;              // the largest number of (element, local node) terms of one node (the G4S_DEBUG line names it)
     bool fixed8 = false;            // every node has <= 8 terms and the shape is (8, 3): use elem_matvec_fixed_kernel
     const double *elt_k = nullptr;  // borrowed device pointer
 };
@@ -207,6 +208,7 @@ G4S_API g4s_status g4s_elem_op_create(g4s_elem_op_t *out, int32_t numElems, int3
     if (nno) G4S_HIP_TRY(hipMemcpy(op->node_eq.p, id, sizeof(int) * (size_t)nno * dof, hipMemcpyHostToDevice));
     int max_terms = 0;
     for (int i = 0; i < nno; ++i) max_terms = std::max(max_terms, cnt[i + 1] - cnt[i]);
+    op->max_terms = max_terms;
     if (npe == 8 && dof == 3 && max_terms <= 8 && nno > 0) {
         std::vector<int> t8((size_t)nno * 8, -1);
         for (int i = 0; i < nno; ++i)
@@ -266,6 +268,10 @@ static int elem_op_launch(g4s_elem_op_t op, const double *elt_k, const double *u
     // equations no node owns receive nothing: with beta == 0 they must read 0 (Element_calculations.c:495-496 zeroes Au first).
     // When every equation has an owner (neq == nno·dof, the CitcomS numbering) the kernel writes all of Au and the memset is skipped.
     if (beta == 0.0 && op->neq && (int64_t)op->nno * op->dof != op->neq) G4S_HIP_TRY(hipMemsetAsync(Au, 0, sizeof(double) * (size_t)op->neq, s));
+    if (getenv("G4S_DEBUG")) {
+        if (op->fixed8) fprintf(stderr, "g4s element mat-vec: fixed8\n");
+        else fprintf(stderr, "g4s element mat-vec: generic npe=%d dof=%d max_terms=%d\n", op->npe, op->dof, op->max_terms);
+    }
     if (op->nno) {
         if (op->fixed8)
             hipLaunchKernelGGL((elem_matvec_fixed_kernel<8, 3>), dim3((op->nno + 3) / 4), dim3(256), 0, s, op->nno, op->terms8.as<int>(),
@@ -664,6 +670,7 @@ int dense_rows_times_matrix_launch(int32_t M, int32_t N, int32_t K, const double
         (reinterpret_cast<uintptr_t>(xx_dev) & 15u) == 0) {
         hipStream_t s = g4s::as_stream(stream);
         const int strips = (M + 15) / 16, grid = std::min(256, (strips + 7) / 8);
+        if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s dense rows x matrix: resident2 KT=%d GT=%d WT=%d grid=%d\n", KT, GT, (int)WT, grid);
         double *dump = nullptr;
         G4S_TRY(g4s::scratch_alloc(reinterpret_cast<void **>(&dump), sizeof(double) * 8 * (size_t)grid, s));
         auto launch = [&](auto kern) -> int {
@@ -695,6 +702,7 @@ int dense_rows_times_matrix_launch(int32_t M, int32_t N, int32_t K, const double
     if (N >= 1 && N <= 128 && K <= 128 && lds <= 96 * 1024 && M >= 4096) {
         // embedding-net shapes: w resident in LDS, persistent strips
         const int strips = (M + 15) / 16, grid = std::min(256 * 1, (strips + 7) / 8);
+        if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s dense rows x matrix: resident KT=%d NS=%d WT=%d grid=%d\n", KT, NS, (int)WT, grid);
         auto launch = [&](auto kern) -> int {
             G4S_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, g4s::as_stream(stream), M, N, K, NS, xx_dev, w_dev, result_dev);
@@ -713,6 +721,7 @@ int dense_rows_times_matrix_launch(int32_t M, int32_t N, int32_t K, const double
         }
         G4S_TRY(st);
     } else {
+        if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s dense rows x matrix: panel WT=%d grid=%d\n", (int)WT, (M + 63) / 64);
         hipLaunchKernelGGL(dense_rows_times_matrix_kernel<WT>, dim3((M + 63) / 64), dim3(256), 0, g4s::as_stream(stream), M, N, K, xx_dev, w_dev, result_dev);
     }
     G4S_HIP_TRY(hipGetLastError());
@@ -747,6 +756,8 @@ G4S_API g4s_status g4s_dense_rows_times_matrix_grad(int32_t M, int32_t N, int32_
         const int rows_per_wg = ((M + wgs - 1) / wgs + kDwSlab - 1) / kDwSlab * kDwSlab;
         const int used = (M + rows_per_wg - 1) / rows_per_wg;
         const size_t elems = (size_t)N * K, lds = sizeof(double) * 2 * kDwSlab * kDwLd;
+        if (getenv("G4S_DEBUG"))
+            fprintf(stderr, "g4s dense dw: KT=%d rows_per_wg=%d ranges=%d blocks=%dx%d\n", K > 128 ? 8 : (K + 15) / 16, rows_per_wg, used, (N + 127) / 128, (K + 127) / 128);
         double *partials = nullptr;                                // stream-ordered scratch: no host sync, the pool keeps the pages
         G4S_TRY(g4s::scratch_alloc(reinterpret_cast<void **>(&partials), sizeof(double) * elems * used, s));
         auto launch = [&](auto kern) -> int {
