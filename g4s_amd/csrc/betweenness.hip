@@ -400,23 +400,22 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
     w.st = wk->state;
     BcState *st = wk->state;
 
-    auto fail = [&](int code) { (void)g4s::reads_sync(s); return code; };   // also settles a noted read of h
-#define BC_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(g4s::set_error(G4S_ERR_HIP, "%s: %s: %s", fn, #expr, hipGetErrorString(e_))); } while (0)
     // New values since the last verdict: the scan runs in front of the first traversal, which reads the values whatever it will say; the verdict
     // comes back with the first state read, so it costs no wait of its own.
     const bool rescan = wk->zeros.state == 0;
-    if (rescan && A->nnz > 0) BC_HIP(wk->zeros.enqueue(A->nnz, A->d_values, wk->cus, &st->zero_values, s));
+    if (rescan && A->nnz > 0) G4S_HIP_TRY(wk->zeros.enqueue(A->nnz, A->d_values, wk->cus, &st->zero_values, s));
     const bool values = wk->zeros.state != 1;
     const bool has_hubs = wk->max_degree > kHubCut;
     const int min_grid = 8;
     const int max_grid = (int)std::max<long long>(min_grid, std::min<long long>(2LL * wk->cus, (A->nnz + rows + kEdgesPerWg - 1) / kEdgesPerWg));
 
+    g4s::ReadScope reads(s);
     BcState h{};
     int waits = 0;
     for (int32_t i = 0; i < n_sources; ++i) {
         const int src = sources[i];
         hipLaunchKernelGGL(init_kernel, dim3(grid_rows(rows, wk->cus)), dim3(WG), 0, s, w, src, (int)(i == 0));
-        BC_HIP(hipGetLastError());
+        G4S_HIP_TRY(hipGetLastError());
         bool know = false, outgrown = false;                               // h is this traversal's state; a frontier outgrew a sized grid once
         int batch = kBatch;
         for (;;) {
@@ -429,9 +428,8 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
                 if (values) hipLaunchKernelGGL(forward_kernel<true>, dim3(grid), dim3(WG), 0, s, w, a);
                 else hipLaunchKernelGGL(forward_kernel<false>, dim3(grid), dim3(WG), 0, s, w, a);
             }
-            BC_HIP(hipGetLastError());
-            BC_HIP(g4s::read_small(&h, st, sizeof(BcState), s));
-            BC_HIP(g4s::reads_sync(s));
+            G4S_HIP_TRY(hipGetLastError());
+            G4S_HIP_TRY(reads.fetch(h, st));
             ++waits;
             if (rescan) wk->zeros.state = h.zero_values ? 2 : 1;
             if (h.stop == 1) break;
@@ -454,13 +452,12 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
                 else hipLaunchKernelGGL(back_long_kernel<false>, dim3(gl), dim3(WG), 0, s, w, d, src);
             }
         }
-        BC_HIP(hipGetLastError());
+        G4S_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(epilogue_kernel, dim3(grid_rows(rows, wk->cus)), dim3(WG), 0, s, rows, scale, (int)((flags & G4S_BC_ACCUMULATE) != 0), (const double *)w.acc, bc);
-    BC_HIP(hipGetLastError());
-    BC_HIP(g4s::reads_sync(s));
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_HIP_TRY(reads.wait());
     ++waits;
-#undef BC_HIP
     if (info) {
         double smax;
         memcpy(&smax, &h.sigma_max_bits, sizeof smax);

@@ -284,10 +284,10 @@ struct CgRun {
         return enqueue(std::max(1, std::min(batch, steps + 1)));
     }
 
-    int read_state_async(CgState *h) { G4S_HIP_TRY(g4s::read_small(h, st, sizeof(CgState), s)); return G4S_OK; }
+    int read_state_async(g4s::ReadScope &reads, CgState &h) { G4S_HIP_TRY(reads.note(h, st)); return G4S_OK; }   // (a scope on this run's stream)
 
     // h: the state after the batches enqueued so far (read by the caller after a synchronisation). Runs on until the loop test is met.
-    int complete(CgState &h)
+    int complete(g4s::ReadScope &reads, CgState &h)
     {
         int batch = std::min(32, std::max(2, enqueued * 2));
         while (!h.done) {
@@ -298,8 +298,8 @@ struct CgRun {
                 if (left > 0.0 && left < 1e6) batch = std::max(2, std::min(32, (int)std::ceil(left) + 1));
             }
             G4S_TRY(enqueue(std::max(1, std::min(batch, steps - enqueued + 1))));
-            G4S_TRY(read_state_async(&h));
-            G4S_HIP_TRY(g4s::reads_sync(s));
+            G4S_TRY(read_state_async(reads, h));
+            G4S_HIP_TRY(reads.wait());
             batch = std::min(32, batch * 2);
         }
         return G4S_OK;
@@ -336,15 +336,16 @@ int conj_grad_impl(const MatVec &matvec, int32_t neq, const double *BI, const in
     hipStream_t s = g4s::as_stream(stream);
     CgRun run;
     G4S_TRY(run.start(matvec, neq, BI, zero_resid, n_zero, F, d0, acc, *cycles, cg_first_batch(), s));
+    g4s::ReadScope reads(s);
     CgState h{};
-    G4S_TRY(run.read_state_async(&h));
-    G4S_HIP_TRY(g4s::reads_sync(s));
-    G4S_TRY(run.complete(h));
+    G4S_TRY(run.read_state_async(reads, h));
+    G4S_HIP_TRY(reads.wait());
+    G4S_TRY(run.complete(reads, h));
     if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s conj_grad: %d iterations, %d enqueued, residual %.3e (acc %.3e)\n", h.count, run.enqueued, h.residual, acc);
     cg_last_iterations() = h.count;
     *cycles = h.count;
     G4S_TRY(run.finish());
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(reads.wait());
     if (residual_out) *residual_out = h.residual;
     return G4S_OK;
 }
@@ -356,10 +357,10 @@ using g4s::conj_grad_impl;
 } // namespace
 namespace g4s {
 struct CgAsync {
+    explicit CgAsync(hipStream_t s) : reads(s) {}
     CgRun run;
     CgState h{};
-    bool read_pending = false;   // an asynchronous copy into h has been enqueued and nobody has settled since: the object must outlive it
-    hipStream_t s = nullptr;
+    g4s::ReadScope reads;        // owns the read into h: an object freed between read and settle waits for the copy and takes the note with it
 };
 
 int cg_async_start(CgAsync **out, g4s_elem_op_t op, g4s_csr_t A, int32_t neq, const double *BI, const int32_t *zero_resid, int32_t n_zero,
@@ -367,24 +368,22 @@ int cg_async_start(CgAsync **out, g4s_elem_op_t op, g4s_csr_t A, int32_t neq, co
 {
     *out = nullptr;
     G4S_REQUIRE((op != nullptr) != (A != nullptr), "exactly one of op / A must be given");
-    auto c = new (std::nothrow) CgAsync();
+    auto c = new (std::nothrow) CgAsync(s);
     if (!c) return set_error(G4S_ERR_NOMEM, "host allocation failed");
     int st = c->run.start(cg_matvec_for(op, A), neq, BI, zero_resid, n_zero, F, d0, acc, steps, cg_first_batch(), s, bc_mask);
     if (st == G4S_OK) st = c->run.finish();
     if (st != G4S_OK) { delete c; return st; }
-    c->s = s;
     *out = c;
     return G4S_OK;
 }
 
-int cg_async_read(CgAsync *c) { c->read_pending = true; return c->run.read_state_async(&c->h); }
+int cg_async_read(CgAsync *c) { return c->run.read_state_async(c->reads, c->h); }
 
 int cg_async_settle(CgAsync *c, bool *speculation_held, int32_t *cycles, double *residual)
 {
-    c->read_pending = false;                                       // (the caller has synchronised: that is the contract of settle)
-    *speculation_held = c->h.done != 0;
+    *speculation_held = c->h.done != 0;                            // (the caller has synchronised with reads_sync: that is the contract of settle)
     if (!c->h.done) {
-        G4S_TRY(c->run.complete(c->h));
+        G4S_TRY(c->run.complete(c->reads, c->h));
         G4S_TRY(c->run.finish());
     }
     cg_last_iterations() = c->h.count;
@@ -393,8 +392,7 @@ int cg_async_settle(CgAsync *c, bool *speculation_held, int32_t *cycles, double 
     return G4S_OK;
 }
 
-// An error between read and settle (the caller's own work failed) frees the object while the copy into c->h may still be in flight: wait for it first.
-void cg_async_free(CgAsync *c) { if (c && c->read_pending) (void)g4s::reads_sync(c->s); if (c) g4s::reads_forget(c, c + 1); delete c; }
+void cg_async_free(CgAsync *c) { delete c; }
 } // namespace g4s
 
 
@@ -496,8 +494,7 @@ G4S_API g4s_status g4s_cg_state(g4s_cg_ws_t ws, int32_t *count, int32_t *done, d
     G4S_REQUIRE(ws, "ws is NULL");
     hipStream_t s = g4s::as_stream(stream);
     CgState h{};
-    G4S_HIP_TRY(g4s::read_small(&h, ws->st, sizeof(CgState), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, ws->st));
     if (count) *count = h.count;
     if (done) *done = h.done;
     if (residual) *residual = h.residual;
@@ -588,6 +585,8 @@ struct DistCgAsync {
     int n_zero = 0, steps = 0, enqueued = 0;
     void *stream = nullptr;
     CgState h{};
+    g4s::ReadScope reads;                                                                   // see CgAsync
+    explicit DistCgAsync(void *stream) : stream(stream), reads(g4s::as_stream(stream)) {}
 
     // Iterations past the one that meets the test are no-ops in the CG kernels; their product and all-reduces still run, on data nothing
     // reads again (the partial sums are rewritten by the next solve's first kernel).
@@ -613,16 +612,14 @@ struct DistCgAsync {
         G4S_TRY(tr->allreduce_sum_f64(tr->ctx, part, 3 * kDotBlocks, stream));              // r·z and r·r of the start vector
         return enqueue(std::max(1, std::min(batch, steps + 1)));
     }
-    bool read_pending = false;                                                              // see CgAsync
-    int read() { read_pending = true; G4S_HIP_TRY(g4s::read_small(&h, ws->st, sizeof(CgState), g4s::as_stream(stream))); return G4S_OK; }
+    int read() { G4S_HIP_TRY(reads.note(h, ws->st)); return G4S_OK; }
     int complete()                                                                          // h: read after a synchronisation
     {
         int batch = std::min(32, std::max(2, enqueued * 2));
         while (!h.done) {
             G4S_TRY(enqueue(std::max(1, std::min(batch, steps - enqueued + 1))));
             G4S_TRY(read());
-            G4S_HIP_TRY(g4s::reads_sync(g4s::as_stream(stream)));
-            read_pending = false;
+            G4S_HIP_TRY(reads.wait());
             batch = std::min(32, batch * 2);
         }
         return G4S_OK;
@@ -639,9 +636,9 @@ int dist_cg_async_start(DistCgAsync **out, g4s_cg_ws_t ws, g4s_spmv_dist_t A, co
                         const double *F, double *d0, double acc, int32_t steps, void *stream)
 {
     *out = nullptr;
-    auto c = new (std::nothrow) DistCgAsync();
+    auto c = new (std::nothrow) DistCgAsync(stream);
     if (!c) return set_error(G4S_ERR_NOMEM, "host allocation failed");
-    c->A = A; c->tr = tr; c->ws = ws; c->BI = BI; c->zero_resid = zero_resid; c->n_zero = n_zero; c->d0 = d0; c->acc = acc; c->steps = steps; c->stream = stream;
+    c->A = A; c->tr = tr; c->ws = ws; c->BI = BI; c->zero_resid = zero_resid; c->n_zero = n_zero; c->d0 = d0; c->acc = acc; c->steps = steps;
     int st = c->start(cg_first_batch(), F);
     if (st == G4S_OK) st = c->finish();
     if (st != G4S_OK) { delete c; return st; }
@@ -652,7 +649,6 @@ void cg_ws_hold_mask(g4s_cg_ws_t ws, bool hold) { if (ws) { ws->hold_mask = hold
 int dist_cg_async_read(DistCgAsync *c) { return c->read(); }
 int dist_cg_async_settle(DistCgAsync *c, bool *speculation_held, int32_t *cycles, double *residual)
 {
-    c->read_pending = false;
     *speculation_held = c->h.done != 0;
     if (!c->h.done) {
         G4S_TRY(c->complete());
@@ -663,7 +659,7 @@ int dist_cg_async_settle(DistCgAsync *c, bool *speculation_held, int32_t *cycles
     if (residual) *residual = c->h.residual;
     return G4S_OK;
 }
-void dist_cg_async_free(DistCgAsync *c) { if (c && c->read_pending) (void)g4s::reads_sync(g4s::as_stream(c->stream)); if (c) g4s::reads_forget(c, c + 1); delete c; }
+void dist_cg_async_free(DistCgAsync *c) { delete c; }
 } // namespace g4s
 
 G4S_API g4s_status g4s_conj_grad_dist_tr(g4s_spmv_dist_t A, const g4s_transport *tr, int32_t n_local, const double *BI_dev, const int32_t *zero_resid_dev,

@@ -351,13 +351,12 @@ G4S_API g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, co
             rp = d_rp.as<int>(); ci = d_ci.as<int>(); lab = d_lab.as<int>();
         }
         G4S_TRY(enqueue(n, rp, ci, lab, symmetric, rounds, no_skip, st, count, hubs, s));
-        G4S_HIP_TRY(g4s::read_small(&h, st, sizeof(CcState), s));
         if (!device) G4S_HIP_TRY(hipMemcpyAsync(labels, lab, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(g4s::reads_sync(s));                           // the call's one wait
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, st));               // the call's one wait
         return G4S_OK;
     };
     int status = run();
-    if (status != G4S_OK) { (void)g4s::reads_sync(s); (void)hipStreamSynchronize(s); }
+    if (status != G4S_OK) (void)hipStreamSynchronize(s);         // the caller's host arrays and the blocks released below: nothing in flight touches them
     work.idle = d_rp.idle = d_ci.idle = d_lab.idle = true;
     if (status == G4S_OK && h.invalid)
         status = g4s::set_error(G4S_ERR_INVALID, "g4s_connected_components: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"

@@ -435,25 +435,19 @@ int symbolic_device(const Job &j, int32_t *crpt, int64_t *cnnz, g4s_ewise_info *
     EwState *st = work.as<EwState>();
     int *upr = reinterpret_cast<int *>(work.as<char>() + 256), *uoff = reinterpret_cast<int *>(work.as<char>() + 256 + n1),
         *cnt = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * n1);
+    g4s::ReadScope reads(s);
     EwState h{};
     int units = 0;
-    auto run = [&]() -> int {
-        G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(EwState), s));
-        hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for((long long)j.rows + 1)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, cnt, st);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.rows + 1, s));
-        if (j.rows > 0) launch<COUNT_ROWS>(j, false, uoff, INT_MAX, cnt, nullptr, nullptr, nullptr, nullptr, st, s);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(cnt), crpt, (long long)j.rows + 1, s));
-        G4S_HIP_TRY(g4s::read_small(&h, st, sizeof(EwState), s));
-        G4S_HIP_TRY(g4s::read_small(&units, uoff + j.rows, sizeof(int), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)g4s::reads_sync(s);
-    work.idle = true;
-    G4S_TRY(status);
+    G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(EwState), s));
+    hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for((long long)j.rows + 1)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, cnt, st);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.rows + 1, s));
+    if (j.rows > 0) launch<COUNT_ROWS>(j, false, uoff, INT_MAX, cnt, nullptr, nullptr, nullptr, nullptr, st, s);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(cnt), crpt, (long long)j.rows + 1, s));
+    G4S_HIP_TRY(reads.note(h, st));
+    G4S_HIP_TRY(reads.fetch(units, uoff + j.rows));
+    work.idle = true;                                              // (an early return above leaves it false: the block is then released behind a device-wide wait)
     if (h.fail) return contract_error(j, h.fail);
     {
         info->nnz_a = h.nnz_a;
@@ -482,25 +476,18 @@ int numeric_device(const Job &j, long long nnz_a, long long nnz_b, long long nnz
     int *upr = reinterpret_cast<int *>(work.as<char>() + 256), *uoff = reinterpret_cast<int *>(work.as<char>() + 256 + n1),
         *ucnt = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * n1), *upos = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * n1 + u1);
     int fail = 0;
-    auto run = [&]() -> int {
-        G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(EwState), s));
-        G4S_HIP_TRY(hipMemsetAsync(ucnt, 0, sizeof(int) * ((size_t)cap + 1), s));
-        hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for((long long)j.rows + 1)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, (int *)nullptr, st);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.rows + 1, s));
-        launch<COUNT_UNITS>(j, false, uoff, (int)cap, ucnt, nullptr, nullptr, nullptr, nullptr, st, s);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(ucnt), upos, cap + 1, s));
-        launch<FILL>(j, cval != nullptr, uoff, (int)cap, nullptr, upos, crpt, ccol, cval, st, s);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::read_small(&fail, &st->fail, sizeof(int), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)g4s::reads_sync(s);
-    work.idle = true;
-    G4S_TRY(status);
+    G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(EwState), s));
+    G4S_HIP_TRY(hipMemsetAsync(ucnt, 0, sizeof(int) * ((size_t)cap + 1), s));
+    hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for((long long)j.rows + 1)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, (int *)nullptr, st);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.rows + 1, s));
+    launch<COUNT_UNITS>(j, false, uoff, (int)cap, ucnt, nullptr, nullptr, nullptr, nullptr, st, s);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(ucnt), upos, cap + 1, s));
+    launch<FILL>(j, cval != nullptr, uoff, (int)cap, nullptr, upos, crpt, ccol, cval, st, s);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(fail, &st->fail));
+    work.idle = true;                                              // (as in symbolic_device)
     if (fail) return contract_error(j, fail);
     return G4S_OK;
 }
@@ -508,11 +495,12 @@ int numeric_device(const Job &j, long long nnz_a, long long nnz_b, long long nnz
 // arpt[rows], brpt[rows] (brpt may be NULL) and crpt[rows] (may be NULL) of device arrays: one wait
 int read_counts(const Job &j, const int32_t *crpt, long long *na, long long *nb, long long *nc, hipStream_t s)
 {
+    g4s::ReadScope reads(s);
     int a = 0, b = 0, c = 0;
-    G4S_HIP_TRY(g4s::read_small(&a, j.arpt + j.rows, sizeof(int), s));
-    if (j.brpt) G4S_HIP_TRY(g4s::read_small(&b, j.brpt + j.rows, sizeof(int), s));
-    if (crpt) G4S_HIP_TRY(g4s::read_small(&c, crpt + j.rows, sizeof(int), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(reads.note(a, j.arpt + j.rows));
+    if (j.brpt) G4S_HIP_TRY(reads.note(b, j.brpt + j.rows));
+    if (crpt) G4S_HIP_TRY(reads.note(c, crpt + j.rows));
+    G4S_HIP_TRY(reads.wait());
     if (a < 0 || b < 0 || c < 0) return g4s::set_error(G4S_ERR_INVALID, "%s: a negative entry count (rowptr[rows] %d, %d, crpt[rows] %d)", j.fn, a, b, c);
     *na = a; *nb = b; *nc = c;
     return G4S_OK;

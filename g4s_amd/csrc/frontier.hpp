@@ -141,8 +141,7 @@ struct ZeroScan {
         int h = 0;
         if (nnz > 0) {
             G4S_HIP_TRY(enqueue(nnz, values, cus, flag_word, s));
-            G4S_HIP_TRY(g4s::read_small(&h, flag_word, sizeof(int), s));
-            G4S_HIP_TRY(g4s::reads_sync(s));
+            G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, flag_word));
             if (waits) *waits += 1;
         }
         state = h ? 2 : 1;

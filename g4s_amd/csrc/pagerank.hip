@@ -390,8 +390,6 @@ int pagerank(g4s_csr_s *A, double damping, double tol, int32_t max_iterations, c
     double *inv_s = w->vec, *x = w->vec + w->n, *y = w->vec + 2 * w->n, *pn = w->vec + 3 * w->n, *part = w->partials;
     PrState *st = w->state;
 
-    auto fail = [&](int code) { (void)g4s::reads_sync(s); return code; };   // also settles a noted read of h
-#define PR_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(g4s::set_error(G4S_ERR_HIP, "%s: %s: %s", fn, #expr, hipGetErrorString(e_))); } while (0)
     G4S_TRY(enqueue_begin(A, s));
     if (pers) hipLaunchKernelGGL(vec_sum_kernel, dim3(G), dim3(WG), 0, s, n, pers, part + P_SUMP * kMaxGrid, st, 1);
     if (warm) hipLaunchKernelGGL(vec_sum_kernel, dim3(G), dim3(WG), 0, s, n, (const double *)rank, part + P_SUMR * kMaxGrid, st, 2);
@@ -401,17 +399,17 @@ int pagerank(g4s_csr_s *A, double damping, double tol, int32_t max_iterations, c
     if (pers) hipLaunchKernelGGL(init_kernel<true>, dim3(G), dim3(WG), 0, s, n, pers, inv_n, (int)warm, (const double *)inv_s, pn, rank, x, part, (const PrState *)st);
     else hipLaunchKernelGGL(init_kernel<false>, dim3(G), dim3(WG), 0, s, n, pers, inv_n, (int)warm, (const double *)inv_s, pn, rank, x, part, (const PrState *)st);
     hipLaunchKernelGGL(verdict_kernel<true>, dim3(1), dim3(WG), 0, s, G, (const double *)part, tol, cap, st);
-    PR_HIP(hipGetLastError());
-    if (A->nnz == 0) PR_HIP(hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, s));   // Aᵀ·x of a matrix without entries, once
+    G4S_HIP_TRY(hipGetLastError());
+    if (A->nnz == 0) G4S_HIP_TRY(hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, s));   // Aᵀ·x of a matrix without entries, once
 
+    g4s::ReadScope reads(s);
     PrState h{};
     int waits = 0, products = 0, batch = kBatch;
     for (;;) {
         const int nb = std::min(batch, cap - h.iter);              // every iteration enqueued so far has run: stop == 0
         for (int b = 0; b < nb; ++b) {
             if (A->nnz > 0) {
-                const int st_mv = g4s_spmv(product_handle, x, y, 1.0, 0.0, s);
-                if (st_mv != G4S_OK) return fail(st_mv);
+                G4S_TRY(g4s_spmv(product_handle, x, y, 1.0, 0.0, s));
                 ++products;
             }
             if (pers) hipLaunchKernelGGL(epilogue_kernel<true>, dim3(G), dim3(WG), 0, s, n, damping, one_minus_damping, inv_n, (const double *)y, (const double *)pn,
@@ -420,14 +418,12 @@ int pagerank(g4s_csr_s *A, double damping, double tol, int32_t max_iterations, c
                                     (const double *)inv_s, rank, x, part, (const PrState *)st);
             hipLaunchKernelGGL(verdict_kernel<false>, dim3(1), dim3(WG), 0, s, G, (const double *)part, tol, cap, st);
         }
-        PR_HIP(hipGetLastError());
-        PR_HIP(g4s::read_small(&h, st, sizeof(PrState), s));
-        PR_HIP(g4s::reads_sync(s));
+        G4S_HIP_TRY(hipGetLastError());
+        G4S_HIP_TRY(reads.fetch(h, st));
         ++waits;
         if (h.stop != 0) break;
         batch = next_batch(h, tol);
     }
-#undef PR_HIP
     if (h.stop == 3) {
         if (h.bad_values) {
             w->values_dirty = true;                                // new values get a new verdict

@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include <algorithm>
 #include "readback.hpp"
+#include "read_ledger.hpp"
 #include <cstring>
 #include <mutex>
 #include <unordered_map>
@@ -247,60 +248,45 @@ int scratch_shutdown()
     return G4S_OK;
 }
 
-// ---- small reads through pinned memory (readback.hpp)
+// ---- small reads through pinned memory (readback.hpp): the thread's block and ledger, and the HIP calls around them
 namespace {
-struct PendingRead { void *dst; size_t off, bytes; hipStream_t s; };
 struct ReadBlock {
-    static constexpr size_t kBytes = 4096;
     char *p = nullptr;                                             // pinned, portable; lives as long as the process (a thread's block is not returned: freeing pinned
-    size_t used = 0;                                               // memory from a thread_local destructor can run behind the runtime's own shutdown)
-    std::vector<PendingRead> pending;
+    ReadLedger ledger;                                             // memory from a thread_local destructor can run behind the runtime's own shutdown)
 };
 thread_local ReadBlock t_reads;
-void settle_reads(hipStream_t s, bool deliver)                     // the reads enqueued on s: handed out (or dropped); the block is reused once nothing is noted
-{
-    ReadBlock &b = t_reads;
-    size_t keep = 0;
-    for (const PendingRead &r : b.pending) {
-        if (r.s != s) { b.pending[keep++] = r; continue; }
-        if (deliver) std::memcpy(r.dst, b.p + r.off, r.bytes);
-    }
-    b.pending.resize(keep);
-    if (!keep) b.used = 0;
-}
 } // namespace
-hipError_t read_small(void *dst, const void *src, size_t bytes, hipStream_t s)
+hipError_t ReadScope::note(void *dst, const void *src, size_t bytes)
 {
     ReadBlock &b = t_reads;
-    if (!b.p && hipHostMalloc(reinterpret_cast<void **>(&b.p), ReadBlock::kBytes, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; }
-    const size_t need = (bytes + 15) & ~(size_t)15;
-    if (!b.p || b.used + need > ReadBlock::kBytes) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);   // (the plain way: correct, only slower)
-    const hipError_t e = hipMemcpyAsync(b.p + b.used, src, bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    b.pending.push_back(PendingRead{dst, b.used, bytes, s});
-    b.used += need;
-    return hipSuccess;
+    if (!b.p && hipHostMalloc(reinterpret_cast<void **>(&b.p), ReadLedger::kBlockBytes, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; }
+    if (char *slot = b.ledger.reserve(b.p, dst, bytes, s_, owner(), &last_)) return hipMemcpyAsync(slot, src, bytes, hipMemcpyDeviceToHost, s_);
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s_);   // (the plain way: correct, only slower)
+    return e != hipSuccess ? e : hipStreamSynchronize(s_);
 }
-hipError_t reads_sync(hipStream_t s)
+hipError_t ReadScope::mark(hipEvent_t ev)
 {
-    const hipError_t e = hipStreamSynchronize(s);
-    settle_reads(s, e == hipSuccess);
-    return e;
+    mark_ = last_;
+    return hipEventRecord(ev, s_);
 }
-hipError_t reads_sync_event(hipEvent_t ev, hipStream_t s)
+hipError_t ReadScope::wait(hipEvent_t ev)
 {
     const hipError_t e = hipEventSynchronize(ev);
-    settle_reads(s, e == hipSuccess);
+    if (e == hipSuccess) t_reads.ledger.deliver(t_reads.p, s_, mark_);
     return e;
 }
-void reads_forget(const void *lo, const void *hi)
+ReadScope::~ReadScope()
 {
-    ReadBlock &b = t_reads;
-    size_t keep = 0;
-    for (const PendingRead &r : b.pending)
-        if (!(static_cast<const char *>(r.dst) >= static_cast<const char *>(lo) && static_cast<const char *>(r.dst) < static_cast<const char *>(hi))) b.pending[keep++] = r;
-    b.pending.resize(keep);
-    if (!keep) b.used = 0;
+    ReadLedger &l = t_reads.ledger;
+    if (!l.count(owner())) return;
+    (void)hipStreamSynchronize(s_);                                // no copy into a slot of this scope is in flight when the slot is handed out again
+    l.drop(owner());
+}
+hipError_t reads_sync(hipStream_t s)                               // (after a failed wait the notes stay with their owners, which drop them)
+{
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) t_reads.ledger.deliver(t_reads.p, s);
+    return e;
 }
 
 } // namespace g4s

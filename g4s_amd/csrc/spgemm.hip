@@ -2078,11 +2078,12 @@ int classify_rows(int M, const long long *d_size, const ClassLimits &lim, int co
     G4S_HIP_TRY(hipMemsetAsync(rc.hist.p, 0, sizeof(int) * 2 * CLS_COUNT, s));
     const int grid = std::min(kClassBlocks, (M + 255) / 256);
     hipLaunchKernelGGL(classify_kernel, dim3(grid), dim3(256), 0, s, M, d_size, lim, cols_clip, rc.cls.as<int>(), rc.hist.as<int>());
-    G4S_HIP_TRY(g4s::read_small(rc.count, rc.hist.p, sizeof(int) * CLS_COUNT, s));
+    g4s::ReadScope reads(s);
+    G4S_HIP_TRY(reads.note(rc.count, rc.hist.p));
     int *cursor = rc.hist.as<int>() + CLS_COUNT;                   // (zeroed with the counts)
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid), dim3(256), 0, s, M, rc.cls.as<int>(), (const int *)rc.hist.as<int>(), cursor, rc.lists.as<int>());
     G4S_HIP_TRY(hipGetLastError());
-    G4S_HIP_TRY(g4s::reads_sync(s));                               // (the host's wait for the counts covers the scatter: it no longer needs anything from the host)
+    G4S_HIP_TRY(reads.wait());                                     // (the host's wait for the counts covers the scatter: it no longer needs anything from the host)
     rc.offset[0] = 0;
     for (int c = 0; c < CLS_COUNT; ++c) rc.offset[c + 1] = rc.offset[c] + rc.count[c];
     return G4S_OK;
@@ -2169,8 +2170,7 @@ int compute_row_flop(int M, const int *arpt, const int *acol, const int *brpt, l
         hipLaunchKernelGGL(row_flop_from_scan_kernel, dim3((M + 255) / 256), dim3(256), 0, s, M, arpt, P.as<long long>(), d_row_flop);
         G4S_HIP_TRY(hipGetLastError());
         long long h = 0;
-        G4S_HIP_TRY(g4s::read_small(&h, P.as<long long>() + annz, sizeof(h), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, P.as<long long>() + annz));
         if (total) *total = (int64_t)h;
         return G4S_OK;
     }
@@ -2180,8 +2180,7 @@ int compute_row_flop(int M, const int *arpt, const int *acol, const int *brpt, l
     if (M > 0) hipLaunchKernelGGL(row_flop_kernel, dim3((M + 31) / 32), dim3(256), 0, s, M, arpt, acol, brpt, d_row_flop, tot.as<unsigned long long>());
     G4S_HIP_TRY(hipGetLastError());
     unsigned long long h = 0;
-    G4S_HIP_TRY(g4s::read_small(&h, tot.p, sizeof(h), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, tot.p));
     if (total) *total = (int64_t)h;
     return G4S_OK;
 }
@@ -2195,8 +2194,7 @@ int check_ids(const int *ids, long long n, int bound, const char *what, hipStrea
     const int grid = (int)std::min<long long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(check_range_kernel, dim3(grid), dim3(256), 0, s, ids, n, bound, flag.as<int>());
     int h = 0;
-    G4S_HIP_TRY(g4s::read_small(&h, flag.p, sizeof(int), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, flag.p));
     if (h) return g4s::set_error(G4S_ERR_INVALID, "SpGEMM: %s outside its valid range [0,%d)", what, bound);
     return G4S_OK;
 }
@@ -2214,8 +2212,7 @@ int check_b(const int *brpt, const int *bcol, int K, long long bnnz, int N, hipS
     hipLaunchKernelGGL(check_descents_kernel, dim3(grid), dim3(256), 0, s, bcol, bnnz, N, reinterpret_cast<int *>(d), d + 1);
     hipLaunchKernelGGL(row_start_descents_kernel, dim3(std::min((K + 255) / 256, 512)), dim3(256), 0, s, K, brpt, bcol, d + 2);
     unsigned long long h[3] = {0, 0, 0};
-    G4S_HIP_TRY(g4s::read_small(h, d, sizeof(h), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, d));
     if (h[0] & 0xffffffffull) return g4s::set_error(G4S_ERR_INVALID, "SpGEMM: a column id of B outside its valid range [0,%d)", N);
     *unsorted = h[1] != h[2];                                       // the caller sorts a private copy of B's rows (sort_b_rows)
     return G4S_OK;
@@ -2333,9 +2330,9 @@ int checked_row_flop(int M, int K, int N, const int *arpt, const int *acol, long
     G4S_HIP_TRY(hipGetLastError());
     unsigned long long h[4] = {0, 0, 0, 0};
     long long tot = 0;
-    G4S_HIP_TRY(g4s::read_small(h, d, sizeof(h), s));
-    G4S_HIP_TRY(g4s::read_small(&tot, P.as<long long>() + annz, sizeof(tot), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    g4s::ReadScope reads(s);
+    G4S_HIP_TRY(reads.note(h, d));
+    G4S_HIP_TRY(reads.fetch(tot, P.as<long long>() + annz));
     if (h[3]) return g4s::set_error(G4S_ERR_INVALID, "SpGEMM: a column id of A outside its valid range [0,%d)", K);
     if (h[0] & 0xffffffffull) return g4s::set_error(G4S_ERR_INVALID, "SpGEMM: a column id of B outside its valid range [0,%d)", N);
     *b_unsorted = h[1] != h[2];                                     // (the flop does not depend on the order inside B's rows: everything computed here stands)
@@ -2346,16 +2343,15 @@ int checked_row_flop(int M, int K, int N, const int *arpt, const int *acol, long
 // the last entries of two row-pointer arrays (nnz(A), nnz(B)) in one host wait
 int read_last2(const int *a_rpt, int na, int *a_out, const int *b_rpt, int nb, int *b_out, hipStream_t s)
 {
-    G4S_HIP_TRY(g4s::read_small(a_out, a_rpt + na, sizeof(int), s));
-    G4S_HIP_TRY(g4s::read_small(b_out, b_rpt + nb, sizeof(int), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    g4s::ReadScope reads(s);
+    G4S_HIP_TRY(reads.note(*a_out, a_rpt + na));
+    G4S_HIP_TRY(reads.fetch(*b_out, b_rpt + nb));
     return G4S_OK;
 }
 
 int read_last(const int *d_rpt, int n, int *out, hipStream_t s)
 {
-    G4S_HIP_TRY(g4s::read_small(out, d_rpt + n, sizeof(int), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(*out, d_rpt + n));
     return G4S_OK;
 }
 
@@ -2443,8 +2439,7 @@ int build_column_map(int N, long long bnnz, const int *bcol, ColumnMap &cm, hipS
     hipLaunchKernelGGL(colmap_popc_kernel, dim3((W + 256) / 256), dim3(256), 0, s, W, N, seen.as<unsigned char>(), bm.as<unsigned>(), cnt.as<int>());
     G4S_TRY(g4s::prims::exclusive_scan(cnt.as<int>(), prefix.as<int>(), (long long)W + 1, s));
     int n2 = 0;
-    G4S_HIP_TRY(g4s::read_small(&n2, prefix.as<int>() + W, sizeof(int), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(n2, prefix.as<int>() + W));
     if (n2 <= 0 || (long long)n2 * 8 > (long long)N * 7) return G4S_OK;
     G4S_TRY(cm.bcol2.alloc(sizeof(int) * (size_t)bnnz, cm.keep));
     G4S_TRY(cm.inv.alloc(sizeof(int) * (size_t)n2, cm.keep));
@@ -2738,8 +2733,7 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         hipLaunchKernelGGL(presorted_need_kernel, dim3((M + 255) / 256), dim3(256), 0, s, M, rc.cls.as<int>(), class_mask, row_flop.as<long long>(), N2, min_flop, need.as<long long>());
         G4S_TRY(g4s::prims::exclusive_scan(need.as<long long>(), pre->off.as<long long>(), (long long)M + 1, s));
         long long total_cols = 0;
-        G4S_HIP_TRY(g4s::read_small(&total_cols, pre->off.as<long long>() + M, sizeof(long long), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(total_cols, pre->off.as<long long>() + M));
         size_t free_b = 0, total_b = 0;
         G4S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         int *cols = nullptr;
@@ -2845,8 +2839,7 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
     // rows too wide for a key table in LDS: the rows whose optimistic table filled up, and the window class → LDS bitmap windows
     int n_ovf = 0;
     if (!x_large) {                                                // (only the optimistic table kernel can overflow)
-        G4S_HIP_TRY(g4s::read_small(&n_ovf, ovf_count.p, sizeof(int), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(n_ovf, ovf_count.p));
         if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s symbolic: %d optimistic tables overflowed, %d window-class rows\n", n_ovf, rc.count[CLS_M2]);
         G4S_TRY(window(1024, ovf_rows.as<int>(), n_ovf, nullptr, nullptr));   // rows of the optimistic table class are not in the scratch
     }
@@ -2874,21 +2867,21 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
     // block sums → block offsets by one workgroup in parallel (a single thread walking the ≈ 1 000 sums took 116 µs of every call)
     hipLaunchKernelGGL(g4s::prims::scan_tile_offsets_kernel<long long>, dim3(1), dim3(g4s::prims::kScanThreads), 0, s, nblocks + 1, block_sums.as<long long>());
     long long h_total = 0;
-    G4S_HIP_TRY(g4s::read_small(&h_total, block_sums.as<long long>() + nblocks, sizeof(long long), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(h_total, block_sums.as<long long>() + nblocks));
     *cnnz = h_total;
     if (h_total > INT32_MAX)
         return g4s::set_error(G4S_ERR_OVERFLOW, "nnz(C) = %lld exceeds the reference's int32 row pointer (mm/inc/define.h:14)", h_total);
     hipLaunchKernelGGL(scan_write_kernel, dim3(nblocks), dim3(256), 0, s, M, nz, block_sums.as<long long>(), crpt);
     G4S_HIP_TRY(hipGetLastError());
     DevBuf hash_buf;
+    g4s::ReadScope reads(s);
     unsigned long long h_hash = 0;
     if (pre && pre->keep) {                                        // the two-call form: what the numeric call must find unchanged to take this state over
         G4S_TRY(hash_buf.alloc(sizeof(unsigned long long)));
         G4S_TRY(enqueue_pattern_hash(M, K, annz, bnnz, arpt, acol, brpt, bcol_caller, crpt, hash_buf.as<unsigned long long>(), s));
-        G4S_HIP_TRY(g4s::read_small(&h_hash, hash_buf.p, sizeof(h_hash), s));
+        G4S_HIP_TRY(reads.note(h_hash, hash_buf.p));
     }
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(reads.wait());
     if (pre) pre->key_hash = h_hash;
     t_idle = true;
     dbg.mark("scan");
@@ -2955,6 +2948,7 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
     if (M == 0) return G4S_OK;
     DbgPhases dbg("numeric");
     ArenaScope arena;
+    g4s::ReadScope reads(s);                                       // (behind the arena: gone, and its stream idle, before the arena's memory is)
     // B with unsorted rows: the kernels read a sorted private copy (sort_b_rows) — the symbolic phase's columns and permutation when they were carried over, else made here.
     // (Done in front of the short-row kernels: every kernel of the phase reads the same B.)
     DevBuf local_perm, local_bs, local_bv;
@@ -3032,13 +3026,13 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
         G4S_TRY(g4s::prims::exclusive_scan(tasks->as<long long>(), toff->as<long long>(), (long long)n + 1, s));
         G4S_TRY(g4s::prims::exclusive_scan(items->as<long long>(), ioff->as<long long>(), (long long)n + 1, s));
         G4S_TRY(g4s::prims::exclusive_scan(nch->as<int>(), choff->as<int>(), (long long)n + 1, s));
-        G4S_HIP_TRY(g4s::read_small(&rank_totals[0], toff->as<long long>() + n, sizeof(long long), s));
-        G4S_HIP_TRY(g4s::read_small(&rank_totals[1], ioff->as<long long>() + n, sizeof(long long), s));
-        G4S_HIP_TRY(g4s::read_small(&rank_nchunks, choff->as<int>() + n, sizeof(int), s));
+        G4S_HIP_TRY(reads.note(rank_totals[0], toff->as<long long>() + n));
+        G4S_HIP_TRY(reads.note(rank_totals[1], ioff->as<long long>() + n));
+        G4S_HIP_TRY(reads.note(rank_nchunks, choff->as<int>() + n));
         {   // an event behind the three copies: stage 2 waits for IT, not for the stream — the mid-size kernel enqueued in between is still running then
             thread_local hipEvent_t ev = nullptr;
             if (!ev) G4S_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            G4S_HIP_TRY(hipEventRecord(ev, s));
+            G4S_HIP_TRY(reads.mark(ev));
             rank_totals_ready = ev;
         }
         G4S_REQUIRE(pre->bnnz >= 0, "carried state without nnz(B)");
@@ -3052,7 +3046,7 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
         constexpr int T = kRankT;
         const int n = rank_n, nseg = pre->nseg;
         const int *rows = rank_sr.rows.as<int>();
-        G4S_HIP_TRY(g4s::reads_sync_event(rank_totals_ready, s));        // stage 1's totals: there long ago (the mid-size launch in between has synchronised the stream)
+        G4S_HIP_TRY(reads.wait(rank_totals_ready));                      // stage 1's totals: there long ago (the mid-size launch in between has synchronised the stream)
         const int nchunks = rank_nchunks;
         const long long ntask = rank_totals[0], nitem = rank_totals[1], nct = nitem - ntask;
         if (ntask <= 0 || nitem <= 0 || nitem > (1ll << 28) || nchunks <= 0)
@@ -3161,10 +3155,10 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
         hipLaunchKernelGGL(unit_rows_kernel, dim3((n + 256) / 256), dim3(256), 0, s, n, rows, arpt, crpt, chunk, nz_lo, nz_hi, tasks->as<long long>(), items->as<long long>());
         G4S_TRY(g4s::prims::exclusive_scan(tasks->as<long long>(), toff->as<long long>(), (long long)n + 1, s));
         G4S_TRY(g4s::prims::exclusive_scan(items->as<long long>(), ioff->as<long long>(), (long long)n + 1, s));
+        g4s::ReadScope reads(s);                                    // (the lambda's own: its destinations are its locals)
         long long totals[2] = {0, 0};
-        G4S_HIP_TRY(g4s::read_small(&totals[0], toff->as<long long>() + n, sizeof(long long), s));
-        G4S_HIP_TRY(g4s::read_small(&totals[1], ioff->as<long long>() + n, sizeof(long long), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(reads.note(totals[0], toff->as<long long>() + n));
+        G4S_HIP_TRY(reads.fetch(totals[1], ioff->as<long long>() + n));
         const long long ntask = totals[0], nitem = totals[1];
         if (ntask <= 0 || nitem <= 0 || nitem > (1ll << 28)) return G4S_OK;
         if (ctb->alloc(sizeof(int) * (size_t)std::max<long long>(nitem - ntask, 1)) != G4S_OK || ucnt->alloc(sizeof(int) * ((size_t)nitem + 1)) != G4S_OK ||
@@ -3184,8 +3178,7 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
         long long ubound = class_flop_bound >= 0 ? class_flop_bound / 64 + nitem : -1;
         if (ubound < 0 || ubound > (1ll << 27)) {                   // no bound from the caller (or a loose one): read the count
             int total_units = 0;
-            G4S_HIP_TRY(g4s::read_small(&total_units, uoff->as<int>() + nitem, sizeof(int), s));
-            G4S_HIP_TRY(g4s::reads_sync(s));
+            G4S_HIP_TRY(reads.fetch(total_units, uoff->as<int>() + nitem));
             if (total_units <= 0 || total_units > (1 << 27)) return G4S_OK;      // (a sum past 2^31 shows up as a negative total)
             ubound = total_units;
         }
@@ -3329,7 +3322,7 @@ G4S_API g4s_status g4s_spgemm_numeric(int32_t M, int32_t K, int32_t N,
         unsigned long long *d_hash = nullptr, h_hash = 0;
         G4S_TRY(g4s::scratch_alloc(reinterpret_cast<void **>(&d_hash), sizeof(unsigned long long), s));
         int st = enqueue_pattern_hash(M, K, pre->annz, pre->bnnz, arpt, acol, brpt, bcol, crpt, d_hash, s);
-        if (st == G4S_OK && (g4s::read_small(&h_hash, d_hash, sizeof(h_hash), s) != hipSuccess || g4s::reads_sync(s) != hipSuccess))
+        if (st == G4S_OK && g4s::ReadScope(s).fetch(h_hash, d_hash) != hipSuccess)
             st = g4s::set_error(G4S_ERR_HIP, "g4s_spgemm_numeric: reading the pattern hash failed");
         g4s::scratch_free(d_hash, s);
         G4S_TRY(st);

@@ -459,11 +459,12 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
 {
     if (info) *info = g4s_masked_info{};
     if (o.M == 0) return G4S_OK;
+    g4s::ReadScope reads(s);
     int annz = 0, bnnz = 0, mnnz = 0;
-    G4S_HIP_TRY(g4s::read_small(&annz, o.arpt + o.M, sizeof(int), s));
-    G4S_HIP_TRY(g4s::read_small(&mnnz, o.mrpt + o.M, sizeof(int), s));
-    if (o.K > 0) G4S_HIP_TRY(g4s::read_small(&bnnz, o.brpt + o.K, sizeof(int), s));
-    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_HIP_TRY(reads.note(annz, o.arpt + o.M));
+    G4S_HIP_TRY(reads.note(mnnz, o.mrpt + o.M));
+    if (o.K > 0) G4S_HIP_TRY(reads.note(bnnz, o.brpt + o.K));
+    G4S_HIP_TRY(reads.wait());
     if (annz < 0 || bnnz < 0 || mnnz < 0) return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: a negative entry count (arpt[M] %d, brpt[K] %d, mrpt[M] %d)", annz, bnnz, mnnz);
     if (info) info->mask_nnz = mnnz;
     if (mnnz == 0) return G4S_OK;
@@ -481,43 +482,38 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
     int *keys = reinterpret_cast<int *>(work.as<char>() + 256), *ids = reinterpret_cast<int *>(work.as<char>() + 256 + m4);
     int *keys_s = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * m4), *list = reinterpret_cast<int *>(work.as<char>() + 256 + 3 * m4);
     OpenState h{};
-    int status = G4S_OK;
-    auto run = [&]() -> int {
-        G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(OpenState), s));
-        const unsigned ring = flags & G4S_SEMIRING_MASK;           // S::identity() on the host
-        const double identity = ring == G4S_SEMIRING_MIN_PLUS ? __builtin_inf() : ring == G4S_SEMIRING_MAX_PLUS ? -__builtin_inf() : 0.0;
-        hipLaunchKernelGGL(mk_fill_kernel, dim3(grid_for(mnnz)), dim3(WG), 0, s, (long long)mnnz, identity, o.cval);
-        if (bnnz) hipLaunchKernelGGL(mk_check_b_kernel, dim3(grid_for(bnnz)), dim3(WG), 0, s, (long long)bnnz, o.N, o.bcol, st);
-        const int rows_per_wg = WG / kOpenLpr;
-        hipLaunchKernelGGL(mk_open_kernel, dim3((o.M + rows_per_wg - 1) / rows_per_wg), dim3(WG), 0, s, o.M, o.K, o.N, annz, bnnz, mnnz, o.arpt, o.acol, o.brpt, o.mrpt,
-                           o.mcol, keys, ids, st, cuts);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::read_small(&h, st, sizeof(OpenState), s));
-        G4S_TRY(g4s::prims::sort_pairs_descending(keys, ids, keys_s, list, keys_s, list, o.M, 3, s));   // one pass: the partners are never written
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        if (h.invalid & BAD_MASK)
-            return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: the mask is not a CSR pattern with strictly ascending rows and column ids in [0, %d)", o.N);
-        if (h.invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: %s", (h.invalid & BAD_A) ? "a row pointer or column id of A is out of range"
-                                                                                                          : "a row pointer or column id of B is out of range");
-        if (h.counts[C_SKIP] < o.M) {
-            G4S_TRY(sr::dispatch(flags, [&](auto p) {
-                return o.aval ? launch_classes<decltype(p), true>(o, list, h.counts, cuts, s) : launch_classes<decltype(p), false>(o, list, h.counts, cuts, s);
-            }));
-        }
-        G4S_HIP_TRY(hipStreamSynchronize(s));
-        return G4S_OK;
-    };
-    status = run();
-    if (status != G4S_OK) (void)g4s::reads_sync(s);               // also settles a noted read of h
+    G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(OpenState), s));
+    const unsigned ring = flags & G4S_SEMIRING_MASK;               // S::identity() on the host
+    const double identity = ring == G4S_SEMIRING_MIN_PLUS ? __builtin_inf() : ring == G4S_SEMIRING_MAX_PLUS ? -__builtin_inf() : 0.0;
+    hipLaunchKernelGGL(mk_fill_kernel, dim3(grid_for(mnnz)), dim3(WG), 0, s, (long long)mnnz, identity, o.cval);
+    if (bnnz) hipLaunchKernelGGL(mk_check_b_kernel, dim3(grid_for(bnnz)), dim3(WG), 0, s, (long long)bnnz, o.N, o.bcol, st);
+    const int rows_per_wg = WG / kOpenLpr;
+    hipLaunchKernelGGL(mk_open_kernel, dim3((o.M + rows_per_wg - 1) / rows_per_wg), dim3(WG), 0, s, o.M, o.K, o.N, annz, bnnz, mnnz, o.arpt, o.acol, o.brpt, o.mrpt,
+                       o.mcol, keys, ids, st, cuts);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_HIP_TRY(reads.note(h, st));
+    G4S_TRY(g4s::prims::sort_pairs_descending(keys, ids, keys_s, list, keys_s, list, o.M, 3, s));   // one pass: the partners are never written
+    G4S_HIP_TRY(reads.wait());
+    if (h.invalid) work.idle = true;                               // refused: the wait has left the stream idle. (Any other early return leaves the flag
+    if (h.invalid & BAD_MASK)                                      // false, and the block is released behind a device-wide wait.)
+        return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: the mask is not a CSR pattern with strictly ascending rows and column ids in [0, %d)", o.N);
+    if (h.invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: %s", (h.invalid & BAD_A) ? "a row pointer or column id of A is out of range"
+                                                                                                      : "a row pointer or column id of B is out of range");
+    if (h.counts[C_SKIP] < o.M) {
+        G4S_TRY(sr::dispatch(flags, [&](auto p) {
+            return o.aval ? launch_classes<decltype(p), true>(o, list, h.counts, cuts, s) : launch_classes<decltype(p), false>(o, list, h.counts, cuts, s);
+        }));
+    }
+    G4S_HIP_TRY(hipStreamSynchronize(s));
     work.idle = true;
-    if (status == G4S_OK && info) {
+    if (info) {
         info->products = (int64_t)h.products;
         info->rows_wave = h.counts[C_WAVE];
         info->rows_lds = h.counts[C_LDS_S] + h.counts[C_LDS_L] + h.counts[C_SPLIT_LDS];
         info->rows_global = h.counts[C_GLOBAL] + h.counts[C_SPLIT_GLOBAL];
         info->rows_split = h.counts[C_SPLIT_LDS] + h.counts[C_SPLIT_GLOBAL];
     }
-    return status;
+    return G4S_OK;
 }
 
 int not_capturing(const char *fn, hipStream_t s)
@@ -545,19 +541,19 @@ int triangles_device(int n, int nnz, const int *rowptr, const int *colids, int64
     OpenState *st = small.as<OpenState>();
     int *lcnt = reinterpret_cast<int *>(small.as<char>() + 256), *lrpt = reinterpret_cast<int *>(small.as<char>() + 256 + n4);
     long long *partial = reinterpret_cast<long long *>(small.as<char>() + 256 + 2 * n4);
+    g4s::ReadScope reads(s);
     int invalid = 0, lnnz = 0;
     long long total = 0;
-    auto run = [&]() -> int {
-        const int rows_per_wg = WG / kOpenLpr;
-        G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(OpenState), s));
-        hipLaunchKernelGGL(tc_lower_kernel, dim3(n / rows_per_wg + 1), dim3(WG), 0, s, n, nnz, rowptr, colids, lcnt, st);
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(lcnt), lrpt, (long long)n + 1, s));
-        G4S_HIP_TRY(g4s::read_small(&invalid, &st->invalid, sizeof(int), s));
-        G4S_HIP_TRY(g4s::read_small(&lnnz, lrpt + n, sizeof(int), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        if (invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_triangle_count: rows must be strictly ascending with column ids in [0, %d) and rowptr non-decreasing from 0", n);
-        if (lnnz == 0) return G4S_OK;
+    const int rows_per_wg = WG / kOpenLpr;
+    G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(OpenState), s));
+    hipLaunchKernelGGL(tc_lower_kernel, dim3(n / rows_per_wg + 1), dim3(WG), 0, s, n, nnz, rowptr, colids, lcnt, st);
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(lcnt), lrpt, (long long)n + 1, s));
+    G4S_HIP_TRY(reads.note(invalid, &st->invalid));
+    G4S_HIP_TRY(reads.fetch(lnnz, lrpt + n));
+    if (invalid || lnnz == 0) small.idle = true;                   // nothing more is enqueued, and the wait has left the stream idle (see masked_device)
+    if (invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_triangle_count: rows must be strictly ascending with column ids in [0, %d) and rowptr non-decreasing from 0", n);
+    if (lnnz > 0) {
         G4S_TRY(lcol.alloc(sizeof(int) * (size_t)lnnz));
         G4S_TRY(cval.alloc(sizeof(double) * (size_t)lnnz));
         hipLaunchKernelGGL(tc_copy_kernel, dim3(n / rows_per_wg + 1), dim3(WG), 0, s, n, rowptr, colids, lrpt, lcol.as<int>());
@@ -567,15 +563,11 @@ int triangles_device(int n, int nnz, const int *rowptr, const int *colids, int64
         hipLaunchKernelGGL(tc_sum_kernel, dim3(kSumBlocks), dim3(WG), 0, s, (long long)lnnz, cval.as<double>(), partial);
         hipLaunchKernelGGL(tc_sum_final_kernel, dim3(1), dim3(64), 0, s, kSumBlocks, partial, partial + kSumBlocks);
         G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::read_small(&total, partial + kSumBlocks, sizeof(long long), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)g4s::reads_sync(s);
-    small.idle = lcol.idle = cval.idle = true;
-    if (status == G4S_OK) *triangles = total;
-    return status;
+        G4S_HIP_TRY(reads.fetch(total, partial + kSumBlocks));
+        small.idle = lcol.idle = cval.idle = true;
+    }
+    *triangles = total;
+    return G4S_OK;
 }
 
 } // namespace
@@ -641,8 +633,7 @@ G4S_API g4s_status g4s_triangle_count(int32_t n, const int32_t *rowptr, const in
     if (n == 0) return G4S_OK;
     if (flags & G4S_DEVICE_POINTERS) {
         int nnz = 0;
-        G4S_HIP_TRY(g4s::read_small(&nnz, rowptr + n, sizeof(int), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(nnz, rowptr + n));
         G4S_REQUIRE(nnz >= 0, "rowptr[n] is negative");
         return triangles_device(n, nnz, rowptr, colids, triangles, info, s);
     }

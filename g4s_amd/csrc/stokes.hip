@@ -256,8 +256,7 @@ G4S_API g4s_status g4s_stokes_uzawa_cg(g4s_elem_op_t op, g4s_csr_t K_csr, const 
     };
     auto fetch = [&]() -> int {
         G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::read_small(hsc, sc, sizeof(hsc), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(hsc, sc));
         return G4S_OK;
     };
     auto each = [&](int n, auto f) { hipLaunchKernelGGL(map_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, n, f); };
@@ -481,8 +480,7 @@ G4S_API g4s_status g4s_stokes_uzawa_cg_dist(g4s_spmv_dist_t K, g4s_spmv_dist_t D
     };
     auto fetch = [&]() -> int {
         G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::read_small(hsc, sc, sizeof(hsc), s));
-        G4S_HIP_TRY(g4s::reads_sync(s));
+        G4S_HIP_TRY(g4s::ReadScope(s).fetch(hsc, sc));
         return G4S_OK;
     };
     auto each = [&](int n, auto f) { hipLaunchKernelGGL(map_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, n, f); };

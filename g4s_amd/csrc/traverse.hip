@@ -379,13 +379,12 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
     TravState *st = w->state;
     int *q0 = w->queue[0], *q1 = w->queue[1];
 
-    auto fail = [&](int code) { (void)g4s::reads_sync(s); return code; };   // also settles a noted read of h
-#define TV_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(g4s::set_error(G4S_ERR_HIP, "%s: %s: %s", fn, #expr, hipGetErrorString(e_))); } while (0)
-    TV_HIP(hipMemcpyAsync(q1, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice, s));
+    G4S_HIP_TRY(hipMemcpyAsync(q1, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(init_fill_kernel<BFS>, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, dist, level, w->mark);
     hipLaunchKernelGGL(init_sources_kernel<BFS>, dim3(1), dim3(WG), 0, s, rows, (int)src.size(), q1, A->d_rowptr, dist, level, q0, st, a);
-    TV_HIP(hipGetLastError());
+    G4S_HIP_TRY(hipGetLastError());
 
+    g4s::ReadScope reads(s);
     TravState h{};
     h.stop = mode == KIND_PULL ? 3 : 0;                            // what the init kernel is bound to decide when the direction is forced
     bool know = false;                                             // h is the device's state
@@ -402,11 +401,10 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
                 else TV_PULL(64);
 #undef TV_PULL
             } else {
-                const int st_mv = g4s_spmv_semiring(pull_handle, dist, w->dist2, G4S_SEMIRING_MIN_PLUS, s);
-                if (st_mv != G4S_OK) return fail(st_mv);
+                G4S_TRY(g4s_spmv_semiring(pull_handle, dist, w->dist2, G4S_SEMIRING_MIN_PLUS, s));
                 hipLaunchKernelGGL(sssp_combine_kernel, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, A->d_rowptr, dist, w->dist2, q0, q1, st, a);
             }
-            TV_HIP(hipGetLastError());
+            G4S_HIP_TRY(hipGetLastError());
         }
         if (mode != KIND_PULL) {                                   // a batch of push steps: no-ops from the first stop on
             int grid = max_grid;
@@ -417,20 +415,18 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
                 if (values || !BFS) hipLaunchKernelGGL((push_kernel<BFS, true>), dim3(grid), dim3(WG), 0, s, rows, A->d_rowptr, A->d_colids, A->d_values, dist, level, w->mark, q0, q1, st, a);
                 else hipLaunchKernelGGL((push_kernel<BFS, false>), dim3(grid), dim3(WG), 0, s, rows, A->d_rowptr, A->d_colids, A->d_values, dist, level, w->mark, q0, q1, st, a);
             }
-            TV_HIP(hipGetLastError());
+            G4S_HIP_TRY(hipGetLastError());
             a.grid_cap = LLONG_MAX;
             a.resume = 0;
             if (know) batch = std::min(kBatchMax, batch * 2);
         }
         hipLaunchKernelGGL(count_kernel<BFS>, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, dist, level, st);
-        TV_HIP(hipGetLastError());
-        TV_HIP(g4s::read_small(&h, st, sizeof(TravState), s));
-        TV_HIP(g4s::reads_sync(s));
+        G4S_HIP_TRY(hipGetLastError());
+        G4S_HIP_TRY(reads.fetch(h, st));
         ++waits;
         know = true;
         if (h.stop == 1 || h.stop == 2) break;
     }
-#undef TV_HIP
     if (info) {
         info->iterations = h.iter;
         info->converged = h.stop == 1;
