@@ -19,6 +19,7 @@ BC_ACCUMULATE, BC_BATCH = 262144, 16                                     # g4s_b
 CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
 EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
 COMBINE_PLUS, COMBINE_TIMES, COMBINE_MIN, COMBINE_MAX, COMBINE_FIRST, COMBINE_SECOND = 0, 1, 2, 3, 4, 5
+DUP_KEEP = -1                                                            # g4s_csr_from_coo_*: dup is DUP_KEEP or a COMBINE_* value (g4s.h)
 SELECT_TRIL, SELECT_TRIU, SELECT_OFFDIAG, SELECT_DIAG, SELECT_NONZERO, SELECT_GT, SELECT_GE, SELECT_LT, SELECT_LE = 0, 1, 2, 3, 4, 5, 6, 7, 8   # g4s_csr_select_*: pred
 SEMIRING_PLUS_TIMES, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_OR_AND, SEMIRING_MASK = 0, 512, 1024, 1536, 1536   # SpGEMM / SpMV value semiring (g4s.h)
 PATTERN_ELEMENT_BLOCK_MATVEC, PATTERN_DENSE_ROW_TIMES_MATRIX, PATTERN_SYM_QUADRATIC_FORM = 1, 2, 3
@@ -74,6 +75,13 @@ class EwiseInfo(C.Structure):
     """g4s_ewise_info: what a g4s_csr_ewise_symbolic call found (entry counts, work units)."""
     _fields_ = [("nnz_a", C.c_int64), ("nnz_b", C.c_int64), ("nnz_c", C.c_int64), ("units", C.c_int64), ("unit_entries", C.c_int32),
                 ("rows_split", C.c_int32), ("host_waits", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CooInfo(C.Structure):
+    """g4s_coo_info: what a g4s_csr_from_coo_symbolic call found and did (counts, the longest run, the sort's shape)."""
+    _fields_ = [("nnz_in", C.c_int64), ("nnz_out", C.c_int64), ("longest_run", C.c_int64), ("row_bits", C.c_int32), ("col_bits", C.c_int32),
+                ("digit_bits", C.c_int32), ("sort_passes", C.c_int32), ("tile_entries", C.c_int32), ("presorted", C.c_int32), ("host_waits", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
 
 
 class DistInfo(C.Structure):
@@ -204,6 +212,9 @@ SIGNATURES = {
     "g4s_csr_ewise_numeric": (C.c_int, [C.c_int, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
     "g4s_csr_select_symbolic": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, i64p, C.c_uint, vp]),
     "g4s_csr_select_numeric": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
+    "g4s_csr_from_coo_symbolic": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, i64p, C.c_uint, C.POINTER(CooInfo), vp]),
+    "g4s_csr_from_coo_numeric": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
+    "g4s_csr_row_indices": (C.c_int, [C.c_int32, C.c_int64, vp, vp, C.c_uint, vp]),
     "g4s_register_pattern":(C.c_int, [FUN_GATHER, FUN_APPLY, C.POINTER(PatternDesc)]),
     "g4s_unregister_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY]),
     "g4s_set_host_callback_policy": (C.c_int, [C.c_int32]),

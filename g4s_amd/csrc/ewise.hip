@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "prims.hpp"
 #include "readback.hpp"
+#include "call_util.hpp"
 #include <algorithm>
 #include <climits>
 
@@ -95,18 +96,6 @@ __device__ __forceinline__ int row_of_unit(const int *__restrict__ uoff, int row
         else hi = mid - 1;
     }
     return lo;
-}
-
-__device__ __forceinline__ double combine_values(int combine, double x, double y)
-{
-    switch (combine) {
-    case G4S_COMBINE_PLUS: return x + y;
-    case G4S_COMBINE_TIMES: return x * y;
-    case G4S_COMBINE_MIN: return y < x ? y : x;
-    case G4S_COMBINE_MAX: return x < y ? y : x;
-    case G4S_COMBINE_FIRST: return x;
-    default: return y;
-    }
 }
 
 template <typename V>
@@ -329,57 +318,6 @@ __global__ __launch_bounds__(WG) void sel_kernel(int pred, long long k, double t
     }
     if (MODE == COUNT_ROWS && total) atomicAdd(&st->cnnz, total);
 }
-
-struct BigBuf {
-    void *p = nullptr;
-    bool idle = false;
-    BigBuf() = default;
-    BigBuf(const BigBuf &) = delete;
-    BigBuf &operator=(const BigBuf &) = delete;
-    ~BigBuf() { if (p) (void)g4s::big_free(p, idle); }
-    int alloc(size_t bytes) { return g4s::big_alloc(&p, bytes); }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
-struct Span {
-    const void *p;
-    size_t bytes;
-};
-
-template <size_t NO, size_t NI>
-bool any_overlap(const Span (&outs)[NO], const Span (&ins)[NI])
-{
-    for (const Span &o : outs)
-        for (const Span &i : ins)
-            if (overlap(o.p, o.bytes, i.p, i.bytes)) return true;
-    for (size_t x = 0; x < NO; ++x)
-        for (size_t y = x + 1; y < NO; ++y)
-            if (overlap(outs[x].p, outs[x].bytes, outs[y].p, outs[y].bytes)) return true;
-    return false;
-}
-
-int not_capturing(const char *fn, hipStream_t s)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads counts back and cannot be captured", fn);
-    return G4S_OK;
-}
-
-int upload(BigBuf &b, const void *src, size_t bytes, hipStream_t s)
-{
-    G4S_TRY(b.alloc(bytes));
-    if (bytes && src) G4S_HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return G4S_OK;
-}
-
-size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
 
 // The operands of one call, device arrays. b* are NULL for select; op / combine are then pred and unused.
 struct Job {

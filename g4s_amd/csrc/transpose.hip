@@ -12,12 +12,15 @@
 //   4. prims::sort_pairs_descending on (key, k): ascending column, and stable, so the entries of one column keep their entry order → perm.
 //   5. tr_gather_kernel — tcolids[k] = row[perm[k]], tvalues[k] = values[perm[k]].
 // Nothing depends on timing: the outputs are the same bits on every run.
+// g4s_csr_row_indices is steps 1 (the row pointers only) and 3 alone: the row of every entry, the array a CSR lacks to be a COO (coo.hip is the way back).
 //
 // A handle's transpose (TransposeWork) holds the arrays of Aᵀ, perm and an inner handle of Aᵀ created from them with A's path flags. The transposed
 // products are the inner handle's g4s_spmv / g4s_spmv_semiring, and g4s_csr_update_values of A refreshes it with one gather through perm.
 #include "common.hpp"
 #include "prims.hpp"
 #include "csr_handle.hpp"
+#include "readback.hpp"
+#include "call_util.hpp"
 #include <algorithm>
 #include <new>
 
@@ -129,6 +132,58 @@ int transpose_device(int32_t rows, int32_t cols, int64_t nnz, const int32_t *row
 #undef TR_TRY
     return done(G4S_OK);
 }
+
+// Device arrays, synchronous on `s`: the row-pointer check read back before tr_rows_kernel indexes by them. Two waits.
+int row_indices_device(int32_t rows, int64_t nnz, const int32_t *rowptr, int32_t *row_out, hipStream_t s)
+{
+    BigBuf flag;
+    G4S_TRY(flag.alloc(256));
+    int fail = 0;
+    G4S_HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+    hipLaunchKernelGGL(tr_check_rowptr_kernel, dim3(grid_for((long long)rows + 1)), dim3(WG), 0, s, rows, (long long)nnz, rowptr, flag.as<int>());
+    G4S_HIP_TRY(hipGetLastError());
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(fail, flag.p));
+    flag.idle = true;
+    if (fail) return g4s::set_error(G4S_ERR_INVALID, "g4s_csr_row_indices: rowptr is not zero-based, non-decreasing and ending at nnz = %lld", (long long)nnz);
+    if (rows > 0 && nnz > 0) {
+        hipLaunchKernelGGL(tr_rows_kernel, dim3((unsigned)(((long long)rows + WG - 1) / WG)), dim3(WG), 0, s, rows, rowptr, row_out);
+        G4S_HIP_TRY(hipGetLastError());
+        G4S_HIP_TRY(hipStreamSynchronize(s));
+    }
+    return G4S_OK;
+}
+
+} // namespace
+
+G4S_API g4s_status g4s_csr_row_indices(int32_t rows, int64_t nnz, const int32_t *rowptr, int32_t *row_out, unsigned flags, void *stream)
+{
+    G4S_REQUIRE((flags & ~G4S_DEVICE_POINTERS) == 0u, "flags other than G4S_HOST_POINTERS / G4S_DEVICE_POINTERS");
+    G4S_REQUIRE(rows >= 0 && nnz >= 0, "negative dimension or entry count");
+    if (nnz > INT32_MAX) return g4s::set_error(G4S_ERR_OVERFLOW, "%s: %lld entries exceed the int32 row pointers", __func__, (long long)nnz);
+    G4S_REQUIRE(rowptr, "rowptr is NULL");
+    G4S_REQUIRE(row_out || nnz == 0, "row_out is NULL with nnz > 0");
+    const size_t rp = sizeof(int32_t) * ((size_t)rows + 1), nb = sizeof(int32_t) * (size_t)nnz;
+    const bool dev = flags & G4S_DEVICE_POINTERS;
+    if (!dev && overlap(row_out, nb, rowptr, rp)) return g4s::set_error(G4S_ERR_INVALID, "%s: row_out overlaps rowptr", __func__);
+    const hipStream_t s = g4s::as_stream(stream);
+    G4S_TRY(not_capturing(__func__, s));
+    if (dev) return row_indices_device(rows, nnz, rowptr, row_out, s);
+    BigBuf d_rp, d_out;
+    auto run = [&]() -> int {
+        G4S_TRY(upload(d_rp, rowptr, rp, s));
+        G4S_TRY(d_out.alloc(nb));
+        G4S_TRY(row_indices_device(rows, nnz, d_rp.as<int32_t>(), d_out.as<int32_t>(), s));
+        if (nb) G4S_HIP_TRY(hipMemcpyAsync(row_out, d_out.p, nb, hipMemcpyDeviceToHost, s));
+        G4S_HIP_TRY(hipStreamSynchronize(s));
+        return G4S_OK;
+    };
+    const int status = run();
+    if (status != G4S_OK) (void)hipStreamSynchronize(s);
+    d_rp.idle = d_out.idle = true;
+    return status;
+}
+
+namespace {
 
 // device_malloc of `count` elements (at least one), NULL-initialised by the caller
 template <class T>

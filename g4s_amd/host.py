@@ -7,6 +7,8 @@ Names and argument meaning follow the reference so that tests read like tests of
   spmv_semiring  — the same over min-plus, max-plus or or-and (SEMIRINGS): y = A ⊗ x, or y ⊕ (A ⊗ x)
   spmm           — the same with a dense block of k vectors, Y = alpha·A·X + beta·Y (the sparse form of mm/src/cblas_dxxmm.c)
   csr_transpose  — Aᵀ as a CSR (the CSC form of A; mm/inc/CSR.h:171-230, mm/inc/convert.h), stable: entries of a column keep their order
+  csr_from_coo   — a CSR from an edge list in any order, repeats merged by a duplicate policy (CSR(graph&), mm/inc/CSR.h:255-329); csr_row_indices /
+                   CSR.to_coo the way back, csr_canonical a CSR with sorted rows and merged repeats
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
@@ -223,6 +225,24 @@ class CSR:
     def symmetrise(self, combine="max", drop_diagonal=False):
         """A ∪ Aᵀ of this square matrix as a new device CSR — csr_symmetrise(self, …)."""
         return csr_symmetrise(self, combine, drop_diagonal)
+
+    @classmethod
+    def from_coo(cls, row, col, val=None, rows=None, cols=None, dup="plus", symmetric=False, **kw):
+        """A device CSR from the triples (row, col, val) — csr_from_coo(…); val=None stores 1.0 everywhere. kw: as for the constructor."""
+        _require_gpu()
+        rows, cols = _coo_shape(row, col, rows, cols, symmetric)
+        rp, ci, va = csr_from_coo(row, col, val, rows, cols, dup, symmetric)
+        if va is None:
+            va = torch.ones(ci.numel(), dtype=torch.float64, device=ci.device)
+        return cls(rp, ci, va, rows, cols, **kw)
+
+    def to_coo(self):
+        """(row, col, val) of the stored entries in stored order: csr_row_indices(self.rowptr, self.nnz) beside colids and values (borrowed)."""
+        return csr_row_indices(self.rowptr, self.nnz), self.colids, self.values
+
+    def canonical(self, dup="plus"):
+        """This matrix with sorted rows and merged repeats as a new device CSR — csr_canonical(self, dup)."""
+        return csr_canonical(self, dup)
 
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
@@ -700,6 +720,94 @@ def csr_symmetrise(a, combine="max", drop_diagonal=False):
         raise ValueError(f"symmetrise needs a square matrix, not {a.rows} x {a.cols}")
     s = csr_ewise(a, a.transpose(), "union", combine)
     return csr_select(s, "offdiag") if drop_diagonal else s
+
+
+# ------------------------------------------------------------------------------------------------ CSR from an edge list
+DUPLICATES = {"keep": capi.DUP_KEEP, **COMBINERS}
+
+
+def _coo_info(info):
+    return {n: getattr(info, n) for n, _ in capi.CooInfo._fields_ if n != "reserved"}
+
+
+def _coo_shape(row, col, rows, cols, symmetric):
+    """rows and cols of an edge list: what was given, else the largest id + 1; one number for a symmetric list."""
+    if rows is None:
+        rows = int(row.max().item()) + 1 if row.numel() else 0
+    if cols is None:
+        cols = int(col.max().item()) + 1 if col.numel() else 0
+    if symmetric:
+        rows = cols = max(rows, cols)
+    return int(rows), int(cols)
+
+
+def csr_from_coo(row, col, val=None, rows=None, cols=None, dup="plus", symmetric=False, return_perm=False, return_info=False):
+    """(rowptr, colids, values-or-None) of the rows × cols CSR that the triples (row[i], col[i], val[i]) describe — int32 / int32 / float64 device
+    tensors in any order, with repeats (g4s_csr_from_coo_symbolic / g4s_csr_from_coo_numeric). dup: "keep" — every triple stays an entry, rows
+    ascending, repeats in input order — or "plus", "times", "min", "max", "first", "second": one entry per position, rows strictly ascending, the
+    value folded from left to right over the repeats in input order. val=None: the pattern only. rows / cols default to the largest id + 1.
+    symmetric=True appends the mirrored copy (col, row, val) of every off-diagonal triple behind the originals first (the mirror of the
+    reference's reader, mm/inc/CSR.h:586-623); rows and cols are then one number. return_perm=True adds perm — the index, in the (concatenated)
+    list, of the triple behind every sorted position — and return_info=True the dict of g4s_coo_info. Synchronous. ValueError (before any GPU
+    call) for an unknown dup, flags that are not bools and sizes that are not integers."""
+    dv = _name(DUPLICATES, dup, "dup")
+    for name, v in (("symmetric", symmetric), ("return_perm", return_perm), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    for name, v in (("rows", rows), ("cols", cols)):
+        if v is not None and (isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0):
+            raise ValueError(f"{name} must be a non-negative integer or None, not {v!r}")
+    if symmetric and rows is not None and cols is not None and rows != cols:
+        raise ValueError(f"symmetric=True needs a square matrix, not {rows} x {cols}")
+    _require_gpu()
+    assert row.is_cuda and col.is_cuda and row.dtype == torch.int32 and col.dtype == torch.int32 and row.numel() == col.numel()
+    assert val is None or (val.is_cuda and val.dtype == torch.float64 and val.numel() == row.numel())
+    row, col = row.contiguous(), col.contiguous()
+    if symmetric:
+        off = row != col
+        row, col = torch.cat([row, col[off]]), torch.cat([col, row[off]])
+        val = None if val is None else torch.cat([val, val[off]])
+    val = None if val is None else val.contiguous()
+    nnz, dev = row.numel(), row.device
+    rows, cols = _coo_shape(row, col, rows, cols, symmetric)
+    lib = capi.load()
+    crp = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    perm = torch.empty(nnz, dtype=torch.int32, device=dev)
+    cnnz, info, null = C.c_int64(0), capi.CooInfo(), C.c_void_p(0)
+    capi.check(lib.g4s_csr_from_coo_symbolic(dv, rows, cols, nnz, _ptr_nn(row), _ptr_nn(col), _ptr_nn(crp), _ptr_nn(perm), C.byref(cnnz), capi.DEVICE_POINTERS,
+                                             C.byref(info), _stream()))
+    cci = torch.empty(cnnz.value, dtype=torch.int32, device=dev)
+    cva = None if val is None else torch.empty(cnnz.value, dtype=torch.float64, device=dev)
+    capi.check(lib.g4s_csr_from_coo_numeric(dv, rows, cols, nnz, _ptr_nn(row), _ptr_nn(col), null if val is None else _ptr_nn(val), _ptr_nn(crp), _ptr_nn(perm),
+                                            _ptr_nn(cci), null if val is None else _ptr_nn(cva), capi.DEVICE_POINTERS, _stream()))
+    out = (crp, cci, cva)
+    if return_perm:
+        out += (perm,)
+    if return_info:
+        out += (_coo_info(info),)
+    return out
+
+
+def csr_row_indices(rowptr, nnz):
+    """The row of every stored entry of a CSR (g4s_csr_row_indices): an int32 device tensor of nnz — with colids and values, the matrix as a COO.
+    rowptr: an int32 device tensor, zero-based, non-decreasing and ending at nnz (checked on the device). Synchronous."""
+    if isinstance(nnz, (bool, np.bool_)) or not isinstance(nnz, (int, np.integer)) or nnz < 0:
+        raise ValueError(f"nnz must be a non-negative integer, not {nnz!r}")
+    _require_gpu()
+    assert rowptr.is_cuda and rowptr.dtype == torch.int32 and rowptr.numel() >= 1
+    rowptr = rowptr.contiguous()
+    out = torch.empty(int(nnz), dtype=torch.int32, device=rowptr.device)
+    capi.check(capi.load().g4s_csr_row_indices(rowptr.numel() - 1, int(nnz), _ptr_nn(rowptr), _ptr_nn(out), capi.DEVICE_POINTERS, _stream()))
+    return out
+
+
+def csr_canonical(a, dup="plus"):
+    """The device CSR a with every row sorted by column and repeats merged by `dup` (a name of DUPLICATES; "keep" only sorts), as a new device CSR:
+    g4s_csr_row_indices followed by csr_from_coo. What csr_ewise, spgemm_masked and triangle_count ask of their inputs. Stable: repeats are folded,
+    or kept, in their stored order. ValueError (before any GPU call) for an unknown dup."""
+    _name(DUPLICATES, dup, "dup")
+    rp, ci, va = csr_from_coo(csr_row_indices(a.rowptr, a.nnz), a.colids, a.values, a.rows, a.cols, dup)
+    return CSR(rp, ci, va, a.rows, a.cols)
 
 
 # ------------------------------------------------------------------------------------------------ synthetic inputs

@@ -114,7 +114,7 @@ typedef struct g4s_csr_info {
  * handle must be ordered (same stream, or an event between them); different handles are independent.
  * Threads and streams (what tests/test_concurrency_gpu.py pins, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -138,7 +138,8 @@ g4s_status g4s_csr_create(g4s_csr_t *out, int32_t rows, int32_t cols, int64_t nn
  * in place. A handle that owns its arrays copies them in; a handle that borrows device arrays borrows the new array from here on (device pointer required).
  * The plan's own copy is refreshed on `stream` (asynchronous like g4s_spmv, ordered with the products on that stream): one gather pass on the blocked path
  * (created with G4S_SPMV_UPDATABLE; without the flag the regrouping is repeated — the cost of a create), a refill of the diagonals / the block-major copy,
- * nothing on the row-streaming path. Results afterwards are those of a handle freshly created from the new values, bit for bit. */
+ * nothing on the row-streaming path. Results afterwards are those of a handle freshly created from the new values, bit for bit. A matrix built from
+ * an edge list gets such values from a repeat of g4s_csr_from_coo_numeric with the new val on the perm and crpt it was built with. */
 g4s_status g4s_csr_update_values(g4s_csr_t A, const double *values, unsigned flags, void *stream);
 g4s_status g4s_csr_destroy(g4s_csr_t A);
 g4s_status g4s_csr_get_info(g4s_csr_t A, g4s_csr_info *info);
@@ -695,8 +696,8 @@ g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, const int3
  *     not flag bits.
  *   Input contract: the rows of A and B are strictly ascending with ids in [0, cols); rowptr is non-decreasing from 0. The symbolic call checks all
  *     of it on the device, the row pointers before any of them is used as an index; a violation returns G4S_ERR_INVALID and leaves the outputs
- *     unspecified (the mask rule of g4s_spgemm_masked). Column ids are only ever compared, never used as an index. Unsorted rows are sorted by a
- *     stable double g4s_csr_transpose ((Aᵀ)ᵀ has ascending rows, repeats in their stored order); duplicates must be merged by the caller. A and B
+ *     unspecified (the mask rule of g4s_spgemm_masked). Column ids are only ever compared, never used as an index. Unsorted rows are sorted, and
+ *     duplicates merged, by g4s_csr_row_indices followed by g4s_csr_from_coo_symbolic / _numeric (below; host.csr_canonical, g4s::SortAndMerge). A and B
  *     may be the very same arrays. The numeric call repeats the row-pointer check, not the one on the ids.
  *   Output: rows strictly ascending. A stored position is an entry whatever its value: explicit zeros are kept, and a sum that is 0.0 stays stored.
  *     Every value is one IEEE operation on two doubles or a copy, so the result is the same bits on every run. NaN and the sign of zero under
@@ -758,6 +759,65 @@ g4s_status g4s_csr_select_symbolic(int pred, int64_t k, double thr, int32_t rows
                                    const double *val, int32_t *crpt, int64_t *cnnz, unsigned flags, void *stream);
 g4s_status g4s_csr_select_numeric(int pred, int64_t k, double thr, int32_t rows, int32_t cols, const int32_t *rpt, const int32_t *col,
                                   const double *val, const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream);
+
+/* ---- CSR from an edge list: (row, col[, val]) triples in any order, with repeats, to a CSR with ascending rows on the device — the role of the
+ * reference's CSR(graph&) (mm/inc/CSR.h:255-329: each source's edges sorted, duplicates summed), of CSC::MergeDuplicates (mm/inc/CSC.h:297-342) and of
+ * the sort in CSR::construct (mm/inc/CSR.h:640-668) — and its inverse, g4s_csr_row_indices. Two calls with caller-allocated outputs, the model of
+ * g4s_csr_ewise_symbolic / _numeric: the symbolic call sorts and writes crpt, perm and *cnnz, the caller allocates ccol / cval of *cnnz entries, the
+ * numeric call fills them. Nothing is kept inside the library between the calls (nothing process-wide: different host threads may call at the same
+ * time).
+ *   Order of the output: perm[p] is the input index of the p-th triple in (row, col, input index) order. The sort is stable, so perm is a function of
+ *     the input alone: perm == lexsort((arange(nnz), col, row)), element for element.
+ *   dup: G4S_DUP_KEEP — every triple stays an entry: *cnnz == nnz, ccol[p] = col[perm[p]], cval[p] = val[perm[p]] (rows ascending, repeats in input
+ *     order). Otherwise a G4S_COMBINE_* value (PLUS, TIMES, MIN, MAX, FIRST: the earliest triple, SECOND: the latest): one entry per distinct
+ *     position, rows strictly ascending, its value the combiner folded from left to right over the run in input order, acc = combine(acc, next).
+ *     Every result is the same bits on every run. NaN and the sign of zero under MIN / MAX are outside the contract, as above. (The reference's
+ *     constructor sorts a source's edges by (col, value) and so adds repeats in ascending value; the two agree bit for bit wherever the sums are
+ *     exact, as for the integer weights of mm/inc/graph.h.)
+ *   Bounds and sizes: ids must lie in [0, rows) × [0, cols); an id outside its range returns G4S_ERR_INVALID from the symbolic call and is never
+ *     used as an index before it has been checked. nnz > INT32_MAX returns G4S_ERR_OVERFLOW before any HIP call. rows, cols or nnz of 0 are valid.
+ *   Pattern-only: val == cval == NULL writes ccol only. Any other mix of NULL value arrays is G4S_ERR_INVALID.
+ *   The numeric call trusts nothing in perm or crpt: a perm element outside [0, nnz), an id outside its range, a sequence whose keys decrease (or whose
+ *     input indices do not increase inside a run of equal keys) and a crpt[rows] that is not the count the call arrives at itself return
+ *     G4S_ERR_INVALID, and nothing is read or written out of bounds in any of these cases (ccol / cval hold crpt[rows] entries; they are unspecified
+ *     after a refusal). It may be called again with new val on the same perm and crpt: the value refresh of a matrix whose pattern is fixed — what
+ *     g4s_csr_update_values then takes.
+ *   flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS for all arrays (cnnz and info are always host memory); any other bit returns G4S_ERR_INVALID.
+ *     Checked before any HIP call: flag bits and dup, negative sizes, the nnz limit, NULL crpt, perm or cnnz (numeric: crpt, perm), NULL row or col
+ *     (numeric: or ccol) with nnz > 0, the NULL rule of the value arrays and — with host pointers — an output that overlaps an input or another output.
+ *   Synchronous on `stream`. On a capturing stream all three calls return G4S_ERR_INVALID and enqueue nothing. The symbolic call waits for the device
+ *     at most twice (the verdict on the ids and on the order; the counts), the numeric call once, with device and with host pointers alike (the
+ *     copies back to host arrays are enqueued in front of the last wait); info.host_waits reports the count.
+ *   Scratch comes from the library's caching allocator and is released before return: 20 bytes per triple in the symbolic call (two 64-bit keys and
+ *     one payload partner; the head flags and their scan reuse the key partner) plus 2 KiB per tile for the digit tables, 16 bytes per triple in the
+ *     numeric call, plus device copies of the arrays with host pointers.
+ *   How (g4s_coo_info): the key row·2^col_bits + col over the significant bits of (rows − 1, cols − 1) only, sorted by a stable radix
+ *     sort with digit_bits = 8 in sort_passes = ceil((row_bits + col_bits) / 8) passes, one workgroup per tile of tile_entries consecutive triples.
+ *     An input already in (row, col) order skips the sort (presorted = 1, perm the identity). Where it loses: a run of L duplicates is folded by one
+ *     lane in L sequential operations.
+ * g4s_csr_row_indices writes the row of every stored entry — the array a CSR lacks to be a COO — with the row-pointer checks of g4s_csr_transpose
+ * (zero-based, non-decreasing, ending at nnz: G4S_ERR_INVALID before anything is written) read back first. Two waits.
+ * A CSR with unsorted rows or repeats becomes canonical — what g4s_csr_ewise_*, g4s_spgemm_masked and g4s_triangle_count ask for — by
+ * g4s_csr_row_indices followed by the two calls here (host.csr_canonical, g4s::SortAndMerge). */
+#define G4S_DUP_KEEP (-1)   /* every triple stays an entry (CSR::construct, CSR.h:640-668); otherwise a G4S_COMBINE_* */
+typedef struct g4s_coo_info {
+    int64_t nnz_in, nnz_out; /* triples given, entries of the result (what *cnnz receives)                       */
+    int64_t longest_run;     /* the most triples on one position (1 without repeats, 0 for an empty list)        */
+    int32_t row_bits;        /* significant bits of rows − 1                                                     */
+    int32_t col_bits;        /* significant bits of cols − 1                                                     */
+    int32_t digit_bits;      /* bits per radix pass (a constant of the build)                                    */
+    int32_t sort_passes;     /* ceil((row_bits + col_bits) / digit_bits): what a sort costs, also when skipped   */
+    int32_t tile_entries;    /* triples one workgroup ranks per pass (a constant of the build)                   */
+    int32_t presorted;       /* 1: the input was in (row, col) order and no pass ran                             */
+    int32_t host_waits;      /* times the call waited for the device                                             */
+    int32_t reserved[3];
+} g4s_coo_info;              /* 64 bytes */
+g4s_status g4s_csr_from_coo_symbolic(int dup, int32_t rows, int32_t cols, int64_t nnz, const int32_t *row, const int32_t *col,
+                                     int32_t *crpt /* rows+1 */, int32_t *perm /* nnz */, int64_t *cnnz, unsigned flags, g4s_coo_info *info /* may be NULL */,
+                                     void *stream);
+g4s_status g4s_csr_from_coo_numeric(int dup, int32_t rows, int32_t cols, int64_t nnz, const int32_t *row, const int32_t *col, const double *val,
+                                    const int32_t *crpt, const int32_t *perm, int32_t *ccol, double *cval, unsigned flags, void *stream);
+g4s_status g4s_csr_row_indices(int32_t rows, int64_t nnz, const int32_t *rowptr, int32_t *row_out /* nnz */, unsigned flags, void *stream);
 
 /* ------------------------------------------------------------------ B3: graph gather/apply */
 

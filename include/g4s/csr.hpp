@@ -9,9 +9,11 @@
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 //   EWiseAdd / EWiseMult / EWiseDifference(a,b,c), Select(a,c,pred,k,thr), Symmetrise(a,c)   A ∪ B, A ∩ B, A ∖ B, a filter, A ∪ Aᵀ (g4s_csr_ewise_*, g4s_csr_select_*)
+//   graph, FromGraph(g,c,dup), FromCOO(…), ToCOO(a,row_out), SortAndMerge(a,c,dup)   an edge list to a CSR with repeats merged and back (CSR(graph&), mm/inc/CSR.h:255-329)
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
 #pragma once
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -322,6 +324,78 @@ void Symmetrise(const CSR<IT, NT> &a, CSR<IT, NT> &c, int combine = G4S_COMBINE_
     CSR<IT, NT> u;
     EWiseAdd(a, at, u, combine);
     Select(u, c, G4S_SELECT_OFFDIAG);
+}
+
+// A CSR from an edge list on the device (g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, host arrays; include/g4s.h has the contract). c's old
+// arrays are released first; c must not be a.
+//   graph                          the reference's edge list (mm/inc/graph.h): m edges e from start[e] to end[e] with weight w[e], n vertices; borrowed arrays
+//   FromGraph(g, c, dup)           the n × n matrix of g, what CSR(graph&) builds (mm/inc/CSR.h:255-329); throws on an id that does not fit int32
+//   FromCOO(rows, cols, nnz, row, col, val, c, dup)   the same from int32 triples; val may be NULL (values 1.0)
+//   ToCOO(a, row_out)              the row of every stored entry of a (a.nnz values): with a.colids and a.values, a as a COO
+//   SortAndMerge(a, c, dup)        a with sorted rows and merged repeats: ToCOO followed by FromCOO (CSC::MergeDuplicates, mm/inc/CSC.h:297-342)
+// dup is G4S_DUP_KEEP or a G4S_COMBINE_* value (default PLUS). Summation order: the reference's constructor sorts each source's edges by (col, value)
+// before it sums, so it adds repeats in ascending value; this library adds them in input order. The two agree bit for bit wherever the sums are exact,
+// which covers the integer weights graph.h describes.
+struct graph {
+    long m, n;
+    long *start, *end;
+    double *w;
+};
+template <typename IT, typename NT>
+void FromCOO(IT rows, IT cols, int64_t nnz, const IT *row, const IT *col, const NT *val, CSR<IT, NT> &c, int dup = G4S_COMBINE_PLUS, g4s_coo_info *info = nullptr)
+{
+    static_assert(std::is_same<IT, int32_t>::value && std::is_same<NT, double>::value, "the device works on CSR<int32_t, double>");
+    c.make_empty();
+    if (rows < 0 || cols < 0 || nnz < 0) throw std::runtime_error("FromCOO: negative size");
+    c.rowptr = (IT *)g4s_malloc(sizeof(IT) * ((size_t)rows + 1));
+    IT *perm = (IT *)g4s_malloc(sizeof(IT) * ((size_t)nnz + 1));
+    if (!c.rowptr || !perm) { g4s_free(perm); c.make_empty(); throw std::runtime_error("FromCOO: host allocation failed"); }
+    int64_t cnnz = 0;
+    g4s_status st = g4s_csr_from_coo_symbolic(dup, rows, cols, nnz, row, col, c.rowptr, perm, &cnnz, G4S_HOST_POINTERS, info, nullptr);
+    if (st == G4S_OK) {
+        try { detail::adopt(c, rows, cols, cnnz, "FromCOO"); } catch (...) { g4s_free(perm); throw; }
+        st = g4s_csr_from_coo_numeric(dup, rows, cols, nnz, row, col, val, c.rowptr, perm, c.colids, val ? c.values : nullptr, G4S_HOST_POINTERS, nullptr);
+        if (st == G4S_OK && !val) for (int64_t k = 0; k < cnnz; ++k) c.values[k] = 1.0;
+    }
+    g4s_free(perm);
+    if (st != G4S_OK) { c.make_empty(); check(st, "FromCOO"); }
+}
+template <typename IT, typename NT>
+void FromGraph(const graph &g, CSR<IT, NT> &c, int dup = G4S_COMBINE_PLUS, g4s_coo_info *info = nullptr)
+{
+    static_assert(std::is_same<IT, int32_t>::value && std::is_same<NT, double>::value, "the device works on CSR<int32_t, double>");
+    if (g.m < 0 || g.n < 0 || g.n > INT32_MAX) throw std::runtime_error("FromGraph: the vertex count does not fit int32");
+    IT *row = (IT *)g4s_malloc(sizeof(IT) * ((size_t)g.m + 1)), *col = (IT *)g4s_malloc(sizeof(IT) * ((size_t)g.m + 1));
+    auto release = [&] { g4s_free(row); g4s_free(col); };
+    if (!row || !col) { release(); throw std::runtime_error("FromGraph: host allocation failed"); }
+    for (long e = 0; e < g.m; ++e) {
+        if (g.start[e] < INT32_MIN || g.start[e] > INT32_MAX || g.end[e] < INT32_MIN || g.end[e] > INT32_MAX) {
+            release();
+            throw std::runtime_error("FromGraph: a vertex id does not fit int32");
+        }
+        row[e] = (IT)g.start[e];
+        col[e] = (IT)g.end[e];
+    }
+    try { FromCOO((IT)g.n, (IT)g.n, (int64_t)g.m, row, col, g.w, c, dup, info); } catch (...) { release(); throw; }
+    release();
+}
+template <typename IT, typename NT>
+void ToCOO(const CSR<IT, NT> &a, IT *row_out)
+{
+    static_assert(std::is_same<IT, int32_t>::value, "the device works on CSR<int32_t, double>");
+    const IT zero = 0;
+    check(g4s_csr_row_indices(a.rowptr ? a.rows : 0, a.nnz, a.rowptr ? a.rowptr : &zero, row_out, G4S_HOST_POINTERS, nullptr), "ToCOO");
+}
+template <typename IT, typename NT>
+void SortAndMerge(const CSR<IT, NT> &a, CSR<IT, NT> &c, int dup = G4S_COMBINE_PLUS, g4s_coo_info *info = nullptr)
+{
+    IT *row = (IT *)g4s_malloc(sizeof(IT) * ((size_t)a.nnz + 1));
+    if (!row) throw std::runtime_error("SortAndMerge: host allocation failed");
+    try {
+        ToCOO(a, row);
+        FromCOO(a.rows, a.cols, (int64_t)a.nnz, row, a.colids, a.values, c, dup, info);
+    } catch (...) { g4s_free(row); throw; }
+    g4s_free(row);
 }
 
 // Shortest-path distances (dist: a.rows values, +inf where unreached) and BFS levels (level: a.rows values, −1 where unreached) from the nearest of
