@@ -176,7 +176,8 @@ g4s_status g4s_spmv_csr_i32_f64(int32_t rows, int32_t cols, const int32_t *rowpt
  *   One product in flight per handle: g4s_spmm and g4s_spmv share the concurrency rule of g4s_csr_create.
  *   New values (g4s_csr_update_values) are used by the next g4s_spmm, owned and borrowed handles alike.
  *   k == 1 with unit-stride X and Y (column-major, or ld = 1) is g4s_spmv on the streaming, diagonal and block-row paths; on the blocked path it
- *     stays on the SpMM kernels, which are reproducible where the blocked SpMV is not. */
+ *     stays on the SpMM kernels, which are reproducible where the blocked SpMV is not. Such a call sums as g4s_spmv does: on the streaming path
+ *     only the rows that one lane sums are bit-identical to the oracle; any other ld keeps the rule above. */
 #define G4S_SPMM_COL_MAJOR 256u /* X and Y column-major: element (i, j) at [i + j·ld]; default row-major: [i·ld + j] */
 
 /* Asynchronous on `stream` like g4s_spmv; X_dev and Y_dev are device pointers. Workspace: the SpMM kernels run on the handle's row-streaming

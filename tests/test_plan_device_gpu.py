@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import stream_cases
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
 
@@ -36,10 +38,13 @@ def test_device_plan_equals_host_plan(oracle, monkeypatch, kind):
     H, D, ih, idv = _two_plans(monkeypatch, A, host, capi, capi.SPMV_STREAM)
     assert ih["spmv_path"] == 0 and idv["spmv_path"] == 0
     assert ih["long_rows"] == idv["long_rows"] and ih["long_chunks"] == idv["long_chunks"]
-    assert idv["stream_blocks"] >= ih["stream_blocks"]              # forced cuts every 4096 rows add blocks, never remove any
+    rp, ci, va = A.to_host()
+    mh, md = stream_cases.host_blocks(rp), stream_cases.device_blocks(rp)   # forced cuts every 4096 rows add blocks, never remove any: the model says how many
+    assert (ih["stream_blocks"], ih["long_rows"], ih["long_chunks"]) == (len(mh.blocks), len(mh.long_rows), len(mh.chunks))
+    assert (idv["stream_blocks"], idv["long_rows"], idv["long_chunks"]) == (len(md.blocks), len(md.long_rows), len(md.chunks))
+    assert len(md.blocks) >= len(mh.blocks)
     x = host.synth_vector(5, A.cols)
     yh, yd = H.spmv(x), D.spmv(x)
-    rp, ci, va = A.to_host()
     xh = x.cpu().numpy()
     yo = oracle.spmv_mt_y(rp, ci, va, xh)                          # the oracle's fp64 left-to-right sums
     _, asum = oracle.spmv_ld(rp, ci, va, xh)
