@@ -84,6 +84,13 @@ class CooInfo(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class ExtractInfo(C.Structure):
+    """g4s_extract_info: what a g4s_csr_extract_symbolic / _numeric call found and did (counts, the kind of J, which class sorted how many rows)."""
+    _fields_ = [("nnz_a", C.c_int64), ("nnz_rows", C.c_int64), ("nnz_c", C.c_int64), ("units", C.c_int64), ("unit_entries", C.c_int32),
+                ("j_kind", C.c_int32), ("rows_in_order", C.c_int32), ("rows_sorted_wave", C.c_int32), ("rows_sorted_lds", C.c_int32),
+                ("rows_sorted_radix", C.c_int32), ("lds_sort_max", C.c_int32), ("host_waits", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class DistInfo(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("local_rows", C.c_int32), ("n_ref", C.c_int32), ("nnz_own", C.c_int64), ("nnz_rem", C.c_int64),
                 ("send_bytes", C.c_int64), ("recv_bytes", C.c_int64), ("own_path", C.c_int32), ("rem_path", C.c_int32), ("connected", C.c_int32),
@@ -215,6 +222,8 @@ SIGNATURES = {
     "g4s_csr_from_coo_symbolic": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, i64p, C.c_uint, C.POINTER(CooInfo), vp]),
     "g4s_csr_from_coo_numeric": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
     "g4s_csr_row_indices": (C.c_int, [C.c_int32, C.c_int64, vp, vp, C.c_uint, vp]),
+    "g4s_csr_extract_symbolic": (C.c_int, [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(ExtractInfo), vp]),
+    "g4s_csr_extract_numeric": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(ExtractInfo), vp]),
     "g4s_register_pattern":(C.c_int, [FUN_GATHER, FUN_APPLY, C.POINTER(PatternDesc)]),
     "g4s_unregister_pattern": (C.c_int, [FUN_GATHER, FUN_APPLY]),
     "g4s_set_host_callback_policy": (C.c_int, [C.c_int32]),

@@ -9,6 +9,8 @@ Names and argument meaning follow the reference so that tests read like tests of
   csr_transpose  — Aᵀ as a CSR (the CSC form of A; mm/inc/CSR.h:171-230, mm/inc/convert.h), stable: entries of a column keep their order
   csr_from_coo   — a CSR from an edge list in any order, repeats merged by a duplicate policy (CSR(graph&), mm/inc/CSR.h:255-329); csr_row_indices /
                    CSR.to_coo the way back, csr_canonical a CSR with sorted rows and merged repeats
+  csr_extract    — C = A[I, J] for id lists in any order, with repeats (g4s_csr_extract_*; the block constructor mm/inc/CSR.h:691-733 and CSC::SpRef,
+                   mm/inc/CSC.h:513-690); csr_permute, csr_induced_subgraph and csr_submatrix are compositions of it
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
@@ -243,6 +245,22 @@ class CSR:
     def canonical(self, dup="plus"):
         """This matrix with sorted rows and merged repeats as a new device CSR — csr_canonical(self, dup)."""
         return csr_canonical(self, dup)
+
+    def extract(self, I=None, J=None, pattern_only=False, return_src=False, return_info=False):
+        """self[I, J] as a new device CSR — csr_extract(self, …)."""
+        return csr_extract(self, I, J, pattern_only, return_src, return_info)
+
+    def permute(self, perm):
+        """self[perm, perm] of this square matrix — csr_permute(self, perm)."""
+        return csr_permute(self, perm)
+
+    def induced_subgraph(self, vertices):
+        """(self[ids, ids], ids) for an id tensor or a bool mask — csr_induced_subgraph(self, vertices)."""
+        return csr_induced_subgraph(self, vertices)
+
+    def submatrix(self, M, N, M_start=0, N_start=0):
+        """The M × N block at (M_start, N_start) — csr_submatrix(self, …)."""
+        return csr_submatrix(self, M, N, M_start, N_start)
 
     def spmm(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha·A·X + beta·Y for a 2-D float64 device tensor X of cols × k, on the current torch stream (asynchronous). Row-major when
@@ -808,6 +826,89 @@ def csr_canonical(a, dup="plus"):
     _name(DUPLICATES, dup, "dup")
     rp, ci, va = csr_from_coo(csr_row_indices(a.rowptr, a.nnz), a.colids, a.values, a.rows, a.cols, dup)
     return CSR(rp, ci, va, a.rows, a.cols)
+
+
+# ------------------------------------------------------------------------------------------------ extract: A[I, J]
+def _extract_info(info):
+    return {n: getattr(info, n) for n, _ in capi.ExtractInfo._fields_ if n != "reserved"}
+
+
+def _id_list(t, name):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda:
+        raise ValueError(f"{name} must be a one-dimensional int32 device tensor or None")
+    return t.contiguous()
+
+
+def csr_extract(a, I=None, J=None, pattern_only=False, return_src=False, return_info=False):
+    """C = A[I, J] as a new device CSR of len(I) × len(J): C(p, q) is stored exactly where A(I[p], J[q]) is (g4s_csr_extract_symbolic /
+    g4s_csr_extract_numeric) — MATLAB's A(I, J). I and J are int32 device tensors of ids in any order, with repeats, or None for every row / every
+    column in order. Rows of a may be in any order and may repeat a column; every output row is ordered by (q, stored position in a's row), so a
+    canonical a gives strictly ascending rows. pattern_only=True reads no values: the result's values are all 1.0. return_src=True adds src, the
+    index into a.colids / a.values behind every entry of C (C.values == a.values[src], bit for bit); return_info=True the dict of g4s_extract_info.
+    Synchronous. ValueError (before any GPU call) for flags that are not bools and for an I or J that is not a one-dimensional int32 device tensor."""
+    for name, v in (("pattern_only", pattern_only), ("return_src", return_src), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    I, J = _id_list(I, "I"), _id_list(J, "J")
+    _require_gpu()
+    ni, nj = (a.rows if I is None else I.numel()), (a.cols if J is None else J.numel())
+    lib, dev, null = capi.load(), a.rowptr.device, C.c_void_p(0)
+    pi, pj = (null if I is None else _ptr_nn(I)), (null if J is None else _ptr_nn(J))
+    crp = torch.empty(ni + 1, dtype=torch.int32, device=dev)
+    cnnz, info = C.c_int64(0), capi.ExtractInfo()
+    capi.check(lib.g4s_csr_extract_symbolic(a.rows, a.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), ni, pi, nj, pj, _ptr_nn(crp), C.byref(cnnz), capi.DEVICE_POINTERS,
+                                            C.byref(info), _stream()))
+    cci = torch.empty(cnnz.value, dtype=torch.int32, device=dev)
+    cva = torch.ones(cnnz.value, dtype=torch.float64, device=dev) if pattern_only else torch.empty(cnnz.value, dtype=torch.float64, device=dev)
+    src = torch.empty(cnnz.value, dtype=torch.int32, device=dev) if return_src else None
+    capi.check(lib.g4s_csr_extract_numeric(a.rows, a.cols, _ptr_nn(a.rowptr), _ptr_nn(a.colids), null if pattern_only else _ptr_nn(a.values), ni, pi, nj, pj,
+                                           _ptr_nn(crp), _ptr_nn(cci), null if pattern_only else _ptr_nn(cva), null if src is None else _ptr_nn(src),
+                                           capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    out = (CSR(crp, cci, cva, ni, nj),)
+    if return_src:
+        out += (src,)
+    if return_info:
+        out += (_extract_info(info),)
+    return out[0] if len(out) == 1 else out
+
+
+def csr_permute(a, perm):
+    """A[perm, perm] of a square device CSR: vertex perm[p] of a becomes vertex p — csr_extract(a, perm, perm). perm: an int32 device tensor of
+    a.rows ids (a permutation relabels; the call itself accepts any ids). ValueError (before any GPU call) for a matrix that is not square and for
+    a perm whose length is not a.rows."""
+    if a.rows != a.cols:
+        raise ValueError(f"permute needs a square matrix, not {a.rows} x {a.cols}")
+    if perm is None or not hasattr(perm, "numel") or perm.numel() != a.rows:
+        raise ValueError(f"perm must hold {a.rows} ids, one per vertex")
+    return csr_extract(a, perm, perm)
+
+
+def csr_induced_subgraph(a, vertices):
+    """(A[ids, ids], ids): the subgraph of the square device CSR a induced by `vertices` — an int32 device tensor of ids, used in the order given,
+    or a bool device mask of a.rows (its True positions in ascending order, through torch.nonzero). Vertex ids[p] of a is vertex p of the result.
+    ValueError (before any GPU call) for a matrix that is not square and for a mask of the wrong length."""
+    if a.rows != a.cols:
+        raise ValueError(f"an induced subgraph needs a square matrix, not {a.rows} x {a.cols}")
+    if getattr(vertices, "dtype", None) == torch.bool:
+        if vertices.numel() != a.rows:
+            raise ValueError(f"a vertex mask must hold {a.rows} flags, not {vertices.numel()}")
+        vertices = torch.nonzero(vertices.reshape(-1)).reshape(-1).to(torch.int32)
+    return csr_extract(a, vertices, vertices), vertices
+
+
+def csr_submatrix(a, M, N, M_start=0, N_start=0):
+    """The M × N block of a that starts at (M_start, N_start) — the reference's CSR(const CSR&, M_, N_, M_start, N_start) (mm/inc/CSR.h:691-733),
+    argument order included — through csr_extract with torch.arange lists. ValueError (before any GPU call) for sizes that are not non-negative
+    integers and for a block that leaves the matrix."""
+    for name, v in (("M", M), ("N", N), ("M_start", M_start), ("N_start", N_start)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"{name} must be a non-negative integer, not {v!r}")
+    if M_start + M > a.rows or N_start + N > a.cols:
+        raise ValueError(f"the block [{M_start}, {M_start + M}) x [{N_start}, {N_start + N}) leaves the {a.rows} x {a.cols} matrix")
+    dev = a.rowptr.device
+    return csr_extract(a, torch.arange(M_start, M_start + M, dtype=torch.int32, device=dev), torch.arange(N_start, N_start + N, dtype=torch.int32, device=dev))
 
 
 # ------------------------------------------------------------------------------------------------ synthetic inputs

@@ -112,9 +112,9 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
- * Threads and streams (what tests/test_concurrency_gpu.py pins, every result compared bit for bit):
+ * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py —, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -819,6 +819,73 @@ g4s_status g4s_csr_from_coo_symbolic(int dup, int32_t rows, int32_t cols, int64_
 g4s_status g4s_csr_from_coo_numeric(int dup, int32_t rows, int32_t cols, int64_t nnz, const int32_t *row, const int32_t *col, const double *val,
                                     const int32_t *crpt, const int32_t *perm, int32_t *ccol, double *cval, unsigned flags, void *stream);
 g4s_status g4s_csr_row_indices(int32_t rows, int64_t nnz, const int32_t *rowptr, int32_t *row_out /* nnz */, unsigned flags, void *stream);
+
+/* ---- Extract: C = A[I, J], the ni × nj matrix with C(p, q) = A(I[p], J[q]) — GraphBLAS extract, MATLAB's A(I, J): induced subgraphs (A[S, S]),
+ * relabellings (A[p, p]), leading and rectangular sub-matrices. The reference has the contiguous block as a constructor,
+ * CSR(const CSR&, M_, N_, M_start, N_start) (mm/inc/CSR.h:691-733, used by mm/src/mkl_spgemm.cpp:50-57), and CSC::SpRef / SpRef2
+ * (mm/inc/CSC.h:513-690), which want sorted lists and keep the original row ids; this call implements the MATLAB meaning SpRef's own comment
+ * states. Two calls with caller-allocated outputs, the model of g4s_csr_ewise_* and g4s_csr_from_coo_*: the symbolic call writes crpt (ni + 1) and
+ * *cnnz, the caller allocates ccol (cval, src) of *cnnz entries, the numeric call fills them. Nothing is kept inside the library between the calls
+ * (nothing process-wide: different host threads may call at the same time).
+ *   Result: C(p, q) is stored exactly where A(I[p], J[q]) is. I and J may be in any order and may repeat ids. I == NULL means every row in order
+ *     and ni must equal rows; J == NULL means every column and nj must equal cols. An id outside [0, rows) or [0, cols) returns G4S_ERR_INVALID
+ *     from the symbolic call and is never used as an index before it has been checked; the row pointers are checked the same way (zero-based,
+ *     non-decreasing), as in g4s_csr_ewise_*, and so is every column id of A before it indexes the column map.
+ *   Input rows: a row of A may be in any order and may repeat a column (each stored entry is extracted on its own).
+ *   Output rows: ordered by (q, stored position of the source entry in A's row). The output is a function of the input alone and the same bits on
+ *     every run. A canonical A (rows strictly ascending) gives strictly ascending output rows, also where J repeats ids.
+ *   src (optional, *cnnz int32; NULL: not wanted): the index into col / val of the entry behind each output entry — cval[e] == val[src[e]] bit
+ *     for bit and col[src[e]] == J[ccol[e]]. It is the perm of g4s_csr_from_coo_*: a caller refreshes the values of a fixed extraction, or carries a
+ *     second per-edge attribute, with one gather.
+ *   Pattern-only: val == cval == NULL writes ccol (and src) only. Any other mix of NULL value arrays is G4S_ERR_INVALID.
+ *   flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS for all arrays (cnnz and info are always host memory); any other bit returns G4S_ERR_INVALID.
+ *     Checked before any HIP call (G4S_ERR_INVALID): flag bits, negative sizes, a NULL rpt, crpt or cnnz, a NULL col unless rows == 0 (numeric:
+ *     a NULL ccol unless ni or nj is 0), ni != rows with I == NULL and nj != cols with J == NULL, the NULL rule of the value arrays and — with
+ *     host pointers — an output that overlaps an input or another output. With device pointers the numeric call makes the overlap check after
+ *     its first wait, when the lengths are known, and before it writes anything.
+ *   Sizes: cnnz is summed in 64 bits; more than INT32_MAX entries return G4S_ERR_OVERFLOW from the symbolic call (crpt unspecified, *cnnz the
+ *     exact count), and so do more than 2^31 work units. ni, nj, rows, cols or an entry count of 0 are valid.
+ *   The numeric call trusts nothing: it works the counts out again from the inputs and refuses a crpt any of whose ni + 1 elements is not what
+ *     it arrives at itself (G4S_ERR_INVALID, nothing written out of bounds, the outputs unspecified).
+ *   Synchronous on `stream`; on a capturing stream both calls return G4S_ERR_INVALID and enqueue nothing. Every small device-to-host read goes
+ *     through the pinned read ledger. Waits (info.host_waits): the symbolic call one. The numeric call two when the fill leaves every row in
+ *     order (the sizes; the end) — always so for a canonical A with a non-decreasing or NULL J — three when rows are sorted, and where rows of
+ *     more than lds_sort_max entries are sorted those of g4s_csr_from_coo_symbolic (at most two) and one more. Host pointers add none.
+ *   Scratch comes from the library's caching allocator and is released before return: 12·ni + 8·cols bytes in the symbolic call; in the numeric
+ *     call 20·ni + 8·cols, 8 per unit, 4·nj + 4·cols more for a J that decreases somewhere, 4·cnnz when src is NULL, and 16 bytes per entry of the
+ *     rows that take the radix path plus the scratch of g4s_csr_from_coo_symbolic; device copies of the arrays with host pointers.
+ *   How (g4s_extract_info): a unit is unit_entries = 64 stored entries of a source row, taken by 16 lanes, so short rows share a
+ *     wave and a hub row spreads over the grid. mult[c] = #{q : J[q] == c} and its scan turn a column into its run of q's (j_kind 1: a range;
+ *     j_kind 2: a list filled through cursors; j_kind 0: q = c, no map); a unit's count is Σ mult, a scan gives its first slot, the fill writes
+ *     (q, src) runs. Rows the fill left non-decreasing in q are done (rows_in_order). The others are sorted by the distinct 64-bit keys
+ *     (q << 32 | position): up to 64 entries in one wave (rows_sorted_wave), up to lds_sort_max in one workgroup's LDS (rows_sorted_lds), longer
+ *     ones through the stable radix sort of g4s_csr_from_coo_symbolic (rows_sorted_radix). With j_kind 2 and ids repeated in J the order inside a
+ *     column's list depends on arrival, so WHICH rows count as in order may differ between runs; the result does not.
+ *   Where it loses: a J that names one column very many times makes one lane write that run sequentially; rows much shorter than 64 entries
+ *     leave most of a unit's lanes idle; the numeric call reads the column ids twice and always writes src (into scratch when not asked for),
+ *     the values following in a gather of their own; a relabelling of a graph with many rows over lds_sort_max entries pays the radix sort's
+ *     passes over those rows. */
+typedef struct g4s_extract_info {
+    int64_t nnz_a;           /* stored entries of A                                                              */
+    int64_t nnz_rows;        /* entries of A in the selected rows, Σ over p of the length of row I[p]            */
+    int64_t nnz_c;           /* entries of the result (what *cnnz receives)                                      */
+    int64_t units;           /* work units: Σ over p of ceil(length of row I[p] / unit_entries)                  */
+    int32_t unit_entries;    /* stored entries per unit (a constant of the build)                                */
+    int32_t j_kind;          /* 0: J == NULL (every column), 1: J never decreases, 2: otherwise                  */
+    int32_t rows_in_order;   /* numeric: output rows the fill left in order (empty ones included): not sorted    */
+    int32_t rows_sorted_wave;  /* numeric: rows of at most 64 entries sorted by one wave                         */
+    int32_t rows_sorted_lds;   /* numeric: rows of at most lds_sort_max entries sorted in one workgroup's LDS    */
+    int32_t rows_sorted_radix; /* numeric: longer rows, sorted by the radix sort of g4s_csr_from_coo_symbolic    */
+    int32_t lds_sort_max;    /* the longest row the LDS class takes (a constant of the build)                    */
+    int32_t host_waits;      /* times the call waited for the device                                             */
+    int32_t reserved[4];
+} g4s_extract_info;          /* 80 bytes */
+g4s_status g4s_csr_extract_symbolic(int32_t rows, int32_t cols, const int32_t *rpt, const int32_t *col, int32_t ni, const int32_t *I, int32_t nj,
+                                    const int32_t *J, int32_t *crpt /* ni+1 */, int64_t *cnnz, unsigned flags, g4s_extract_info *info /* may be NULL */,
+                                    void *stream);
+g4s_status g4s_csr_extract_numeric(int32_t rows, int32_t cols, const int32_t *rpt, const int32_t *col, const double *val, int32_t ni, const int32_t *I,
+                                   int32_t nj, const int32_t *J, const int32_t *crpt, int32_t *ccol, double *cval, int32_t *src /* may be NULL */,
+                                   unsigned flags, g4s_extract_info *info /* may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------ B3: graph gather/apply */
 

@@ -10,6 +10,7 @@
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 //   EWiseAdd / EWiseMult / EWiseDifference(a,b,c), Select(a,c,pred,k,thr), Symmetrise(a,c)   A ∪ B, A ∩ B, A ∖ B, a filter, A ∪ Aᵀ (g4s_csr_ewise_*, g4s_csr_select_*)
 //   graph, FromGraph(g,c,dup), FromCOO(…), ToCOO(a,row_out), SortAndMerge(a,c,dup)   an edge list to a CSR with repeats merged and back (CSR(graph&), mm/inc/CSR.h:255-329)
+//   Extract(a,ri,ci), SpRef / SpRef2, Permute(a,perm), SubMatrix(a,M_,N_,M_start,N_start)   A[I, J] for id lists in any order, with repeats (CSC::SpRef, mm/inc/CSC.h:513-690; the block constructor, mm/inc/CSR.h:691-733)
 // Only IT = int32_t, NT = double exist in the reference (mm/inc/define.h:14-15) and on the device. Arrays handed back by the
 // library are allocated with g4s_malloc and released with g4s_free (the my_malloc/my_free pairing of mm/inc/utility.h:126-153).
 #pragma once
@@ -21,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <vector>
 #include "../g4s.h"
 
 namespace g4s {
@@ -396,6 +398,77 @@ void SortAndMerge(const CSR<IT, NT> &a, CSR<IT, NT> &c, int dup = G4S_COMBINE_PL
         FromCOO(a.rows, a.cols, (int64_t)a.nnz, row, a.colids, a.values, c, dup, info);
     } catch (...) { g4s_free(row); throw; }
     g4s_free(row);
+}
+
+// C = A[I, J] on the device (g4s_csr_extract_symbolic / _numeric, host arrays; include/g4s.h has the contract): C(p, q) is stored exactly where
+// A(ri[p], ci[q]) is — MATLAB's A(I, J). The lists may be in any order and may repeat ids; every row of the result is ordered by (q, stored position).
+//   Extract(a, ri, ci, src, info)  the ri.size() × ci.size() result; src (optional) receives the index into a.colids / a.values behind every entry
+//   SpRef(a, ri, ci), SpRef2(a, ri, rilen, ci, cilen)   the reference's spelling (CSC::SpRef / SpRef2, mm/inc/CSC.h:513-690). The reference wants sorted lists
+//                                  and keeps the original row ids in the result; this is the MATLAB meaning its comment states: rows are renumbered 0 … rilen − 1
+//   Permute(a, perm)               a[perm, perm] of a square matrix: vertex perm[p] becomes vertex p
+//   SubMatrix(a, M_, N_, M_start, N_start)   the M_ × N_ block at (M_start, N_start): CSR(const CSR&, M_, N_, M_start, N_start), mm/inc/CSR.h:691-733
+// (leading_submatrix of g4s/mtx.hpp stays the host loop it is.)
+namespace detail {
+// src_vec (or NULL) is sized between the two calls, when the entry count is known; src_raw (or NULL) is the caller's array of that many ids.
+template <typename IT, typename NT>
+CSR<IT, NT> extract(const CSR<IT, NT> &a, const IT *ri, IT rilen, const IT *ci, IT cilen, IT *src_raw, std::vector<IT> *src_vec, g4s_extract_info *info)
+{
+    static_assert(std::is_same<IT, int32_t>::value && std::is_same<NT, double>::value, "the device works on CSR<int32_t, double>");
+    if (rilen < 0 || cilen < 0) throw std::runtime_error("Extract: negative list length");
+    CSR<IT, NT> c;
+    const IT zero = 0, none = 0;                           // an empty CSR holds no arrays; an empty list is still a list, not "every row"
+    const IT *rp = a.rowptr ? a.rowptr : &zero;
+    const IT rows = a.rowptr ? a.rows : 0;
+    if (!a.rowptr && rilen > 0) throw std::runtime_error("Extract: a row id of an empty matrix");
+    if (!ri) ri = &none;
+    if (!ci) ci = &none;
+    c.rowptr = (IT *)g4s_malloc(sizeof(IT) * ((size_t)rilen + 1));
+    if (!c.rowptr) throw std::runtime_error("Extract: host allocation failed");
+    int64_t cnnz = 0;
+    g4s_status st = g4s_csr_extract_symbolic(rows, a.cols, rp, a.colids, rilen, ri, cilen, ci, c.rowptr, &cnnz, G4S_HOST_POINTERS, info, nullptr);
+    if (st != G4S_OK) { c.make_empty(); check(st, "Extract"); }
+    adopt(c, rilen, cilen, cnnz, "Extract");
+    if (src_vec) {
+        src_vec->assign((size_t)cnnz + 1, 0);
+        src_raw = src_vec->data();
+    }
+    st = g4s_csr_extract_numeric(rows, a.cols, rp, a.colids, a.values, rilen, ri, cilen, ci, c.rowptr, c.colids, a.values ? c.values : nullptr, src_raw,
+                                 G4S_HOST_POINTERS, info, nullptr);
+    if (st != G4S_OK) { c.make_empty(); check(st, "Extract"); }
+    if (src_vec) src_vec->resize((size_t)cnnz);
+    if (!a.values) for (int64_t k = 0; k < cnnz; ++k) c.values[k] = 1.0;
+    return c;
+}
+} // namespace detail
+template <typename IT, typename NT>
+CSR<IT, NT> SpRef2(const CSR<IT, NT> &a, const IT *ri, IT rilen, const IT *ci, IT cilen, IT *src = nullptr, g4s_extract_info *info = nullptr)
+{
+    return detail::extract(a, ri, rilen, ci, cilen, src, (std::vector<IT> *)nullptr, info);
+}
+template <typename IT, typename NT>
+CSR<IT, NT> Extract(const CSR<IT, NT> &a, const std::vector<IT> &ri, const std::vector<IT> &ci, std::vector<IT> *src = nullptr, g4s_extract_info *info = nullptr)
+{
+    if (ri.size() > (size_t)INT32_MAX || ci.size() > (size_t)INT32_MAX) throw std::runtime_error("Extract: a list does not fit int32");
+    return detail::extract(a, ri.data(), (IT)ri.size(), ci.data(), (IT)ci.size(), (IT *)nullptr, src, info);
+}
+template <typename IT, typename NT>
+CSR<IT, NT> SpRef(const CSR<IT, NT> &a, const std::vector<IT> &ri, const std::vector<IT> &ci) { return Extract(a, ri, ci); }
+template <typename IT, typename NT>
+CSR<IT, NT> Permute(const CSR<IT, NT> &a, const std::vector<IT> &perm)
+{
+    if (a.rows != a.cols) throw std::runtime_error("Permute: the matrix is not square");
+    if (perm.size() != (size_t)a.rows) throw std::runtime_error("Permute: perm must hold one id per vertex");
+    return Extract(a, perm, perm);
+}
+template <typename IT, typename NT>
+CSR<IT, NT> SubMatrix(const CSR<IT, NT> &a, IT M_, IT N_, IT M_start = 0, IT N_start = 0)
+{
+    if (M_ < 0 || N_ < 0 || M_start < 0 || N_start < 0 || (int64_t)M_start + M_ > a.rows || (int64_t)N_start + N_ > a.cols)
+        throw std::runtime_error("SubMatrix: the block leaves the matrix");
+    std::vector<IT> ri((size_t)M_), ci((size_t)N_);
+    for (IT p = 0; p < M_; ++p) ri[(size_t)p] = M_start + p;
+    for (IT q = 0; q < N_; ++q) ci[(size_t)q] = N_start + q;
+    return Extract(a, ri, ci);
 }
 
 // Shortest-path distances (dist: a.rows values, +inf where unreached) and BFS levels (level: a.rows values, −1 where unreached) from the nearest of
