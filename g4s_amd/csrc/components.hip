@@ -29,6 +29,7 @@
 // Environment switches: G4S_CC_SAMPLE_ROUNDS (0 … 4, default 2), G4S_CC_NO_SKIP=1; every setting gives the same labels.
 #include "common.hpp"
 #include "frontier.hpp"
+#include "call_util.hpp"
 #include <algorithm>
 #include <climits>
 
@@ -258,18 +259,6 @@ __global__ __launch_bounds__(WG) void cc_largest_kernel(int n, const int *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// A block of the library's caching allocator, handed back on every path. `idle`: the stream that used it has been synchronised.
-struct BigBuf {
-    void *p = nullptr;
-    bool idle = false;
-    BigBuf() = default;
-    BigBuf(const BigBuf &) = delete;
-    BigBuf &operator=(const BigBuf &) = delete;
-    ~BigBuf() { if (p) (void)g4s::big_free(p, idle); }
-    int alloc(size_t bytes) { return g4s::big_alloc(&p, bytes); }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 int env_int(const char *name, int dflt, int lo, int hi)
 {
     const char *e = getenv(name);
@@ -277,12 +266,10 @@ int env_int(const char *name, int dflt, int lo, int hi)
     return std::max(lo, std::min(hi, atoi(e)));
 }
 
-int grid_for(long long n, long long cap) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, cap)); }
-
 // Enqueues the whole labelling on device arrays. `st` has room for kStateBytes, `count` for n ints, `hubs` for min(n, kHubCap).
 int enqueue(int n, const int *rowptr, const int *colids, int *labels, bool symmetric, int rounds, bool no_skip, CcState *st, int *count, int *hubs, hipStream_t s)
 {
-    const int g = grid_for(n, 8192), g_edges = grid_for(n, 2048);
+    const int g = grid_for<WG>(n, 8192), g_edges = grid_for<WG>(n, 2048);
     int compression = 0;
     auto compress = [&]() {
         const int base = compression++ * (kJumpPasses + 1);
@@ -305,10 +292,9 @@ int enqueue(int n, const int *rowptr, const int *colids, int *labels, bool symme
     return G4S_OK;
 }
 
-int upload(BigBuf &b, const void *src, size_t bytes, hipStream_t s)
+int fetch_state(CcState *h, const CcState *st, hipStream_t s)
 {
-    G4S_TRY(b.alloc(bytes ? bytes : 4));
-    if (bytes) G4S_HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(*h, st));
     return G4S_OK;
 }
 
@@ -322,9 +308,7 @@ G4S_API g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, co
     G4S_REQUIRE(rowptr && labels, "rowptr or labels is NULL");
     G4S_REQUIRE(colids || n == 0, "colids is NULL");
     const hipStream_t s = g4s::as_stream(stream);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its result back and cannot be captured", __func__);
+    G4S_TRY(not_capturing(__func__, s, "its result"));
     if (info) *info = g4s_cc_info{};
     if (n == 0) return G4S_OK;
 
@@ -335,29 +319,27 @@ G4S_API g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, co
         nnz = rowptr[n];
         G4S_REQUIRE(nnz >= 0, "rowptr[n] is negative");
     }
-    BigBuf work, d_rp, d_ci, d_lab;                                // the state, the size count (n ints), the hub list
-    const size_t n4 = (sizeof(int) * (size_t)n + 255) / 256 * 256, hub4 = sizeof(int) * (size_t)std::min(n, kHubCap);
-    CcState h{};
-    auto run = [&]() -> int {
-        G4S_TRY(work.alloc(kStateBytes + n4 + hub4));
-        CcState *st = work.as<CcState>();
-        int *count = reinterpret_cast<int *>(work.as<char>() + kStateBytes), *hubs = reinterpret_cast<int *>(work.as<char>() + kStateBytes + n4);
-        const int *rp = rowptr, *ci = colids;
-        int *lab = labels;
-        if (!device) {
-            G4S_TRY(upload(d_rp, rowptr, sizeof(int) * ((size_t)n + 1), s));
-            G4S_TRY(upload(d_ci, colids, sizeof(int) * (size_t)nnz, s));
-            G4S_TRY(d_lab.alloc(sizeof(int) * (size_t)n));
-            rp = d_rp.as<int>(); ci = d_ci.as<int>(); lab = d_lab.as<int>();
-        }
-        G4S_TRY(enqueue(n, rp, ci, lab, symmetric, rounds, no_skip, st, count, hubs, s));
-        if (!device) G4S_HIP_TRY(hipMemcpyAsync(labels, lab, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(g4s::ReadScope(s).fetch(h, st));               // the call's one wait
-        return G4S_OK;
-    };
-    int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);         // the caller's host arrays and the blocks released below: nothing in flight touches them
-    work.idle = d_rp.idle = d_ci.idle = d_lab.idle = true;
+    CcState *st, h{};
+    int *count, *hubs;                                             // the size count (n ints), the hub list
+    Carver work;
+    work.piece(&st, kStateBytes);
+    work.piece(&count, sizeof(int) * (size_t)n);
+    work.tail(&hubs, sizeof(int) * (size_t)std::min(n, kHubCap));
+    Staged stage(s);
+    int status = work.alloc();
+    const int *rp = rowptr, *ci = colids;
+    int *lab = labels;
+    if (status == G4S_OK && !device) {
+        rp = stage.in(rowptr, sizeof(int) * ((size_t)n + 1));
+        ci = stage.in(colids, sizeof(int) * (size_t)nnz);
+        lab = stage.out<int>(sizeof(int) * (size_t)n);
+        status = stage.error();
+    }
+    if (status == G4S_OK) status = enqueue(n, rp, ci, lab, symmetric, rounds, no_skip, st, count, hubs, s);
+    if (status == G4S_OK && !device) status = stage.to_host(labels, lab, sizeof(int) * (size_t)n);
+    if (status == G4S_OK) status = fetch_state(&h, st, s);         // the call's one wait
+    status = stage.finish(status);                                 // the caller's host arrays and the blocks: nothing in flight touches them
+    work.idle();
     if (status == G4S_OK && h.invalid)
         status = g4s::set_error(G4S_ERR_INVALID, "g4s_connected_components: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"
                                                                                                   : "a column id is outside [0, n)");

@@ -42,7 +42,6 @@ struct CooState {
     int fail, unsorted, longest, pad;
 };
 
-inline int grid_for(long long n) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, kMaxGrid)); }
 inline int bits_of(int32_t n) { return n > 1 ? 32 - __builtin_clz((unsigned)(n - 1)) : 0; }
 
 __global__ __launch_bounds__(WG) void coo_key_kernel(long long n, int rows, int cols, int col_bits, const int32_t *__restrict__ row, const int32_t *__restrict__ col,
@@ -318,25 +317,30 @@ int symbolic_device(const Shape &sh, const int32_t *row, const int32_t *col, int
     const long long n = sh.n;
     const bool keep = sh.dup == G4S_DUP_KEEP;
     const int ntiles = (int)((n + kTile - 1) / kTile);
-    const size_t kb = pad256(8 * ((size_t)n + 1)), ib = pad256(4 * (size_t)n), tb = pad256(4 * ((size_t)kRadix * ntiles + 1));
-    BigBuf work;
-    G4S_TRY(work.alloc(256 + 2 * kb + ib + 2 * tb));
-    char *base = work.as<char>();
-    CooState *st = reinterpret_cast<CooState *>(base);
-    u64 *ka = reinterpret_cast<u64 *>(base + 256), *kbuf = reinterpret_cast<u64 *>(base + 256 + kb);
-    int32_t *itmp = reinterpret_cast<int32_t *>(base + 256 + 2 * kb);
-    int *cnt = reinterpret_cast<int *>(base + 256 + 2 * kb + ib), *first = reinterpret_cast<int *>(base + 256 + 2 * kb + ib + tb);
+    const size_t kb = 8 * ((size_t)n + 1), tb = 4 * ((size_t)kRadix * ntiles + 1);
+    CooState *st;
+    u64 *ka, *kbuf;                                                 // the keys and their partner of the sort
+    int32_t *itmp;
+    int *cnt, *first;
+    Carver work;
+    work.piece(&st, sizeof(CooState));
+    work.piece(&ka, kb);
+    work.piece(&kbuf, kb);
+    work.piece(&itmp, 4 * (size_t)n);
+    work.piece(&cnt, tb);
+    work.piece(&first, tb);
+    G4S_TRY(work.alloc());
     g4s::ReadScope reads(s);
     CooState h{};
     int waits = 0;
     G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(CooState), s));
     if (n > 0) {
-        hipLaunchKernelGGL(coo_key_kernel, dim3(grid_for(n)), dim3(WG), 0, s, n, sh.rows, sh.cols, sh.col_bits, row, col, ka, perm, st);
+        hipLaunchKernelGGL(coo_key_kernel, dim3(grid_for<WG>(n, kMaxGrid)), dim3(WG), 0, s, n, sh.rows, sh.cols, sh.col_bits, row, col, ka, perm, st);
         G4S_HIP_TRY(hipGetLastError());
         G4S_HIP_TRY(reads.fetch(h, st));
         ++waits;
         if (h.fail) {
-            work.idle = true;
+            work.idle();
             return contract_error(sh, h.fail);
         }
     }
@@ -363,10 +367,10 @@ int symbolic_device(const Shape &sh, const int32_t *row, const int32_t *col, int
     }
     // the key partner is free now: the head flags and their scan, n + 1 ints each
     int *head = reinterpret_cast<int *>(sorted == ka ? kbuf : ka), *excl = head + (n + 1);
-    hipLaunchKernelGGL(coo_heads_kernel<false>, dim3(grid_for(n + 1)), dim3(WG), 0, s, n, sorted, (const int32_t *)nullptr, keep ? (int *)nullptr : head, st);
+    hipLaunchKernelGGL(coo_heads_kernel<false>, dim3(grid_for<WG>(n + 1, kMaxGrid)), dim3(WG), 0, s, n, sorted, (const int32_t *)nullptr, keep ? (int *)nullptr : head, st);
     G4S_HIP_TRY(hipGetLastError());
     if (!keep) G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(head), excl, n + 1, s));
-    hipLaunchKernelGGL(coo_rowptr_kernel, dim3(grid_for((long long)sh.rows + 1)), dim3(WG), 0, s, sh.rows, n, sh.col_bits, sorted, keep ? (const int *)nullptr : excl, crpt);
+    hipLaunchKernelGGL(coo_rowptr_kernel, dim3(grid_for<WG>((long long)sh.rows + 1, kMaxGrid)), dim3(WG), 0, s, sh.rows, n, sh.col_bits, sorted, keep ? (const int *)nullptr : excl, crpt);
     G4S_HIP_TRY(hipGetLastError());
     if (h_crpt) G4S_HIP_TRY(hipMemcpyAsync(h_crpt, crpt, 4 * ((size_t)sh.rows + 1), hipMemcpyDeviceToHost, s));
     if (h_perm && n > 0) G4S_HIP_TRY(hipMemcpyAsync(h_perm, perm, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -375,7 +379,7 @@ int symbolic_device(const Shape &sh, const int32_t *row, const int32_t *col, int
     if (!keep) G4S_HIP_TRY(reads.note(total, excl + n));
     G4S_HIP_TRY(reads.wait());
     ++waits;
-    work.idle = true;                                              // (an early return above leaves it false: the block is then released behind a device-wide wait)
+    work.idle();                                                   // (an early return above leaves it out: the block is then released behind a device-wide wait)
     info->nnz_in = n;
     info->nnz_out = total;
     info->longest_run = h.longest;
@@ -392,28 +396,31 @@ int numeric_device(const Shape &sh, const int32_t *row, const int32_t *col, cons
 {
     const long long n = sh.n;
     const bool keep = sh.dup == G4S_DUP_KEEP;
-    const size_t kb = pad256(8 * ((size_t)n + 1)), hb = pad256(4 * ((size_t)n + 1));
-    BigBuf work;
-    G4S_TRY(work.alloc(256 + kb + 2 * hb));
-    char *base = work.as<char>();
-    CooState *st = reinterpret_cast<CooState *>(base);
-    u64 *keys = reinterpret_cast<u64 *>(base + 256);
-    int *head = reinterpret_cast<int *>(base + 256 + kb), *excl = reinterpret_cast<int *>(base + 256 + kb + hb);
+    const size_t hb = 4 * ((size_t)n + 1);
+    CooState *st;
+    u64 *keys;
+    int *head, *excl;
+    Carver work;
+    work.piece(&st, sizeof(CooState));
+    work.piece(&keys, 8 * ((size_t)n + 1));
+    work.piece(&head, hb);
+    work.piece(&excl, hb);
+    G4S_TRY(work.alloc());
     int fail = 0;
     G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(CooState), s));
-    hipLaunchKernelGGL(coo_perm_keys_kernel, dim3(grid_for(n)), dim3(WG), 0, s, n, sh.rows, sh.cols, sh.col_bits, row, col, perm, keys, st);
-    hipLaunchKernelGGL(coo_heads_kernel<true>, dim3(grid_for(n + 1)), dim3(WG), 0, s, n, static_cast<const u64 *>(keys), perm, keep ? (int *)nullptr : head, st);
+    hipLaunchKernelGGL(coo_perm_keys_kernel, dim3(grid_for<WG>(n, kMaxGrid)), dim3(WG), 0, s, n, sh.rows, sh.cols, sh.col_bits, row, col, perm, keys, st);
+    hipLaunchKernelGGL(coo_heads_kernel<true>, dim3(grid_for<WG>(n + 1, kMaxGrid)), dim3(WG), 0, s, n, static_cast<const u64 *>(keys), perm, keep ? (int *)nullptr : head, st);
     G4S_HIP_TRY(hipGetLastError());
     if (!keep) G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(head), excl, n + 1, s));   // (behind a set fail flag head is unwritten: the scan reads the library's own block, the fill returns at once)
 #define FILL_ARGS sh.dup, n, sh.col_bits, static_cast<const u64 *>(keys), perm, val, static_cast<const int *>(head), static_cast<const int *>(excl), crpt_last, ccol, cval, st
-    if (cval) hipLaunchKernelGGL(coo_fill_kernel<true>, dim3(grid_for(n)), dim3(WG), 0, s, FILL_ARGS);
-    else hipLaunchKernelGGL(coo_fill_kernel<false>, dim3(grid_for(n)), dim3(WG), 0, s, FILL_ARGS);
+    if (cval) hipLaunchKernelGGL(coo_fill_kernel<true>, dim3(grid_for<WG>(n, kMaxGrid)), dim3(WG), 0, s, FILL_ARGS);
+    else hipLaunchKernelGGL(coo_fill_kernel<false>, dim3(grid_for<WG>(n, kMaxGrid)), dim3(WG), 0, s, FILL_ARGS);
 #undef FILL_ARGS
     G4S_HIP_TRY(hipGetLastError());
     if (h_ccol && cn > 0) G4S_HIP_TRY(hipMemcpyAsync(h_ccol, ccol, 4 * (size_t)cn, hipMemcpyDeviceToHost, s));
     if (h_cval && cn > 0) G4S_HIP_TRY(hipMemcpyAsync(h_cval, cval, 8 * (size_t)cn, hipMemcpyDeviceToHost, s));
     G4S_HIP_TRY(g4s::ReadScope(s).fetch(fail, &st->fail));
-    work.idle = true;                                              // (as in symbolic_device)
+    work.idle();                                                   // (as in symbolic_device)
     if (fail) return contract_error(sh, fail);
     return G4S_OK;
 }
@@ -450,18 +457,12 @@ G4S_API g4s_status g4s_csr_from_coo_symbolic(int dup, int32_t rows, int32_t cols
     info->tile_entries = kTile;
     *cnnz = 0;
     if (dev) return symbolic_device(sh, row, col, crpt, perm, cnnz, info, nullptr, nullptr, s);
-    BigBuf d_row, d_col, d_crpt, d_perm;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_row, row, nb, s));
-        G4S_TRY(upload(d_col, col, nb, s));
-        G4S_TRY(d_crpt.alloc(rp));
-        G4S_TRY(d_perm.alloc(nb));
-        return symbolic_device(sh, d_row.as<int32_t>(), d_col.as<int32_t>(), d_crpt.as<int32_t>(), d_perm.as<int32_t>(), cnnz, info, crpt, perm, s);
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_row, &d_col, &d_crpt, &d_perm}) b->idle = true;
-    return status;
+    Staged stage(s);
+    const int32_t *d_row = stage.in(row, nb), *d_col = stage.in(col, nb);
+    int32_t *d_crpt = stage.out<int32_t>(rp), *d_perm = stage.out<int32_t>(nb);
+    int status = stage.error();
+    if (status == G4S_OK) status = symbolic_device(sh, d_row, d_col, d_crpt, d_perm, cnnz, info, crpt, perm, s);   // the copies to crpt / perm: its own
+    return stage.finish(status);
 }
 
 G4S_API g4s_status g4s_csr_from_coo_numeric(int dup, int32_t rows, int32_t cols, int64_t nnz, const int32_t *row, const int32_t *col, const double *val,
@@ -487,20 +488,13 @@ G4S_API g4s_status g4s_csr_from_coo_numeric(int dup, int32_t rows, int32_t cols,
     G4S_TRY(not_capturing(__func__, s));
     const Shape sh(__func__, dup, rows, cols, nnz);
     if (dev) return numeric_device(sh, row, col, val, crpt + rows, perm, ccol, cval, nullptr, nullptr, 0, s);
-    BigBuf d_row, d_col, d_val, d_last, d_perm, d_ccol, d_cval;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_row, row, nb, s));
-        G4S_TRY(upload(d_col, col, nb, s));
-        if (val) G4S_TRY(upload(d_val, val, 2 * nb, s));
-        G4S_TRY(upload(d_last, crpt + rows, 4, s));
-        G4S_TRY(upload(d_perm, perm, nb, s));
-        G4S_TRY(d_ccol.alloc(4 * (size_t)cn));
-        if (cval) G4S_TRY(d_cval.alloc(8 * (size_t)cn));
-        return numeric_device(sh, d_row.as<int32_t>(), d_col.as<int32_t>(), d_val.as<double>(), d_last.as<int32_t>(), d_perm.as<int32_t>(), d_ccol.as<int32_t>(),
-                              cval ? d_cval.as<double>() : nullptr, ccol, cval, cn, s);
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_row, &d_col, &d_val, &d_last, &d_perm, &d_ccol, &d_cval}) b->idle = true;
-    return status;
+    Staged stage(s);
+    const int32_t *d_row = stage.in(row, nb), *d_col = stage.in(col, nb);
+    const double *d_val = stage.in(val, 2 * nb);
+    const int32_t *d_last = stage.in(crpt + rows, 4), *d_perm = stage.in(perm, nb);
+    int32_t *d_ccol = stage.out<int32_t>(4 * (size_t)cn);
+    double *d_cval = cval ? stage.out<double>(8 * (size_t)cn) : nullptr;
+    int status = stage.error();
+    if (status == G4S_OK) status = numeric_device(sh, d_row, d_col, d_val, d_last, d_perm, d_ccol, d_cval, ccol, cval, cn, s);   // the copies to ccol / cval: its own
+    return stage.finish(status);
 }

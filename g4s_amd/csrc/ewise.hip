@@ -1,7 +1,8 @@
 // ewise.hip — element-wise combination and filtering of CSR matrices on the device (include/g4s.h: g4s_csr_ewise_symbolic / _numeric, g4s_csr_select_symbolic /
 // _numeric). The reference has no such call: its reader mirrors a symmetric MatrixMarket file on the host (mm/inc/CSR.h:586-623).
 //
-// One work unit for every path. The merged sequence of a row — its la entries of A and lb entries of B in ascending column order, A first on a tie, so that a
+// One work unit for every path (unit_walk.hpp: its constants, the row search, the walk of a wave through its run of units, the 16-lane sums; extract.hip
+// shares it). The merged sequence of a row — its la entries of A and lb entries of B in ascending column order, A first on a tie, so that a
 // matched pair is adjacent — is cut into units of T = kUnit positions; a row of la + lb positions has ceil((la + lb) / T) units and an empty row none. A unit is
 // taken by kLanes = 16 adjacent lanes of a wave, kPer = 4 consecutive positions each:
 //   ew_rows_kernel      rowptr of A (and B): zero-based and non-decreasing (fail bit 1), units per row, rows cut into more than one unit, the entry counts.
@@ -27,24 +28,17 @@
 #include "prims.hpp"
 #include "readback.hpp"
 #include "call_util.hpp"
+#include "unit_walk.hpp"
 #include <algorithm>
-#include <climits>
 
 namespace {
 
-constexpr int WG = 256, kLanes = 16, kPer = 4, kUnit = kLanes * kPer, kGroups = 64 / kLanes;
-constexpr int kGridWG = 2048;                                      // 8 workgroups per CU of the 256: 8192 waves, each with a contiguous run of units
-constexpr long long kWaves = (long long)kGridWG * (WG / 64);
 constexpr int BAD_ROWPTR = 1, BAD_ENTRY = 2, BAD_CRPT = 4;
 
 struct EwState {
     int fail, nnz_a, nnz_b, rows_split;
     unsigned long long cnnz;
 };
-
-enum Mode { COUNT_ROWS = 0, COUNT_UNITS = 1, FILL = 2 };
-
-inline int grid_for(long long n) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, (long long)kGridWG)); }
 
 // b may be NULL (select): its rows are empty. cnt (may be NULL): zeroed for COUNT_ROWS.
 __global__ __launch_bounds__(WG) void ew_rows_kernel(int rows, const int32_t *__restrict__ arpt, const int32_t *__restrict__ brpt, int *__restrict__ upr,
@@ -81,31 +75,6 @@ __device__ __forceinline__ int merge_path(const int32_t *__restrict__ a, const i
     return lo;
 }
 
-// the last row r in [lo, rows) with uoff[r] <= u, given uoff[lo] <= u < uoff[rows]: gallop, then bisect (the next unit is mostly in the same or the next row)
-__device__ __forceinline__ int row_of_unit(const int *__restrict__ uoff, int rows, int lo, int u)
-{
-    int step = 1;
-    while (lo + step < rows && uoff[lo + step] <= u) {
-        lo += step;
-        step <<= 1;
-    }
-    int hi = min(lo + step, rows) - 1;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo + 1) >> 1);
-        if (uoff[mid] <= u) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-template <typename V>
-__device__ __forceinline__ V group_sum(V v)
-{
-#pragma unroll
-    for (int off = kLanes / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kLanes);
-    return v;
-}
-
 // out: COUNT_ROWS → cnt[rows + 1] (zeroed), COUNT_UNITS → cnt[units], FILL → upos[units + 1] is read, ccol / cval are written.
 template <int MODE, bool VALUES>
 __global__ __launch_bounds__(WG) void ew_merge_kernel(int op, int combine, int rows, int cols, const int32_t *__restrict__ arpt, const int32_t *__restrict__ acol,
@@ -124,23 +93,20 @@ __global__ __launch_bounds__(WG) void ew_merge_kernel(int op, int combine, int r
         if (threadIdx.x == 0 && !st->fail) atomicOr(&st->fail, BAD_CRPT);
         return;
     }
-    const long long chunk = ((long long)units + kWaves - 1) / kWaves;
-    const long long wave = (long long)blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
-    const long long c0 = wave * chunk, c1 = min(c0 + chunk, (long long)units);
-    const int lane = threadIdx.x & (kLanes - 1), group = (threadIdx.x & 63) / kLanes;
+    UnitWalk w(units);
+    const int lane = w.lane;
     int r = -1;
     unsigned long long total = 0;
-    for (long long it = 0; it < chunk; it += kGroups) {            // the same trip count for every lane of the wave: the shuffles below are never divergent
-        const long long ul = c0 + it + group;
-        const bool live = ul < c1;
+    for (long long it = 0; it < w.chunk; it += kGroups) {          // the same trip count for every lane of the wave: the shuffles below are never divergent
+        const long long ul = w.unit(it);
+        const bool live = w.live(ul);
         int ia_s = 0, ia_e = 0, ib_s = 0, ib_e = 0, la = 0, lb = 0, last = 0;
         const int32_t *a = acol, *b = bcol;
         long long ka = 0, kb = 0;
         bool bad = false;
         if (live) {
             const int u = (int)ul;
-            if (r < 0) r = row_of_unit(uoff, rows, 0, u);
-            else if (uoff[r + 1] <= u) r = row_of_unit(uoff, rows, r + 1, u);
+            r = row_after(uoff, rows, r, u);
             ka = arpt[r];
             kb = brpt[r];
             la = arpt[r + 1] - (int)ka;
@@ -199,12 +165,7 @@ __global__ __launch_bounds__(WG) void ew_merge_kernel(int op, int combine, int r
             }
         }
         if (MODE == FILL) {
-            int incl = kept;
-#pragma unroll
-            for (int off = 1; off < kLanes; off <<= 1) {
-                const int v = __shfl_up(incl, off, kLanes);
-                if (lane >= off) incl += v;
-            }
+            const int incl = group_inclusive(kept, lane);
             if (live) {
                 long long pos = (long long)upos[(int)ul] + incl - kept;
 #pragma unroll
@@ -264,21 +225,18 @@ __global__ __launch_bounds__(WG) void sel_kernel(int pred, long long k, double t
         if (threadIdx.x == 0 && !st->fail) atomicOr(&st->fail, BAD_CRPT);
         return;
     }
-    const long long chunk = ((long long)units + kWaves - 1) / kWaves;
-    const long long wave = (long long)blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
-    const long long c0 = wave * chunk, c1 = min(c0 + chunk, (long long)units);
-    const int lane = threadIdx.x & (kLanes - 1), group = (threadIdx.x & 63) / kLanes;
+    UnitWalk w(units);
+    const int lane = w.lane, group = w.group;
     const unsigned below = (1u << lane) - 1u;
     int r = -1;
     unsigned long long total = 0;
-    for (long long it = 0; it < chunk; it += kGroups) {            // uniform over the wave: the ballots see all four groups
-        const long long ul = c0 + it + group;
-        const bool live = ul < c1;
+    for (long long it = 0; it < w.chunk; it += kGroups) {          // uniform over the wave: the ballots see all four groups
+        const long long ul = w.unit(it);
+        const bool live = w.live(ul);
         long long k0 = 0, k1 = 0, pos = 0;
         if (live) {
             const int u = (int)ul;
-            if (r < 0) r = row_of_unit(uoff, rows, 0, u);
-            else if (uoff[r + 1] <= u) r = row_of_unit(uoff, rows, r + 1, u);
+            r = row_after(uoff, rows, r, u);
             k0 = rpt[r] + (long long)(u - uoff[r]) * kUnit;
             k1 = min(k0 + kUnit, (long long)rpt[r + 1]);
             if (MODE == FILL) pos = upos[u];
@@ -367,17 +325,20 @@ int contract_error(const Job &j, int fail)
 // Device arrays; the stream is synchronised on return. crpt: rows + 1 ints, written. One wait.
 int symbolic_device(const Job &j, int32_t *crpt, int64_t *cnnz, g4s_ewise_info *info, hipStream_t s)
 {
-    const size_t n1 = pad256(sizeof(int) * ((size_t)j.rows + 1));
-    BigBuf work;
-    G4S_TRY(work.alloc(256 + 3 * n1));
-    EwState *st = work.as<EwState>();
-    int *upr = reinterpret_cast<int *>(work.as<char>() + 256), *uoff = reinterpret_cast<int *>(work.as<char>() + 256 + n1),
-        *cnt = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * n1);
+    const size_t n1 = sizeof(int) * ((size_t)j.rows + 1);
+    EwState *st;
+    int *upr, *uoff, *cnt;
+    Carver work;
+    work.piece(&st, sizeof(EwState));
+    work.piece(&upr, n1);
+    work.piece(&uoff, n1);
+    work.piece(&cnt, n1);
+    G4S_TRY(work.alloc());
     g4s::ReadScope reads(s);
     EwState h{};
     int units = 0;
     G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(EwState), s));
-    hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for((long long)j.rows + 1)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, cnt, st);
+    hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for<WG>((long long)j.rows + 1, kGridWG)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, cnt, st);
     G4S_HIP_TRY(hipGetLastError());
     G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.rows + 1, s));
     if (j.rows > 0) launch<COUNT_ROWS>(j, false, uoff, INT_MAX, cnt, nullptr, nullptr, nullptr, nullptr, st, s);
@@ -385,7 +346,7 @@ int symbolic_device(const Job &j, int32_t *crpt, int64_t *cnnz, g4s_ewise_info *
     G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(cnt), crpt, (long long)j.rows + 1, s));
     G4S_HIP_TRY(reads.note(h, st));
     G4S_HIP_TRY(reads.fetch(units, uoff + j.rows));
-    work.idle = true;                                              // (an early return above leaves it false: the block is then released behind a device-wide wait)
+    work.idle();                                                   // (an early return above leaves it out: the block is then released behind a device-wide wait)
     if (h.fail) return contract_error(j, h.fail);
     {
         info->nnz_a = h.nnz_a;
@@ -405,18 +366,22 @@ int symbolic_device(const Job &j, int32_t *crpt, int64_t *cnnz, g4s_ewise_info *
 int numeric_device(const Job &j, long long nnz_a, long long nnz_b, long long nnz_c, const int32_t *crpt, int32_t *ccol, double *cval, hipStream_t s)
 {
     if (nnz_c == 0) return G4S_OK;
-    const long long cap = (long long)j.rows + (nnz_a + nnz_b) / kUnit + 1;   // every row's last unit may be a partial one
-    if (cap > INT_MAX - 1) return g4s::set_error(G4S_ERR_OVERFLOW, "%s: more than 2^31 work units", j.fn);
-    const size_t n1 = pad256(sizeof(int) * ((size_t)j.rows + 1)), u1 = pad256(sizeof(int) * ((size_t)cap + 1));
-    BigBuf work;
-    G4S_TRY(work.alloc(256 + 2 * n1 + 2 * u1));
-    EwState *st = work.as<EwState>();
-    int *upr = reinterpret_cast<int *>(work.as<char>() + 256), *uoff = reinterpret_cast<int *>(work.as<char>() + 256 + n1),
-        *ucnt = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * n1), *upos = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * n1 + u1);
+    if (too_many_units(j.rows, (unsigned long long)(nnz_a + nnz_b))) return g4s::set_error(G4S_ERR_OVERFLOW, "%s: more than 2^31 work units", j.fn);
+    const long long cap = unit_cap(j.rows, (unsigned long long)(nnz_a + nnz_b));
+    const size_t n1 = sizeof(int) * ((size_t)j.rows + 1), u1 = sizeof(int) * ((size_t)cap + 1);
+    EwState *st;
+    int *upr, *uoff, *ucnt, *upos;
+    Carver work;
+    work.piece(&st, sizeof(EwState));
+    work.piece(&upr, n1);
+    work.piece(&uoff, n1);
+    work.piece(&ucnt, u1);
+    work.piece(&upos, u1);
+    G4S_TRY(work.alloc());
     int fail = 0;
     G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(EwState), s));
-    G4S_HIP_TRY(hipMemsetAsync(ucnt, 0, sizeof(int) * ((size_t)cap + 1), s));
-    hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for((long long)j.rows + 1)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, (int *)nullptr, st);
+    G4S_HIP_TRY(hipMemsetAsync(ucnt, 0, u1, s));
+    hipLaunchKernelGGL(ew_rows_kernel, dim3(grid_for<WG>((long long)j.rows + 1, kGridWG)), dim3(WG), 0, s, j.rows, j.arpt, j.brpt, upr, (int *)nullptr, st);
     G4S_HIP_TRY(hipGetLastError());
     G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.rows + 1, s));
     launch<COUNT_UNITS>(j, false, uoff, (int)cap, ucnt, nullptr, nullptr, nullptr, nullptr, st, s);
@@ -425,7 +390,7 @@ int numeric_device(const Job &j, long long nnz_a, long long nnz_b, long long nnz
     launch<FILL>(j, cval != nullptr, uoff, (int)cap, nullptr, upos, crpt, ccol, cval, st, s);
     G4S_HIP_TRY(hipGetLastError());
     G4S_HIP_TRY(g4s::ReadScope(s).fetch(fail, &st->fail));
-    work.idle = true;                                              // (as in symbolic_device)
+    work.idle();                                                   // (as in symbolic_device)
     if (fail) return contract_error(j, fail);
     return G4S_OK;
 }
@@ -479,29 +444,23 @@ int symbolic(Job j, int32_t *crpt, int64_t *cnnz, unsigned flags, g4s_ewise_info
             return g4s::set_error(G4S_ERR_INVALID, "%s: crpt overlaps a column or value array", j.fn);
         return st;
     }
-    BigBuf d_arpt, d_acol, d_aval, d_brpt, d_bcol, d_bval, d_crpt;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_arpt, j.arpt, rp, s));
-        G4S_TRY(upload(d_acol, j.acol, 4 * (size_t)na, s));
-        if (j.use_val()) G4S_TRY(upload(d_aval, j.aval, 8 * (size_t)na, s));
-        if (j.brpt) {
-            G4S_TRY(upload(d_brpt, j.brpt, rp, s));
-            G4S_TRY(upload(d_bcol, j.bcol, 4 * (size_t)nb, s));
-        }
-        G4S_TRY(d_crpt.alloc(rp));
-        Job d = j;
-        d.arpt = d_arpt.as<int32_t>(); d.acol = d_acol.as<int32_t>(); d.aval = d_aval.as<double>();
-        d.brpt = d_brpt.as<int32_t>(); d.bcol = d_bcol.as<int32_t>(); d.bval = nullptr;
-        int st = symbolic_device(d, d_crpt.as<int32_t>(), cnnz, info, s);
-        if (st != G4S_OK && st != G4S_ERR_OVERFLOW) return st;
-        G4S_HIP_TRY(hipMemcpyAsync(crpt, d_crpt.p, rp, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(hipStreamSynchronize(s));
-        return st;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_arpt, &d_acol, &d_aval, &d_brpt, &d_bcol, &d_bval, &d_crpt}) b->idle = true;
-    return status;
+    Staged stage(s);
+    Job d = j;
+    d.arpt = stage.in(j.arpt, rp);
+    d.acol = stage.in(j.acol, 4 * (size_t)na);
+    d.aval = j.use_val() ? stage.in(j.aval, 8 * (size_t)na) : nullptr;
+    d.brpt = stage.in(j.brpt, rp);                                   // (NULL for select)
+    d.bcol = stage.in(j.bcol, 4 * (size_t)nb);
+    d.bval = nullptr;
+    int32_t *d_crpt = stage.out<int32_t>(rp);
+    int status = stage.error();
+    if (status == G4S_OK) status = symbolic_device(d, d_crpt, cnnz, info, s);
+    if (status == G4S_OK || status == G4S_ERR_OVERFLOW) {          // crpt comes back with the overflow too
+        int back = stage.to_host(crpt, d_crpt, rp);
+        if (back == G4S_OK) back = stage.wait();
+        if (back != G4S_OK) status = back;
+    }
+    return stage.finish(status);
 }
 
 int numeric(Job j, const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, hipStream_t s)
@@ -529,32 +488,23 @@ int numeric(Job j, const int32_t *crpt, int32_t *ccol, double *cval, unsigned fl
         return numeric_device(j, na, nb, nc, crpt, ccol, cval, s);
     }
     if (nc == 0) return G4S_OK;
-    BigBuf d_arpt, d_acol, d_aval, d_brpt, d_bcol, d_bval, d_crpt, d_ccol, d_cval;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_arpt, j.arpt, rp, s));
-        G4S_TRY(upload(d_acol, j.acol, 4 * (size_t)na, s));
-        if (j.aval) G4S_TRY(upload(d_aval, j.aval, 8 * (size_t)na, s));
-        if (j.brpt) {
-            G4S_TRY(upload(d_brpt, j.brpt, rp, s));
-            G4S_TRY(upload(d_bcol, j.bcol, 4 * (size_t)nb, s));
-            if (j.bval) G4S_TRY(upload(d_bval, j.bval, 8 * (size_t)nb, s));
-        }
-        G4S_TRY(upload(d_crpt, crpt, rp, s));
-        G4S_TRY(d_ccol.alloc(4 * (size_t)nc));
-        if (cval) G4S_TRY(d_cval.alloc(8 * (size_t)nc));
-        Job d = j;
-        d.arpt = d_arpt.as<int32_t>(); d.acol = d_acol.as<int32_t>(); d.aval = d_aval.as<double>();
-        d.brpt = d_brpt.as<int32_t>(); d.bcol = d_bcol.as<int32_t>(); d.bval = d_bval.as<double>();
-        G4S_TRY(numeric_device(d, na, nb, nc, d_crpt.as<int32_t>(), d_ccol.as<int32_t>(), d_cval.as<double>(), s));
-        G4S_HIP_TRY(hipMemcpyAsync(ccol, d_ccol.p, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
-        if (cval) G4S_HIP_TRY(hipMemcpyAsync(cval, d_cval.p, 8 * (size_t)nc, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(hipStreamSynchronize(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_arpt, &d_acol, &d_aval, &d_brpt, &d_bcol, &d_bval, &d_crpt, &d_ccol, &d_cval}) b->idle = true;
-    return status;
+    Staged stage(s);
+    Job d = j;
+    d.arpt = stage.in(j.arpt, rp);
+    d.acol = stage.in(j.acol, 4 * (size_t)na);
+    d.aval = stage.in(j.aval, 8 * (size_t)na);
+    d.brpt = stage.in(j.brpt, rp);                                   // (NULL for select)
+    d.bcol = stage.in(j.bcol, 4 * (size_t)nb);
+    d.bval = stage.in(j.bval, 8 * (size_t)nb);
+    const int32_t *d_crpt = stage.in(crpt, rp);
+    int32_t *d_ccol = stage.out<int32_t>(4 * (size_t)nc);
+    double *d_cval = cval ? stage.out<double>(8 * (size_t)nc) : nullptr;
+    int status = stage.error();
+    if (status == G4S_OK) status = numeric_device(d, na, nb, nc, d_crpt, d_ccol, d_cval, s);
+    if (status == G4S_OK) status = stage.to_host(ccol, d_ccol, 4 * (size_t)nc);
+    if (status == G4S_OK && cval) status = stage.to_host(cval, d_cval, 8 * (size_t)nc);
+    if (status == G4S_OK) status = stage.wait();
+    return stage.finish(status);
 }
 
 bool valid_op(int op) { return op >= G4S_EWISE_UNION && op <= G4S_EWISE_DIFFERENCE; }

@@ -2,7 +2,7 @@
 // The reference has CSR(const CSR&, M_, N_, M_start, N_start) for a contiguous block (mm/inc/CSR.h:691-733) and CSC::SpRef / SpRef2 for sorted lists
 // (mm/inc/CSC.h:513-690), both host loops. I and J may be in any order and may repeat ids — MATLAB's A(I, J).
 //
-// The work unit is sel_kernel's (ewise.hip): kUnit = 64 stored entries of the source row I[p], taken by kLanes = 16 adjacent lanes, four entries each in
+// The work unit is unit_walk.hpp's, cut as sel_kernel (ewise.hip) cuts it: kUnit = 64 stored entries of the source row I[p], taken by kLanes = 16 adjacent lanes, four entries each in
 // stored order; short rows share a wave and a hub row spreads over the grid.
 //   ex_check_kernel     one pass: the row pointers (zero-based, non-decreasing: BAD_ROWPTR) as in ew_rows_kernel, every id of I and J range-checked (BAD_ID)
 //                       before anything is made of it, whether J ever decreases, the units of every output row, the entries of A in the selected rows, and
@@ -34,16 +34,13 @@
 #include "prims.hpp"
 #include "readback.hpp"
 #include "call_util.hpp"
+#include "unit_walk.hpp"
 #include <algorithm>
-#include <climits>
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int WG = 256, kLanes = 16, kPer = 4, kUnit = kLanes * kPer, kGroups = 64 / kLanes;
-constexpr int kGridWG = 2048;                                      // 8 workgroups per CU of the 256, as in ewise.hip
-constexpr long long kWaves = (long long)kGridWG * (WG / 64);
 constexpr int kCheckWG = 1024;                                    // ex_check_kernel: one 64-bit atomic per workgroup on one address
 constexpr int kClassifyWG = 512;                                 // ex_classify_kernel: one atomic per workgroup and list
 constexpr int kWaveMax = 64, kLdsMax = 4096;                       // 4096 keys of 8 bytes + 4096 payloads of 4: 48 KiB of the CU's 160, three workgroups per CU
@@ -55,13 +52,7 @@ struct ExState {
     int n_wave, n_lds, n_long, pad;
 };
 
-enum Mode { COUNT_ROWS = 0, COUNT_UNITS = 1, FILL = 2 };
-
-inline int grid_for(long long n) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, (long long)kGridWG)); }
-
-// more units than an int32 table holds: Σ ceil(len / kUnit) <= nnz_rows / kUnit + ni
-__host__ __device__ inline bool too_many_units(u64 nnz_rows, int ni) { return nnz_rows / kUnit + (u64)ni > (u64)(INT_MAX - 1); }
-__device__ __forceinline__ bool dead(const ExState *st, int ni) { return st->fail || too_many_units(st->nnz_rows, ni); }
+__device__ __forceinline__ bool dead(const ExState *st, int ni) { return st->fail || too_many_units(ni, st->nnz_rows); }
 
 // mult (may be NULL: J == NULL): cols + 1 ints, zeroed. upr: ni + 1 ints.
 __global__ __launch_bounds__(WG) void ex_check_kernel(int rows, int cols, const int32_t *__restrict__ rpt, int ni, const int32_t *__restrict__ I, int nj,
@@ -107,18 +98,7 @@ __global__ __launch_bounds__(WG) void ex_check_kernel(int rows, int cols, const 
             }
         }
     }
-    // one 64-bit atomic per workgroup: thousands of waves adding to one address were most of this kernel's time (profiles/extract.txt)
-    __shared__ u64 wsum[WG / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) len_sum += __shfl_xor(len_sum, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = len_sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 t = 0;
-#pragma unroll
-        for (int w = 0; w < WG / 64; ++w) t += wsum[w];
-        if (t) atomicAdd(&st->nnz_rows, t);
-    }
+    workgroup_add_u64(&st->nnz_rows, len_sum);
     if (__any(unsorted) && (threadIdx.x & 63) == 0 && !*(volatile int *)&st->j_unsorted) atomicOr(&st->j_unsorted, 1);
     if (bad) atomicOr(&st->fail, bad);
 }
@@ -133,23 +113,6 @@ __global__ __launch_bounds__(WG) void ex_jlist_kernel(int ni, int nj, const int3
         const int pos = jptr[c] + atomicAdd(&cursor[c], 1);
         if ((unsigned)pos < (unsigned)nj) jlist[pos] = (int)q;
     }
-}
-
-// the last row r in [lo, rows) with uoff[r] <= u, given uoff[lo] <= u < uoff[rows]: gallop, then bisect (ewise.hip)
-__device__ __forceinline__ int row_of_unit(const int *__restrict__ uoff, int rows, int lo, int u)
-{
-    int step = 1;
-    while (lo + step < rows && uoff[lo + step] <= u) {
-        lo += step;
-        step <<= 1;
-    }
-    int hi = min(lo + step, rows) - 1;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo + 1) >> 1);
-        if (uoff[mid] <= u) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 // cnt: COUNT_ROWS → ni + 1 counters (zeroed), COUNT_UNITS → one per unit. FILL: upos[units + 1] is read, ccol / src (nc entries each) are written.
@@ -171,21 +134,18 @@ __global__ __launch_bounds__(WG) void ex_walk_kernel(int rows, int cols, const i
         if (threadIdx.x == 0) atomicOr(&st->fail, BAD_CRPT);
         return;
     }
-    const long long chunk = ((long long)units + kWaves - 1) / kWaves;
-    const long long wave = (long long)blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
-    const long long c0 = wave * chunk, c1 = min(c0 + chunk, (long long)units);
-    const int lane = threadIdx.x & (kLanes - 1), group = (threadIdx.x & 63) / kLanes;
+    UnitWalk w(units);
+    const int lane = w.lane;
     int p = -1;
     u64 total = 0;
     bool bad = false;
-    for (long long it = 0; it < chunk; it += kGroups) {            // the same trip count for every lane of the wave: the shuffles below are never divergent
-        const long long ul = c0 + it + group;
-        bool live = ul < c1;
+    for (long long it = 0; it < w.chunk; it += kGroups) {          // the same trip count for every lane of the wave: the shuffles below are never divergent
+        const long long ul = w.unit(it);
+        const bool live = w.live(ul);
         long long k0 = 0, k1 = 0, pos = 0, uend = 0;
         if (live) {
             const int u = (int)ul;
-            if (p < 0) p = row_of_unit(uoff, ni, 0, u);
-            else if (uoff[p + 1] <= u) p = row_of_unit(uoff, ni, p + 1, u);
+            p = row_after(uoff, ni, p, u);
             const int r = I ? I[p] : p;
             if ((unsigned)r < (unsigned)rows) {
                 k0 = rpt[r] + (long long)(u - uoff[p]) * kUnit;
@@ -208,12 +168,7 @@ __global__ __launch_bounds__(WG) void ex_walk_kernel(int rows, int cols, const i
                 else m = mult ? (unsigned)mult[c] : 1u;
             }
             if (MODE == FILL) {
-                unsigned incl = m;
-#pragma unroll
-                for (int off = 1; off < kLanes; off <<= 1) {
-                    const unsigned v = __shfl_up(incl, off, kLanes);
-                    if (lane >= off) incl += v;
-                }
+                const unsigned incl = group_inclusive(m, lane);
                 const unsigned step = __shfl(incl, kLanes - 1, kLanes);
                 long long o = pos + (incl - m);
                 const int base = mult && m ? jptr[c] : 0;             // (m != 0: c has passed its range check)
@@ -227,8 +182,7 @@ __global__ __launch_bounds__(WG) void ex_walk_kernel(int rows, int cols, const i
             }
         }
         if (MODE != FILL) {
-#pragma unroll
-            for (int off = kLanes / 2; off > 0; off >>= 1) kept += __shfl_xor(kept, off, kLanes);
+            kept = group_sum(kept);
             if (live && lane == 0) {
                 if (MODE == COUNT_ROWS) {
                     if (kept) atomicAdd(&cnt[p], (unsigned)kept);    // (wraps only where the 64-bit total below reports the overflow)
@@ -239,18 +193,8 @@ __global__ __launch_bounds__(WG) void ex_walk_kernel(int rows, int cols, const i
             }
         }
     }
-    if (MODE != FILL) {                                            // one 64-bit add per workgroup on st->cnnz, as in ex_check_kernel
-        __shared__ u64 wsum[WG / 64];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = total;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            u64 t = 0;
-#pragma unroll
-            for (int w = 0; w < WG / 64; ++w) t += wsum[w];
-            if (t) atomicAdd(&st->cnnz, t);
-        }
+    if (MODE != FILL) {
+        workgroup_add_u64(&st->cnnz, total);
         if (bad) atomicOr(&st->fail, BAD_COL);
     }
 }
@@ -497,8 +441,6 @@ int contract_error(const Job &j, int fail)
     return g4s::set_error(G4S_ERR_INVALID, "%s: crpt is not the row pointer of this extraction: crpt must come from the symbolic call", j.fn);
 }
 
-char *at(const BigBuf &b, size_t off) { return b.as<char>() + off; }
-
 void report(g4s_extract_info *info, const ExState &h, long long units, bool has_j, int waits)
 {
     info->nnz_a = h.nnz_a;
@@ -517,31 +459,27 @@ void report(g4s_extract_info *info, const ExState &h, long long units, bool has_
 
 // The state, the unit table of the output rows and the column map: what both calls start with. Enqueues only.
 struct Front {
-    BigBuf work;
+    Carver work;
     ExState *st = nullptr;
     int *upr = nullptr, *uoff = nullptr, *mult = nullptr, *jptr = nullptr;
     unsigned *cnt = nullptr;                                        // ni + 1 counters, zeroed (the symbolic call's)
     int build(const Job &j, bool with_cnt, hipStream_t s)
     {
-        const size_t n1 = pad256(4 * ((size_t)j.ni + 1)), c1 = j.J ? pad256(4 * ((size_t)j.cols + 1)) : 0;
-        G4S_TRY(work.alloc(256 + (with_cnt ? 3 : 2) * n1 + 2 * c1));
-        st = work.as<ExState>();
-        upr = reinterpret_cast<int *>(at(work, 256));
-        uoff = reinterpret_cast<int *>(at(work, 256 + n1));
-        size_t off = 256 + 2 * n1;
-        if (with_cnt) {
-            cnt = reinterpret_cast<unsigned *>(at(work, off));
-            off += n1;
-            G4S_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * ((size_t)j.ni + 1), s));
-        }
+        const size_t n1 = 4 * ((size_t)j.ni + 1), c1 = 4 * ((size_t)j.cols + 1);
+        work.piece(&st, sizeof(ExState));
+        work.piece(&upr, n1);
+        work.piece(&uoff, n1);
+        if (with_cnt) work.piece(&cnt, n1);
         if (j.J) {
-            mult = reinterpret_cast<int *>(at(work, off));
-            jptr = reinterpret_cast<int *>(at(work, off + c1));
-            G4S_HIP_TRY(hipMemsetAsync(mult, 0, 4 * ((size_t)j.cols + 1), s));
+            work.piece(&mult, c1);
+            work.piece(&jptr, c1);
         }
+        G4S_TRY(work.alloc());
+        if (with_cnt) G4S_HIP_TRY(hipMemsetAsync(cnt, 0, n1, s));
+        if (j.J) G4S_HIP_TRY(hipMemsetAsync(mult, 0, c1, s));
         G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(ExState), s));
         const long long n = (long long)std::max(j.rows, std::max(j.ni, j.nj)) + 1;
-        hipLaunchKernelGGL(ex_check_kernel, dim3(std::min(grid_for(n), kCheckWG)), dim3(WG), 0, s, j.rows, j.cols, j.rpt, j.ni, j.I, j.nj, j.J, upr, mult, st);
+        hipLaunchKernelGGL(ex_check_kernel, dim3(std::min(grid_for<WG>(n, kGridWG), kCheckWG)), dim3(WG), 0, s, j.rows, j.cols, j.rpt, j.ni, j.I, j.nj, j.J, upr, mult, st);
         G4S_HIP_TRY(hipGetLastError());
         G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(upr), uoff, (long long)j.ni + 1, s));
         if (j.J) G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(mult), jptr, (long long)j.cols + 1, s));
@@ -566,9 +504,9 @@ int symbolic_device(const Job &j, int32_t *crpt, int64_t *cnnz, g4s_extract_info
     G4S_HIP_TRY(reads.note(h, f.st));
     G4S_HIP_TRY(reads.note(units, f.uoff + j.ni));
     G4S_HIP_TRY(reads.wait());
-    f.work.idle = true;                                            // (an early return above leaves it false: the block is then released behind a device-wide wait)
+    f.work.idle();                                                 // (an early return above leaves it out: the block is then released behind a device-wide wait)
     if (h.fail) return contract_error(j, h.fail);
-    if (too_many_units(h.nnz_rows, j.ni)) return g4s::set_error(G4S_ERR_OVERFLOW, "%s: more than 2^31 work units", j.fn);
+    if (too_many_units(j.ni, h.nnz_rows)) return g4s::set_error(G4S_ERR_OVERFLOW, "%s: more than 2^31 work units", j.fn);
     report(info, h, units, j.J != nullptr, 1);
     *cnnz = (int64_t)h.cnnz;
     if (h.cnnz > (u64)INT32_MAX) return g4s::set_error(G4S_ERR_OVERFLOW, "%s: %llu entries exceed the int32 row pointers", j.fn, h.cnnz);
@@ -580,12 +518,17 @@ int sort_long_rows(const Job &j, const ExState &h, const int *lrows, int *llen, 
 {
     const long long ne = (long long)h.long_entries;
     const int nl = h.n_long;
-    const size_t eb = pad256(4 * (size_t)ne), lb = pad256(4 * ((size_t)nl + 1));
-    BigBuf buf;
-    G4S_TRY(buf.alloc(4 * eb + 2 * lb));
-    int32_t *rrow = reinterpret_cast<int32_t *>(at(buf, 0)), *rq = reinterpret_cast<int32_t *>(at(buf, eb)), *rsrc = reinterpret_cast<int32_t *>(at(buf, 2 * eb)),
-            *perm = reinterpret_cast<int32_t *>(at(buf, 3 * eb)), *rcrpt = reinterpret_cast<int32_t *>(at(buf, 4 * eb));
-    int *loff = reinterpret_cast<int *>(at(buf, 4 * eb + lb));
+    const size_t eb = 4 * (size_t)ne, lb = 4 * ((size_t)nl + 1);
+    int32_t *rrow, *rq, *rsrc, *perm, *rcrpt;
+    int *loff;
+    Carver buf;
+    buf.piece(&rrow, eb);
+    buf.piece(&rq, eb);
+    buf.piece(&rsrc, eb);
+    buf.piece(&perm, eb);
+    buf.piece(&rcrpt, lb);
+    buf.piece(&loff, lb);
+    G4S_TRY(buf.alloc());
     G4S_HIP_TRY(hipMemsetAsync(llen + nl, 0, 4, s));
     G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(llen), loff, (long long)nl + 1, s));
     hipLaunchKernelGGL(ex_long_gather_kernel, dim3(std::min(nl, kGridWG)), dim3(WG), 0, s, nl, lrows, static_cast<const int *>(loff), ne, crpt,
@@ -595,11 +538,11 @@ int sort_long_rows(const Job &j, const ExState &h, const int *lrows, int *llen, 
     g4s_coo_info ci{};
     G4S_TRY(g4s_csr_from_coo_symbolic(G4S_DUP_KEEP, nl, std::max(j.nj, 1), ne, rrow, rq, rcrpt, perm, &cn, G4S_DEVICE_POINTERS, &ci, s));
     *coo_waits = ci.host_waits;
-    hipLaunchKernelGGL(ex_long_apply_kernel, dim3(grid_for(ne)), dim3(WG), 0, s, nl, ne, lrows, static_cast<const int *>(loff), static_cast<const int32_t *>(perm),
+    hipLaunchKernelGGL(ex_long_apply_kernel, dim3(grid_for<WG>(ne, kGridWG)), dim3(WG), 0, s, nl, ne, lrows, static_cast<const int *>(loff), static_cast<const int32_t *>(perm),
                        static_cast<const int32_t *>(rrow), static_cast<const int32_t *>(rq), static_cast<const int32_t *>(rsrc), crpt, ccol, src);
     G4S_HIP_TRY(hipGetLastError());
     G4S_HIP_TRY(hipStreamSynchronize(s));                          // the block goes back idle; the caller's last wait follows at once
-    buf.idle = true;
+    buf.idle();
     return G4S_OK;
 }
 
@@ -619,9 +562,9 @@ int numeric_device(const Job &j, const int32_t *crpt, int32_t *ccol, double *cva
     G4S_HIP_TRY(reads.note(nc32, crpt + j.ni));
     G4S_HIP_TRY(reads.wait());
     ++waits;
-    auto refuse = [&](int st) { f.work.idle = true; return st; };
+    auto refuse = [&](int st) { f.work.idle(); return st; };
     if (h.fail) return refuse(contract_error(j, h.fail));
-    if (too_many_units(h.nnz_rows, j.ni)) return refuse(g4s::set_error(G4S_ERR_OVERFLOW, "%s: more than 2^31 work units", j.fn));
+    if (too_many_units(j.ni, h.nnz_rows)) return refuse(g4s::set_error(G4S_ERR_OVERFLOW, "%s: more than 2^31 work units", j.fn));
     if (nc32 < 0 || units < 0) return refuse(g4s::set_error(G4S_ERR_INVALID, "%s: crpt[ni] = %d is not an entry count: crpt must come from the symbolic call", j.fn, nc32));
     const long long nc = nc32, na = h.nnz_a;
     {
@@ -632,36 +575,42 @@ int numeric_device(const Job &j, const int32_t *crpt, int32_t *ccol, double *cva
     }
     const bool jl = j.J && h.j_unsorted;
     const int long_cap = (int)(nc / (kLdsMax + 1)) + 1;
-    const size_t ub = pad256(4 * ((size_t)units + 1)), nb = pad256(4 * ((size_t)j.ni + 1)), jb = jl ? pad256(4 * (size_t)j.nj) : 0,
-                 cb = jl ? pad256(4 * ((size_t)j.cols + 1)) : 0, sb = src ? 0 : pad256(4 * (size_t)nc), lb = pad256(4 * ((size_t)long_cap + 1));
-    BigBuf work;
-    G4S_TRY(work.alloc(2 * ub + 3 * nb + jb + cb + sb + 2 * lb));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = at(work, off); off += bytes; return p; };
-    unsigned *ucnt = reinterpret_cast<unsigned *>(take(ub)), *upos = reinterpret_cast<unsigned *>(take(ub));
-    int *rowflag = reinterpret_cast<int *>(take(nb)), *wlist = reinterpret_cast<int *>(take(nb)), *llist = reinterpret_cast<int *>(take(nb));
-    int *jlist = jl ? reinterpret_cast<int *>(take(jb)) : nullptr, *cursor = jl ? reinterpret_cast<int *>(take(cb)) : nullptr;
-    if (!src) src = reinterpret_cast<int32_t *>(take(sb));
-    int *lrows = reinterpret_cast<int *>(take(lb)), *llen = reinterpret_cast<int *>(take(lb));
-    G4S_HIP_TRY(hipMemsetAsync(ucnt, 0, 4 * ((size_t)units + 1), s));
-    G4S_HIP_TRY(hipMemsetAsync(rowflag, 0, 4 * ((size_t)j.ni + 1), s));
+    const size_t ub = 4 * ((size_t)units + 1), nb = 4 * ((size_t)j.ni + 1), cb = 4 * ((size_t)j.cols + 1), lb = 4 * ((size_t)long_cap + 1);
+    unsigned *ucnt, *upos;
+    int *rowflag, *wlist, *llist, *jlist = nullptr, *cursor = nullptr, *lrows, *llen;
+    Carver work;
+    work.piece(&ucnt, ub);
+    work.piece(&upos, ub);
+    work.piece(&rowflag, nb);
+    work.piece(&wlist, nb);
+    work.piece(&llist, nb);
     if (jl) {
-        G4S_HIP_TRY(hipMemsetAsync(cursor, 0, 4 * ((size_t)j.cols + 1), s));
-        hipLaunchKernelGGL(ex_jlist_kernel, dim3(grid_for(j.nj)), dim3(WG), 0, s, j.ni, j.nj, j.J, static_cast<const int *>(f.jptr), cursor, jlist, f.st);
+        work.piece(&jlist, 4 * (size_t)j.nj);
+        work.piece(&cursor, cb);
+    }
+    if (!src) work.piece(&src, 4 * (size_t)nc);
+    work.piece(&lrows, lb);
+    work.piece(&llen, lb);
+    G4S_TRY(work.alloc());
+    G4S_HIP_TRY(hipMemsetAsync(ucnt, 0, ub, s));
+    G4S_HIP_TRY(hipMemsetAsync(rowflag, 0, nb, s));
+    if (jl) {
+        G4S_HIP_TRY(hipMemsetAsync(cursor, 0, cb, s));
+        hipLaunchKernelGGL(ex_jlist_kernel, dim3(grid_for<WG>(j.nj, kGridWG)), dim3(WG), 0, s, j.ni, j.nj, j.J, static_cast<const int *>(f.jptr), cursor, jlist, f.st);
     }
     hipLaunchKernelGGL(ex_walk_kernel<COUNT_UNITS>, dim3(kGridWG), dim3(WG), 0, s, WALK_ARGS(j, f), (const int *)nullptr, static_cast<const int *>(f.uoff), units, ucnt,
                        (const unsigned *)nullptr, 0LL, (int32_t *)nullptr, (int32_t *)nullptr, f.st);
     G4S_HIP_TRY(hipGetLastError());
     G4S_TRY(g4s::prims::exclusive_scan(static_cast<const unsigned *>(ucnt), upos, (long long)units + 1, s));
-    hipLaunchKernelGGL(ex_crpt_kernel, dim3(grid_for((long long)j.ni + 1)), dim3(WG), 0, s, j.ni, static_cast<const int *>(f.uoff), units,
+    hipLaunchKernelGGL(ex_crpt_kernel, dim3(grid_for<WG>((long long)j.ni + 1, kGridWG)), dim3(WG), 0, s, j.ni, static_cast<const int *>(f.uoff), units,
                        static_cast<const unsigned *>(upos), crpt, f.st);
     hipLaunchKernelGGL(ex_walk_kernel<FILL>, dim3(kGridWG), dim3(WG), 0, s, WALK_ARGS(j, f), static_cast<const int *>(jlist), static_cast<const int *>(f.uoff), units,
                        (unsigned *)nullptr, static_cast<const unsigned *>(upos), nc, ccol, src, f.st);
-    hipLaunchKernelGGL(ex_order_kernel, dim3(grid_for(nc)), dim3(WG), 0, s, j.ni, nc, crpt, static_cast<const int32_t *>(ccol), rowflag, f.st);
-    hipLaunchKernelGGL(ex_classify_kernel, dim3(std::min(grid_for(j.ni), kClassifyWG)), dim3(WG), 0, s, j.ni, crpt, static_cast<const int *>(rowflag), wlist, llist, lrows, llen, long_cap, f.st);
+    hipLaunchKernelGGL(ex_order_kernel, dim3(grid_for<WG>(nc, kGridWG)), dim3(WG), 0, s, j.ni, nc, crpt, static_cast<const int32_t *>(ccol), rowflag, f.st);
+    hipLaunchKernelGGL(ex_classify_kernel, dim3(std::min(grid_for<WG>(j.ni, kGridWG), kClassifyWG)), dim3(WG), 0, s, j.ni, crpt, static_cast<const int *>(rowflag), wlist, llist, lrows, llen, long_cap, f.st);
     G4S_HIP_TRY(hipGetLastError());
     auto finish = [&]() -> int {                                     // the values, the copies for a caller with host arrays; then the state
-        if (cval) hipLaunchKernelGGL(ex_values_kernel, dim3(grid_for(nc)), dim3(WG), 0, s, j.ni, nc, na, static_cast<const int32_t *>(src), j.val, cval, f.st);
+        if (cval) hipLaunchKernelGGL(ex_values_kernel, dim3(grid_for<WG>(nc, kGridWG)), dim3(WG), 0, s, j.ni, nc, na, static_cast<const int32_t *>(src), j.val, cval, f.st);
         G4S_HIP_TRY(hipGetLastError());
         if (nc > 0) {
             if (h_ccol) G4S_HIP_TRY(hipMemcpyAsync(h_ccol, ccol, 4 * (size_t)nc, hipMemcpyDeviceToHost, s));
@@ -685,7 +634,8 @@ int numeric_device(const Job &j, const int32_t *crpt, int32_t *ccol, double *cva
         }
         G4S_TRY(finish());
     }
-    f.work.idle = work.idle = true;                                // (an early return above leaves them false: released behind a device-wide wait)
+    f.work.idle();                                                 // (an early return above leaves them out: released behind a device-wide wait)
+    work.idle();
     if (h.fail) return contract_error(j, h.fail);
     report(info, h, units, j.J != nullptr, waits);
     return G4S_OK;
@@ -708,26 +658,19 @@ int symbolic(const Job &j, int32_t *crpt, int64_t *cnnz, unsigned flags, g4s_ext
     *info = g4s_extract_info{};
     *cnnz = 0;
     if (dev) return symbolic_device(j, crpt, cnnz, info, s);
-    BigBuf d_rpt, d_col, d_i, d_j, d_crpt;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_rpt, j.rpt, rp, s));
-        G4S_TRY(upload(d_col, j.col, 4 * (size_t)na, s));
-        if (j.I) G4S_TRY(upload(d_i, j.I, 4 * (size_t)j.ni, s));
-        if (j.J) G4S_TRY(upload(d_j, j.J, 4 * (size_t)j.nj, s));
-        G4S_TRY(d_crpt.alloc(cp));
-        Job d = j;
-        d.rpt = d_rpt.as<int32_t>(); d.col = d_col.as<int32_t>(); d.val = nullptr;
-        d.I = j.I ? d_i.as<int32_t>() : nullptr; d.J = j.J ? d_j.as<int32_t>() : nullptr;
-        const int st = symbolic_device(d, d_crpt.as<int32_t>(), cnnz, info, s);
-        if (st != G4S_OK) return st;
-        G4S_HIP_TRY(hipMemcpyAsync(crpt, d_crpt.p, cp, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(hipStreamSynchronize(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_rpt, &d_col, &d_i, &d_j, &d_crpt}) b->idle = true;
-    return status;
+    Staged stage(s);
+    Job d = j;
+    d.rpt = stage.in(j.rpt, rp);
+    d.col = stage.in(j.col, 4 * (size_t)na);
+    d.val = nullptr;
+    d.I = stage.in(j.I, 4 * (size_t)j.ni);
+    d.J = stage.in(j.J, 4 * (size_t)j.nj);
+    int32_t *d_crpt = stage.out<int32_t>(cp);
+    int status = stage.error();
+    if (status == G4S_OK) status = symbolic_device(d, d_crpt, cnnz, info, s);
+    if (status == G4S_OK) status = stage.to_host(crpt, d_crpt, cp);
+    if (status == G4S_OK) status = stage.wait();
+    return stage.finish(status);
 }
 
 int numeric(const Job &j, const int32_t *crpt, int32_t *ccol, double *cval, int32_t *src, unsigned flags, g4s_extract_info *info, hipStream_t s)
@@ -748,27 +691,20 @@ int numeric(const Job &j, const int32_t *crpt, int32_t *ccol, double *cval, int3
     if (!info) info = &local;
     *info = g4s_extract_info{};
     if (dev) return numeric_device(j, crpt, ccol, cval, src, info, nullptr, nullptr, nullptr, s);
-    BigBuf d_rpt, d_col, d_val, d_i, d_j, d_crpt, d_ccol, d_cval, d_src;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_rpt, j.rpt, rp, s));
-        G4S_TRY(upload(d_col, j.col, 4 * (size_t)na, s));
-        if (j.val) G4S_TRY(upload(d_val, j.val, 8 * (size_t)na, s));
-        if (j.I) G4S_TRY(upload(d_i, j.I, 4 * (size_t)j.ni, s));
-        if (j.J) G4S_TRY(upload(d_j, j.J, 4 * (size_t)j.nj, s));
-        G4S_TRY(upload(d_crpt, crpt, cp, s));
-        G4S_TRY(d_ccol.alloc(4 * (size_t)nc));
-        if (cval) G4S_TRY(d_cval.alloc(8 * (size_t)nc));
-        if (src) G4S_TRY(d_src.alloc(4 * (size_t)nc));
-        Job d = j;
-        d.rpt = d_rpt.as<int32_t>(); d.col = d_col.as<int32_t>(); d.val = j.val ? d_val.as<double>() : nullptr;
-        d.I = j.I ? d_i.as<int32_t>() : nullptr; d.J = j.J ? d_j.as<int32_t>() : nullptr;
-        return numeric_device(d, d_crpt.as<int32_t>(), d_ccol.as<int32_t>(), cval ? d_cval.as<double>() : nullptr, src ? d_src.as<int32_t>() : nullptr, info, ccol, cval,
-                              src, s);
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_rpt, &d_col, &d_val, &d_i, &d_j, &d_crpt, &d_ccol, &d_cval, &d_src}) b->idle = true;
-    return status;
+    Staged stage(s);
+    Job d = j;
+    d.rpt = stage.in(j.rpt, rp);
+    d.col = stage.in(j.col, 4 * (size_t)na);
+    d.val = stage.in(j.val, 8 * (size_t)na);
+    d.I = stage.in(j.I, 4 * (size_t)j.ni);
+    d.J = stage.in(j.J, 4 * (size_t)j.nj);
+    const int32_t *d_crpt = stage.in(crpt, cp);
+    int32_t *d_ccol = stage.out<int32_t>(4 * (size_t)nc);
+    double *d_cval = cval ? stage.out<double>(8 * (size_t)nc) : nullptr;
+    int32_t *d_src = src ? stage.out<int32_t>(4 * (size_t)nc) : nullptr;
+    int status = stage.error();
+    if (status == G4S_OK) status = numeric_device(d, d_crpt, d_ccol, d_cval, d_src, info, ccol, cval, src, s);   // the copies to ccol / cval / src: its own
+    return stage.finish(status);
 }
 
 } // namespace

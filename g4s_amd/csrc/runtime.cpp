@@ -201,7 +201,8 @@ bool big_free(void *p, bool idle)
     }
     // nothing in flight may still touch the block when it is handed out again: synchronise the device that OWNS it
     // (idle: the caller has already synchronised the one stream the block was used on — a device-wide synchronisation costs ≈ 0.2 ms per block on
-    // this stack even when nothing runs, and a SpGEMM call releases a dozen blocks)
+    // this stack even when nothing runs, and a SpGEMM call releases a dozen blocks. For the device copies of a call with host pointers that promise is
+    // kept in one place, Staged::finish of call_util.hpp)
     if (!idle) {
         const int cur = current_device();
         if (cur != blk.device) (void)hipSetDevice(blk.device);

@@ -29,6 +29,7 @@
 #include "prims.hpp"
 #include "readback.hpp"
 #include "semiring.hpp"
+#include "call_util.hpp"
 #include <algorithm>
 #include <climits>
 
@@ -378,18 +379,6 @@ __global__ __launch_bounds__(64) void tc_sum_final_kernel(int nb, const long lon
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// A block of the library's caching allocator, handed back on every path. `idle`: the stream that used it has been synchronised.
-struct BigBuf {
-    void *p = nullptr;
-    bool idle = false;
-    BigBuf() = default;
-    BigBuf(const BigBuf &) = delete;
-    BigBuf &operator=(const BigBuf &) = delete;
-    ~BigBuf() { if (p) (void)g4s::big_free(p, idle); }
-    int alloc(size_t bytes) { return g4s::big_alloc(&p, bytes); }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 long long env_ll(const char *name, long long dflt, long long lo, long long hi)
 {
     const char *e = getenv(name);
@@ -407,8 +396,6 @@ Cuts read_cuts()
     c.split_ways = (int)env_ll("G4S_MASKED_SPLIT_WAYS", kSplitWays, 2, 4096);
     return c;
 }
-
-int grid_for(long long n) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, 8192LL)); }
 
 template <typename Kernel>
 int allow_lds(Kernel k, size_t bytes)
@@ -448,12 +435,6 @@ int launch_classes(const Operands &o, const int *list, const int *cnt, const Cut
     return G4S_OK;
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
-    return na && nb && x < y + nb && y < x + na;
-}
-
 // Everything on device arrays; returns with the stream synchronised (on success and on G4S_ERR_INVALID alike). The caller has ruled out a capture.
 int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipStream_t s)
 {
@@ -475,18 +456,22 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
         return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: cval overlaps an input array");
 
     const Cuts cuts = read_cuts();
-    BigBuf work;                                                   // the state, then four int arrays of M: keys, row ids, and both sorted
-    const size_t m4 = (sizeof(int) * (size_t)o.M + 255) / 256 * 256;
-    G4S_TRY(work.alloc(256 + 4 * m4));
-    OpenState *st = work.as<OpenState>();
-    int *keys = reinterpret_cast<int *>(work.as<char>() + 256), *ids = reinterpret_cast<int *>(work.as<char>() + 256 + m4);
-    int *keys_s = reinterpret_cast<int *>(work.as<char>() + 256 + 2 * m4), *list = reinterpret_cast<int *>(work.as<char>() + 256 + 3 * m4);
+    const size_t m4 = sizeof(int) * (size_t)o.M;
+    OpenState *st;
+    int *keys, *ids, *keys_s, *list;                               // four int arrays of M: keys, row ids, and both sorted
+    Carver work;
+    work.piece(&st, sizeof(OpenState));
+    work.piece(&keys, m4);
+    work.piece(&ids, m4);
+    work.piece(&keys_s, m4);
+    work.piece(&list, m4);
+    G4S_TRY(work.alloc());
     OpenState h{};
     G4S_HIP_TRY(hipMemsetAsync(st, 0, sizeof(OpenState), s));
     const unsigned ring = flags & G4S_SEMIRING_MASK;               // S::identity() on the host
     const double identity = ring == G4S_SEMIRING_MIN_PLUS ? __builtin_inf() : ring == G4S_SEMIRING_MAX_PLUS ? -__builtin_inf() : 0.0;
-    hipLaunchKernelGGL(mk_fill_kernel, dim3(grid_for(mnnz)), dim3(WG), 0, s, (long long)mnnz, identity, o.cval);
-    if (bnnz) hipLaunchKernelGGL(mk_check_b_kernel, dim3(grid_for(bnnz)), dim3(WG), 0, s, (long long)bnnz, o.N, o.bcol, st);
+    hipLaunchKernelGGL(mk_fill_kernel, dim3(grid_for<WG>(mnnz, 8192)), dim3(WG), 0, s, (long long)mnnz, identity, o.cval);
+    if (bnnz) hipLaunchKernelGGL(mk_check_b_kernel, dim3(grid_for<WG>(bnnz, 8192)), dim3(WG), 0, s, (long long)bnnz, o.N, o.bcol, st);
     const int rows_per_wg = WG / kOpenLpr;
     hipLaunchKernelGGL(mk_open_kernel, dim3((o.M + rows_per_wg - 1) / rows_per_wg), dim3(WG), 0, s, o.M, o.K, o.N, annz, bnnz, mnnz, o.arpt, o.acol, o.brpt, o.mrpt,
                        o.mcol, keys, ids, st, cuts);
@@ -494,8 +479,8 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
     G4S_HIP_TRY(reads.note(h, st));
     G4S_TRY(g4s::prims::sort_pairs_descending(keys, ids, keys_s, list, keys_s, list, o.M, 3, s));   // one pass: the partners are never written
     G4S_HIP_TRY(reads.wait());
-    if (h.invalid) work.idle = true;                               // refused: the wait has left the stream idle. (Any other early return leaves the flag
-    if (h.invalid & BAD_MASK)                                      // false, and the block is released behind a device-wide wait.)
+    if (h.invalid) work.idle();                                    // refused: the wait has left the stream idle. (Any other early return leaves it
+    if (h.invalid & BAD_MASK)                                      // out, and the block is released behind a device-wide wait.)
         return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: the mask is not a CSR pattern with strictly ascending rows and column ids in [0, %d)", o.N);
     if (h.invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: %s", (h.invalid & BAD_A) ? "a row pointer or column id of A is out of range"
                                                                                                       : "a row pointer or column id of B is out of range");
@@ -505,7 +490,7 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
         }));
     }
     G4S_HIP_TRY(hipStreamSynchronize(s));
-    work.idle = true;
+    work.idle();
     if (info) {
         info->products = (int64_t)h.products;
         info->rows_wave = h.counts[C_WAVE];
@@ -516,31 +501,20 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
     return G4S_OK;
 }
 
-int not_capturing(const char *fn, hipStream_t s)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads counts back and cannot be captured", fn);
-    return G4S_OK;
-}
-
-// host array → a block of the caching allocator, on the stream
-int upload(BigBuf &b, const void *src, size_t bytes, hipStream_t s)
-{
-    G4S_TRY(b.alloc(bytes));
-    if (bytes) G4S_HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return G4S_OK;
-}
-
 // The triangles of the strictly lower triangle L of an n × n pattern on the device: L compacted, Σ (L·L⟨L⟩) in int64.
 int triangles_device(int n, int nnz, const int *rowptr, const int *colids, int64_t *triangles, g4s_masked_info *info, hipStream_t s)
 {
-    BigBuf small, lcol, cval;
-    const size_t n4 = (sizeof(int) * ((size_t)n + 1) + 255) / 256 * 256;
-    G4S_TRY(small.alloc(256 + 2 * n4 + sizeof(long long) * (kSumBlocks + 1)));
-    OpenState *st = small.as<OpenState>();
-    int *lcnt = reinterpret_cast<int *>(small.as<char>() + 256), *lrpt = reinterpret_cast<int *>(small.as<char>() + 256 + n4);
-    long long *partial = reinterpret_cast<long long *>(small.as<char>() + 256 + 2 * n4);
+    BigBuf lcol, cval;
+    const size_t n4 = sizeof(int) * ((size_t)n + 1);
+    OpenState *st;
+    int *lcnt, *lrpt;
+    long long *partial;
+    Carver small;
+    small.piece(&st, sizeof(OpenState));
+    small.piece(&lcnt, n4);
+    small.piece(&lrpt, n4);
+    small.tail(&partial, sizeof(long long) * (kSumBlocks + 1));
+    G4S_TRY(small.alloc());
     g4s::ReadScope reads(s);
     int invalid = 0, lnnz = 0;
     long long total = 0;
@@ -551,7 +525,7 @@ int triangles_device(int n, int nnz, const int *rowptr, const int *colids, int64
     G4S_TRY(g4s::prims::exclusive_scan(static_cast<const int *>(lcnt), lrpt, (long long)n + 1, s));
     G4S_HIP_TRY(reads.note(invalid, &st->invalid));
     G4S_HIP_TRY(reads.fetch(lnnz, lrpt + n));
-    if (invalid || lnnz == 0) small.idle = true;                   // nothing more is enqueued, and the wait has left the stream idle (see masked_device)
+    if (invalid || lnnz == 0) small.idle();                        // nothing more is enqueued, and the wait has left the stream idle (see masked_device)
     if (invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_triangle_count: rows must be strictly ascending with column ids in [0, %d) and rowptr non-decreasing from 0", n);
     if (lnnz > 0) {
         G4S_TRY(lcol.alloc(sizeof(int) * (size_t)lnnz));
@@ -564,7 +538,8 @@ int triangles_device(int n, int nnz, const int *rowptr, const int *colids, int64
         hipLaunchKernelGGL(tc_sum_final_kernel, dim3(1), dim3(64), 0, s, kSumBlocks, partial, partial + kSumBlocks);
         G4S_HIP_TRY(hipGetLastError());
         G4S_HIP_TRY(reads.fetch(total, partial + kSumBlocks));
-        small.idle = lcol.idle = cval.idle = true;
+        small.idle();
+        lcol.idle = cval.idle = true;
     }
     *triangles = total;
     return G4S_OK;
@@ -593,30 +568,15 @@ G4S_API g4s_status g4s_spgemm_masked(int32_t M, int32_t K, int32_t N, const int3
     if (M == 0) return G4S_OK;
     const int annz = arpt[M], bnnz = K ? brpt[K] : 0, mnnz = mrpt[M];
     G4S_REQUIRE(annz >= 0 && bnnz >= 0 && mnnz >= 0, "a negative entry count");
-    BigBuf d_arpt, d_acol, d_aval, d_brpt, d_bcol, d_bval, d_mrpt, d_mcol, d_cval;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_arpt, arpt, sizeof(int) * ((size_t)M + 1), s));
-        G4S_TRY(upload(d_acol, acol, sizeof(int) * (size_t)annz, s));
-        G4S_TRY(upload(d_brpt, brpt, sizeof(int) * ((size_t)K + 1), s));
-        G4S_TRY(upload(d_bcol, bcol, sizeof(int) * (size_t)bnnz, s));
-        G4S_TRY(upload(d_mrpt, mrpt, sizeof(int) * ((size_t)M + 1), s));
-        G4S_TRY(upload(d_mcol, mcol, sizeof(int) * (size_t)mnnz, s));
-        if (aval) {
-            G4S_TRY(upload(d_aval, aval, sizeof(double) * (size_t)annz, s));
-            G4S_TRY(upload(d_bval, bval, sizeof(double) * (size_t)bnnz, s));
-        }
-        G4S_TRY(d_cval.alloc(sizeof(double) * (size_t)mnnz));
-        const Operands o{M, K, N, d_arpt.as<int>(), d_acol.as<int>(), d_aval.as<double>(), d_brpt.as<int>(), d_bcol.as<int>(), d_bval.as<double>(),
-                         d_mrpt.as<int>(), d_mcol.as<int>(), d_cval.as<double>()};
-        G4S_TRY(masked_device(o, flags, info, s));
-        if (mnnz) G4S_HIP_TRY(hipMemcpyAsync(cval, d_cval.p, sizeof(double) * (size_t)mnnz, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(hipStreamSynchronize(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    for (BigBuf *b : {&d_arpt, &d_acol, &d_aval, &d_brpt, &d_bcol, &d_bval, &d_mrpt, &d_mcol, &d_cval}) b->idle = true;
-    return status;
+    Staged stage(s);
+    const Operands o{M, K, N, stage.in(arpt, sizeof(int) * ((size_t)M + 1)), stage.in(acol, sizeof(int) * (size_t)annz), stage.in(aval, sizeof(double) * (size_t)annz),
+                     stage.in(brpt, sizeof(int) * ((size_t)K + 1)), stage.in(bcol, sizeof(int) * (size_t)bnnz), stage.in(bval, sizeof(double) * (size_t)bnnz),
+                     stage.in(mrpt, sizeof(int) * ((size_t)M + 1)), stage.in(mcol, sizeof(int) * (size_t)mnnz), stage.out<double>(sizeof(double) * (size_t)mnnz)};
+    int status = stage.error();
+    if (status == G4S_OK) status = masked_device(o, flags, info, s);
+    if (status == G4S_OK) status = stage.to_host(cval, o.cval, sizeof(double) * (size_t)mnnz);
+    if (status == G4S_OK) status = stage.wait();
+    return stage.finish(status);
 }
 
 G4S_API g4s_status g4s_triangle_count(int32_t n, const int32_t *rowptr, const int32_t *colids, int64_t *triangles, unsigned flags, g4s_masked_info *info,
@@ -639,14 +599,9 @@ G4S_API g4s_status g4s_triangle_count(int32_t n, const int32_t *rowptr, const in
     }
     const int nnz = rowptr[n];
     G4S_REQUIRE(nnz >= 0, "rowptr[n] is negative");
-    BigBuf d_rp, d_ci;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_rp, rowptr, sizeof(int) * ((size_t)n + 1), s));
-        G4S_TRY(upload(d_ci, colids, sizeof(int) * (size_t)nnz, s));
-        return triangles_device(n, nnz, d_rp.as<int>(), d_ci.as<int>(), triangles, info, s);
-    };
-    const int status = run();
-    (void)hipStreamSynchronize(s);
-    d_rp.idle = d_ci.idle = true;
-    return status;
+    Staged stage(s);
+    const int *d_rp = stage.in(rowptr, sizeof(int) * ((size_t)n + 1)), *d_ci = stage.in(colids, sizeof(int) * (size_t)nnz);
+    int status = stage.error();
+    if (status == G4S_OK) status = triangles_device(n, nnz, d_rp, d_ci, triangles, info, s);
+    return stage.finish(status);
 }

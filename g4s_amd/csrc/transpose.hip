@@ -29,7 +29,6 @@ namespace {
 constexpr int WG = 256;
 constexpr long long kMaxGrid = 16384;   // grid-stride kernels: at most 64 workgroups per CU of the 256
 
-inline int grid_for(long long n) { return (int)std::max(1LL, std::min((n + WG - 1) / WG, kMaxGrid)); }
 
 // fail bit 1: rowptr[0] != 0, rowptr[rows] != nnz or a decrease
 __global__ __launch_bounds__(WG) void tr_check_rowptr_kernel(int rows, long long nnz, const int32_t *__restrict__ rowptr, int *__restrict__ fail)
@@ -111,8 +110,8 @@ int transpose_device(int32_t rows, int32_t cols, int64_t nnz, const int32_t *row
     };
 #define TR_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return done(g4s::set_error(G4S_ERR_HIP, "g4s_csr_transpose: %s: %s", #expr, hipGetErrorString(e_))); } while (0)
     TR_TRY(hipMemsetAsync(counts, 0, sizeof(int) * ((size_t)cols + 5), s));   // the counts, their trailing 0 and the flags
-    hipLaunchKernelGGL(tr_check_rowptr_kernel, dim3(grid_for((long long)rows + 1)), dim3(WG), 0, s, rows, (long long)nnz, rowptr, fail);
-    if (nnz > 0) hipLaunchKernelGGL(tr_key_kernel, dim3(grid_for(nnz)), dim3(WG), 0, s, (long long)nnz, cols, colids, keys, idx, counts, fail);
+    hipLaunchKernelGGL(tr_check_rowptr_kernel, dim3(grid_for<WG>((long long)rows + 1, kMaxGrid)), dim3(WG), 0, s, rows, (long long)nnz, rowptr, fail);
+    if (nnz > 0) hipLaunchKernelGGL(tr_key_kernel, dim3(grid_for<WG>(nnz, kMaxGrid)), dim3(WG), 0, s, (long long)nnz, cols, colids, keys, idx, counts, fail);
     TR_TRY(hipGetLastError());
     int h_fail = 0;
     TR_TRY(hipMemcpyAsync(&h_fail, fail, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -126,8 +125,8 @@ int transpose_device(int32_t rows, int32_t cols, int64_t nnz, const int32_t *row
     const int key_bits = cols > 1 ? 32 - __builtin_clz((unsigned)(cols - 1)) : 1;
     st = g4s::prims::sort_pairs_descending(keys, idx, keys_out, perm, tmp_k, tmp_v, (int)nnz, key_bits, s);
     if (st != G4S_OK) return done(st);
-    if (tvalues) hipLaunchKernelGGL(tr_gather_kernel<true>, dim3(grid_for(nnz)), dim3(WG), 0, s, (long long)nnz, perm, row_of, values, tcolids, tvalues);
-    else hipLaunchKernelGGL(tr_gather_kernel<false>, dim3(grid_for(nnz)), dim3(WG), 0, s, (long long)nnz, perm, row_of, values, tcolids, tvalues);
+    if (tvalues) hipLaunchKernelGGL(tr_gather_kernel<true>, dim3(grid_for<WG>(nnz, kMaxGrid)), dim3(WG), 0, s, (long long)nnz, perm, row_of, values, tcolids, tvalues);
+    else hipLaunchKernelGGL(tr_gather_kernel<false>, dim3(grid_for<WG>(nnz, kMaxGrid)), dim3(WG), 0, s, (long long)nnz, perm, row_of, values, tcolids, tvalues);
     TR_TRY(hipGetLastError());
 #undef TR_TRY
     return done(G4S_OK);
@@ -140,7 +139,7 @@ int row_indices_device(int32_t rows, int64_t nnz, const int32_t *rowptr, int32_t
     G4S_TRY(flag.alloc(256));
     int fail = 0;
     G4S_HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), s));
-    hipLaunchKernelGGL(tr_check_rowptr_kernel, dim3(grid_for((long long)rows + 1)), dim3(WG), 0, s, rows, (long long)nnz, rowptr, flag.as<int>());
+    hipLaunchKernelGGL(tr_check_rowptr_kernel, dim3(grid_for<WG>((long long)rows + 1, kMaxGrid)), dim3(WG), 0, s, rows, (long long)nnz, rowptr, flag.as<int>());
     G4S_HIP_TRY(hipGetLastError());
     G4S_HIP_TRY(g4s::ReadScope(s).fetch(fail, flag.p));
     flag.idle = true;
@@ -168,19 +167,14 @@ G4S_API g4s_status g4s_csr_row_indices(int32_t rows, int64_t nnz, const int32_t 
     const hipStream_t s = g4s::as_stream(stream);
     G4S_TRY(not_capturing(__func__, s));
     if (dev) return row_indices_device(rows, nnz, rowptr, row_out, s);
-    BigBuf d_rp, d_out;
-    auto run = [&]() -> int {
-        G4S_TRY(upload(d_rp, rowptr, rp, s));
-        G4S_TRY(d_out.alloc(nb));
-        G4S_TRY(row_indices_device(rows, nnz, d_rp.as<int32_t>(), d_out.as<int32_t>(), s));
-        if (nb) G4S_HIP_TRY(hipMemcpyAsync(row_out, d_out.p, nb, hipMemcpyDeviceToHost, s));
-        G4S_HIP_TRY(hipStreamSynchronize(s));
-        return G4S_OK;
-    };
-    const int status = run();
-    if (status != G4S_OK) (void)hipStreamSynchronize(s);
-    d_rp.idle = d_out.idle = true;
-    return status;
+    Staged stage(s);
+    const int32_t *d_rp = stage.in(rowptr, rp);
+    int32_t *d_out = stage.out<int32_t>(nb);
+    int status = stage.error();
+    if (status == G4S_OK) status = row_indices_device(rows, nnz, d_rp, d_out, s);
+    if (status == G4S_OK) status = stage.to_host(row_out, d_out, nb);
+    if (status == G4S_OK) status = stage.wait();
+    return stage.finish(status);
 }
 
 namespace {
@@ -279,7 +273,7 @@ void transpose_work_view(const TransposeWork *w, const int32_t **rowptr, const i
 int transpose_update_values(TransposeWork *w, const double *values, hipStream_t s)
 {
     if (w->nnz > 0) {
-        hipLaunchKernelGGL(tr_refill_kernel, dim3(grid_for(w->nnz)), dim3(WG), 0, s, (long long)w->nnz, w->perm, values, w->values);
+        hipLaunchKernelGGL(tr_refill_kernel, dim3(grid_for<WG>(w->nnz, kMaxGrid)), dim3(WG), 0, s, (long long)w->nnz, w->perm, values, w->values);
         G4S_HIP_TRY(hipGetLastError());
     }
     return g4s_csr_update_values(w->inner, w->values, G4S_DEVICE_POINTERS, s);   // the same array: only the inner plan's own copy is refreshed

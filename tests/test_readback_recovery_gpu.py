@@ -8,6 +8,10 @@ PageRank and components find the violation on the device (the verdict comes back
 device-side refusal that fits in 64 rows (betweenness' only one, σ past the range of a double, takes 3 301), so theirs is the out-of-range source
 of test_traverse_gpu / test_betweenness_gpu, refused on the host.
 
+The host-pointer cases at the end go through the staging frame of the two-call builders (g4s_amd/csrc/call_util.hpp): the refused call hands its device
+copies back to the block cache, a valid call of the same sizes takes the same blocks out again, and a device-pointer call follows. One of their matrices
+has a row of 65 entries (two work units) and an empty row. Only the first of them ends with the 300-row product.
+
 Bit for bit: all values are small integers or dyadic fractions, so every sum is exact in float64 whatever its order — the float64 results and the
 longdouble references are the same numbers. PageRank: unit weights, out-degrees 0, 1, 2 and 4, damping 0.5, n = 64 = 2⁶; an iteration divides by at
 most 4, by 64 (dangling mass · p) and by 2: 9 more fraction bits, 6 + 4 · 9 = 42 < 53 after four iterations."""
@@ -18,7 +22,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import betweenness_ref, components_ref, ewise_ref, masked_ref, pagerank_ref, semiring_ref, traverse_ref
+from tests import betweenness_ref, components_ref, coo_ref, ewise_ref, extract_ref, masked_ref, pagerank_ref, semiring_ref, traverse_ref
+from tests import test_coo_gpu as coo_calls, test_ewise_gpu as ewise_calls, test_extract_gpu as extract_calls   # their ctypes wrappers of both pointer forms
 
 pytestmark = pytest.mark.gpu
 
@@ -212,3 +217,77 @@ def test_components(rank_product, monkeypatch, capfd):
     got = host.connected_components((t(rp), t(ci)))
     assert len(np.unique(want)) >= 4 and np.array_equal(got.cpu().numpy(), want)
     _then_the_rank_product(rank_product, monkeypatch, capfd)
+
+
+# ------------------------------------------------------------------------------------------------ host pointers: the staging frame after a refusal
+COLS = 128
+
+
+def _ragged(seed):
+    """64 × 128 with integer values: eight ascending columns a row, but 65 in row 5 (two work units) and none in row 6"""
+    rng = np.random.default_rng(seed)
+    lengths = np.full(N, 8)
+    lengths[5], lengths[6] = 65, 0
+    ci = np.concatenate([np.sort(rng.choice(COLS, n, replace=False)) for n in lengths]).astype(np.int32)
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32), ci, _ints(rng, ci.size)
+
+
+def _rowptr_from_one(A):
+    rp = A[0].copy()
+    rp[0] = 1
+    return rp, A[1], A[2]
+
+
+def test_ewise_host_pointers(rank_product, monkeypatch, capfd):
+    capi, _ = _host()
+    A, B = _square(11), _square(12)
+    want = ewise_ref.ewise(A, B, N, N, "union", "plus")
+    assert ewise_calls._ewise(_unsorted(A), B, N, N, "union", device=False)[0] == capi.ERR_INVALID        # found by the symbolic call on the device
+    assert ewise_calls._ewise(_rowptr_from_one(A), B, N, N, "union", device=False)[0] == capi.ERR_INVALID
+    for device in (False, True):
+        st, got, _ = ewise_calls._ewise(A, B, N, N, "union", "plus", device=device)
+        assert st == 0
+        ewise_calls._same(got, want, device)
+    _then_the_rank_product(rank_product, monkeypatch, capfd)
+
+
+def test_select_host_pointers():
+    capi, _ = _host()
+    A = _ragged(13)
+    want = ewise_ref.select(A, N, "triu", 3)
+    assert 0 < len(want[1]) < len(A[1]) and want[0][6] == want[0][7]
+    _refused(capi, lambda: ewise_calls._select(_rowptr_from_one(A), N, COLS, "triu", 3, device=False))
+    for device in (False, True):
+        ewise_calls._same(ewise_calls._select(A, N, COLS, "triu", 3, device=device), want, device)
+
+
+def test_from_coo_host_pointers():
+    capi, _ = _host()
+    rp, col, val = _ragged(14)
+    rng = np.random.default_rng(15)
+    order = rng.permutation(col.size + 40)                            # forty triples twice, in no order: the sort and the fold both run
+    row = np.concatenate([ewise_ref.row_of_entry(rp), ewise_ref.row_of_entry(rp)[:40]]).astype(np.int32)[order]
+    col, val = np.concatenate([col, col[:40]])[order], np.concatenate([val, val[:40]])[order]
+    want = coo_ref.from_coo(row, col, val, N, COLS, "plus")
+    assert len(want[1]) == rp[N] and np.diff(want[0])[5] == 65 and np.diff(want[0])[6] == 0
+    bad = row.copy()
+    bad[17] = N
+    assert coo_calls._symbolic(bad, col, N, COLS, "plus", device=False)[0] == capi.ERR_INVALID
+    for device in (False, True):
+        coo_calls._check(row, col, val, N, COLS, "plus", want, device=device)
+
+
+def test_extract_host_pointers():
+    capi, _ = _host()
+    A = _ragged(16)
+    rng = np.random.default_rng(17)
+    I, J = rng.permutation(N)[:48], rng.integers(0, COLS, 96)         # rows 5 and 6 among them, columns in no order with repeats
+    I[:2] = 5, 6
+    want = extract_ref.extract(A[0], A[1], A[2], N, COLS, I, J)
+    assert len(want[1]) > 0
+    bad = I.copy()
+    bad[9] = N
+    out = extract_calls._raw(A, N, COLS, bad, J, device=False)
+    assert out[0] == capi.ERR_INVALID and out[1] is None
+    for device in (False, True):
+        extract_calls._exact(extract_calls._raw(A, N, COLS, I, J, device=device), want)
