@@ -13,6 +13,7 @@ Names and argument meaning follow the reference so that tests read like tests of
                    mm/inc/CSC.h:513-690); csr_permute, csr_induced_subgraph and csr_submatrix are compositions of it
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
+  kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
   pagerank       — PageRank of a graph stored by out-edges (g4s_pagerank): one call, the loop, the dangling mass and the stop test on the device
   betweenness    — betweenness centrality from a list of sources (g4s_betweenness): Brandes' two sweeps per source, both on the device
@@ -215,6 +216,10 @@ class CSR:
         """Canonical labels of the weakly connected components of this square pattern — connected_components(self). Needs no plan: the handle
         is not touched."""
         return connected_components(self, symmetric, return_info)
+
+    def kcore(self, max_k=None, return_round=False, return_info=False):
+        """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
+        return kcore(self, max_k, return_round, return_info)
 
     def ewise(self, other, op="union", combine="plus", pattern_only=False, return_info=False):
         """self ∪ other, self ∩ other or self ∖ other as a new device CSR — csr_ewise(self, other, …)."""
@@ -661,6 +666,82 @@ def connected_components(A, symmetric=False, return_info=False):
         labels = torch.from_numpy(out[:n]).cuda()
     inf = {n_: getattr(info, n_) for n_, _ in capi.CCInfo._fields_}
     return (labels, inf) if return_info else labels
+
+
+def _pattern_of(A, what):
+    """(rowptr, colids, n) of a CSR or of a (rowptr, colids) pair; ValueError for a pair of the wrong length, an empty rowptr, a CSR that is not square"""
+    if isinstance(A, (tuple, list)):
+        if len(A) != 2:
+            raise ValueError("expected a CSR or a (rowptr, colids) pair")
+        rowptr, colids = A
+        n = int(rowptr.numel() if isinstance(rowptr, torch.Tensor) else np.asarray(rowptr).size) - 1
+        if n < 0:
+            raise ValueError("rowptr is empty: a pattern of n rows has n + 1 row pointers")
+        return rowptr, colids, n
+    if A.rows != A.cols:
+        raise ValueError(f"{what} needs a square pattern, not {A.rows} x {A.cols}")
+    return A.rowptr, A.colids, int(A.rows)
+
+
+def _is_count(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and v >= 0
+
+
+def kcore(A, max_k=None, return_round=False, return_info=False):
+    """core (int32 device tensor of n): core[v] = the largest k such that v belongs to a subgraph in which every vertex has at least k neighbours
+    (g4s_kcore) — networkx.core_number of the graph without self-loops. A is a CSR, or a (rowptr, colids) pair of int32 device tensors or of numpy
+    arrays (host pointers; the results come back on the device all the same), and holds the SYMMETRIC pattern of a simple undirected graph with
+    strictly ascending rows (csr_symmetrise gives one); a stored diagonal entry is ignored. max_k: peel the levels below it only — the vertices of the
+    max_k-core then get core = max_k and round = −1; None is the full decomposition. return_round=True adds round (int32 device tensor): the index of
+    the peel frontier that removed each vertex, a function of the graph alone. return_info=True adds the dict of g4s_kcore_info. Synchronous; no plan
+    is built. ValueError (before any GPU call) for a CSR that is not square, a max_k that is not a non-negative integer below 2^31, and return_round /
+    return_info that are not bools."""
+    if max_k is not None and not (_is_count(max_k) and max_k <= capi.KCORE_FULL):
+        raise ValueError(f"max_k must be None or a non-negative integer below 2^31, not {max_k!r}")
+    for name, v in (("return_round", return_round), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    rowptr, colids, n = _pattern_of(A, "a k-core decomposition")
+    _require_gpu()
+    cap = capi.KCORE_FULL if max_k is None else int(max_k)
+    info, null = capi.KCoreInfo(), C.c_void_p(0)
+    if isinstance(rowptr, torch.Tensor):
+        assert rowptr.is_cuda and colids.is_cuda and rowptr.dtype == torch.int32 and colids.dtype == torch.int32
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        core = torch.empty(n, dtype=torch.int32, device=rowptr.device)
+        rnd = torch.empty(n, dtype=torch.int32, device=rowptr.device) if return_round else None
+        capi.check(capi.load().g4s_kcore(n, _ptr_nn(rowptr), _ptr_nn(colids), cap, _ptr_nn(core), _ptr_nn(rnd) if return_round else null,
+                                         capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        out, out_r = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32)
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        capi.check(capi.load().g4s_kcore(n, P(rowptr), P(colids if colids.size else out), cap, P(out), P(out_r) if return_round else null,
+                                         capi.HOST_POINTERS, C.byref(info), _stream()))
+        core = torch.from_numpy(out[:n]).cuda()
+        rnd = torch.from_numpy(out_r[:n]).cuda() if return_round else None
+    res = (core,) + ((rnd,) if return_round else ()) + (({n_: getattr(info, n_) for n_, _ in capi.KCoreInfo._fields_},) if return_info else ())
+    return res[0] if len(res) == 1 else res
+
+
+def degeneracy_order(A):
+    """perm (int32 device tensor of n): the vertices sorted by (peel round, id) — a stable device sort of kcore's round. Every vertex has at most
+    core[v] <= degeneracy neighbours at or after its own position, so csr_permute(A, perm) is a matrix in which every row has at most `degeneracy`
+    entries at or right of its diagonal: the ordering a triangle count wants. A: as for kcore."""
+    _, rnd = kcore(A, return_round=True)
+    return torch.sort(rnd, stable=True).indices.to(torch.int32)
+
+
+def kcore_subgraph(A, k):
+    """(sub, ids): the k-core of the square device CSR A — its largest subgraph in which every vertex has at least k neighbours — as the subgraph induced
+    by the vertices ids (ascending; vertex ids[p] of A is vertex p of sub). A composition: kcore with max_k = k, which peels the levels below k only,
+    then csr_induced_subgraph on the vertices with core >= k. ValueError (before any GPU call) for a matrix that is not square and a k that is not a
+    non-negative integer below 2^31."""
+    if not (_is_count(k) and k <= capi.KCORE_FULL):
+        raise ValueError(f"k must be a non-negative integer below 2^31, not {k!r}")
+    if A.rows != A.cols:
+        raise ValueError(f"a k-core subgraph needs a square matrix, not {A.rows} x {A.cols}")
+    return csr_induced_subgraph(A, kcore(A, max_k=int(k)) >= int(k))
 
 
 # ------------------------------------------------------------------------------------------------ element-wise combination and select

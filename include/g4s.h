@@ -112,9 +112,9 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
- * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py —, every result compared bit for bit):
+ * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py —, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_kcore, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -685,6 +685,57 @@ typedef struct g4s_cc_info {
 } g4s_cc_info;               /* 40 bytes */
 g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, const int32_t *colids,
                                     int32_t *labels, unsigned flags, g4s_cc_info *info, void *stream);
+
+/* k-core decomposition: core[v] (n int32, device or host like the other arrays, only written) = the largest k such that v belongs to a subgraph in
+ * which every vertex has at least k neighbours — what networkx.core_number returns on the graph without self-loops; an isolated vertex has core 0.
+ * Raw arrays, no handle, no plan, no values: the call reads the pattern only.
+ *   Pattern: the adjacency of a simple undirected graph. Rows strictly ascending with ids in [0, n), rowptr non-decreasing from 0: all of it checked
+ *     on the device before any id is an index (G4S_ERR_INVALID, outputs unspecified afterwards: the rule of g4s_triangle_count). The caller declares
+ *     the pattern symmetric; symmetry is not checked. On a pattern that is not, the call still terminates and writes core[v] in [0, row length], but
+ *     the values are outside the contract. A stored diagonal entry is ignored: not counted in a degree, not walked.
+ *   round[v] (n int32, may be NULL): the graph is peeled level by level — k = the smallest remaining degree, never decreasing — and inside a level
+ *     frontier by frontier: a frontier is ALL remaining vertices of degree <= k, removed at once; the next frontier is the vertices that this removal
+ *     brought to <= k. round[v] is the 0-based index, over the whole call, of the non-empty frontier that removed v. That partition is a function of
+ *     the graph alone, so core and round are the same on every run, stream and launch grid and are compared with ==. Sorting the vertices by
+ *     (round, id) gives a degeneracy ordering: every vertex has at most core[v] neighbours at or after its own position.
+ *   max_k: only the levels k < max_k are peeled. The vertices still present afterwards — exactly the max_k-core — get core = max_k and round = −1, and
+ *     info.capped = 1. INT32_MAX asks for the full decomposition; a negative max_k is G4S_ERR_INVALID.
+ *   Checks before any HIP call (G4S_ERR_INVALID): any flag bit other than G4S_DEVICE_POINTERS, a NULL rowptr or core, a NULL colids with n > 0, a
+ *     negative n or max_k, and with host pointers outputs that overlap the inputs or each other. n == 0 is valid and writes nothing; nnz == 0 is
+ *     valid: every core is 0 and every round is 0. info may be NULL.
+ *   Algorithm: deg[v] = row length minus the diagonal. A scan over all vertices collects those with deg <= k into the frontier; when it
+ *     collects none it raises k to the smallest remaining degree, so a non-empty level costs at most two scans. A peel walks the frontier's rows
+ *     balanced over entries (rows above 4096 entries in chunks of 1024 over all workgroups): a plain load of deg[v], skipped when <= k, else one
+ *     atomic decrement — the lane that brings v from k + 1 to k appends it. Every vertex is queued once, so one array of n ints holds all frontiers.
+ *   Synchronous: runs on `stream` and returns when core, round and info are complete. Scans and peels are enqueued blind in batches of at least
+ *     G4S_KCORE_BATCH launches (doubling to 64) with one read of the 104-byte state per batch: info.host_waits <= info.launches / 16 + 2. The peel
+ *     grid follows the frontier seen at the last read; a frontier that outgrows it stops the batch, which resumes on a larger grid (info.resumes).
+ *     On a capturing stream it returns G4S_ERR_INVALID and enqueues nothing. Scratch — a 256-byte state block, 4·n bytes of remaining degrees, 4·n
+ *     for the queue, two lists of 4·min(n, 2^19) for long rows, plus device copies of the arrays with host pointers — comes from the library's
+ *     caching allocator and is released before the call returns. No process-wide state: different host threads may call at the same time.
+ *   Environment: G4S_KCORE_SCAN_WGS (the cap on the scan's workgroups, default one per CU), G4S_KCORE_MIN_GRID (the smallest peel grid,
+ *     default 8). The outputs do not depend on them.
+ *   Where it loses (profiles/kcore.txt, one MI355X): against the host loop of g4s_spmv on an alive vector plus torch compares it wins on all three
+ *     graphs measured — 18.8 against 61.2 ms on the 1000 × 1000 grid, 246 against 822 ms on configs[1] symmetrised — but only 1.6x on the symmetrised
+ *     R-MAT-20 (54.6 against 87.8 ms), and it runs far below the walk's own rate everywhere (0.29 G entries/s there): it is bound by the number of
+ *     dependent kernels, and inside the few dense rounds by one atomic per entry and one tail counter per append. A small-diameter graph of few dense
+ *     rounds is its worst case, a graph of many sparse levels pays two scans over all vertices per level. */
+#define G4S_KCORE_BATCH 16          /* step launches enqueued behind one read of the state, at least (doubles up to 64 within a call) */
+typedef struct g4s_kcore_info {
+    int64_t edges_walked;    /* stored entries walked by peel rounds                                  */
+    int64_t top_core_size;   /* vertices whose core number equals `degeneracy`                        */
+    int32_t degeneracy;      /* the largest core number written (max_k when capped)                   */
+    int32_t levels;          /* distinct k at which at least one vertex was removed                   */
+    int32_t rounds;          /* non-empty frontiers peeled = 1 + the largest value written to `round` */
+    int32_t scans;           /* passes over all vertices that did work                                */
+    int32_t launches;        /* kernels enqueued, those that returned at once included                */
+    int32_t resumes;         /* batches restarted because the frontier outgrew the launch grid        */
+    int32_t host_waits;      /* times the call waited for the device                                  */
+    int32_t capped;          /* 1: max_k ended the peeling with vertices left                         */
+} g4s_kcore_info;            /* 48 bytes */
+g4s_status g4s_kcore(int32_t n, const int32_t *rowptr, const int32_t *colids, int32_t max_k,
+                     int32_t *core, int32_t *round /* may be NULL */, unsigned flags,
+                     g4s_kcore_info *info /* may be NULL */, void *stream);
 
 /* Element-wise combination of two CSR matrices of the same shape, and filtering of one, on the device. Two calls each, on the model of
  * g4s_spgemm_symbolic / g4s_spgemm_numeric, with caller-allocated outputs: the symbolic call writes crpt (rows + 1) and *cnnz, the caller allocates

@@ -7,6 +7,7 @@
 //   SpMVSemiring(a,x,y,multop,addop)   the same over min-plus, max-plus or or-and (y := A ⊗ x, or y ⊕ (A ⊗ x))
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
+//   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 //   EWiseAdd / EWiseMult / EWiseDifference(a,b,c), Select(a,c,pred,k,thr), Symmetrise(a,c)   A ∪ B, A ∩ B, A ∖ B, a filter, A ∪ Aᵀ (g4s_csr_ewise_*, g4s_csr_select_*)
 //   graph, FromGraph(g,c,dup), FromCOO(…), ToCOO(a,row_out), SortAndMerge(a,c,dup)   an edge list to a CSR with repeats merged and back (CSR(graph&), mm/inc/CSR.h:255-329)
@@ -200,6 +201,20 @@ void ConnectedComponents(const CSR<IT, NT> &a, int32_t *labels, bool symmetric =
     int32_t none = 0;
     check(g4s_connected_components(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, a.rows ? labels : &none,
                                    G4S_HOST_POINTERS | (symmetric ? G4S_CC_SYMMETRIC : 0u), info, nullptr), "ConnectedComponents");
+}
+
+// core[v] (a.rows values) = the largest k such that v belongs to a subgraph of the simple undirected graph `a` in which every vertex has at least k
+// neighbours (g4s_kcore, host arrays): `a` holds the graph's symmetric pattern with ascending rows (Symmetrise gives one), a stored diagonal entry is
+// ignored. round (may be NULL): the index of the peel frontier that removed v; sorted by (round, id) the vertices are in a degeneracy ordering. max_k:
+// only the levels below it are peeled, what is left gets core = max_k and round = −1 (info->capped).
+template <typename IT, typename NT>
+void KCore(const CSR<IT, NT> &a, int32_t *core, int32_t *round = nullptr, int32_t max_k = INT32_MAX, g4s_kcore_info *info = nullptr)
+{
+    if (a.rows != a.cols) throw std::runtime_error("KCore: the pattern is not square");
+    const IT zero = 0;                                      // an empty CSR holds no arrays: nothing is read or written for rows == 0
+    int32_t none = 0;
+    check(g4s_kcore(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, max_k, a.rows ? core : &none, a.rows ? round : nullptr, G4S_HOST_POINTERS, info, nullptr),
+          "KCore");
 }
 
 // The wrapper the shipped benchmark calls: mkl(A,B,C,timing) (mm/inc/mkl_mult.h:113-124 ← mm/src/mkl_spgemm.cpp:67,74).
