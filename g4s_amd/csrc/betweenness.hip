@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "csr_handle.hpp"
 #include "frontier.hpp"
+#include "call_util.hpp"
 #include "betweenness.hpp"
 #include <algorithm>
 #include <climits>
@@ -34,10 +35,7 @@ namespace {
 
 using g4s::BcState;
 
-constexpr int kBatch = G4S_BC_BATCH;
-constexpr int kBatchMax = 64;
-constexpr long long kEdgesPerWg = 2048;   // the launch grid of a batch: one workgroup per 2048 frontier edges
-constexpr long long kGridGrowth = 8;      // stop = 4 once the frontier has 8 times the edges the grid was sized for
+constexpr int kBatch = G4S_BC_BATCH;      // forward launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
 
 static_assert(sizeof(BcState) == 104, "the host reads BcState as one small block");
 
@@ -113,32 +111,22 @@ __device__ __forceinline__ bool relax(int k, int v, double su, int d, const Arra
     return won;
 }
 
-// The end of a forward step: the block's share of the next frontier's out-edges and of the σ maximum, then the ticket; the last block turns the page.
+// The end of a forward step: the block's share of the next frontier's out-edges and of the σ maximum, then the ticket; the last block turns the page (turn_page).
 __device__ __forceinline__ void finish(const Arrays &w, long long deg_sum, double smax, int d, int end, const StepArgs a)
 {
     __shared__ long long s_red[WG / 64];
     __shared__ double s_max[WG / 64];
-    __shared__ int s_last;
     BcState *st = w.st;
-    for (int o = 32; o > 0; o >>= 1) {
-        deg_sum += __shfl_down(deg_sum, o);
-        smax = fmax(smax, __shfl_down(smax, o));
-    }
+    deg_sum = wave_sum(deg_sum);
+    smax = wave_max(smax);
     if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = deg_sum; s_max[threadIdx.x >> 6] = smax; }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
+    if (!turn_page(&st->tickets, [&] {
         long long sum = 0;
         double mx = 0.0;
         for (int i = 0; i < WG / 64; ++i) { sum += s_red[i]; mx = fmax(mx, s_max[i]); }
         if (sum) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)sum);
         if (mx > 0.0) atomicMax(&st->sigma_max_bits, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order as their bits
-        __threadfence();
-        s_last = atomicAdd(&st->tickets, 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last || threadIdx.x != 0) return;
-    __threadfence();
+    })) return;
     const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0);
     const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
     const int n_new = tail - end;
@@ -164,7 +152,7 @@ template <bool VALUES>
 __global__ __launch_bounds__(WG) void forward_kernel(const Arrays w, const StepArgs a)
 {
     BcState *st = w.st;
-    if (st->stop != 0 && !(st->stop == 4 && a.resume)) return;        // the same word for every block: it changes only after the last ticket
+    if (!step_runs(st->stop, a.resume)) return;
     const int d = st->depth, cur = st->cur;
     const int begin = w.level_start[d], end = w.level_start[d + 1];
     const int *hubs = cur ? w.hub1 : w.hub0;
@@ -276,7 +264,7 @@ __global__ __launch_bounds__(WG) void back_long_kernel(const Arrays w, int d, in
                 const double su = w.sigma[u];
                 double s = 0.0;
                 for (int k = b + t; k < e; k += WG) s += term<VALUES>(k, su, d, w);
-                for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+                s = wave_sum(s);
                 if ((t & 63) == 0) s_red[t >> 6] = s;
                 __syncthreads();
                 if (t == 0) {
@@ -301,7 +289,7 @@ __global__ __launch_bounds__(WG) void max_degree_kernel(int rows, const int *__r
 {
     int m = 0;
     for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) m = max(m, rowptr[i + 1] - rowptr[i]);
-    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_down(m, o));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&st->max_degree, m);
 }
 
@@ -315,26 +303,15 @@ struct BcWork {
     unsigned char *lpr = nullptr; // lanes per vertex of every level's backward step (n + 2 bytes)
     double *vec = nullptr;        // sigma | delta | acc, n doubles each
     BcState *state = nullptr;
-    int cus = 1;
     int hub_cap = 1;
     int max_degree = 0;
     ZeroScan zeros;               // is a stored value 0.0? the kernels then have to read the values
     int64_t n = 0;
-    int64_t bytes = 0;
+    DevicePieces mem;             // owns the arrays above
 };
 
-void betweenness_work_destroy(BcWork *w)
-{
-    if (!w) return;
-    (void)hipFree(w->ints);
-    (void)hipFree(w->lpr);
-    (void)hipFree(w->vec);
-    (void)hipFree(w->state);
-    delete w;
-}
-
-long long betweenness_work_bytes(const BcWork *w) { return w ? w->bytes : 0; }
-
+void betweenness_work_destroy(BcWork *w) { delete w; }
+long long betweenness_work_bytes(const BcWork *w) { return w ? w->mem.bytes : 0; }
 void betweenness_values_changed(BcWork *w) { if (w) w->zeros.changed(); }
 
 } // namespace g4s
@@ -345,35 +322,27 @@ namespace {
 int reserve(g4s_csr_s *A)
 {
     if (!A->bc) {
-        g4s::BcWork *w = new (std::nothrow) g4s::BcWork();
+        std::unique_ptr<g4s::BcWork> w(new (std::nothrow) g4s::BcWork());
         if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
         const size_t n = (size_t)std::max(A->rows, 1);
         w->n = (int64_t)n;
         w->hub_cap = (int)std::min<int64_t>((int64_t)n, A->nnz / (kHubCut + 1)) + 1;
         const size_t n_ints = 3 * n + 2 + 2 * (size_t)w->hub_cap;
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->ints, sizeof(int32_t) * n_ints);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->lpr, n + 2);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->vec, sizeof(double) * 3 * n);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->state, sizeof(BcState));
-        if (e == hipSuccess) e = hipMemset(w->state, 0, sizeof(BcState));
-        if (e == hipSuccess && A->rows > 0) {
-            hipLaunchKernelGGL(max_degree_kernel, dim3(grid_rows(A->rows, std::max(w->cus, 1))), dim3(WG), 0, nullptr, A->rows, A->d_rowptr, w->state);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpy(&w->max_degree, &w->state->max_degree, sizeof(int), hipMemcpyDeviceToHost);
+        w->mem.take(&w->ints, sizeof(int32_t) * n_ints);
+        w->mem.take(&w->lpr, n + 2);
+        w->mem.take(&w->vec, sizeof(double) * 3 * n);
+        w->mem.take(&w->state, sizeof(BcState));
+        if (w->mem.ok()) w->mem.note(hipMemset(w->state, 0, sizeof(BcState)));
+        if (w->mem.ok() && A->rows > 0) {
+            hipLaunchKernelGGL(max_degree_kernel, dim3(grid_rows(A->rows, w->mem.cus)), dim3(WG), 0, nullptr, A->rows, A->d_rowptr, w->state);
+            w->mem.note(hipGetLastError());
+            if (w->mem.ok()) w->mem.note(hipMemcpy(&w->max_degree, &w->state->max_degree, sizeof(int), hipMemcpyDeviceToHost));
         }
-        if (e != hipSuccess) {
-            g4s::betweenness_work_destroy(w);
-            return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "g4s_csr_betweenness_reserve: %s", hipGetErrorString(e));
-        }
-        w->cus = std::max(w->cus, 1);
-        w->bytes = (int64_t)sizeof(int32_t) * (int64_t)n_ints + (int64_t)(n + 2) + (int64_t)sizeof(double) * 3 * (int64_t)n + (int64_t)sizeof(BcState);
-        A->bc = w;
+        if (!w->mem.ok()) return w->mem.report("g4s_csr_betweenness_reserve");
+        A->bc = w.release();
     }
     g4s::BcWork *w = A->bc;
-    return w->zeros.scan(A->nnz, A->d_values, w->cus, &w->state->zero_values, nullptr, nullptr);
+    return w->zeros.scan(A->nnz, A->d_values, w->mem.cus, &w->state->zero_values, nullptr, nullptr);
 }
 
 int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double scale, double *bc, unsigned flags, g4s_bc_info *info, hipStream_t s)
@@ -382,9 +351,7 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
     if (A->rows != A->cols) return g4s::set_error(G4S_ERR_INVALID, "%s: the handle is %d x %d, betweenness needs a square matrix", fn, A->rows, A->cols);
     for (int32_t i = 0; i < n_sources; ++i)
         if (sources[i] < 0 || sources[i] >= A->rows) return g4s::set_error(G4S_ERR_INVALID, "%s: sources[%d] = %d is outside [0, %d)", fn, i, sources[i], A->rows);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its state back and cannot be captured", fn);
+    G4S_TRY(not_capturing(fn, s, "its state"));
     if (info) *info = g4s_bc_info{};
     if (!A->bc) G4S_TRY(reserve(A));
     g4s::BcWork *wk = A->bc;
@@ -403,26 +370,25 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
     // New values since the last verdict: the scan runs in front of the first traversal, which reads the values whatever it will say; the verdict
     // comes back with the first state read, so it costs no wait of its own.
     const bool rescan = wk->zeros.state == 0;
-    if (rescan && A->nnz > 0) G4S_HIP_TRY(wk->zeros.enqueue(A->nnz, A->d_values, wk->cus, &st->zero_values, s));
+    if (rescan && A->nnz > 0) G4S_HIP_TRY(wk->zeros.enqueue(A->nnz, A->d_values, wk->mem.cus, &st->zero_values, s));
     const bool values = wk->zeros.state != 1;
     const bool has_hubs = wk->max_degree > kHubCut;
-    const int min_grid = 8;
-    const int max_grid = (int)std::max<long long>(min_grid, std::min<long long>(2LL * wk->cus, (A->nnz + rows + kEdgesPerWg - 1) / kEdgesPerWg));
+    using g4s::kEdgesPerWg;                                                // the forward grid: 8 workgroups to two per CU, and no more than the graph is work for
+    const g4s::StepGrid sized(g4s::kMinGrid, (int)std::min<long long>(2LL * wk->mem.cus, (A->nnz + rows + kEdgesPerWg - 1) / kEdgesPerWg));
 
     g4s::ReadScope reads(s);
     BcState h{};
     int waits = 0;
     for (int32_t i = 0; i < n_sources; ++i) {
         const int src = sources[i];
-        hipLaunchKernelGGL(init_kernel, dim3(grid_rows(rows, wk->cus)), dim3(WG), 0, s, w, src, (int)(i == 0));
+        hipLaunchKernelGGL(init_kernel, dim3(grid_rows(rows, wk->mem.cus)), dim3(WG), 0, s, w, src, (int)(i == 0));
         G4S_HIP_TRY(hipGetLastError());
         bool know = false, outgrown = false;                               // h is this traversal's state; a frontier outgrew a sized grid once
         int batch = kBatch;
         for (;;) {
-            int grid = max_grid;
-            if (know && !outgrown) grid = (int)std::max((long long)min_grid, std::min((long long)max_grid, (h.edges_cur + h.n_cur) / kEdgesPerWg));
+            const int grid = know && !outgrown ? sized.grid(h.edges_cur + h.n_cur) : sized.max_grid;
             StepArgs a;
-            a.grid_cap = grid == max_grid ? LLONG_MAX : (long long)grid * kEdgesPerWg * kGridGrowth;
+            a.grid_cap = sized.cap(grid);
             for (int b = 0; b < batch; ++b) {
                 a.resume = b == 0;
                 if (values) hipLaunchKernelGGL(forward_kernel<true>, dim3(grid), dim3(WG), 0, s, w, a);
@@ -434,7 +400,7 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
             if (rescan) wk->zeros.state = h.zero_values ? 2 : 1;
             if (h.stop == 1) break;
             if (h.stop == 4) outgrown = true;                              // the rest of this traversal runs on the full grid: one resume per source
-            if (know) batch = std::min(kBatchMax, batch * 2);
+            if (know) batch = sized.next_batch(batch);
             know = true;
         }
         double smax;
@@ -442,8 +408,8 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
         if (!(smax < (double)INFINITY))
             return g4s::set_error(G4S_ERR_OVERFLOW, "%s: the number of shortest paths from sources[%d] = %d exceeds the range of a double", fn, i, src);
         const int D = h.depth;
-        const int gb = (int)std::max(1LL, std::min(4LL * wk->cus, (h.edges_level_max + h.width_max + kEdgesPerWg - 1) / kEdgesPerWg));
-        const int gl = (int)std::max(1LL, std::min(4LL * wk->cus, ((long long)h.width_max + WG - 1) / WG));
+        const int gb = (int)std::max(1LL, std::min(4LL * wk->mem.cus, (h.edges_level_max + h.width_max + kEdgesPerWg - 1) / kEdgesPerWg));
+        const int gl = (int)std::max(1LL, std::min(4LL * wk->mem.cus, ((long long)h.width_max + WG - 1) / WG));
         for (int d = D - 1; d >= 1; --d) {
             if (values) hipLaunchKernelGGL(backward_kernel<true>, dim3(gb), dim3(WG), 0, s, w, d, src);
             else hipLaunchKernelGGL(backward_kernel<false>, dim3(gb), dim3(WG), 0, s, w, d, src);
@@ -454,7 +420,7 @@ int betweenness(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double 
         }
         G4S_HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(epilogue_kernel, dim3(grid_rows(rows, wk->cus)), dim3(WG), 0, s, rows, scale, (int)((flags & G4S_BC_ACCUMULATE) != 0), (const double *)w.acc, bc);
+    hipLaunchKernelGGL(epilogue_kernel, dim3(grid_rows(rows, wk->mem.cus)), dim3(WG), 0, s, rows, scale, (int)((flags & G4S_BC_ACCUMULATE) != 0), (const double *)w.acc, bc);
     G4S_HIP_TRY(hipGetLastError());
     G4S_HIP_TRY(reads.wait());
     ++waits;

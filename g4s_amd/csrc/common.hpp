@@ -54,6 +54,16 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// The compute units of the current device, at least 1.
+inline hipError_t device_cus(int *cus)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess || *cus < 1) *cus = 1;
+    return e;
+}
+
 // 8 XCDs, each with its own L2: block b and b+8 share one (MI355X_MICROARCH.md, Workgroup dispatch).
 constexpr int kXcds = 8;
 

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(WG) void cc_pick_kernel(int n, const int *__restric
         const unsigned long long key = ((unsigned long long)c << 32) | (unsigned)(INT_MAX - l);
         best = key > best ? key : best;
     }
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_down(best, o); best = y > best ? y : best; }
+    best = wave_max(best);
     if ((t & 63) == 0) s_red[t >> 6] = best;
     __syncthreads();
     if (t == 0) {
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(WG) void cc_pick_kernel(int n, const int *__restric
 __device__ __forceinline__ void add_linked(long long linked, CcState *st)
 {
     __shared__ long long s_lk[WG / 64];
-    for (int o = 32; o > 0; o >>= 1) linked += __shfl_down(linked, o);
+    linked = wave_sum(linked);
     if ((threadIdx.x & 63) == 0) s_lk[threadIdx.x >> 6] = linked;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(WG) void cc_count_kernel(int n, const int *__restri
             m &= ~same;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) { roots += __shfl_down(roots, o); bigc += __shfl_down(bigc, o); }
+    roots = wave_sum(roots), bigc = wave_sum(bigc);
     if (lane == 0) { s_red[0][threadIdx.x >> 6] = roots; s_red[1][threadIdx.x >> 6] = bigc; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(WG) void cc_largest_kernel(int n, const int *__rest
         const unsigned long long key = ((unsigned long long)(unsigned)count[v] << 32) | (unsigned)(INT_MAX - (int)v);
         best = key > best ? key : best;
     }
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_down(best, o); best = y > best ? y : best; }
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -1,5 +1,6 @@
 // csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip,
-// traverse.hip, pagerank.hip, betweenness.hip. The device code that traverse.hip and betweenness.hip share (and components.hip, which has no handle) is frontier.hpp.
+// traverse.hip, pagerank.hip, betweenness.hip. The device arrays of the last three's workspaces have one owner, DevicePieces below. What
+// traverse.hip and betweenness.hip share with kcore.hip and components.hip, which have no handle, is frontier.hpp (device) and step_batch.hpp (host).
 #pragma once
 #include "common.hpp"
 #include "spmv_stream.hpp"
@@ -7,6 +8,7 @@
 #include "spmv_dia.hpp"
 #include "spmv_bcsr.hpp"
 #include <functional>
+#include <memory>
 
 namespace g4s {
 
@@ -66,6 +68,31 @@ struct g4s_csr_s {
 };
 
 namespace g4s {
+
+// What TraverseWork, PagerankWork and BcWork hold: one device_malloc per take(), all freed with the owner. The first failure is kept — the CU
+// count's, a take's or a noted call's — and every take() behind it does nothing; `bytes` sums what was allocated (g4s_csr_info.plan_bytes).
+class DevicePieces {
+    static constexpr int kMost = 8;   // TraverseWork takes five; a take() past kMost is a mistake in this library, reported as hipErrorInvalidValue
+    void *p_[kMost];
+    int n_ = 0;
+    hipError_t err_;
+public:
+    int cus = 1;          // compute units of the device
+    int64_t bytes = 0;    // allocated by take()
+    DevicePieces() { err_ = device_cus(&cus); }
+    DevicePieces(const DevicePieces &) = delete;
+    ~DevicePieces() { for (int i = 0; i < n_; ++i) (void)hipFree(p_[i]); }
+    template <typename T> void take(T **ptr, size_t n_bytes)
+    {
+        if (err_ == hipSuccess) err_ = n_ < kMost ? device_malloc(&p_[n_], n_bytes) : hipErrorInvalidValue;
+        if (err_ != hipSuccess) return;
+        *ptr = static_cast<T *>(p_[n_++]);
+        bytes += (int64_t)n_bytes;
+    }
+    void note(hipError_t e) { if (err_ == hipSuccess) err_ = e; }   // a call that belongs to building the workspace
+    bool ok() const { return err_ == hipSuccess; }
+    int report(const char *fn) const { return set_error(err_ == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "%s: %s", fn, hipGetErrorString(err_)); }
+};
 
 int csr_spmv_path(const g4s_csr_s *A);   // g4s_csr_info.spmv_path: 0 row-streaming, 1 blocked, 3 diagonal, 4 block-row
 

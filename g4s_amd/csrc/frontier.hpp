@@ -1,13 +1,15 @@
-// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, components.hip): the walk over the entries of a
-// level's rows, balanced over entries (walk_tiles for ordinary rows, walk_hubs for long ones), the one-atomicAdd-per-wave append, the scan for
-// stored zeros and the row grid. What a row is, what travels with it (the payload) and what happens per entry stay with the caller, as callables.
+// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, kcore.hip, components.hip): the walk over the entries
+// of a level's rows, balanced over entries (walk_tiles for ordinary rows, walk_hubs for long ones), the one-atomicAdd-per-wave append, the two ends of
+// a step kernel (step_runs; turn_page: the last workgroup to take a ticket turns the page of the state block), the scan for stored zeros and the row
+// grid; what a row is, its payload, what happens per entry and what a page turn writes stay with the caller, as callables. It brings along WG and the
+// wave reductions (wave_reduce.hpp, which pagerank.hip takes alone) and the host side of the stepped loop (step_batch.hpp).
 #pragma once
-#include "common.hpp"
 #include "readback.hpp"
+#include "step_batch.hpp"
+#include "wave_reduce.hpp"
 
 namespace {
 
-constexpr int WG = 256;
 // A row above kHubCut entries is a hub. Inside a tile a row is one lane's binary-search interval and a tile is one workgroup's loop, so one long row
 // would hold a whole workgroup while the others idle; a hub is walked by ALL workgroups instead, kHubChunk entries per visit. 4096 = 16 rounds of a
 // workgroup: above it the row is worth the hub loop's header loads in every workgroup, and 256 rows of at most 4096 entries keep a tile's scan total
@@ -112,6 +114,37 @@ __device__ __forceinline__ int wave_append(bool want, int *counter)
     if (lane == leader) base = atomicAdd(counter, __popcll(m));
     base = __shfl(base, leader);
     return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// May a resumable step kernel run? `stop` is the state's word, the same for every block (it changes only after the last ticket): 0 goes on, 4 (the
+// frontier outgrew the launch grid) goes on in the first launch of the next batch, which the host marks `resume`; every other value ends the steps.
+__device__ __forceinline__ bool step_runs(int stop, int resume) { return stop == 0 || (stop == 4 && resume); }
+
+// The end of a step kernel, called by every thread of every workgroup once its waves' shares are in the caller's LDS slots: thread 0 publishes the
+// workgroup's share (`publish()`: atomics on the caller's state) and takes a ticket; true for thread 0 of the workgroup that took the last one, which
+// then turns the page: it reads the totals back with atomicAdd(…, 0), writes the next step's state with plain stores and sets *tickets = 0 for the
+// next kernel. Nobody waits for anybody. This is the only ordering between workgroups inside a kernel:
+//   the first fence, by every thread in front of the barrier, makes the workgroup's own stores and appends visible device-wide before thread 0 can
+//     take the ticket (the XCDs' L2s are not coherent with each other for plain stores); the barrier also hands the LDS slots to thread 0;
+//   the second fence orders thread 0's publishing atomics before its ticket, so whoever sees the ticket sees them;
+//   the ticket is a device-scope atomic on one word: exactly one workgroup reads gridDim.x − 1, and every other ticket came before it;
+//   the closing fence keeps the winner's reads behind its ticket, and those reads are atomics, performed in memory and not in a cache that may hold
+//     an older copy (a plain load of what another workgroup wrote in this kernel may be stale). The next kernel reads what it writes.
+template <typename Publish>
+__device__ __forceinline__ bool turn_page(int *tickets, Publish publish)
+{
+    __shared__ int s_last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        publish();
+        __threadfence();
+        s_last = atomicAdd(tickets, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last || threadIdx.x != 0) return false;
+    __threadfence();
+    return true;
 }
 
 // *flag |= 1 when a stored value is 0.0: or-and takes a stored zero for no edge, so the kernels of such a matrix have to read the values

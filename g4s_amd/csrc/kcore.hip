@@ -33,11 +33,8 @@ namespace {
 
 using g4s::KcState;
 
-constexpr int kBatch = G4S_KCORE_BATCH;      // step launches behind one state read, at least; doubles up to kBatchMax
-constexpr int kBatchMax = 64;
+constexpr int kBatch = G4S_KCORE_BATCH;      // step launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
 constexpr int kHubCap = 1 << 19;             // rows above kHubCut entries: fewer than 2^31 / 4096
-constexpr long long kEdgesPerWg = 2048;      // the peel grid of a batch: one workgroup per 2048 frontier entries, between 8 and two per CU
-constexpr long long kGridGrowth = 8;         // stop = 4 once a frontier has 8 times the entries the grid was sized for
 constexpr int kScanUnroll = 4;                // vertices per thread and trip of a scan
 constexpr size_t kStateBytes = 256;
 static_assert(sizeof(KcState) <= kStateBytes, "state block");
@@ -71,22 +68,16 @@ __device__ __forceinline__ void append(bool want, int v, int len, const StepArgs
     if (want) len_sum += len;
 }
 
-// The end of a step kernel: the block's shares of the sums and of the minimum, then the ticket; the last block to arrive turns the page.
+// The end of a step kernel: the block's shares of the sums and of the minimum, then the ticket; the last block to arrive turns the page (turn_page).
 __device__ __forceinline__ void finish(KcState *st, long long len_sum, long long walked, int mn, int kind, const StepArgs a)
 {
     __shared__ long long s_len[WG / 64], s_walk[WG / 64];
     __shared__ int s_min[WG / 64];
-    __shared__ int s_last;
-    for (int o = 32; o > 0; o >>= 1) {
-        len_sum += __shfl_down(len_sum, o);
-        walked += __shfl_down(walked, o);
-        const int y = __shfl_down(mn, o);
-        mn = y < mn ? y : mn;
-    }
+    len_sum = wave_sum(len_sum);
+    walked = wave_sum(walked);
+    mn = wave_min(mn);
     if ((threadIdx.x & 63) == 0) { s_len[threadIdx.x >> 6] = len_sum; s_walk[threadIdx.x >> 6] = walked; s_min[threadIdx.x >> 6] = mn; }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
+    if (!turn_page(&st->tickets, [&] {
         long long ls = 0, ws = 0;
         int m = INT_MAX;
         for (int w = 0; w < WG / 64; ++w) { ls += s_len[w]; ws += s_walk[w]; m = s_min[w] < m ? s_min[w] : m; }
@@ -95,12 +86,7 @@ __device__ __forceinline__ void finish(KcState *st, long long len_sum, long long
         // the word only decreases while the kernel runs, so a value read earlier is too large and costs one atomic; read at agent scope, past the
         // copy of the state line this CU has held since the kernel's first lines
         if (m < __hip_atomic_load(&st->min_deg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&st->min_deg, m);
-        __threadfence();
-        s_last = atomicAdd(&st->tickets, 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last || threadIdx.x != 0) return;
-    __threadfence();
+    })) return;
     const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0), m = atomicAdd(&st->min_deg, 0);
     const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
     const int got = tail - st->end;                                // what this kernel appended
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(WG) void kc_scan_kernel(const int *__restrict__ row
 __global__ __launch_bounds__(WG) void kc_peel_kernel(const int *__restrict__ rowptr, const int *__restrict__ colids, int *deg, int *core, int *round, int *queue,
                                                      int *hubs0, int *hubs1, KcState *st, const StepArgs a)
 {
-    if (st->invalid || st->end == st->head || (st->stop != 0 && !(st->stop == 4 && a.resume))) return;
+    if (st->invalid || st->end == st->head || !step_runs(st->stop, a.resume)) return;
     const int kk = st->k, r = st->round + 1, head = st->head;
     const int *hubs_cur = st->hub_cur ? hubs1 : hubs0;
     int *hubs_next = st->hub_cur ? hubs0 : hubs1;
@@ -279,7 +265,7 @@ __global__ __launch_bounds__(WG) void kc_finish_kernel(int n, int max_k, int *__
         if (x == -1) core[i] = x = max_k;
         c += x == top;
     }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -307,7 +293,7 @@ int run(int n, const int *rowptr, const int *colids, int max_k, int *core, int *
 {
     // a scan ends in one ticket per workgroup on one word, so its grid is kept small: kScanUnroll vertices a thread and trip, at most one workgroup
     // per CU (the sweep in profiles/kcore.txt). G4S_KCORE_SCAN_WGS and G4S_KCORE_MIN_GRID are A/B switches: the outputs do not depend on them.
-    const int max_grid = 2 * cus, min_grid = env_int("G4S_KCORE_MIN_GRID", 8, 1, max_grid);
+    const g4s::StepGrid sized(env_int("G4S_KCORE_MIN_GRID", g4s::kMinGrid, 1, 2 * cus), 2 * cus);   // the peel grid of a batch: between 8 workgroups and two per CU
     const int g_rows = grid_rows(n, cus), g_scan = grid_for<WG * kScanUnroll>(n, env_int("G4S_KCORE_SCAN_WGS", cus, 1, 8 * cus));
     StepArgs a;
     a.grid_cap = LLONG_MAX;
@@ -327,9 +313,8 @@ int run(int n, const int *rowptr, const int *colids, int max_k, int *core, int *
     int batch = kBatch, peels = 2;                                 // a batch is units of two scans (the level jump, the collect) and `peels` peels
     int levels_seen = 0, rounds_seen = 0;
     for (;;) {
-        int grid = max_grid;
-        if (know) grid = (int)std::max((long long)min_grid, std::min((long long)max_grid, (h->edges_cur + (h->end - h->head) + h->n_hub_cur) / kEdgesPerWg));
-        a.grid_cap = grid == max_grid ? LLONG_MAX : (long long)grid * kEdgesPerWg * kGridGrowth;
+        const int grid = know ? sized.grid(h->edges_cur + (h->end - h->head) + h->n_hub_cur) : sized.max_grid;
+        a.grid_cap = sized.cap(grid);
         int pos = know && h->end != h->head ? 2 : 0;               // a frontier is waiting: begin with the peels
         for (int b = 0; b < batch; ++b) {
             if (pos < 2) {
@@ -352,7 +337,7 @@ int run(int n, const int *rowptr, const int *colids, int max_k, int *core, int *
         const int dl = std::max(h->levels - levels_seen, 1), dr = h->round - rounds_seen;
         levels_seen = h->levels;
         rounds_seen = h->round;
-        if (know) batch = std::min(kBatchMax, batch * 2);
+        if (know) batch = sized.next_batch(batch);
         peels = std::max(2, std::min(batch - 2, (dr + dl - 1) / dl + 1));
         know = true;
     }
@@ -383,10 +368,8 @@ G4S_API g4s_status g4s_kcore(int32_t n, const int32_t *rowptr, const int32_t *co
     if (info) *info = g4s_kcore_info{};
     if (n == 0) return G4S_OK;
 
-    int dev = 0, cus = 1;
-    G4S_HIP_TRY(hipGetDevice(&dev));
-    G4S_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    cus = std::max(cus, 1);
+    int cus = 1;
+    G4S_HIP_TRY(g4s::device_cus(&cus));
     const int hub_cap = std::min(n, kHubCap);
     KcState *st, h{};
     int *deg, *queue, *hubs[2];

@@ -21,7 +21,10 @@
 #include "common.hpp"
 #include "csr_handle.hpp"
 #include "pagerank.hpp"
+#include "call_util.hpp"
 #include "readback.hpp"
+#include "step_batch.hpp"
+#include "wave_reduce.hpp"
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -30,12 +33,10 @@ namespace {
 
 using g4s::PrState;
 
-constexpr int WG = 256;
 constexpr int kItems = 8;          // entries per thread the epilogue's grid is sized for
 constexpr int kMaxGrid = 512;      // workgroups of the epilogue at most: the verdict sums that many partials in order
 constexpr int kLongRow = 4096;     // a row with more entries is summed by a whole workgroup
 constexpr int kBatch = G4S_PAGERANK_BATCH;
-constexpr int kBatchMax = 64;
 enum { P_RES = 0, P_MASS = 1, P_SUMP = 2, P_SUMR = 3, P_LISTS = 4 };   // the lists of per-workgroup partials, kMaxGrid doubles each
 
 static_assert(sizeof(PrState) == 64, "the host reads PrState as one small block");
@@ -45,7 +46,7 @@ inline int epilogue_grid(int n) { return (int)std::max(1LL, std::min(((long long
 // The workgroup's sum, in a fixed order: a shuffle tree per wave, then the waves in index order. Every thread gets it.
 __device__ __forceinline__ double block_sum(double v, double *s_red)
 {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
     __syncthreads();
     double s = 0.0;
@@ -99,7 +100,7 @@ __device__ __forceinline__ void strength_store(long long u, double s, double *__
 
 __device__ __forceinline__ void strength_finish(int bad, long long dang, PrState *st)
 {
-    for (int o = 32; o > 0; o >>= 1) dang += __shfl_down(dang, o);
+    dang = wave_sum(dang);
     if ((threadIdx.x & 63) == 0 && dang) atomicAdd((unsigned long long *)&st->dangling, (unsigned long long)dang);
     if (bad) atomicOr(&st->bad_values, 1);
 }
@@ -278,23 +279,13 @@ struct PagerankWork {
     double *vec = nullptr;        // inv_s | x | y | pn, n doubles each
     double *partials = nullptr;   // P_LISTS lists of kMaxGrid
     PrState *state = nullptr;
-    int cus = 1;
     bool values_dirty = true;     // the strength pass has to run (again)
     int64_t n = 0;
-    int64_t bytes = 0;
+    DevicePieces mem;             // owns the arrays above
 };
 
-void pagerank_work_destroy(PagerankWork *w)
-{
-    if (!w) return;
-    (void)hipFree(w->vec);
-    (void)hipFree(w->partials);
-    (void)hipFree(w->state);
-    delete w;
-}
-
-long long pagerank_work_bytes(const PagerankWork *w) { return w ? w->bytes : 0; }
-
+void pagerank_work_destroy(PagerankWork *w) { delete w; }
+long long pagerank_work_bytes(const PagerankWork *w) { return w ? w->mem.bytes : 0; }
 void pagerank_values_changed(PagerankWork *w) { if (w) w->values_dirty = true; }
 
 } // namespace g4s
@@ -307,23 +298,15 @@ constexpr unsigned kAllFlags = G4S_PAGERANK_SYMMETRIC | G4S_PAGERANK_WARM_START;
 int reserve(g4s_csr_s *A, unsigned flags)
 {
     if (!A->prk) {
-        g4s::PagerankWork *w = new (std::nothrow) g4s::PagerankWork();
+        std::unique_ptr<g4s::PagerankWork> w(new (std::nothrow) g4s::PagerankWork());
         if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
         const size_t n = (size_t)std::max(A->rows, 1);
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->vec, sizeof(double) * 4 * n);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->partials, sizeof(double) * P_LISTS * kMaxGrid);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->state, sizeof(PrState));
-        if (e != hipSuccess) {
-            g4s::pagerank_work_destroy(w);
-            return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "g4s_csr_pagerank_reserve: %s", hipGetErrorString(e));
-        }
-        w->cus = std::max(w->cus, 1);
+        w->mem.take(&w->vec, sizeof(double) * 4 * n);
+        w->mem.take(&w->partials, sizeof(double) * P_LISTS * kMaxGrid);
+        w->mem.take(&w->state, sizeof(PrState));
+        if (!w->mem.ok()) return w->mem.report("g4s_csr_pagerank_reserve");
         w->n = (int64_t)n;
-        w->bytes = (int64_t)sizeof(double) * (4 * (int64_t)n + P_LISTS * kMaxGrid) + (int64_t)sizeof(PrState);
-        A->prk = w;
+        A->prk = w.release();
     }
     if (!(flags & G4S_PAGERANK_SYMMETRIC) && A->nnz > 0 && !A->tr) G4S_TRY(g4s_csr_transpose_reserve(A));
     return G4S_OK;
@@ -339,11 +322,11 @@ int enqueue_begin(g4s_csr_s *A, hipStream_t s)
         double *inv_s = w->vec;
         const long long avg = n ? A->nnz / n : 0;
         const int lpr = avg <= 4 ? 4 : avg <= 16 ? 16 : 64;
-        const int g = (int)std::max(1LL, std::min(((long long)n * lpr + WG - 1) / WG, 8LL * w->cus));
+        const int g = (int)std::max(1LL, std::min(((long long)n * lpr + WG - 1) / WG, 8LL * w->mem.cus));
         if (lpr == 4) hipLaunchKernelGGL(strength_kernel<4>, dim3(g), dim3(WG), 0, s, n, A->d_rowptr, A->d_values, inv_s, w->state);
         else if (lpr == 16) hipLaunchKernelGGL(strength_kernel<16>, dim3(g), dim3(WG), 0, s, n, A->d_rowptr, A->d_values, inv_s, w->state);
         else hipLaunchKernelGGL(strength_kernel<64>, dim3(g), dim3(WG), 0, s, n, A->d_rowptr, A->d_values, inv_s, w->state);
-        const int gl = (int)std::max(1LL, std::min(((long long)n + WG - 1) / WG, 4LL * w->cus));
+        const int gl = (int)std::max(1LL, std::min(((long long)n + WG - 1) / WG, 4LL * w->mem.cus));
         hipLaunchKernelGGL(strength_long_kernel, dim3(gl), dim3(WG), 0, s, n, A->d_rowptr, A->d_values, inv_s, w->state);
     }
     G4S_HIP_TRY(hipGetLastError());
@@ -354,11 +337,11 @@ int enqueue_begin(g4s_csr_s *A, hipStream_t s)
 // The iterations to enqueue behind a read of `h`: what the geometric decay of the last two residuals says is left, at least kBatch.
 int next_batch(const PrState &h, double tol)
 {
-    if (!(tol > 0.0)) return kBatchMax;
+    if (!(tol > 0.0)) return g4s::kBatchMax;
     if (!(h.residual > 0.0) || !(h.prev_residual > h.residual)) return kBatch;
     const double left = std::ceil(std::log(tol / h.residual) / std::log(h.residual / h.prev_residual));
     if (!(left >= (double)kBatch)) return kBatch;
-    return left > (double)kBatchMax ? kBatchMax : (int)left;
+    return left > (double)g4s::kBatchMax ? g4s::kBatchMax : (int)left;
 }
 
 int pagerank(g4s_csr_s *A, double damping, double tol, int32_t max_iterations, const double *pers, double *rank, unsigned flags, g4s_pagerank_info *info,
@@ -366,9 +349,7 @@ int pagerank(g4s_csr_s *A, double damping, double tol, int32_t max_iterations, c
 {
     const char *fn = "g4s_pagerank";
     if (A->rows != A->cols) return g4s::set_error(G4S_ERR_INVALID, "%s: the handle is %d x %d, PageRank needs a square matrix", fn, A->rows, A->cols);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its state back and cannot be captured", fn);
+    G4S_TRY(not_capturing(fn, s, "its state"));
     if (info) *info = g4s_pagerank_info{};
     const int n = A->rows;
     if (n == 0) {

@@ -22,6 +22,7 @@
 #include "common.hpp"
 #include "csr_handle.hpp"
 #include "frontier.hpp"
+#include "call_util.hpp"
 #include "traverse.hpp"
 #include <algorithm>
 #include <climits>
@@ -32,10 +33,7 @@ namespace {
 
 using g4s::TravState;
 
-constexpr int kBatch = G4S_TRAVERSE_BATCH;   // push launches behind one state read, at least; doubles up to kBatchMax
-constexpr int kBatchMax = 64;
-constexpr long long kEdgesPerWg = 2048;      // the launch grid of a batch: one workgroup per 2048 frontier edges, 8..2 per CU
-constexpr long long kGridGrowth = 8;         // stop = 4 once the frontier has 8 times the edges the grid was sized for
+constexpr int kBatch = G4S_TRAVERSE_BATCH;   // push launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
 
 enum { KIND_INIT = 0, KIND_PUSH = 1, KIND_PULL = 2 };
 
@@ -61,25 +59,17 @@ __device__ __forceinline__ void append(bool want, int v, int deg, int rows, int 
     if (want) deg_sum += deg;
 }
 
-// The end of a step kernel: the block's share of the next frontier's out-edges, then the ticket; the last block to arrive turns the page.
+// The end of a step kernel: the block's share of the next frontier's out-edges, then the ticket; the last block to arrive turns the page (turn_page).
 __device__ __forceinline__ void finish(TravState *st, long long deg_sum, int kind, const StepArgs a)
 {
     __shared__ long long s_red[WG / 64];
-    __shared__ int s_last;
-    for (int o = 32; o > 0; o >>= 1) deg_sum += __shfl_down(deg_sum, o);
+    deg_sum = wave_sum(deg_sum);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = deg_sum;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
+    if (!turn_page(&st->tickets, [&] {
         long long sum = 0;
         for (int w = 0; w < (int)blockDim.x / 64; ++w) sum += s_red[w];
         if (sum) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)sum);
-        __threadfence();
-        s_last = atomicAdd(&st->tickets, 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last || threadIdx.x != 0) return;
-    __threadfence();
+    })) return;
     const int n = atomicAdd(&st->n_next, 0), nh = atomicAdd(&st->n_hub_next, 0);
     const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
     if (kind == KIND_PUSH) { st->edges_relaxed += st->edges_cur; st->push_steps += 1; st->iter += 1; }
@@ -151,7 +141,7 @@ template <bool BFS, bool VALUES>
 __global__ __launch_bounds__(WG) void push_kernel(int rows, const int *__restrict__ rowptr, const int *__restrict__ colids, const double *__restrict__ values,
                                                   double *dist, int *level, int *mark, int *q0, int *q1, TravState *st, const StepArgs a)
 {
-    if (st->stop != 0 && !(st->stop == 4 && a.resume)) return;     // the same word for every block: it changes only after the last ticket
+    if (!step_runs(st->stop, a.resume)) return;
     const int cur = st->cur, stamp = st->iter + 1;
     const int *q = cur ? q1 : q0;
     int *qn = cur ? q0 : q1;
@@ -245,7 +235,7 @@ __global__ __launch_bounds__(WG) void count_kernel(int rows, const double *__res
     if (st->stop != 1 && st->stop != 2) return;
     int c = 0;
     for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < rows; i += (long long)gridDim.x * WG) c += BFS ? (level[i] >= 0) : (dist[i] < __builtin_inf());
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -265,24 +255,12 @@ struct TraverseWork {
     int32_t *mark = nullptr;                  // rows ints: the step in which a vertex last joined a queue (SSSP)
     double *dist2 = nullptr;                  // rows doubles: y of the pull step
     TravState *state = nullptr;
-    int cus = 1;
     ZeroScan zeros;                           // is a stored value 0.0? BFS then has to read the values
-    int64_t bytes = 0;
+    DevicePieces mem;                         // owns the arrays above
 };
 
-void traverse_work_destroy(TraverseWork *w)
-{
-    if (!w) return;
-    (void)hipFree(w->queue[0]);
-    (void)hipFree(w->queue[1]);
-    (void)hipFree(w->mark);
-    (void)hipFree(w->dist2);
-    (void)hipFree(w->state);
-    delete w;
-}
-
-long long traverse_work_bytes(const TraverseWork *w) { return w ? w->bytes : 0; }
-
+void traverse_work_destroy(TraverseWork *w) { delete w; }
+long long traverse_work_bytes(const TraverseWork *w) { return w ? w->mem.bytes : 0; }
 void traverse_values_changed(TraverseWork *w) { if (w) w->zeros.changed(); }
 
 } // namespace g4s
@@ -296,32 +274,24 @@ constexpr unsigned kAllFlags = kDirFlags | G4S_TRAVERSE_SYMMETRIC;
 int scan_values(g4s_csr_s *A, hipStream_t s, int *waits)
 {
     g4s::TraverseWork *w = A->trv;
-    return w->zeros.scan(A->nnz, A->d_values, w->cus, &w->state->zero_values, s, waits);
+    return w->zeros.scan(A->nnz, A->d_values, w->mem.cus, &w->state->zero_values, s, waits);
 }
 
 // The workspace (once) and, unless the flags rule a pull out or declare A symmetric, the handle's transpose. NULL stream, synchronous.
 int reserve(g4s_csr_s *A, unsigned flags)
 {
     if (!A->trv) {
-        g4s::TraverseWork *w = new (std::nothrow) g4s::TraverseWork();
+        std::unique_ptr<g4s::TraverseWork> w(new (std::nothrow) g4s::TraverseWork());
         if (!w) return g4s::set_error(G4S_ERR_NOMEM, "host allocation failed");
         const size_t n = (size_t)std::max(A->rows, 1);
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->queue[0], sizeof(int32_t) * n);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->queue[1], sizeof(int32_t) * n);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->mark, sizeof(int32_t) * n);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->dist2, sizeof(double) * n);
-        if (e == hipSuccess) e = g4s::device_malloc((void **)&w->state, sizeof(TravState));
-        if (e == hipSuccess) e = hipMemset(w->state, 0, sizeof(TravState));
-        if (e != hipSuccess) {
-            g4s::traverse_work_destroy(w);
-            return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "g4s_csr_traverse_reserve: %s", hipGetErrorString(e));
-        }
-        w->cus = std::max(w->cus, 1);
-        w->bytes = (int64_t)(3 * sizeof(int32_t) + sizeof(double)) * (int64_t)n + (int64_t)sizeof(TravState);
-        A->trv = w;
+        w->mem.take(&w->queue[0], sizeof(int32_t) * n);
+        w->mem.take(&w->queue[1], sizeof(int32_t) * n);
+        w->mem.take(&w->mark, sizeof(int32_t) * n);
+        w->mem.take(&w->dist2, sizeof(double) * n);
+        w->mem.take(&w->state, sizeof(TravState));
+        if (w->mem.ok()) w->mem.note(hipMemset(w->state, 0, sizeof(TravState)));
+        if (!w->mem.ok()) return w->mem.report("g4s_csr_traverse_reserve");
+        A->trv = w.release();
     }
     G4S_TRY(scan_values(A, nullptr, nullptr));
     if (!(flags & (G4S_TRAVERSE_SYMMETRIC | G4S_TRAVERSE_PUSH)) && !A->tr) G4S_TRY(g4s_csr_transpose_reserve(A));
@@ -350,9 +320,7 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
         if (v < 0 || v >= A->rows) return g4s::set_error(G4S_ERR_INVALID, "%s: source %d is outside [0, %d)", fn, v, A->rows);
     std::sort(src.begin(), src.end());
     src.erase(std::unique(src.begin(), src.end()), src.end());
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    G4S_HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) return g4s::set_error(G4S_ERR_INVALID, "%s: the call reads its state back and cannot be captured", fn);
+    G4S_TRY(not_capturing(fn, s, "its state"));
 
     const bool symmetric = (flags & G4S_TRAVERSE_SYMMETRIC) != 0;
     const int mode = (flags & G4S_TRAVERSE_PUSH) ? KIND_PUSH : (flags & G4S_TRAVERSE_PULL) ? KIND_PULL : 0;
@@ -375,12 +343,12 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
     a.threshold = mode == KIND_PUSH ? LLONG_MAX : mode == KIND_PULL ? -1 : (long long)((double)A->nnz / switch_alpha(BFS));
     a.grid_cap = LLONG_MAX;
     a.resume = 0;
-    const int max_grid = 2 * w->cus, min_grid = 8;
+    const g4s::StepGrid sized(g4s::kMinGrid, 2 * w->mem.cus);  // the push grid of a batch: between 8 workgroups and two per CU
     TravState *st = w->state;
     int *q0 = w->queue[0], *q1 = w->queue[1];
 
     G4S_HIP_TRY(hipMemcpyAsync(q1, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(init_fill_kernel<BFS>, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, dist, level, w->mark);
+    hipLaunchKernelGGL(init_fill_kernel<BFS>, dim3(grid_rows(rows, w->mem.cus)), dim3(WG), 0, s, rows, dist, level, w->mark);
     hipLaunchKernelGGL(init_sources_kernel<BFS>, dim3(1), dim3(WG), 0, s, rows, (int)src.size(), q1, A->d_rowptr, dist, level, q0, st, a);
     G4S_HIP_TRY(hipGetLastError());
 
@@ -393,7 +361,7 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
         if (h.stop == 3) {                                         // one pull step
             if constexpr (BFS) {
                 const long long avg = rows ? A->nnz / rows : 0;
-                const int g = grid_rows((long long)rows * (avg <= 4 ? 4 : avg <= 16 ? 16 : 64), w->cus);
+                const int g = grid_rows((long long)rows * (avg <= 4 ? 4 : avg <= 16 ? 16 : 64), w->mem.cus);
 #define TV_PULL(LPR) do { if (values) hipLaunchKernelGGL((bfs_pull_kernel<LPR, true>), dim3(g), dim3(WG), 0, s, rows, A->d_rowptr, trowptr, tcolids, tvalues, level, q0, q1, st, a); \
                           else hipLaunchKernelGGL((bfs_pull_kernel<LPR, false>), dim3(g), dim3(WG), 0, s, rows, A->d_rowptr, trowptr, tcolids, tvalues, level, q0, q1, st, a); } while (0)
                 if (avg <= 4) TV_PULL(4);
@@ -402,14 +370,13 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
 #undef TV_PULL
             } else {
                 G4S_TRY(g4s_spmv_semiring(pull_handle, dist, w->dist2, G4S_SEMIRING_MIN_PLUS, s));
-                hipLaunchKernelGGL(sssp_combine_kernel, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, A->d_rowptr, dist, w->dist2, q0, q1, st, a);
+                hipLaunchKernelGGL(sssp_combine_kernel, dim3(grid_rows(rows, w->mem.cus)), dim3(WG), 0, s, rows, A->d_rowptr, dist, w->dist2, q0, q1, st, a);
             }
             G4S_HIP_TRY(hipGetLastError());
         }
         if (mode != KIND_PULL) {                                   // a batch of push steps: no-ops from the first stop on
-            int grid = max_grid;
-            if (know && h.stop != 3) grid = (int)std::max((long long)min_grid, std::min((long long)max_grid, (h.edges_cur + h.n_cur + h.n_hub_cur) / kEdgesPerWg));
-            a.grid_cap = grid == max_grid ? LLONG_MAX : (long long)grid * kEdgesPerWg * kGridGrowth;
+            const int grid = know && h.stop != 3 ? sized.grid(h.edges_cur + h.n_cur + h.n_hub_cur) : sized.max_grid;
+            a.grid_cap = sized.cap(grid);
             for (int b = 0; b < batch; ++b) {
                 a.resume = b == 0;
                 if (values || !BFS) hipLaunchKernelGGL((push_kernel<BFS, true>), dim3(grid), dim3(WG), 0, s, rows, A->d_rowptr, A->d_colids, A->d_values, dist, level, w->mark, q0, q1, st, a);
@@ -418,9 +385,9 @@ int traverse(g4s_csr_s *A, const int32_t *sources, int32_t n_sources, double *di
             G4S_HIP_TRY(hipGetLastError());
             a.grid_cap = LLONG_MAX;
             a.resume = 0;
-            if (know) batch = std::min(kBatchMax, batch * 2);
+            if (know) batch = sized.next_batch(batch);
         }
-        hipLaunchKernelGGL(count_kernel<BFS>, dim3(grid_rows(rows, w->cus)), dim3(WG), 0, s, rows, dist, level, st);
+        hipLaunchKernelGGL(count_kernel<BFS>, dim3(grid_rows(rows, w->mem.cus)), dim3(WG), 0, s, rows, dist, level, st);
         G4S_HIP_TRY(hipGetLastError());
         G4S_HIP_TRY(reads.fetch(h, st));
         ++waits;

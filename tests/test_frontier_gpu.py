@@ -1,11 +1,11 @@
-"""The frontier walk that g4s_sssp / g4s_bfs, g4s_betweenness and g4s_connected_components share (g4s_amd/csrc/frontier.hpp), on one graph
+"""The frontier walk that g4s_sssp / g4s_bfs, g4s_betweenness, g4s_connected_components and g4s_kcore share (g4s_amd/csrc/frontier.hpp), on one graph
 made for its edges. The "fan" is directed, 6262 vertices and 25 805 entries:
   vertex 0 → 257 mid vertices 1 … 257: one full tile of 256 rows plus one row;
   mid 1 has exactly 4096 out-edges (the hub cut: not a hub), mid 2 has 4097 (a hub whose last chunk holds one edge), mid 3 has 6000, mid 4 has 5000:
   three hubs in one frontier, so chunk ownership runs with h >= 1; mids 5 … 20 have none and mid i of 21 … 257 has i % 4, so 75 rows of length
   zero sit inside the tile; every one of the 6000 leaves → one sink: a level of 23.4 tiles whose edges all land on one vertex; three isolated
   vertices at the end. Source 3 makes the source itself a hub; symmetrised, the sink is a fourth hub.
-Compared with the references of tests/traverse_ref.py, betweenness_ref.py and components_ref.py as the three features' own test files compare."""
+Compared with the references of tests/traverse_ref.py, betweenness_ref.py, components_ref.py and kcore_ref.py as the features' own test files compare."""
 import os
 
 import numpy as np
@@ -13,6 +13,7 @@ import pytest
 
 from tests import betweenness_ref as bref
 from tests import components_ref as cref
+from tests import kcore_ref as kref
 from tests import traverse_ref
 from tests.traverse_ref import same_values
 
@@ -83,16 +84,22 @@ def test_betweenness_with_three_hubs_in_one_frontier(fan, handle):
     bref.check_parity("fan", bc.cpu().numpy(), ref.bc)
 
 
-@pytest.mark.parametrize("rounds", [0, 2])
-def test_components_of_the_symmetrised_fan(fan, rounds):
+@pytest.fixture(scope="module")
+def sym_fan(fan):
+    """(rowptr, colids) of the fan's pattern with both directions of every edge, rows ascending"""
     import scipy.sparse as sp
-    import torch
-    from g4s_amd import host
     rp, ci, _ = fan
     G = sp.csr_matrix((np.ones(ci.size), ci, rp), shape=(N, N))
     S = (G + G.T).tocsr()
     S.sort_indices()
-    srp, sci = S.indptr.astype(np.int32), S.indices.astype(np.int32)
+    return S.indptr.astype(np.int32), S.indices.astype(np.int32)
+
+
+@pytest.mark.parametrize("rounds", [0, 2])
+def test_components_of_the_symmetrised_fan(sym_fan, rounds):
+    import torch
+    from g4s_amd import host
+    srp, sci = sym_fan
     deg = np.diff(srp)
     assert deg[N - 4] == N_LEAF and (deg - rounds > 4096).sum() == (5 if rounds == 0 else 3)     # the sink is a hub too
     want, _ = cref.labels(srp, sci, N)
@@ -112,3 +119,20 @@ def test_components_of_the_symmetrised_fan(fan, rounds):
             os.environ.pop("G4S_CC_SAMPLE_ROUNDS", None)
         else:
             os.environ["G4S_CC_SAMPLE_ROUNDS"] = saved
+
+
+@pytest.mark.parametrize("max_k", [None, 2])
+def test_kcore_of_the_symmetrised_fan(sym_fan, max_k):
+    """Five hubs (mid 1 has 4096 leaves and the root here): the full peel takes them with the 5-core, its last level; max_k = 2 leaves them standing."""
+    import torch
+    from g4s_amd import host
+    srp, sci = sym_fan
+    assert (np.diff(srp) > 4096).sum() == 5
+    core, rnd, levels, rounds, capped = kref.kcore(srp, sci, N, max_k)
+    assert (int(core.max()), levels, rounds, capped, int((rnd < 0).sum())) == ((5, 6, 8, 0, 0) if max_k is None else (2, 2, 2, 1, 6184))
+    assert np.all(core[np.diff(srp) > 4096] == int(core.max()))
+    for _ in range(2):
+        c, r, info = host.kcore((torch.from_numpy(srp).cuda(), torch.from_numpy(sci).cuda()), max_k=max_k, return_round=True, return_info=True)
+        print(f"fan kcore max_k={max_k}: {info}")
+        assert np.array_equal(c.cpu().numpy(), core) and np.array_equal(r.cpu().numpy(), rnd), (max_k, info)
+        assert (info["degeneracy"], info["top_core_size"], info["levels"], info["rounds"], info["capped"]) == (*kref.top_core(core), levels, rounds, capped), info
