@@ -2636,8 +2636,8 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
     if (pre) pre->sym_rc_valid = only_short && !pre->keep;
     dbg.mark("classes");
     if (getenv("G4S_DEBUG"))
-        fprintf(stderr, "g4s symbolic classes: empty %d tiny %d small %d medium %d large %d hub %d (flop %lld)\n", rc.count[CLS_EMPTY], rc.count[CLS_TINY],
-                rc.count[CLS_SMALL], rc.count[CLS_MEDIUM], rc.count[CLS_LARGE], rc.count[CLS_HUB], (long long)flop);
+        fprintf(stderr, "g4s symbolic classes: empty %d tiny %d small %d medium %d large %d window %d hub %d (flop %lld)\n", rc.count[CLS_EMPTY], rc.count[CLS_TINY],
+                rc.count[CLS_SMALL], rc.count[CLS_MEDIUM], rc.count[CLS_LARGE], rc.count[CLS_M2], rc.count[CLS_HUB], (long long)flop);
     // the bitmap-window kernels work on B's non-empty columns, renumbered (N2 of them; the original ids when that would not pay)
     ColumnMap local_map;
     ColumnMap &cmap = pre ? pre->cmap : local_map;
@@ -2982,8 +2982,11 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
     const bool reuse_rc = pre && pre->sym_rc_valid;                // (see PreSorted::sym_rc)
     // With the rank path on, what is left for the window kernels past 4 096 outputs is the rows of at most 8 192 products (and symbolic hub rows): those of up to
     // 8 192 outputs join the mid-size launch (four 2 048-output chunks at most) instead of being a launch — a row sort, unit lists, a persistent kernel — of their own.
+    // Only while the window kernel takes that class: the key table that G4S_SPGEMM_MID_TABLES=4 (or a B past window_max_n() columns) puts in its place sorts through
+    // a dense copy of TABLE / 2 = 4 096 entries and would store the first 4 096 outputs of a longer row only. (rank ⇒ pre: the column map is the carried one.)
+    const bool m2_windows = pre && pre->cmap.width(N) <= window_max_n() && !(mid_tables() & 4);
     ClassLimits num_limits = kNumLimits;
-    if (rank) num_limits.lim[4] = 8192;
+    if (rank && m2_windows) num_limits.lim[4] = 8192;
     if (!reuse_rc) G4S_TRY(classify_rows(M, row_size.as<long long>(), num_limits, 0, local_rc, s));
     const RowClasses &rc = reuse_rc ? pre->sym_rc : local_rc;
     const bool num_only_short = rc.count[CLS_MEDIUM] + rc.count[CLS_LARGE] + rc.count[CLS_M2] + rc.count[CLS_M3] + rc.count[CLS_HUB] + rc.count[CLS_RANK] == 0;
