@@ -14,6 +14,7 @@ Names and argument meaning follow the reference so that tests read like tests of
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
+  color          — greedy colouring in a priority order (g4s_color); color_smallest_last, maximal_independent_set and color_classes go with it
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
   pagerank       — PageRank of a graph stored by out-edges (g4s_pagerank): one call, the loop, the dangling mass and the stop test on the device
   betweenness    — betweenness centrality from a list of sources (g4s_betweenness): Brandes' two sweeps per source, both on the device
@@ -220,6 +221,10 @@ class CSR:
     def kcore(self, max_k=None, return_round=False, return_info=False):
         """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
         return kcore(self, max_k, return_round, return_info)
+
+    def color(self, key=None, seed=0, largest_first=False, return_round=False, return_info=False):
+        """The first-fit colouring in decreasing priority (key, hash) of the graph whose symmetric pattern this matrix stores — color(self, …)."""
+        return color(self, key, seed, largest_first, return_round, return_info)
 
     def ewise(self, other, op="union", combine="plus", pattern_only=False, return_info=False):
         """self ∪ other, self ∩ other or self ∖ other as a new device CSR — csr_ewise(self, other, …)."""
@@ -742,6 +747,86 @@ def kcore_subgraph(A, k):
     if A.rows != A.cols:
         raise ValueError(f"a k-core subgraph needs a square matrix, not {A.rows} x {A.cols}")
     return csr_induced_subgraph(A, kcore(A, max_k=int(k)) >= int(k))
+
+
+def _is_seed(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and 0 <= v < 2**32
+
+
+def color(A, key=None, seed=0, largest_first=False, return_round=False, return_info=False):
+    """color (int32 device tensor of n): the first-fit colouring of the graph in decreasing priority (g4s_color) — color[v] is the smallest colour not
+    held by a neighbour above v, what networkx.greedy_color returns for that order on the graph without self-loops. A is a CSR, or a (rowptr, colids)
+    pair of int32 device tensors or of numpy arrays (host pointers; the results come back on the device all the same), and holds the SYMMETRIC pattern
+    of a simple undirected graph with strictly ascending rows (csr_symmetrise gives one); a stored diagonal entry is ignored. The priority is the pair
+    (key[v], fmix32(v ^ seed)), larger first: key=None is a pure hash order, key = kcore's round is smallest-last (color_smallest_last),
+    largest_first=True takes the degree as the key (key must then be None). key: n int32 values of the kind of A's arrays. return_round=True adds
+    round (int32 device tensor): the depth of each vertex in the priority DAG. return_info=True adds the dict of g4s_color_info. Both outputs are
+    functions of graph, key and seed alone. Synchronous; no plan is built. ValueError (before any GPU call) for a CSR that is not square, a seed that
+    is not an integer in [0, 2^32), a key together with largest_first, a key of the wrong length or kind, and flags that are not bools."""
+    if not _is_seed(seed):
+        raise ValueError(f"seed must be an integer in [0, 2^32), not {seed!r}")
+    for name, v in (("largest_first", largest_first), ("return_round", return_round), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    if largest_first and key is not None:
+        raise ValueError("key must be None with largest_first=True: the degree is the key")
+    rowptr, colids, n = _pattern_of(A, "a colouring")
+    on_device = isinstance(rowptr, torch.Tensor)
+    if key is not None:
+        if isinstance(key, torch.Tensor) != on_device:
+            raise ValueError("key must be of the kind of the pattern's arrays: a device tensor with device tensors, a numpy array with numpy arrays")
+        if int(key.numel() if on_device else np.asarray(key).size) != n:
+            raise ValueError(f"key must hold one value per vertex ({n})")
+        if on_device and key.dtype != torch.int32:
+            raise ValueError(f"key must be int32, not {key.dtype}")
+    _require_gpu()
+    flags = capi.COLOR_LARGEST_FIRST if largest_first else 0
+    info, null = capi.ColorInfo(), C.c_void_p(0)
+    if on_device:
+        assert rowptr.is_cuda and colids.is_cuda and rowptr.dtype == torch.int32 and colids.dtype == torch.int32
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        key = key.contiguous() if key is not None else None
+        col = torch.empty(n, dtype=torch.int32, device=rowptr.device)
+        rnd = torch.empty(n, dtype=torch.int32, device=rowptr.device) if return_round else None
+        capi.check(capi.load().g4s_color(n, _ptr_nn(rowptr), _ptr_nn(colids), _ptr_nn(key) if key is not None and n else null, int(seed), _ptr_nn(col),
+                                         _ptr_nn(rnd) if return_round else null, flags | capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        key = np.ascontiguousarray(key, np.int32) if key is not None else None
+        out, out_r = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32)
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        capi.check(capi.load().g4s_color(n, P(rowptr), P(colids if colids.size else out), P(key) if key is not None and n else null, int(seed), P(out),
+                                         P(out_r) if return_round else null, flags | capi.HOST_POINTERS, C.byref(info), _stream()))
+        col = torch.from_numpy(out[:n]).cuda()
+        rnd = torch.from_numpy(out_r[:n]).cuda() if return_round else None
+    res = (col,) + ((rnd,) if return_round else ()) + (({n_: getattr(info, n_) for n_, _ in capi.ColorInfo._fields_ if n_ != "reserved"},) if return_info else ())
+    return res[0] if len(res) == 1 else res
+
+
+def color_smallest_last(A, seed=0, return_info=False):
+    """The smallest-last colouring: color with key = kcore's peel round, i.e. greedy colouring in the reverse of the degeneracy ordering. It uses at
+    most degeneracy + 1 colours. A: as for color."""
+    _, rnd = kcore(A, return_round=True)
+    rowptr = _pattern_of(A, "a colouring")[0]
+    return color(A, key=rnd if isinstance(rowptr, torch.Tensor) else rnd.cpu().numpy(), seed=seed, return_info=return_info)
+
+
+def maximal_independent_set(A, key=None, seed=0):
+    """A bool device tensor of n: the greedy maximal independent set in priority order — colour class 0 of color(A, key, seed)."""
+    return color(A, key=key, seed=seed) == 0
+
+
+def color_classes(color):
+    """(perm, offsets): perm (int32 device tensor of n) = the vertices sorted by (colour, id), ready for csr_permute; offsets (int64 device tensor of
+    colours + 1) = where each colour class starts in perm. No stored off-diagonal entry of the permuted matrix lies inside a diagonal block
+    [offsets[c], offsets[c + 1])². color: the int32 device tensor that color() returns."""
+    if not (isinstance(color, torch.Tensor) and color.dim() == 1 and color.dtype == torch.int32):
+        raise ValueError("color must be a one-dimensional int32 tensor")
+    perm = torch.sort(color, stable=True).indices.to(torch.int32)
+    offsets = torch.zeros(int(color.max()) + 2 if color.numel() else 1, dtype=torch.int64, device=color.device)
+    if color.numel():
+        offsets[1:] = torch.cumsum(torch.bincount(color), 0)
+    return perm, offsets
 
 
 # ------------------------------------------------------------------------------------------------ element-wise combination and select

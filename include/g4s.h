@@ -112,9 +112,9 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
- * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py —, every result compared bit for bit):
+ * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py —, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_kcore, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_kcore, g4s_color, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -736,6 +736,70 @@ typedef struct g4s_kcore_info {
 g4s_status g4s_kcore(int32_t n, const int32_t *rowptr, const int32_t *colids, int32_t max_k,
                      int32_t *core, int32_t *round /* may be NULL */, unsigned flags,
                      g4s_kcore_info *info /* may be NULL */, void *stream);
+
+/* Greedy colouring and independent sets: color[v] (n int32, device or host like the other arrays, only written) = the first-fit colour of v — the
+ * smallest colour >= 0 not held by a neighbour of higher priority — i.e. sequential greedy colouring of the vertices in decreasing priority: what
+ * networkx.greedy_color(G, strategy=<that order>) returns on the graph without self-loops. Raw arrays, no handle, no plan, no values.
+ *   Pattern: exactly g4s_kcore's. The adjacency of a simple undirected graph, rows strictly ascending with ids in [0, n), rowptr non-decreasing from
+ *     0: all of it checked on the device before any id is an index (G4S_ERR_INVALID, outputs unspecified afterwards). The caller declares the pattern
+ *     symmetric; symmetry is not checked. On a pattern that is not, the call still terminates and gives every vertex a colour >= 0 and at most 64 +
+ *     its row length, but the values are outside the contract. A stored diagonal entry is ignored: not counted, not walked.
+ *   Priority: a strict total order, the pair (key[v], h(v)) compared lexicographically, larger first. key (n int32, may be NULL: all keys equal; any
+ *     int32 is valid); h(v) = fmix32((uint32_t)v ^ seed) with the murmur3 finaliser x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35;
+ *     x ^= x >> 16 — a bijection on 32 bits, so there are no ties. Distinct keys give any explicit order; key = the round of g4s_kcore gives
+ *     smallest-last, which uses at most degeneracy + 1 colours; G4S_COLOR_LARGEST_FIRST (key must then be NULL) takes the degree without the diagonal,
+ *     computed inside, as the key.
+ *   round[v] (n int32, may be NULL): 0 when no neighbour has higher priority, else 1 + the largest round among those neighbours — the depth of v in
+ *     the priority DAG and the step that coloured it; sorted by (round, id) the vertices are in a level schedule.
+ *   Both outputs are functions of the pattern, the keys and the seed alone: the same on every run, stream, launch grid and tuning switch, compared
+ *     with ==. {v : color[v] == 0} is a maximal independent set, the greedy one in priority order.
+ *   info (may be NULL): colors = 1 + the largest colour, rounds = 1 + the largest round, class0 = the vertices coloured 0, overflow = the vertices whose
+ *     higher-priority neighbours hold all of the colours 0 … 63 (a function of graph and order like the outputs), edges_walked = the stored
+ *     off-diagonal entries (every row is walked once), and what the call did: launches, resumes, scan_resumes, host_waits.
+ *   Checks before any HIP call (G4S_ERR_INVALID): any flag bit other than G4S_DEVICE_POINTERS and G4S_COLOR_LARGEST_FIRST, a NULL rowptr or color, a
+ *     NULL colids with n > 0, a negative n, a non-NULL key together with G4S_COLOR_LARGEST_FIRST, and with host pointers outputs that overlap the
+ *     inputs or each other. n == 0 is valid and writes nothing; nnz == 0 is valid: every colour is 0 and every round is 0.
+ *   Algorithm: a Jones–Plassmann sweep. pred[v] = the higher-priority neighbours of v, by one walk over all rows; the vertices with
+ *     pred == 0 are frontier 0. A step walks the frontier's rows balanced over entries (rows above 4096 entries in chunks of 1024 over all
+ *     workgroups): v takes the lowest clear bit of its 64-bit mask, and for every lower-priority neighbour w sets that bit in w's mask and takes one
+ *     off pred[w] — the lane that brings it to 0 appends w. Every vertex is queued once, so one array of n ints holds all frontiers. A vertex whose
+ *     mask is full goes to an overflow list; a scan kernel behind the step marks the colours >= 64 of its higher-priority neighbours in an LDS bitmap
+ *     of G4S_COLOR_WINDOW colours, window after window, and takes the first clear one. The scan joins the batches only once the list has an entry
+ *     (info.scan_resumes = 1), so a graph below 65 colours never pays for it.
+ *   Synchronous: runs on `stream` and returns when color, round and info are complete. Steps are enqueued blind in batches of at least G4S_COLOR_BATCH
+ *     (doubling to 64) with one read of the 96-byte state per batch and one behind the opening pass: info.host_waits <= info.launches / 16 + 2 + info.resumes + info.scan_resumes. The
+ *     grid follows the frontier seen at the last read; a frontier that outgrows it stops the batch, which resumes on a larger grid (info.resumes).
+ *     On a capturing stream it returns G4S_ERR_INVALID and enqueues nothing. Scratch — a 256-byte state block, 8·n bytes of masks, 4·n each for pred,
+ *     the queue and the overflow list (and the degrees under G4S_COLOR_LARGEST_FIRST), two lists of 4·min(n, 2^19) for long rows, plus device copies
+ *     of the arrays with host pointers — comes from the library's caching allocator and is released before the call returns. No process-wide state:
+ *     different host threads may call at the same time.
+ *   Environment: G4S_COLOR_MIN_GRID (the smallest step grid, default 8). The outputs do not depend on it.
+ *   Where it loses (profiles/color.txt, one MI355X): against the host loop of independent-set rounds over g4s_spmv_semiring max-plus — whose colouring
+ *     is proper but spends one colour per round — it wins wherever the priority DAG is deep: 25.5 against 70.5 ms on the 1000 x 1000 grid under
+ *     smallest-last (1262 rounds), 80 … 93 against 121 … 131 ms on the symmetrised R-MAT-20, 490 … 536 against 2073 … 2205 ms on configs[1]
+ *     symmetrised. It loses 3x on that grid under a hash or largest-first order (2.56 against 0.85 ms): 14 rounds, where the loop is 14 products at
+ *     the SpMV rate and the call pays its opening pass, two atomics per live entry and the largest grid for every step. It runs far below the walk's
+ *     own rate everywhere (0.17 … 0.40 G entries/s on the R-MATs): one dependent kernel per level of the priority DAG, 20 us each on the grid, 80 us
+ *     on the R-MATs. */
+#define G4S_COLOR_LARGEST_FIRST 524288u  /* key := the degree without the diagonal, computed inside; `key` must be NULL */
+#define G4S_COLOR_BATCH 16               /* step launches enqueued behind one read of the state, at least (doubles up to 64 within a call) */
+#define G4S_COLOR_MASK_COLORS 64         /* the colours 0 … 63 travel as a pushed bitmask; above them a row scan decides */
+#define G4S_COLOR_WINDOW 256             /* colours examined per pass of that row scan */
+typedef struct g4s_color_info {
+    int64_t edges_walked;    /* stored off-diagonal entries walked by the steps                        */
+    int64_t class0;          /* vertices with colour 0: the size of the maximal independent set        */
+    int32_t colors;          /* 1 + the largest colour written                                         */
+    int32_t rounds;          /* non-empty frontiers coloured = 1 + the largest value written to `round` */
+    int32_t overflow;        /* vertices whose higher-priority neighbours hold all of the colours 0 … 63 */
+    int32_t launches;        /* kernels enqueued, those that returned at once included                 */
+    int32_t resumes;         /* batches restarted because the frontier outgrew the launch grid         */
+    int32_t scan_resumes;    /* batches restarted to bring the overflow scan in: 0 or 1                */
+    int32_t host_waits;      /* times the call waited for the device                                   */
+    int32_t reserved;
+} g4s_color_info;            /* 48 bytes */
+g4s_status g4s_color(int32_t n, const int32_t *rowptr, const int32_t *colids, const int32_t *key /* may be NULL */, uint32_t seed,
+                     int32_t *color, int32_t *round /* may be NULL */, unsigned flags,
+                     g4s_color_info *info /* may be NULL */, void *stream);
 
 /* Element-wise combination of two CSR matrices of the same shape, and filtering of one, on the device. Two calls each, on the model of
  * g4s_spgemm_symbolic / g4s_spgemm_numeric, with caller-allocated outputs: the symbolic call writes crpt (rows + 1) and *cnnz, the caller allocates

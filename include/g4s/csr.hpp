@@ -8,6 +8,7 @@
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
+//   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 //   EWiseAdd / EWiseMult / EWiseDifference(a,b,c), Select(a,c,pred,k,thr), Symmetrise(a,c)   A ∪ B, A ∩ B, A ∖ B, a filter, A ∪ Aᵀ (g4s_csr_ewise_*, g4s_csr_select_*)
 //   graph, FromGraph(g,c,dup), FromCOO(…), ToCOO(a,row_out), SortAndMerge(a,c,dup)   an edge list to a CSR with repeats merged and back (CSR(graph&), mm/inc/CSR.h:255-329)
@@ -215,6 +216,32 @@ void KCore(const CSR<IT, NT> &a, int32_t *core, int32_t *round = nullptr, int32_
     int32_t none = 0;
     check(g4s_kcore(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, max_k, a.rows ? core : &none, a.rows ? round : nullptr, G4S_HOST_POINTERS, info, nullptr),
           "KCore");
+}
+
+// color[v] (a.rows values) = the first-fit colour of v in the simple undirected graph `a`: the smallest colour not held by a neighbour of higher
+// priority, the priority being the pair (key[v], fmix32(v ^ seed)), larger first (g4s_color, host arrays). `a` holds the graph's symmetric pattern
+// with ascending rows (Symmetrise gives one), a stored diagonal entry is ignored. key (may be NULL: a pure hash order): the round of KCore gives
+// smallest-last, at most degeneracy + 1 colours; largest_first takes the degree as the key (key must then be NULL). round (may be NULL): the depth
+// of v in the priority DAG.
+template <typename IT, typename NT>
+void GreedyColor(const CSR<IT, NT> &a, int32_t *color, const int32_t *key = nullptr, uint32_t seed = 0, int32_t *round = nullptr, bool largest_first = false,
+                 g4s_color_info *info = nullptr)
+{
+    if (a.rows != a.cols) throw std::runtime_error("GreedyColor: the pattern is not square");
+    const IT zero = 0;                                      // an empty CSR holds no arrays: nothing is read or written for rows == 0
+    int32_t none = 0;
+    check(g4s_color(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, a.rows ? key : nullptr, seed, a.rows ? color : &none, a.rows ? round : nullptr,
+                    G4S_HOST_POINTERS | (largest_first ? G4S_COLOR_LARGEST_FIRST : 0u), info, nullptr), "GreedyColor");
+}
+
+// in_set[v] = 1 for the vertices of the greedy maximal independent set in priority order — colour class 0 of GreedyColor(a, …, key, seed) —, else 0.
+template <typename IT, typename NT>
+void MaximalIndependentSet(const CSR<IT, NT> &a, std::vector<char> &in_set, const int32_t *key = nullptr, uint32_t seed = 0)
+{
+    std::vector<int32_t> color((size_t)(a.rows > 0 ? a.rows : 0));
+    GreedyColor(a, color.data(), key, seed);
+    in_set.resize(color.size());
+    for (size_t v = 0; v < color.size(); ++v) in_set[v] = color[v] == 0;
 }
 
 // The wrapper the shipped benchmark calls: mkl(A,B,C,timing) (mm/inc/mkl_mult.h:113-124 ← mm/src/mkl_spgemm.cpp:67,74).
