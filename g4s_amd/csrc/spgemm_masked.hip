@@ -484,6 +484,9 @@ int masked_device(const Operands &o, unsigned flags, g4s_masked_info *info, hipS
         return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: the mask is not a CSR pattern with strictly ascending rows and column ids in [0, %d)", o.N);
     if (h.invalid) return g4s::set_error(G4S_ERR_INVALID, "g4s_spgemm_masked: %s", (h.invalid & BAD_A) ? "a row pointer or column id of A is out of range"
                                                                                                       : "a row pointer or column id of B is out of range");
+    if (getenv("G4S_DEBUG"))
+        fprintf(stderr, "g4s masked classes: skip %d wave %d lds_small %d lds_large %d global %d split_lds %d split_global %d (products %llu)\n", h.counts[C_SKIP],
+                h.counts[C_WAVE], h.counts[C_LDS_S], h.counts[C_LDS_L], h.counts[C_GLOBAL], h.counts[C_SPLIT_LDS], h.counts[C_SPLIT_GLOBAL], h.products);
     if (h.counts[C_SKIP] < o.M) {
         G4S_TRY(sr::dispatch(flags, [&](auto p) {
             return o.aval ? launch_classes<decltype(p), true>(o, list, h.counts, cuts, s) : launch_classes<decltype(p), false>(o, list, h.counts, cuts, s);

@@ -1,7 +1,8 @@
 """g4s_spgemm_masked (C⟨M⟩ = A ⊗ B at the positions of a pattern M) and g4s_triangle_count on the device, against tests/masked_ref.py.
 Values are compared as the semiring tests do: min-plus, max-plus and or-and bit for bit (semiring_ref.same_values); plus-times bit for bit on
 integer-valued and pattern-only inputs, and within 1e-10·Σ|a·b| per entry on real values (the Σ computed by the reference). Every row class —
-wave, LDS, global, split — is reached by at least one test, shown by g4s_masked_info."""
+wave, LDS, global, split — is reached by at least one test, shown by g4s_masked_info; the inputs here are statistical. Rows AT and just past every
+limit between the seven classes (and the counts of each class, which g4s_masked_info merges) are pinned by tests/test_spgemm_masked_limits_gpu.py."""
 import ctypes as C
 import os
 import subprocess
