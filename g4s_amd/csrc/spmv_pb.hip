@@ -543,7 +543,11 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
             const unsigned r0_ = lr[u][0], r3_ = lr[u][3];
             const bool lane_uniform = r0_ == r3_ && lr[u][1] == r0_ && lr[u][2] == r0_;
             const unsigned first_row = (unsigned)__builtin_amdgcn_readfirstlane((int)r0_);
-            if (__all(active && lane_uniform && r0_ == first_row)) {     // wave-uniform branch, every lane active: the shuffles read live registers
+            // wave-uniform branch, all 64 lanes in it: the shuffles read live registers. The ballot is compared with the full mask, not taken over the lanes that
+            // are left (__all): in the tail wave of an item the lanes past the end have LEFT the loop, and a tail whose remaining groups sat on one row took this
+            // branch with dead lanes under its shuffles — those read 0.0, neutral for plus-times, but the minimum of a min-plus row of positive sums (and the
+            // maximum of a max-plus row of negative ones).
+            if (__ballot(active && lane_uniform && r0_ == first_row) == ~0ull) {
                 double t = Sr::combine(Sr::combine(p[0], p[1]), Sr::combine(p[2], p[3]));
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) t = Sr::combine(t, __shfl_down(t, off, 64));

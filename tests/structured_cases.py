@@ -8,6 +8,8 @@ from typing import Callable, NamedTuple
 
 import numpy as np
 
+from tests.pb_cases import PATH_BLOCKED, PB_MIN_NNZ, PB_MIN_X_BYTES, should_use   # the blocked path's probe, restated beside its plan (tests/pb_cases.py)
+
 # ---- selection thresholds, each beside the source line it mirrors
 DIA_MIN_ROWS = 1024          # spmv_dia.hip, dia_try_build: `if (rows < 1024 || nnz < 4096) return G4S_OK;`
 DIA_MIN_NNZ = 4096           # (the same line)
@@ -20,8 +22,7 @@ BCSR_ORDER = (3, 2)          # bcsr_try_build: `for (int b : {3, 2})` — the fi
 BCSR_MIN_BLOCKS = 2          # bcsr_try_build: `nnz < 2ll * b * rows` — two blocks per block-row on average
 BCSR_TILE = 1024             # spmv_bcsr.hip: `#define G4S_BCSR_TILE 1024`; bcsr_check_kernel: `L / b <= tile_blocks`, tile_blocks = kTile / b²
 BCSR_MAX_BROWS = 512         # spmv_bcsr.hip: `kMaxBrows = 512` — block-rows per work item
-PB_MIN_X_BYTES = 8 << 20     # spmv_pb.hip, pb_should_use: `cols * 8 < (8ll << 20) || nnz < (4ll << 20)` → never the blocked path
-PB_MIN_NNZ = 4 << 20         # (the same line)
+assert (PB_MIN_X_BYTES, PB_MIN_NNZ) == (8 << 20, 4 << 20)   # spmv_pb.hip, pb_should_use: `cols * 8 < (8ll << 20) || nnz < (4ll << 20)` → never the blocked path
 DIA_WG = 256                 # spmv_dia.hip: `constexpr int WG = 256;`
 XCDS = 8                     # common.hpp: kXcds — the grid of a diagonal launch is rounded up to a multiple of it
 
@@ -162,11 +163,13 @@ def bcsr_block(rows, cols, rowptr, colids):
 
 def expected_path(rows, cols, rowptr, colids, force_stream=False):   # force_stream: created with G4S_SPMV_STREAM
     """g4s_csr_info.spmv_path of a handle created from this matrix (csr.hip, g4s_csr_create): the diagonal form first, then the block-row form,
-    else the row-streaming kernel. Matrices large enough for the blocked path's locality probe are outside what this models."""
+    else the row-streaming kernel. A matrix large enough for the blocked path's locality probe takes the blocked path where the probe says so
+    (pb_cases.should_use), before the structured forms are tried."""
     nnz = int(rowptr[-1])
-    assert cols * 8 < PB_MIN_X_BYTES or nnz < PB_MIN_NNZ, "large enough for the blocked path's probe: not modelled"
     if force_stream or nnz == 0:
         return PATH_STREAM
+    if cols * 8 >= PB_MIN_X_BYTES and nnz >= PB_MIN_NNZ and should_use(rows, cols, nnz, colids)[0]:
+        return PATH_BLOCKED
     if dia_offsets(rows, cols, rowptr, colids) is not None:
         return PATH_DIAGONAL
     return PATH_BLOCKROW if bcsr_block(rows, cols, rowptr, colids) else PATH_STREAM
