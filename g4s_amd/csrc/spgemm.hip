@@ -26,7 +26,7 @@
 // Integer results (crpt, ccol) are exact; fp64 sums are accumulated with LDS/HBM atomics, i.e. in a different order than
 // the reference's (j outer, k inner): equal within the 1e-10 relative tolerance of the north star, not bit for bit.
 // The numeric kernels are templates on a value policy (semiring.hpp: plus-times, min-plus, max-plus, or-and), chosen once per call from the
-// G4S_SEMIRING_* flag bits (spgemm_numeric_impl); min and max atomics do not depend on the order of arrival, so those values are exact.
+// G4S_SEMIRING_* flag bits (sr::dispatch around spgemm_numeric_run); min and max atomics do not depend on the order of arrival, so those values are exact.
 #include "common.hpp"
 #ifndef G4S_SPGEMM_UPR
 #define G4S_SPGEMM_UPR 6   /* 4 until the end of round 4; with a round's descriptors requested together 5 / 6 / 7 / 8 units ran 31.2 / 31.0 / 31.25 / 31.75 ms against 31.6 (2: 34.1) */
@@ -88,6 +88,29 @@ struct ArenaScope {
 // window classes, which are latency-bound too: 33.5 ms against 32.6 for the call, three alternating runs each. The persistent window kernels behind the pre-passes
 // start on CUs the short rows still hold, and their longest-first tickets then run late on those. One stream.)
 
+// which shape takes which row class (G4S_SPGEMM_T_* override them for sweeps)
+constexpr int kShapeNumMedium = 256, kShapeSymMedium = 256, kShapeNumLarge = 256, kShapeNumM2 = 256, kShapeNumM3 = 1024, kNumM3Cut = 8192;
+constexpr int kWindowMaxN = 4 << 20;                  // widest B for which the window kernels take the mid-size rows too
+// The switches of one API call: every G4S_SPGEMM_* environment value and G4S_DEBUG, read ONCE at the top of g4s_spgemm_symbolic, g4s_spgemm_numeric and
+// g4s_spgemm_csr_i32_f64 and handed down by const reference (the one-call form: one snapshot for both phases). Read on every call, never cached: the tests change
+// the environment between calls of one process. Nothing else in this file reads the environment; what the values MEAN for a product is the plans' business
+// (SymPlan, NumPlan). No constructor is written out: the initialisers below are it.
+struct Switches {
+    static bool has(const char *name) { return getenv(name) != nullptr; }
+    static int num(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+    static int shape(const char *name, int dflt) { const int v = num(name, dflt); return v == 256 || v == 512 ? v : 1024; }   // a G4S_SPGEMM_T_* shape (sweeps): 256 and 512 are kept, anything else is 1024
+    bool debug = has("G4S_DEBUG"), no_wave_rows = has("G4S_SPGEMM_NO_WAVE_ROWS"), no_units = has("G4S_SPGEMM_NO_UNITS"), no_rank = has("G4S_SPGEMM_NO_RANK");
+    bool no_colscratch = has("G4S_SPGEMM_NO_COLSCRATCH"), no_colmap = has("G4S_SPGEMM_NO_COLMAP"), no_carry = has("G4S_SPGEMM_NO_CARRY"), static_rows = has("G4S_SPGEMM_STATIC_ROWS");
+    int mid_tables = num("G4S_SPGEMM_MID_TABLES", 0);              // A/B: bit 0 the ≤ 1024 class (and the symbolic mid class), 1: ≤ 2048, 2: ≤ 4096 through key tables
+    int window_max_n = num("G4S_SPGEMM_WINDOW_MAX_N", kWindowMaxN);   // tests force the table kernels with 0
+    int t_sym_med = shape("G4S_SPGEMM_T_SYM_MED", kShapeSymMedium);
+    // 0: not set — the default of the symbolic long classes is not a constant, it follows B's width (sym_plan)
+    int t_sym_large = has("G4S_SPGEMM_T_SYM_LARGE") ? shape("G4S_SPGEMM_T_SYM_LARGE", 0) : 0, t_sym_window = has("G4S_SPGEMM_T_SYM_WINDOW") ? shape("G4S_SPGEMM_T_SYM_WINDOW", 0) : 0;
+    int t_num_med = !has("G4S_SPGEMM_T_NUM_MED") ? kShapeNumMedium : num("G4S_SPGEMM_T_NUM_MED", 0) ? shape("G4S_SPGEMM_T_NUM_MED", 0) : 0;   // a value of 0: the table kernel
+    int t_num_large = shape("G4S_SPGEMM_T_NUM_LARGE", kShapeNumLarge), t_num_m2 = shape("G4S_SPGEMM_T_NUM_M2", kShapeNumM2), t_num_m3 = shape("G4S_SPGEMM_T_NUM_M3", kShapeNumM3);
+    int m3_cut = num("G4S_SPGEMM_M3_CUT", kNumM3Cut);
+};
+
 // Host-side phase times of one call under G4S_DEBUG (declared first in a function: its destructor runs after every buffer of the call has been released).
 struct DbgPhases {
     using clk = std::chrono::steady_clock;
@@ -95,7 +118,7 @@ struct DbgPhases {
     bool on;
     clk::time_point t0, last;
     std::string line;
-    explicit DbgPhases(const char *w) : what(w), on(getenv("G4S_DEBUG") != nullptr), t0(clk::now()), last(t0) {}
+    DbgPhases(const char *w, const Switches &sw) : what(w), on(sw.debug), t0(clk::now()), last(t0) {}
     void mark(const char *name)
     {
         if (!on) return;
@@ -681,9 +704,6 @@ struct BigCfg {
     static constexpr int kPerCu = 1024 / T;                          // workgroups per CU that fit in LDS (136 / 72 / 40 KiB each)
 };
 constexpr int kFlatUnitsPerRound = G4S_SPGEMM_UPR;   // 64-entry units of B rows a wave loads per round (independent loads in flight per lane)
-// which shape takes which row class (G4S_SPGEMM_T_* override them for sweeps)
-constexpr int kShapeNumMedium = 256, kShapeSymMedium = 256, kShapeNumLarge = 256, kShapeNumM2 = 256, kShapeNumM3 = 1024, kNumM3Cut = 8192;
-inline int shape_of(const char *env, int dflt) { const char *e = getenv(env); const int v = e ? atoi(e) : dflt; return v == 256 || v == 512 ? v : 1024; }
 // granularity of the window splits: the column range in 16 pieces (at most — the table holds a position per piece and B row), never finer
 // than 2^16 columns; every window size is a multiple, and a value chunk's columns are bracketed by whole pieces
 __host__ __device__ __forceinline__ int split_bits(int N)
@@ -696,9 +716,6 @@ __host__ __device__ __forceinline__ int split_bits(int N)
 // 4-word groups (bits 2–4 only), so a group stays one aligned 16-byte read, and within each of the instruction's four 16-lane groups
 // (MI355X_MICROARCH.md §LDS) the sixteen lanes land on sixteen different slots.
 __device__ __forceinline__ int bm_slot(int w) { return w ^ (((w >> 6) & 7) << 2); }
-constexpr int kWindowMaxN = 4 << 20;                  // widest B for which the window kernels take the mid-size rows too
-inline int mid_tables() { const char *e = getenv("G4S_SPGEMM_MID_TABLES"); return e ? atoi(e) : 0; }   // A/B: bit 0 the ≤ 1024 class (and the symbolic mid class), 1: ≤ 2048, 2: ≤ 4096 through key tables
-inline int window_max_n() { const char *e = getenv("G4S_SPGEMM_WINDOW_MAX_N"); return e ? atoi(e) : kWindowMaxN; }   // tests force the table kernels with 0
 // grid of the persistent big-row kernels: one workgroup per CU (their LDS allows no more), fewer when the class is small
 inline int big_grid(int nrows, int wgs_per_cu = 1)
 {
@@ -2099,10 +2116,9 @@ int allow_lds(Kernel k, size_t bytes)
 // Hub rows: mark → prefix (→ counts) [→ emit → accumulate], in batches bounded by the bitmap workspace.
 template <typename SR = sr::PlusTimes>
 int run_hub_rows(bool numeric, const std::vector<int> &hub_rows, const std::vector<int> &h_arpt_of_rows /*2 per row*/, int N,
-                 const int *arpt, const int *acol, const double *aval, const int *brpt, const int *bcol, const double *bval,
+                 const int *acol, const double *aval, const int *brpt, const int *bcol, const double *bval,
                  int *row_nz, const int *crpt, int *ccol, double *cval, hipStream_t s)
 {
-    (void)arpt;
     if (hub_rows.empty()) return G4S_OK;
     const int W = (N + 31) / 32;
     const size_t per_row = (size_t)W * 8; // bitmap + prefix words
@@ -2424,10 +2440,10 @@ __global__ void colmap_apply_kernel(long long nnz, const int *__restrict__ bcol,
     const int c = bcol[k];
     bcol2[k] = prefix[c >> 5] + __popc(bm[c >> 5] & ((1u << (c & 31)) - 1u));
 }
-int build_column_map(int N, long long bnnz, const int *bcol, ColumnMap &cm, hipStream_t s)
+int build_column_map(const Switches &sw, int N, long long bnnz, const int *bcol, ColumnMap &cm, hipStream_t s)
 {
     cm.n2 = 0;
-    if (N < (1 << 16) || bnnz <= 0 || getenv("G4S_SPGEMM_NO_COLMAP")) return G4S_OK;   // a single small window either way
+    if (N < (1 << 16) || bnnz <= 0 || sw.no_colmap) return G4S_OK;   // a single small window either way
     const int W = (N + 31) >> 5;
     DevBuf bm, cnt, prefix, seen;
     G4S_TRY(bm.alloc(sizeof(unsigned) * (size_t)W));
@@ -2448,7 +2464,7 @@ int build_column_map(int N, long long bnnz, const int *bcol, ColumnMap &cm, hipS
                        cm.bcol2.as<int>());
     G4S_HIP_TRY(hipGetLastError());                               // (bm / prefix / seen are released in stream order — or with the call's arena: no wait here)
     cm.n2 = n2;
-    if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s column map: %d of %d columns of B hold entries\n", n2, N);
+    if (sw.debug) fprintf(stderr, "g4s column map: %d of %d columns of B hold entries\n", n2, N);
     return G4S_OK;
 }
 
@@ -2531,7 +2547,7 @@ __global__ void row_size_keys_kernel(int n, const int *__restrict__ rows, const 
 }
 struct SortedRows {
     DevBuf keys, keys_sorted, rows, tmp, counter;
-    int build(int n, const int *list, const long long *size, const int *crpt, long long key_bound, hipStream_t s)
+    int build(int n, const int *list, const long long *size, const int *crpt, hipStream_t s)
     {
         G4S_TRY(keys.alloc(sizeof(int) * (size_t)n));
         G4S_TRY(keys_sorted.alloc(sizeof(int) * (size_t)n));
@@ -2539,7 +2555,6 @@ struct SortedRows {
         G4S_TRY(counter.alloc(sizeof(int)));
         G4S_HIP_TRY(hipMemsetAsync(counter.p, 0, sizeof(int), s));
         hipLaunchKernelGGL(row_size_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, list, size, crpt, keys.as<int>());
-        (void)key_bound;
         if (n <= g4s::prims::kSortSmallMax)                       // a short list: one launch (the keys are < 2^11; the order among equal keys decides nothing but who takes a row first)
             return g4s::prims::sort_pairs_descending_small_unstable(keys.as<int>(), list, keys_sorted.as<int>(), rows.as<int>(), n, s);
         G4S_TRY(tmp.alloc(sizeof(int) * 2 * (size_t)n));
@@ -2572,9 +2587,7 @@ __global__ void presorted_mark_kernel(int M, const long long *__restrict__ need,
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < M && need[i] == 0) off[i] = -1;
 }
-} // namespace
 
-namespace {
 // wsplit for the window kernels (see window_splits_kernel); left empty (kernels then read whole rows) for a single window or when
 // the table would be large (more than 16 windows).
 int build_window_splits(int K, int N, const int *brpt, const int *bcol, DevBuf &buf, const int **out, hipStream_t s, bool keep = false)
@@ -2589,10 +2602,137 @@ int build_window_splits(int K, int N, const int *brpt, const int *bcol, DevBuf &
     *out = buf.as<int>();
     return G4S_OK;
 }
-} // namespace
 
-namespace {
-int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, const int32_t *acol, const int32_t *brpt, const int32_t *bcol,
+template <int V> using int_c = std::integral_constant<int, V>;
+// A thread count as the window kernels' shape: f(int_c<256 | 512 | 1024>{}).
+template <typename F>
+int with_shape(int threads, F &&f)
+{
+    if (threads == 256) return f(int_c<256>{});
+    if (threads == 512) return f(int_c<512>{});
+    return f(int_c<1024>{});
+}
+
+// What a phase's launches leave behind — unit lists, row metadata, sorted row lists: their kernels are enqueued, not finished, when the code that
+// built them returns. One holder per API call, declared behind its ArenaScope: everything goes after the call's last wait and before the arena does.
+struct Transients {
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    std::vector<std::unique_ptr<SortedRows>> sorted;
+    DevBuf *buf() { bufs.push_back(std::make_unique<DevBuf>()); return bufs.back().get(); }
+    void take(std::unique_ptr<DevBuf> b) { bufs.push_back(std::move(b)); }   // (built outside: what a launch gives up on is released there and then, not at the end of the call)
+    SortedRows *rows() { sorted.push_back(std::make_unique<SortedRows>()); return sorted.back().get(); }
+};
+
+// every row has at most 512 products (symbolic) / outputs (numeric)
+inline bool only_short_rows(const RowClasses &rc) { return rc.count[CLS_MEDIUM] + rc.count[CLS_LARGE] + rc.count[CLS_M2] + rc.count[CLS_M3] + rc.count[CLS_HUB] + rc.count[CLS_RANK] == 0; }
+
+// The short rows of both phases (the tiny and the small class: their lists are adjacent): one wavefront merges a row (spgemm_small_wave_kernel; the first
+// n_tiny_form rows in its 64-product form); what does not fit it lands on a list that the phase's table kernel takes, its count read on the device. Without the wave
+// kernel the table kernel takes both classes. table(int_c<slots>, grid, rows, n, n_dev) launches the phase's table kernel: 64 slots per wavefront and four rows per
+// workgroup (64), or 1 024 slots per workgroup.
+template <bool NUMERIC, typename SR, typename Table>
+int launch_short_rows(bool use_wave, const RowClasses &rc, int n_tiny_form, const int *arpt, const int *acol, const double *aval, const int *brpt, const int *bcol,
+                      const double *bval, int *nz, const int *crpt, int *ccol, double *cval, DevBuf &ovf, DevBuf &ovf_n /* the hand-back list and its count: the caller's, they live to the end of its call */, hipStream_t s, Table table)
+{
+    if (int n = rc.count[CLS_TINY] + rc.count[CLS_SMALL]; n && use_wave) {
+        G4S_TRY(ovf.alloc(sizeof(int) * (size_t)n));
+        G4S_TRY(ovf_n.alloc(sizeof(int)));
+        G4S_HIP_TRY(hipMemsetAsync(ovf_n.p, 0, sizeof(int), s));
+        auto wave = [&](auto cap, const int *rows, int nr) {
+            constexpr int CAP = decltype(cap)::value;
+            auto k = spgemm_small_wave_kernel<NUMERIC, CAP, SR>;
+            constexpr size_t lds = sizeof(int) * 4 * small_wave_ints<NUMERIC, CAP>();
+            if (nr) hipLaunchKernelGGL(k, dim3((nr + 3) / 4), dim3(256), lds, s, rows, nr, arpt, acol, aval, brpt, bcol, bval, nz, crpt, ccol,
+                                       cval, ovf.as<int>(), ovf_n.as<int>());
+        };
+        wave(int_c<kTinyCap>{}, rc.list(CLS_TINY), n_tiny_form);
+        wave(int_c<kSmallCap>{}, rc.list(CLS_TINY) + n_tiny_form, n - n_tiny_form);
+        return table(int_c<1024>{}, std::min(n, 256), ovf.as<int>(), 0, ovf_n.as<int>());
+    }
+    if (int n = rc.count[CLS_TINY]) G4S_TRY(table(int_c<64>{}, (n + 3) / 4, rc.list(CLS_TINY), n, nullptr));
+    if (int n = rc.count[CLS_SMALL]) G4S_TRY(table(int_c<1024>{}, n, rc.list(CLS_SMALL), n, nullptr));
+    return G4S_OK;
+}
+
+// What the symbolic phase launches for one product: decided HERE, once, from the switches, the class counts, the width N2 of B's (compacted) column range and
+// whether there is a PreSorted to carry state in. The launch code reads these fields and derives nothing from a switch itself.
+struct SymPlan {
+    bool use_wave, use_units, longest_first, col_scratch;
+    bool x_med, x_large;         // the window kernel takes the MEDIUM / the LARGE class (else key tables)
+    int t_med, t_large, t_win;   // the shapes of the MEDIUM, LARGE and M2 launches
+    bool one_long_launch;        // LARGE and M2 share a shape and their lists are adjacent: one launch
+    int n_long;
+    bool rank;                   // the long classes write cuts. Eligible here: no memory for the cuts, or too many of them, still turns it off (set_rank)
+    unsigned class_mask;         // which classes the window kernel counts AND EMITS in this call: M2 always, MEDIUM / LARGE while B is narrow enough — without the classes that write cuts
+    void set_rank(bool on) { rank = on; class_mask = (x_med ? 1u << CLS_MEDIUM : 0u) | (on ? 0u : (1u << CLS_M2) | (x_large ? 1u << CLS_LARGE : 0u)); }
+};
+SymPlan sym_plan(const Switches &sw, const RowClasses &rc, int N2, bool can_carry)
+{
+    SymPlan p{};
+    p.use_wave = !sw.no_wave_rows; p.use_units = !sw.no_units; p.longest_first = !sw.static_rows; p.col_scratch = !sw.no_colscratch;
+    // Up to kWindowMaxN columns (4 bitmap windows) the window kernel beats the key tables for every row past 512 products (it has no
+    // probe chains and cannot overflow); with more windows each row would re-walk its products once per window, so tables take over.
+    p.x_large = N2 <= sw.window_max_n;
+    p.x_med = p.x_large && !sw.mid_tables;
+    // The long classes' shape follows B's width (round 5): the count-and-cut pass is barriers and round trips per window, not bitmap work, so four 256-thread
+    // workgroups per CU that fill each other's waits beat one of 1 024 threads even with five windows per row instead of two (configs[2]: 26.55 against 27.5 ms,
+    // 512 threads 27.1: profiles/r05_spgemm_ab.txt) — while the number of windows stays small.
+    const int long_shape = N2 <= 6 * (1 << 18) ? 256 : N2 <= 6 * (1 << 19) ? 512 : 1024;
+    p.t_med = sw.t_sym_med; p.t_large = sw.t_sym_large ? sw.t_sym_large : long_shape; p.t_win = sw.t_sym_window ? sw.t_sym_window : long_shape;
+    p.one_long_launch = p.x_large && p.t_large == p.t_win;
+    // Round 5: the long classes (more than 8 K products) write CUTS instead of columns and take the rank kernel in the numeric phase (spgemm_rank.hpp). Needs what the
+    // carried columns needed (a PreSorted to carry them in) plus the unit lists and the one long launch.
+    p.n_long = rc.count[CLS_LARGE] + rc.count[CLS_M2];
+    p.set_rank(can_carry && p.one_long_launch && p.use_units && p.n_long > 0 && !sw.no_rank);
+    return p;
+}
+
+// … and for the numeric phase, in two parts. What it must know BEFORE it classifies the rows comes from the carried state alone (pre; NULL: none); which kernel and
+// shape takes which class (NumPlan) waits for N2 — without a carried state the column map is built behind the classification.
+inline bool windows_take(const Switches &sw, int N2, int table_bit) { return N2 <= sw.window_max_n && !(sw.mid_tables & table_bit); }   // a mid-size class (bit 2: ≤ 2048, 4: ≤ 4096) goes to the window kernel, not to its key table
+struct NumClassing {
+    bool rank;                   // the rows with cuts take the rank kernel (spgemm_rank.hpp)
+    int fifth_limit;             // of the numeric classes: 4 096 outputs, or 8 192 (below)
+};
+NumClassing num_classing(const Switches &sw, const PreSorted *pre, int N)
+{
+    NumClassing c{};
+    // (a snapshot with no_rank never meets carried cuts: the symbolic phase of the one-call form wrote none under it, and g4s_spgemm_numeric does not take over
+    // a state that holds some)
+    c.rank = pre && pre->rank && pre->d_cut_off;
+    // With the rank path on, what is left for the window kernels past 4 096 outputs is the rows of at most 8 192 products (and symbolic hub rows): those of up to
+    // 8 192 outputs join the mid-size launch (four 2 048-output chunks at most) instead of being a launch — a row sort, unit lists, a persistent kernel — of their own.
+    // Only while the window kernel takes that class: the key table that G4S_SPGEMM_MID_TABLES=4 (or a B past window_max_n columns) puts in its place sorts through
+    // a dense copy of TABLE / 2 = 4 096 entries and would store the first 4 096 outputs of a longer row only. (rank ⇒ pre: the column map is the carried one.)
+    c.fifth_limit = c.rank && windows_take(sw, pre->cmap.width(N), 4) ? 8192 : kNumLimits.lim[4];
+    return c;
+}
+enum M3Form { M3_TWO_SHAPES, M3_STATIC, M3_LONGEST_FIRST };
+struct NumPlan {
+    bool use_wave, use_units;
+    bool win_med, win_large, win_m2;   // the window kernel takes the ≤ 1024 / ≤ 2048 / ≤ 4096 class (else key tables)
+    int t_med, t_large, t_m2, t_m3;    // the shapes of the four window classes
+    int m3_cut;
+    bool one_mid_launch;         // the three mid-size classes (512 < nz <= 4 096) share a shape and their lists are adjacent: one launch, one set of unit lists, one tail instead of three
+    M3Form m3_form;              // the ≤ 1M class: short rows in t_m3 and the rest in 1 024 threads; or one launch in list order; or one launch longest first …
+    int t_m3_whole;              // … in this shape (G4S_SPGEMM_M3_CUT=0 + G4S_SPGEMM_T_NUM_M3: the whole class in another shape than 1 024 threads)
+};
+NumPlan num_plan(const Switches &sw, int N2)
+{
+    NumPlan p{};
+    p.use_wave = !sw.no_wave_rows; p.use_units = !sw.no_units;
+    p.t_med = (sw.mid_tables & 1) ? 0 : sw.t_num_med;              // 0: the table kernel
+    p.t_large = sw.t_num_large; p.t_m2 = sw.t_num_m2; p.t_m3 = sw.t_num_m3; p.m3_cut = sw.m3_cut;
+    // Rows past 1 K entries: bitmap windows + bucketed slots beat table + in-LDS bitonic sort while the column range is <= 4 windows.
+    p.win_large = windows_take(sw, N2, 2); p.win_m2 = windows_take(sw, N2, 4); p.win_med = p.t_med && p.win_large;
+    p.one_mid_launch = p.win_med && p.win_m2 && p.t_med == p.t_large && p.t_large == p.t_m2;
+    // the ≤ 1M class spans 4 K … 128 K entries: its short rows go to the many-workgroups shape, the long ones keep 1 024 threads
+    p.m3_form = p.t_m3 != 1024 && p.m3_cut > 0 ? M3_TWO_SHAPES : sw.static_rows ? M3_STATIC : M3_LONGEST_FIRST;
+    p.t_m3_whole = p.m3_cut <= 0 ? p.t_m3 : 1024;
+    return p;
+}
+
+int spgemm_symbolic_impl(const Switches &sw, int32_t M, int32_t K, int32_t N, const int32_t *arpt, const int32_t *acol, const int32_t *brpt, const int32_t *bcol,
                          int32_t *crpt, int64_t *cnnz, void *stream, PreSorted *pre)
 {
     G4S_REQUIRE(M >= 0 && K >= 0 && N >= 0, "negative dimension");
@@ -2602,8 +2742,9 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
     t_idle = false;
     *cnnz = 0;
     if (M == 0) { G4S_HIP_TRY(hipMemsetAsync(crpt, 0, sizeof(int), s)); return G4S_OK; }
-    DbgPhases dbg("symbolic");
+    DbgPhases dbg("symbolic", sw);
     ArenaScope arena;
+    Transients keep;
     int annz = 0, bnnz = 0;
     G4S_TRY(read_last2(arpt, M, &annz, brpt, K, &bnnz, s));
 
@@ -2625,23 +2766,23 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         G4S_TRY(gather_b(bnnz, pm.as<int>(), bcol, nullptr, bs.as<int>(), nullptr, s));
         bcol = bs.as<int>();
         if (pre) pre->b_unsorted = true;
-        if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s symbolic: the rows of B are not sorted by column — working on a sorted private copy\n");
+        if (sw.debug) fprintf(stderr, "g4s symbolic: the rows of B are not sorted by column — working on a sorted private copy\n");
     }
 
     dbg.mark("row_flop");
     RowClasses local_rc;
     RowClasses &rc = pre ? pre->sym_rc : local_rc;
     G4S_TRY(classify_rows(M, row_flop.as<long long>(), kSymLimits, N, rc, s));
-    const bool only_short = rc.count[CLS_MEDIUM] + rc.count[CLS_LARGE] + rc.count[CLS_M2] + rc.count[CLS_M3] + rc.count[CLS_HUB] == 0;   // every row ≤ 512 products
+    const bool only_short = only_short_rows(rc);
     if (pre) pre->sym_rc_valid = only_short && !pre->keep;
     dbg.mark("classes");
-    if (getenv("G4S_DEBUG"))
+    if (sw.debug)
         fprintf(stderr, "g4s symbolic classes: empty %d tiny %d small %d medium %d large %d window %d hub %d (flop %lld)\n", rc.count[CLS_EMPTY], rc.count[CLS_TINY],
                 rc.count[CLS_SMALL], rc.count[CLS_MEDIUM], rc.count[CLS_LARGE], rc.count[CLS_M2], rc.count[CLS_HUB], (long long)flop);
     // the bitmap-window kernels work on B's non-empty columns, renumbered (N2 of them; the original ids when that would not pay)
     ColumnMap local_map;
     ColumnMap &cmap = pre ? pre->cmap : local_map;
-    if (!only_short) G4S_TRY(build_column_map(N, bnnz, bcol, cmap, s));   // (left out, the map is the identity)
+    if (!only_short) G4S_TRY(build_column_map(sw, N, bnnz, bcol, cmap, s));   // (left out, the map is the identity)
     const int *wcol = cmap.cols(bcol);
     const int N2 = cmap.width(N);
     DevBuf wsplit_local;
@@ -2651,68 +2792,33 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         if (pre) { pre->wsplit = wsplit; pre->has_wsplit = true; }
     }
     dbg.mark("colmap+splits");
+    SymPlan plan = sym_plan(sw, rc, N2, pre != nullptr);
     G4S_TRY(ovf_rows.alloc(sizeof(int) * (size_t)std::max(1, rc.count[CLS_LARGE])));
     G4S_TRY(ovf_count.alloc(sizeof(int)));
     G4S_HIP_TRY(hipMemsetAsync(ovf_count.p, 0, sizeof(int), s));
     int *nz = row_nz.as<int>();
 
-    // rows of at most 512 products (the tiny and the small class: their lists are adjacent): one wavefront merges a row (spgemm_small_wave_kernel); what does not
-    // fit it (more than 64 A-entries) lands on a list that the table kernel takes, its count read on the device
+    // the key-table kernel on a list of rows, by table size: 64 slots per wavefront and four rows per workgroup, else one row per 256-thread workgroup
+    auto table = [&](auto slots, int grid, const int *rows, int n, const int *n_dev) -> int {
+        constexpr int S = decltype(slots)::value, RPB = S == 64 ? 4 : 1;
+        auto k = spgemm_symbolic_lds_kernel<256, S == 64 ? 64 : 256, S, false>;
+        G4S_TRY(allow_lds(k, sym_lds_bytes(RPB, S)));
+        hipLaunchKernelGGL(k, dim3(grid), dim3(256), sym_lds_bytes(RPB, S), s, rows, n, arpt, acol, brpt, bcol, row_flop.as<long long>(), nz, nullptr, nullptr, n_dev);
+        return G4S_OK;
+    };
+    // rows of at most 512 products: launch_short_rows; what the wave kernel hands back (more than 64 A-entries) goes to the 1 024-slot table
     DevBuf small_ovf, small_ovf_n;
-    const bool use_wave = !getenv("G4S_SPGEMM_NO_WAVE_ROWS");
-    if (int n = rc.count[CLS_TINY] + rc.count[CLS_SMALL]; n && use_wave) {
-        G4S_TRY(small_ovf.alloc(sizeof(int) * (size_t)n));
-        G4S_TRY(small_ovf_n.alloc(sizeof(int)));
-        G4S_HIP_TRY(hipMemsetAsync(small_ovf_n.p, 0, sizeof(int), s));
-        if (int nt = rc.count[CLS_TINY]) {                          // at most 32 products each
-            auto k = spgemm_small_wave_kernel<false, kTinyCap>;
-            constexpr size_t lds = sizeof(int) * 4 * small_wave_ints<false, kTinyCap>();
-            hipLaunchKernelGGL(k, dim3((nt + 3) / 4), dim3(256), lds, s, rc.list(CLS_TINY), nt, arpt, acol, (const double *)nullptr, brpt, bcol,
-                               (const double *)nullptr, nz, (const int *)nullptr, (int *)nullptr, (double *)nullptr, small_ovf.as<int>(), small_ovf_n.as<int>());
-        }
-        if (int ns = rc.count[CLS_SMALL]) {
-            auto k = spgemm_small_wave_kernel<false>;
-            hipLaunchKernelGGL(k, dim3((ns + 3) / 4), dim3(256), sizeof(int) * 4 * small_wave_ints<false>(), s, rc.list(CLS_SMALL), ns, arpt, acol, (const double *)nullptr, brpt, bcol,
-                               (const double *)nullptr, nz, (const int *)nullptr, (int *)nullptr, (double *)nullptr, small_ovf.as<int>(), small_ovf_n.as<int>());
-        }
-        auto k2 = spgemm_symbolic_lds_kernel<256, 256, 1024, false>;
-        hipLaunchKernelGGL(k2, dim3(std::min(n, 256)), dim3(256), sym_lds_bytes(1, 1024), s, small_ovf.as<int>(), 0, arpt, acol, brpt, bcol, row_flop.as<long long>(), nz, nullptr, nullptr,
-                           (const int *)small_ovf_n.as<int>());
-    } else {
-    if (int n = rc.count[CLS_TINY]) {
-        auto k = spgemm_symbolic_lds_kernel<256, 64, 64, false>;
-        hipLaunchKernelGGL(k, dim3((n + 3) / 4), dim3(256), sym_lds_bytes(4, 64), s, rc.list(CLS_TINY), n, arpt, acol, brpt, bcol, row_flop.as<long long>(), nz, nullptr, nullptr, (const int *)nullptr);
-    }
-    if (int n = rc.count[CLS_SMALL]) {
-        auto k = spgemm_symbolic_lds_kernel<256, 256, 1024, false>;
-        hipLaunchKernelGGL(k, dim3(n), dim3(256), sym_lds_bytes(1, 1024), s, rc.list(CLS_SMALL), n, arpt, acol, brpt, bcol, row_flop.as<long long>(), nz, nullptr, nullptr, (const int *)nullptr);
-    }
-    }
-    // Up to kWindowMaxN columns (4 bitmap windows) the window kernel beats the key tables for every row past 512 products (it has no
-    // probe chains and cannot overflow); with more windows each row would re-walk its products once per window, so tables take over.
-    const bool x_large = N2 <= window_max_n(), x_med = x_large && !mid_tables();
+    G4S_TRY((launch_short_rows<false, sr::PlusTimes>(plan.use_wave, rc, rc.count[CLS_TINY], arpt, acol, nullptr, brpt, bcol, nullptr, nz, nullptr, nullptr, nullptr, small_ovf, small_ovf_n, s, table)));
     const long long *pre_off = nullptr;
     int *pre_cols = nullptr;
-    const bool use_units = !getenv("G4S_SPGEMM_NO_UNITS");
-    // The long classes' shape follows B's width (round 5): the count-and-cut pass is barriers and round trips per window, not bitmap work, so four 256-thread
-    // workgroups per CU that fill each other's waits beat one of 1 024 threads even with five windows per row instead of two (configs[2]: 26.55 against 27.5 ms,
-    // 512 threads 27.1: profiles/r05_spgemm_ab.txt) — while the number of windows stays small.
-    const int long_shape = N2 <= 6 * (1 << 18) ? 256 : N2 <= 6 * (1 << 19) ? 512 : 1024;
-    const int t_med = shape_of("G4S_SPGEMM_T_SYM_MED", kShapeSymMedium), t_large = shape_of("G4S_SPGEMM_T_SYM_LARGE", long_shape),
-              t_win = shape_of("G4S_SPGEMM_T_SYM_WINDOW", long_shape);
-    const bool one_long_launch = x_large && t_large == t_win;   // LARGE and M2 share a shape and their lists are adjacent: one launch
-    // Round 5: the long classes (more than 8 K products) write CUTS instead of columns and take the rank kernel in the numeric phase (spgemm_rank.hpp). Needs what the
-    // carried columns needed (a PreSorted to carry them in) plus the unit lists and the one long launch.
-    const int n_long = rc.count[CLS_LARGE] + rc.count[CLS_M2];
-    bool use_rank = pre && one_long_launch && use_units && n_long > 0 && !getenv("G4S_SPGEMM_NO_RANK");
     const int nseg = rank_segments(N2);
     long long *cut_off = nullptr;
     int *cuts = nullptr;
-    if (use_rank) {
-        const long long cut_bound = (long long)n_long * (nseg + 1) + flop / kRankCut + 1;   // Σ (nseg + min(flop_i, N2) / chunk + 1) over the long rows: no count comes back
+    if (plan.rank) {
+        const long long cut_bound = (long long)plan.n_long * (nseg + 1) + flop / kRankCut + 1;   // Σ (nseg + min(flop_i, N2) / chunk + 1) over the long rows: no count comes back
         DevBuf need;
         if (cut_bound >= (1ll << 30) || need.alloc(sizeof(long long) * ((size_t)M + 1)) != G4S_OK || pre->cut_off_buf.alloc(sizeof(long long) * ((size_t)M + 1), pre->keep) != G4S_OK ||
-            pre->cuts_buf.alloc(sizeof(int) * (size_t)cut_bound, pre->keep) != G4S_OK) { (void)hipGetLastError(); use_rank = false; }
+            pre->cuts_buf.alloc(sizeof(int) * (size_t)cut_bound, pre->keep) != G4S_OK) { (void)hipGetLastError(); plan.set_rank(false); }
         else {
             const unsigned long_mask = (1u << CLS_LARGE) | (1u << CLS_M2);
             hipLaunchKernelGGL(rank_need_kernel, dim3((M + 256) / 256), dim3(256), 0, s, M, rc.cls.as<int>(), long_mask, row_flop.as<long long>(), N2, nseg, need.as<long long>());
@@ -2723,14 +2829,11 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         }
     }
     if (pre && !only_short) {
-        // which classes the window kernel counts AND EMITS in this call: M2 always, MEDIUM / LARGE while B is narrow enough — without the classes that write cuts
-        const unsigned class_mask = use_rank ? (x_med ? (1u << CLS_MEDIUM) : 0u) : ((1u << CLS_M2) | (x_med ? (1u << CLS_MEDIUM) : 0u) | (x_large ? (1u << CLS_LARGE) : 0u));
         DevBuf need;
         G4S_TRY(need.alloc(sizeof(long long) * ((size_t)M + 1)));
         G4S_TRY(pre->off.alloc(sizeof(long long) * ((size_t)M + 1), pre->keep));
         G4S_HIP_TRY(hipMemsetAsync(need.p, 0, sizeof(long long) * ((size_t)M + 1), s));
-        const long long min_flop = kPresortMinFlop;
-        hipLaunchKernelGGL(presorted_need_kernel, dim3((M + 255) / 256), dim3(256), 0, s, M, rc.cls.as<int>(), class_mask, row_flop.as<long long>(), N2, min_flop, need.as<long long>());
+        hipLaunchKernelGGL(presorted_need_kernel, dim3((M + 255) / 256), dim3(256), 0, s, M, rc.cls.as<int>(), plan.class_mask, row_flop.as<long long>(), N2, kPresortMinFlop, need.as<long long>());
         G4S_TRY(g4s::prims::exclusive_scan(need.as<long long>(), pre->off.as<long long>(), (long long)M + 1, s));
         long long total_cols = 0;
         G4S_HIP_TRY(g4s::ReadScope(s).fetch(total_cols, pre->off.as<long long>() + M));
@@ -2740,7 +2843,7 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         // (g_col_cache.bytes is read here without its lock, beside other threads' products: only a hint for whether to ask at all — acquire_column_scratch
         // decides under the lock, and a stale size costs at most one product the scratch)
         // G4S_SPGEMM_NO_COLSCRATCH=1: the product runs as it does while another call holds the scratch (the numeric phase marks and emits its rows itself)
-        if (total_cols > 0 && !getenv("G4S_SPGEMM_NO_COLSCRATCH") &&
+        if (total_cols > 0 && plan.col_scratch &&
             ((size_t)total_cols * sizeof(int) <= free_b / 4 || (size_t)total_cols * sizeof(int) <= g_col_cache.bytes))
             cols = acquire_column_scratch(sizeof(int) * (size_t)total_cols);
         if (cols) {
@@ -2749,11 +2852,10 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
             G4S_HIP_TRY(hipGetLastError());                        // (need is released in stream order — or with the call's arena: no wait here)
             pre->d_off = pre_off = pre->off.as<long long>();
             pre->d_cols = pre_cols = cols;
-            if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s symbolic: %.2f GB scratch for pre-sorted columns\n", total_cols * 4 / 1e9);
+            if (sw.debug) fprintf(stderr, "g4s symbolic: %.2f GB scratch for pre-sorted columns\n", total_cols * 4 / 1e9);
         }
     }
     dbg.mark("tables+presort");
-    std::vector<std::unique_ptr<DevBuf>> unit_keep;                // unit lists of the window launches: live until the stream is synchronised below
     bool rank_done = false;                                        // the long launch ran in its cut-writing form
     auto window_t = [&](auto shape, const int *rows, int n, const long long *poff, int *pcols, int *next_row, bool cuts_mode) -> int {
         constexpr int T = decltype(shape)::value;
@@ -2764,7 +2866,7 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         // come back from the device in front of the launch
         const int nwin = (N2 + (1 << BigCfg<T>::kWindowBits) - 1) >> BigCfg<T>::kWindowBits;
         const long long ibound = (long long)annz * nwin, ubound = flop / 64 + ibound;
-        if (use_units && ibound > 0 && ibound <= (1ll << 28) && ubound <= (1ll << 28)) {
+        if (plan.use_units && ibound > 0 && ibound <= (1ll << 28) && ubound <= (1ll << 28)) {
             auto items = std::make_unique<DevBuf>(), ioff = std::make_unique<DevBuf>(), ucnt = std::make_unique<DevBuf>(), uoff = std::make_unique<DevBuf>(), ud = std::make_unique<DevBuf>();
             bool ok = items->alloc(sizeof(long long) * ((size_t)n + 1)) == G4S_OK && ioff->alloc(sizeof(long long) * ((size_t)n + 1)) == G4S_OK &&
                       ucnt->alloc(sizeof(int) * ((size_t)ibound + 1)) == G4S_OK && uoff->alloc(sizeof(int) * ((size_t)ibound + 1)) == G4S_OK &&
@@ -2779,22 +2881,19 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
                 G4S_TRY(g4s::prims::exclusive_scan(ucnt->as<int>(), uoff->as<int>(), ibound + 1, s));
                 hipLaunchKernelGGL(sym_unit_kernel<true>, dim3(ugrid), dim3(256), 0, s, ibound, n, rows, ioff->as<long long>(), arpt, acol, brpt, K, N2, wsplit, BigCfg<T>::kWindowBits,
                                    (int *)nullptr, uoff->as<int>(), ud->as<SymUnit>());
-                auto rmeta = std::make_unique<DevBuf>();
+                DevBuf *rmeta = keep.buf();
                 G4S_TRY(rmeta->alloc(sizeof(SymRowMeta) * (size_t)n));
                 hipLaunchKernelGGL(sym_row_meta_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, arpt, poff, ioff->as<long long>(), uoff->as<int>(), rmeta->as<SymRowMeta>());
-                if (cuts_mode) {
-                    auto k = spgemm_symbolic_units_kernel<T, true>;
+                auto launch = [&](auto with_cuts) -> int {
+                    auto k = spgemm_symbolic_units_kernel<T, decltype(with_cuts)::value>;
                     G4S_TRY(allow_lds(k, lds));
                     hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, next_row, N2, arpt, wcol, nz, poff, pcols, ioff->as<long long>(), uoff->as<int>(), ud->as<SymUnit>(), rmeta->as<SymRowMeta>());
-                    rank_done = true;
-                } else {
-                    auto k = spgemm_symbolic_units_kernel<T, false>;
-                    G4S_TRY(allow_lds(k, lds));
-                    hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, next_row, N2, arpt, wcol, nz, poff, pcols, ioff->as<long long>(), uoff->as<int>(), ud->as<SymUnit>(), rmeta->as<SymRowMeta>());
-                }
+                    return G4S_OK;
+                };
+                G4S_TRY(cuts_mode ? launch(std::true_type{}) : launch(std::false_type{}));
+                if (cuts_mode) rank_done = true;
                 G4S_HIP_TRY(hipGetLastError());
-                unit_keep.push_back(std::move(rmeta));
-                unit_keep.push_back(std::move(items)); unit_keep.push_back(std::move(ioff)); unit_keep.push_back(std::move(ucnt)); unit_keep.push_back(std::move(uoff)); unit_keep.push_back(std::move(ud));
+                for (auto *b : {&items, &ioff, &ucnt, &uoff, &ud}) keep.take(std::move(*b));
                 return G4S_OK;
             }
         }
@@ -2804,30 +2903,21 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
         hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, next_row, N2, K, wsplit, arpt, acol, brpt, wcol, row_flop.as<long long>(), nz, poff, pcols, (const int *)nullptr, 0, 0);
         return G4S_OK;
     };
-    SortedRows sorted[3];                                          // live until the stream is synchronised below
-    int n_sorted = 0;
     auto window = [&](int threads, const int *rows, int n, const long long *poff, int *pcols, bool longest_first = false, bool cuts_mode = false) -> int {
         int *next_row = nullptr;
-        if (longest_first && n > 1 && !getenv("G4S_SPGEMM_STATIC_ROWS")) {
-            SortedRows &sr = sorted[n_sorted++];
-            G4S_TRY(sr.build(n, rows, row_flop.as<long long>(), nullptr, INT_MAX, s));
-            rows = sr.rows.as<int>(); next_row = sr.counter.as<int>();
+        if (longest_first && n > 1 && plan.longest_first) {
+            SortedRows *sr = keep.rows();
+            G4S_TRY(sr->build(n, rows, row_flop.as<long long>(), nullptr, s));
+            rows = sr->rows.as<int>(); next_row = sr->counter.as<int>();
         }
-        if (threads == 256) return window_t(std::integral_constant<int, 256>{}, rows, n, poff, pcols, next_row, cuts_mode);
-        if (threads == 512) return window_t(std::integral_constant<int, 512>{}, rows, n, poff, pcols, next_row, cuts_mode);
-        return window_t(std::integral_constant<int, 1024>{}, rows, n, poff, pcols, next_row, cuts_mode);
+        return with_shape(threads, [&](auto shape) { return window_t(shape, rows, n, poff, pcols, next_row, cuts_mode); });
     };
     // (Round 5 measured the long classes' launch on a side stream, its pre-passes beside the mid-size class's kernel, and the same for the numeric phase: 31.9 / 31.0 ms
     // against 31.3 / 31.6 on one stream — nothing. The persistent kernels run four waves of 128 registers per SIMD: no wave of another kernel fits beside them.)
-    if (x_med) { G4S_TRY(window(t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM], pre_off, pre_cols, true)); }
-    else if (int n = rc.count[CLS_MEDIUM]) {
-        auto k = spgemm_symbolic_lds_kernel<256, 256, 16384, false>;
-        G4S_TRY(allow_lds(k, sym_lds_bytes(1, 16384)));
-        hipLaunchKernelGGL(k, dim3(n), dim3(256), sym_lds_bytes(1, 16384), s, rc.list(CLS_MEDIUM), n, arpt, acol, brpt, bcol, row_flop.as<long long>(), nz, nullptr, nullptr, (const int *)nullptr);
-    }
-    if (one_long_launch && use_rank) { G4S_TRY(window(t_large, rc.list(CLS_LARGE), n_long, cut_off, cuts, true, true)); }
-    else if (one_long_launch) { G4S_TRY(window(t_large, rc.list(CLS_LARGE), rc.count[CLS_LARGE] + rc.count[CLS_M2], pre_off, pre_cols, true)); }
-    else if (x_large) { G4S_TRY(window(t_large, rc.list(CLS_LARGE), rc.count[CLS_LARGE], pre_off, pre_cols, true)); }
+    if (plan.x_med) { G4S_TRY(window(plan.t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM], pre_off, pre_cols, true)); }
+    else if (int n = rc.count[CLS_MEDIUM]) G4S_TRY(table(int_c<16384>{}, n, rc.list(CLS_MEDIUM), n, nullptr));
+    if (plan.rank) { G4S_TRY(window(plan.t_large, rc.list(CLS_LARGE), plan.n_long, cut_off, cuts, true, true)); }   // (rank ⇒ one_long_launch)
+    else if (plan.x_large) { G4S_TRY(window(plan.t_large, rc.list(CLS_LARGE), plan.one_long_launch ? plan.n_long : rc.count[CLS_LARGE], pre_off, pre_cols, true)); }
     else if (int n = rc.count[CLS_LARGE]) {
         auto k = spgemm_symbolic_lds_kernel<1024, 1024, 32768, true>;
         G4S_TRY(allow_lds(k, sym_lds_bytes(1, 32768)));
@@ -2838,24 +2928,24 @@ int spgemm_symbolic_impl(int32_t M, int32_t K, int32_t N, const int32_t *arpt, c
 
     // rows too wide for a key table in LDS: the rows whose optimistic table filled up, and the window class → LDS bitmap windows
     int n_ovf = 0;
-    if (!x_large) {                                                // (only the optimistic table kernel can overflow)
+    if (!plan.x_large) {                                           // (only the optimistic table kernel can overflow)
         G4S_HIP_TRY(g4s::ReadScope(s).fetch(n_ovf, ovf_count.p));
-        if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s symbolic: %d optimistic tables overflowed, %d window-class rows\n", n_ovf, rc.count[CLS_M2]);
+        if (sw.debug) fprintf(stderr, "g4s symbolic: %d optimistic tables overflowed, %d window-class rows\n", n_ovf, rc.count[CLS_M2]);
         G4S_TRY(window(1024, ovf_rows.as<int>(), n_ovf, nullptr, nullptr));   // rows of the optimistic table class are not in the scratch
     }
     if (pre) {
         pre->rank = rank_done; pre->nseg = nseg; pre->bnnz = bnnz; pre->annz = annz;
         if (rank_done) { pre->d_cut_off = cut_off; pre->d_cuts = cuts; }
         // complete: every row the numeric WINDOW kernels will take carries its columns (the rows with cuts take the rank kernel and need none)
-        pre->complete = pre_off != nullptr && n_ovf == 0 && rc.count[CLS_HUB] == 0 && x_med && x_large && (!use_rank || rank_done);
+        pre->complete = pre_off != nullptr && n_ovf == 0 && rc.count[CLS_HUB] == 0 && plan.x_med && plan.x_large && (!plan.rank || rank_done);
         pre->flop = flop;
     }
-    if (!one_long_launch) G4S_TRY(window(t_win, rc.list(CLS_M2), rc.count[CLS_M2], pre_off, pre_cols, true));
+    if (!plan.one_long_launch) G4S_TRY(window(plan.t_win, rc.list(CLS_M2), rc.count[CLS_M2], pre_off, pre_cols, true));
     G4S_HIP_TRY(hipGetLastError());
     // hub rows (flop > 2 M): many workgroups per row on a bitmap in HBM
     std::vector<int> hub, ranges;
     G4S_TRY(fetch_rows_and_ranges(rc.list(CLS_HUB), rc.count[CLS_HUB], arpt, hub, ranges, s));
-    G4S_TRY(run_hub_rows(false, hub, ranges, N, arpt, acol, nullptr, brpt, bcol, nullptr, nz, nullptr, nullptr, nullptr, s));
+    G4S_TRY(run_hub_rows(false, hub, ranges, N, acol, nullptr, brpt, bcol, nullptr, nz, nullptr, nullptr, nullptr, s));
 
     dbg.mark("windows+hub(+sync)");
     // scan(bin.row_nz, crpt, nrow+1); *nnz = crpt[nrow]   (hash_mult.h:506-507)
@@ -2916,11 +3006,12 @@ G4S_API g4s_status g4s_spgemm_symbolic(int32_t M, int32_t K, int32_t N,
                                        const int32_t *arpt, const int32_t *acol, const int32_t *brpt, const int32_t *bcol,
                                        int32_t *crpt, int64_t *cnnz, void *stream)
 {
+    const Switches sw{};
     drop_carried();
-    if (getenv("G4S_SPGEMM_NO_CARRY")) return spgemm_symbolic_impl(M, K, N, arpt, acol, brpt, bcol, crpt, cnnz, stream, nullptr);
+    if (sw.no_carry) return spgemm_symbolic_impl(sw, M, K, N, arpt, acol, brpt, bcol, crpt, cnnz, stream, nullptr);
     auto pre = std::make_shared<PreSorted>();
     pre->keep = true; pre->cmap.keep = true;
-    const int st = spgemm_symbolic_impl(M, K, N, arpt, acol, brpt, bcol, crpt, cnnz, stream, pre.get());
+    const int st = spgemm_symbolic_impl(sw, M, K, N, arpt, acol, brpt, bcol, crpt, cnnz, stream, pre.get());
     if (st != G4S_OK) return st;
     std::lock_guard<std::mutex> lock(g_carried.m);
     g_carried.pre = std::move(pre);
@@ -2932,23 +3023,24 @@ G4S_API g4s_status g4s_spgemm_symbolic(int32_t M, int32_t K, int32_t N,
 namespace {
 // One instantiation per semiring (semiring.hpp): the host logic is the same for all four, only the numeric kernels it launches differ.
 template <typename SR>
-int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
+int spgemm_numeric_run(const Switches &sw, int32_t M, int32_t K, int32_t N,
                        const int32_t *arpt, const int32_t *acol, const double *aval,
                        const int32_t *brpt, const int32_t *bcol, const double *bval,
-                       const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream, const PreSorted *pre)
+                       const int32_t *crpt, int32_t *ccol, double *cval, void *stream, const PreSorted *pre)
 {
     const long long *pre_off = pre ? pre->d_off : nullptr;
     const int *pre_cols = pre ? pre->d_cols : nullptr;
-    (void)flags; // the semiring bits chose SR (spgemm_numeric_impl); rows always come out sorted by column: the sorted form is the only ordering contract (hash_mult.h:530-551)
+    // the semiring bits of the flags chose SR (sr::dispatch at the two callers); rows always come out sorted by column: the sorted form is the only ordering contract (hash_mult.h:530-551)
     G4S_REQUIRE(M >= 0 && N >= 0, "negative dimension");
     G4S_REQUIRE(arpt && brpt && crpt, "NULL argument");
     hipStream_t s = g4s::as_stream(stream);
     t_stream = s;
     t_idle = false;
     if (M == 0) return G4S_OK;
-    DbgPhases dbg("numeric");
+    DbgPhases dbg("numeric", sw);
     ArenaScope arena;
     g4s::ReadScope reads(s);                                       // (behind the arena: gone, and its stream idle, before the arena's memory is)
+    Transients keep;
     // B with unsorted rows: the kernels read a sorted private copy (sort_b_rows) — the symbolic phase's columns and permutation when they were carried over, else made here.
     // (Done in front of the short-row kernels: every kernel of the phase reads the same B.)
     DevBuf local_perm, local_bs, local_bv;
@@ -2974,51 +3066,68 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
     // lanes per A-entry are sized from the row's average B-row length; the exact nz of the output row (known here) stands in for
     // the flop count of the symbolic phase (they differ by the row's compression ratio), which saves a pass over A
     DevBuf row_size;
-    DevBuf &row_flop = row_size;
     G4S_TRY(row_size.alloc(sizeof(long long) * (size_t)M));
-    const bool rank = pre && pre->rank && pre->d_cut_off && !getenv("G4S_SPGEMM_NO_RANK");   // the rows with cuts take the rank kernel (spgemm_rank.hpp)
-    hipLaunchKernelGGL(nz_to_ll_kernel, dim3((M + 255) / 256), dim3(256), 0, s, M, crpt, rank ? pre->d_cut_off : (const long long *)nullptr, row_size.as<long long>());
+    const NumClassing classing = num_classing(sw, pre, N);
+    hipLaunchKernelGGL(nz_to_ll_kernel, dim3((M + 255) / 256), dim3(256), 0, s, M, crpt, classing.rank ? pre->d_cut_off : (const long long *)nullptr, row_size.as<long long>());
     RowClasses local_rc;
     const bool reuse_rc = pre && pre->sym_rc_valid;                // (see PreSorted::sym_rc)
-    // With the rank path on, what is left for the window kernels past 4 096 outputs is the rows of at most 8 192 products (and symbolic hub rows): those of up to
-    // 8 192 outputs join the mid-size launch (four 2 048-output chunks at most) instead of being a launch — a row sort, unit lists, a persistent kernel — of their own.
-    // Only while the window kernel takes that class: the key table that G4S_SPGEMM_MID_TABLES=4 (or a B past window_max_n() columns) puts in its place sorts through
-    // a dense copy of TABLE / 2 = 4 096 entries and would store the first 4 096 outputs of a longer row only. (rank ⇒ pre: the column map is the carried one.)
-    const bool m2_windows = pre && pre->cmap.width(N) <= window_max_n() && !(mid_tables() & 4);
     ClassLimits num_limits = kNumLimits;
-    if (rank && m2_windows) num_limits.lim[4] = 8192;
+    num_limits.lim[4] = classing.fifth_limit;
     if (!reuse_rc) G4S_TRY(classify_rows(M, row_size.as<long long>(), num_limits, 0, local_rc, s));
     const RowClasses &rc = reuse_rc ? pre->sym_rc : local_rc;
-    const bool num_only_short = rc.count[CLS_MEDIUM] + rc.count[CLS_LARGE] + rc.count[CLS_M2] + rc.count[CLS_M3] + rc.count[CLS_HUB] + rc.count[CLS_RANK] == 0;
-    if (getenv("G4S_DEBUG"))
+    const bool num_only_short = only_short_rows(rc);
+    if (sw.debug)
         fprintf(stderr, "g4s numeric classes: empty %d <=32 %d <=512 %d <=1024 %d <=2048 %d <=4096 %d <=1M %d hub %d rank %d\n", rc.count[CLS_EMPTY], rc.count[CLS_TINY],
                 rc.count[CLS_SMALL], rc.count[CLS_MEDIUM], rc.count[CLS_LARGE], rc.count[CLS_M2], rc.count[CLS_M3], rc.count[CLS_HUB], rc.count[CLS_RANK]);
 
     dbg.mark("classes");
     ColumnMap local_map;                                           // see spgemm_symbolic_impl; the one-shot call hands its map over
     if (!pre && !num_only_short) {
-        G4S_TRY(build_column_map(N, bnnz_local, bcol, local_map, s));
+        G4S_TRY(build_column_map(sw, N, bnnz_local, bcol, local_map, s));
     }
     const ColumnMap &cmap = pre ? pre->cmap : local_map;
     const int *wcol = cmap.cols(bcol), *winv = cmap.inverse();
     const int N2 = cmap.width(N);
+    const NumPlan plan = num_plan(sw, N2);
     DevBuf wsplit_buf;
     const int *wsplit = pre && pre->has_wsplit ? pre->wsplit : nullptr;
     if (!(pre && pre->has_wsplit) && !num_only_short) G4S_TRY(build_window_splits(K, N2, brpt, wcol, wsplit_buf, &wsplit, s));
-    std::vector<std::unique_ptr<DevBuf>> ct_keep;                  // transients of the launches below: live until the end of this call
     // ---- the rows with cuts (spgemm_rank.hpp), longest first: chunk lists from the cuts, exact splits and unit lists per chunk, then the rank kernel. In two stages:
     // stage 1 (row order, chunk counts, their scans, B's records) is enqueued before the short rows and the mid-size classes, so that its three totals have long
     // arrived when stage 2 (chunk lists, splits, unit lists, the kernel) is enqueued behind them — the host never waits for the rank launch's counts.
     const int rank_n = rc.count[CLS_RANK];
     SortedRows rank_sr;
-    auto mk = [&]() { ct_keep.push_back(std::make_unique<DevBuf>()); return ct_keep.back().get(); };
-    DevBuf *tasks = mk(), *toff = mk(), *items = mk(), *ioff = mk(), *nch = mk(), *choff = mk(), *chunks = mk(), *ctoff = mk(), *ctb = mk(), *ucnt = mk(), *uoff = mk(), *ud = mk(), *bpack = mk();
+    // The unit lists of one launch by (row, A-entry) tasks, behind the rows' task and item offsets — the same steps for a class launch and for the rank launch: the
+    // splits' offsets = item_off − task_off (entries · (chunks − 1) per row), the splits (chunk_splits_kernel: one thread per (entry, interior chunk boundary)), the
+    // units per item and their scan (count_units); then the descriptors (fill_units), once the caller has room for them.
+    struct UnitWork {
+        int n; const int *rows; long long ntask, nitem; int chunk;
+        const long long *toff, *ioff; long long *ctoff; int *ctb, *ucnt, *uoff;
+        const long long *poff; const int *pcols, *cols;            // where a row's sorted columns are read: carried over, or in ccol (all NULL for the rank launch, whose …
+        const int *choff; const RankChunk *chunks;                 // … chunk lists give the boundaries)
+    };
+    auto count_units = [&](const UnitWork &w) -> int {
+        const long long nct = w.nitem - w.ntask;
+        hipLaunchKernelGGL(diff_ll_kernel, dim3((w.n + 256) / 256), dim3(256), 0, s, w.n + 1, w.ioff, w.toff, w.ctoff);
+        if (nct > 0)
+            hipLaunchKernelGGL(chunk_splits_kernel, dim3((unsigned)((nct + 255) / 256)), dim3(256), 0, s, nct, w.n, w.rows, K, N2, wsplit, arpt, acol, brpt, wcol, crpt, w.poff, w.pcols, w.cols, w.chunk,
+                               (const long long *)w.ctoff, w.ctb, w.choff, w.chunks);
+        hipLaunchKernelGGL(unit_task_kernel<false>, dim3((unsigned)((w.ntask + 255) / 256)), dim3(256), 0, s, w.ntask, w.n, w.rows, w.toff, w.ioff, arpt, acol, aval, brpt, wcol, crpt,
+                           w.poff, w.pcols, w.cols, w.chunk, w.ctb, w.ucnt, (const int *)nullptr, (UnitDesc *)nullptr, 1, w.choff);
+        return g4s::prims::exclusive_scan(w.ucnt, w.uoff, w.nitem + 1, s);
+    };
+    auto fill_units = [&](const UnitWork &w, UnitDesc *U) {
+        hipLaunchKernelGGL(unit_task_kernel<true>, dim3((unsigned)((w.ntask + 255) / 256)), dim3(256), 0, s, w.ntask, w.n, w.rows, w.toff, w.ioff, arpt, acol, aval, brpt, wcol, crpt,
+                           w.poff, w.pcols, w.cols, w.chunk, w.ctb, (int *)nullptr, (const int *)w.uoff, U, 1, w.choff);
+    };
+    DevBuf *tasks = keep.buf(), *toff = keep.buf(), *items = keep.buf(), *ioff = keep.buf(), *nch = keep.buf(), *choff = keep.buf(), *chunks = keep.buf(), *ctoff = keep.buf(), *ctb = keep.buf(),
+           *ucnt = keep.buf(), *uoff = keep.buf(), *ud = keep.buf(), *bpack = keep.buf();
     long long rank_totals[2] = {0, 0};
     int rank_nchunks = 0;
     hipEvent_t rank_totals_ready = nullptr;
     auto rank_stage1 = [&]() -> int {
         const int n = rank_n;
-        G4S_TRY(rank_sr.build(n, rc.list(CLS_RANK), nullptr, crpt, N, s));
+        G4S_TRY(rank_sr.build(n, rc.list(CLS_RANK), nullptr, crpt, s));
         const int *rows = rank_sr.rows.as<int>();
         G4S_TRY(tasks->alloc(sizeof(long long) * ((size_t)n + 1))); G4S_TRY(toff->alloc(sizeof(long long) * ((size_t)n + 1)));
         G4S_TRY(items->alloc(sizeof(long long) * ((size_t)n + 1))); G4S_TRY(ioff->alloc(sizeof(long long) * ((size_t)n + 1)));
@@ -3062,122 +3171,78 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
         G4S_TRY(ud->alloc(sizeof(UnitDesc) * (size_t)ubound));
         hipLaunchKernelGGL(rank_chunks_kernel<true>, dim3((n + 256) / 256), dim3(256), 0, s, n, rows, arpt, crpt, pre->d_cut_off, pre->d_cuts, nseg, (long long *)nullptr, (long long *)nullptr,
                            (int *)nullptr, (const int *)choff->as<int>(), chunks->as<RankChunk>());
-        hipLaunchKernelGGL(diff_ll_kernel, dim3((n + 256) / 256), dim3(256), 0, s, n + 1, ioff->as<long long>(), toff->as<long long>(), ctoff->as<long long>());
-        if (nct > 0)
-            hipLaunchKernelGGL(chunk_splits_kernel, dim3((unsigned)((nct + 255) / 256)), dim3(256), 0, s, nct, n, rows, K, N2, wsplit, arpt, acol, brpt, wcol, crpt, (const long long *)nullptr, (const int *)nullptr,
-                               (const int *)nullptr, kRankChunk, ctoff->as<long long>(), ctb->as<int>(), (const int *)choff->as<int>(), (const RankChunk *)chunks->as<RankChunk>());
-        const unsigned tgrid = (unsigned)((ntask + 255) / 256);
-        hipLaunchKernelGGL(unit_task_kernel<false>, dim3(tgrid), dim3(256), 0, s, ntask, n, rows, toff->as<long long>(), ioff->as<long long>(), arpt, acol, aval, brpt, wcol, crpt,
-                           (const long long *)nullptr, (const int *)nullptr, (const int *)nullptr, kRankChunk, ctb->as<int>(), ucnt->as<int>(), (const int *)nullptr, (UnitDesc *)nullptr, 1, (const int *)choff->as<int>());
-        G4S_TRY(g4s::prims::exclusive_scan(ucnt->as<int>(), uoff->as<int>(), nitem + 1, s));
-        hipLaunchKernelGGL(unit_task_kernel<true>, dim3(tgrid), dim3(256), 0, s, ntask, n, rows, toff->as<long long>(), ioff->as<long long>(), arpt, acol, aval, brpt, wcol, crpt,
-                           (const long long *)nullptr, (const int *)nullptr, (const int *)nullptr, kRankChunk, ctb->as<int>(), (int *)nullptr, (const int *)uoff->as<int>(), ud->as<UnitDesc>(), 1, (const int *)choff->as<int>());
+        const UnitWork w{n, rows, ntask, nitem, kRankChunk, toff->as<long long>(), ioff->as<long long>(), ctoff->as<long long>(), ctb->as<int>(), ucnt->as<int>(), uoff->as<int>(),
+                         nullptr, nullptr, nullptr, choff->as<int>(), chunks->as<RankChunk>()};
+        G4S_TRY(count_units(w));
+        fill_units(w, ud->as<UnitDesc>());
         constexpr size_t lds = sizeof(int) * (3 * (size_t)kRankChunk + 2 * (size_t)kRankWords + 64);
         // the flat chunk list (spgemm_numeric_rank2_kernel): one self-contained item per chunk, dealt round-robin
-        DevBuf *ritems = mk();
+        DevBuf *ritems = keep.buf();
         G4S_TRY(ritems->alloc(sizeof(RankItem) * (size_t)nchunks));
         hipLaunchKernelGGL(rank_items_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, arpt, crpt, (const long long *)ioff->as<long long>(), (const int *)uoff->as<int>(), (const int *)choff->as<int>(),
                            (const RankChunk *)chunks->as<RankChunk>(), ritems->as<RankItem>());
         // split by size (spgemm_rank.hpp): the chunks of at most kRankSmallCap outputs take the 512-thread shape, two workgroups per CU
-        const bool two_shapes = !getenv("G4S_SPGEMM_RANK_ONE_SHAPE");
-        DevBuf *sflag = mk(), *spos = mk(), *rbig = mk(), *rsmall = mk(), *rcounts = mk();
-        const RankItem *big_items = ritems->as<RankItem>();
-        const int *n_big = nullptr;
-        if (two_shapes) {
-            G4S_TRY(sflag->alloc(sizeof(int) * ((size_t)nchunks + 1))); G4S_TRY(spos->alloc(sizeof(int) * ((size_t)nchunks + 1)));
-            G4S_TRY(rbig->alloc(sizeof(RankItem) * (size_t)nchunks)); G4S_TRY(rsmall->alloc(sizeof(RankItem) * (size_t)nchunks)); G4S_TRY(rcounts->alloc(sizeof(int) * 2));
-            hipLaunchKernelGGL(rank_small_flags_kernel, dim3((nchunks + 256) / 256), dim3(256), 0, s, nchunks, (const RankItem *)ritems->as<RankItem>(), sflag->as<int>());
-            G4S_TRY(g4s::prims::exclusive_scan(sflag->as<int>(), spos->as<int>(), (long long)nchunks + 1, s));
-            hipLaunchKernelGGL(rank_split_items_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, nchunks, (const RankItem *)ritems->as<RankItem>(), (const int *)spos->as<int>(), rbig->as<RankItem>(),
-                               rsmall->as<RankItem>(), rcounts->as<int>());
-            big_items = rbig->as<RankItem>(); n_big = rcounts->as<int>();
-        }
+        DevBuf *sflag = keep.buf(), *spos = keep.buf(), *rbig = keep.buf(), *rsmall = keep.buf(), *rcounts = keep.buf();
+        G4S_TRY(sflag->alloc(sizeof(int) * ((size_t)nchunks + 1))); G4S_TRY(spos->alloc(sizeof(int) * ((size_t)nchunks + 1)));
+        G4S_TRY(rbig->alloc(sizeof(RankItem) * (size_t)nchunks)); G4S_TRY(rsmall->alloc(sizeof(RankItem) * (size_t)nchunks)); G4S_TRY(rcounts->alloc(sizeof(int) * 2));
+        hipLaunchKernelGGL(rank_small_flags_kernel, dim3((nchunks + 256) / 256), dim3(256), 0, s, nchunks, (const RankItem *)ritems->as<RankItem>(), sflag->as<int>());
+        G4S_TRY(g4s::prims::exclusive_scan(sflag->as<int>(), spos->as<int>(), (long long)nchunks + 1, s));
+        hipLaunchKernelGGL(rank_split_items_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, nchunks, (const RankItem *)ritems->as<RankItem>(), (const int *)spos->as<int>(), rbig->as<RankItem>(),
+                           rsmall->as<RankItem>(), rcounts->as<int>());
         auto k = spgemm_numeric_rank2_kernel<T, kRankChunk, G4S_SPGEMM_RANK_UPR, SR>;
         G4S_TRY(allow_lds(k, lds));
-        hipLaunchKernelGGL(k, dim3(big_grid(nchunks, 1)), dim3(T), lds, s, nchunks, n_big, big_items, wcol, (const BPack *)bpack->as<BPack>(), (const UnitDesc *)ud->as<UnitDesc>(), ccol, cval);
-        if (two_shapes) {
-            auto ks = spgemm_numeric_rank2_kernel<kRankSmallT, kRankSmallCap, 8, SR>;
-            constexpr size_t lds_s = rank_lds_bytes(kRankSmallCap);
-            G4S_TRY(allow_lds(ks, lds_s));
-            hipLaunchKernelGGL(ks, dim3(big_grid(nchunks, 2)), dim3(kRankSmallT), lds_s, s, nchunks, (const int *)(rcounts->as<int>() + 1), (const RankItem *)rsmall->as<RankItem>(), wcol,
-                               (const BPack *)bpack->as<BPack>(), (const UnitDesc *)ud->as<UnitDesc>(), ccol, cval);
-        }
+        hipLaunchKernelGGL(k, dim3(big_grid(nchunks, 1)), dim3(T), lds, s, nchunks, (const int *)rcounts->as<int>(), (const RankItem *)rbig->as<RankItem>(), wcol, (const BPack *)bpack->as<BPack>(),
+                           (const UnitDesc *)ud->as<UnitDesc>(), ccol, cval);
+        auto ks = spgemm_numeric_rank2_kernel<kRankSmallT, kRankSmallCap, 8, SR>;
+        constexpr size_t lds_s = rank_lds_bytes(kRankSmallCap);
+        G4S_TRY(allow_lds(ks, lds_s));
+        hipLaunchKernelGGL(ks, dim3(big_grid(nchunks, 2)), dim3(kRankSmallT), lds_s, s, nchunks, (const int *)(rcounts->as<int>() + 1), (const RankItem *)rsmall->as<RankItem>(), wcol,
+                           (const BPack *)bpack->as<BPack>(), (const UnitDesc *)ud->as<UnitDesc>(), ccol, cval);
         G4S_HIP_TRY(hipGetLastError());
         return G4S_OK;
     };
     if (rank_n) G4S_TRY(rank_stage1());
-    // rows of at most 512 outputs: one wavefront merges a row (spgemm_small_wave_kernel); a row of more than 512 PRODUCTS (the classes are cut by output length) or
-    // more than 64 A-entries lands on a list that the table kernel takes, its count read on the device
+    // rows of at most 512 outputs: launch_short_rows; a row of more than 512 PRODUCTS (the classes are cut by output length) or more than 64 A-entries is handed back
+    // to the 1 024-slot table. (The lists of a carried symbolic classification are cut by PRODUCTS: its tiny class fits the 64-product form; the numeric classes are
+    // cut by outputs.)
+    // the key-table kernel on a list of rows, by table size: 64 slots per wavefront and four rows per workgroup, else one row per workgroup — of 256 threads up
+    // to 2 048 slots, 512 for 4 096, 1 024 for 8 192
+    auto table = [&](auto slots, int grid, const int *rows, int n, const int *n_dev) -> int {
+        constexpr int S = decltype(slots)::value, T = S == 64 ? 64 : S <= 2048 ? 256 : S / 8, WG = T < 256 ? 256 : T;
+        constexpr size_t lds = S == 64 ? 4 * 64 * 12 : num_lds_bytes(S);
+        auto k = spgemm_numeric_lds_kernel<WG, T, S, SR>;
+        G4S_TRY(allow_lds(k, lds));
+        hipLaunchKernelGGL(k, dim3(grid), dim3(WG), lds, s, rows, n, arpt, acol, aval, brpt, bcol, bval, row_size.as<long long>(), crpt, ccol, cval, n_dev);
+        return G4S_OK;
+    };
     DevBuf small_ovf, small_ovf_n;
-    if (int n = rc.count[CLS_TINY] + rc.count[CLS_SMALL]; n && !getenv("G4S_SPGEMM_NO_WAVE_ROWS")) {
-        G4S_TRY(small_ovf.alloc(sizeof(int) * (size_t)n));
-        G4S_TRY(small_ovf_n.alloc(sizeof(int)));
-        G4S_HIP_TRY(hipMemsetAsync(small_ovf_n.p, 0, sizeof(int), s));
-        // (the lists of a carried symbolic classification are cut by PRODUCTS: its tiny class fits the 64-product form; the numeric classes are cut by outputs)
-        const int nt = reuse_rc ? rc.count[CLS_TINY] : 0;
-        if (nt) {
-            auto k = spgemm_small_wave_kernel<true, kTinyCap, SR>;
-            constexpr size_t lds = sizeof(int) * 4 * small_wave_ints<true, kTinyCap>();
-            hipLaunchKernelGGL(k, dim3((nt + 3) / 4), dim3(256), lds, s, rc.list(CLS_TINY), nt, arpt, acol, aval, brpt, bcol, bval, (int *)nullptr, crpt, ccol,
-                               cval, small_ovf.as<int>(), small_ovf_n.as<int>());
-        }
-        if (n - nt) {
-            auto k = spgemm_small_wave_kernel<true, kSmallCap, SR>;
-            hipLaunchKernelGGL(k, dim3((n - nt + 3) / 4), dim3(256), sizeof(int) * 4 * small_wave_ints<true>(), s, rc.list(CLS_TINY) + nt, n - nt, arpt, acol, aval, brpt, bcol, bval, (int *)nullptr, crpt,
-                               ccol, cval, small_ovf.as<int>(), small_ovf_n.as<int>());
-        }
-        auto k2 = spgemm_numeric_lds_kernel<256, 256, 1024, SR>;
-        hipLaunchKernelGGL(k2, dim3(std::min(n, 256)), dim3(256), num_lds_bytes(1024), s, small_ovf.as<int>(), 0, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval,
-                           (const int *)small_ovf_n.as<int>());
-    } else {
-    if (int n = rc.count[CLS_TINY]) {
-        auto k = spgemm_numeric_lds_kernel<256, 64, 64, SR>;
-        hipLaunchKernelGGL(k, dim3((n + 3) / 4), dim3(256), 4 * 64 * 12, s, rc.list(CLS_TINY), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
-    }
-    if (int n = rc.count[CLS_SMALL]) {
-        auto k = spgemm_numeric_lds_kernel<256, 256, 1024, SR>;
-        hipLaunchKernelGGL(k, dim3(n), dim3(256), num_lds_bytes(1024), s, rc.list(CLS_SMALL), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
-    }
-    }
-    // Rows past 1 K entries: bitmap windows + bucketed slots beat table + in-LDS bitonic sort while the column range is <= 4 windows.
-    const bool xn_wide = N2 <= window_max_n(), xn_large = xn_wide && !(mid_tables() & 2), xn_m2 = xn_wide && !(mid_tables() & 4);
+    G4S_TRY((launch_short_rows<true, SR>(plan.use_wave, rc, reuse_rc ? rc.count[CLS_TINY] : 0, arpt, acol, aval, brpt, bcol, bval, nullptr, crpt, ccol, cval, small_ovf, small_ovf_n, s, table)));
     // exact chunk splits (chunk_splits_kernel) for the rows of one launch that hold more than one value chunk: one-shot call only (the sorted columns must
     // exist before the numeric kernel runs); the buffers live until the end of this call
-    const bool use_units = !getenv("G4S_SPGEMM_NO_UNITS");
     // Unit lists of one launch, by (row, A-entry) tasks (unit_task_kernel): splits, counts and descriptors in two passes over the tasks, ONE count read back. Never a
     // reason to fail: without them (a table past its cap, no memory) the kernel walks its rows with the per-chunk entry pass and the window pieces (no exact splits).
     struct UnitLists { const long long *item_off = nullptr; const int *uoff = nullptr; const UnitDesc *U = nullptr; };
     const long long class_flop_bound = pre ? pre->flop : -1;       // units <= flop / 64 + items; the one-shot call knows the product's flop (−1: unknown → the count is read back)
     auto unit_lists_by_tasks = [&](int threads, const int *rows, int n, int nz_lo, int nz_hi, UnitLists *out) -> int {
-        *out = UnitLists{};
         const int chunk = 8 * threads;
         auto tasks = std::make_unique<DevBuf>(), toff = std::make_unique<DevBuf>(), items = std::make_unique<DevBuf>(), ioff = std::make_unique<DevBuf>(), ctb = std::make_unique<DevBuf>(),
-             ucnt = std::make_unique<DevBuf>(), uoff = std::make_unique<DevBuf>(), ud = std::make_unique<DevBuf>();
+             ucnt = std::make_unique<DevBuf>(), uoff = std::make_unique<DevBuf>(), ud = std::make_unique<DevBuf>(), ctoff = std::make_unique<DevBuf>();
         G4S_TRY(tasks->alloc(sizeof(long long) * ((size_t)n + 1))); G4S_TRY(toff->alloc(sizeof(long long) * ((size_t)n + 1)));
         G4S_TRY(items->alloc(sizeof(long long) * ((size_t)n + 1))); G4S_TRY(ioff->alloc(sizeof(long long) * ((size_t)n + 1)));
         hipLaunchKernelGGL(unit_rows_kernel, dim3((n + 256) / 256), dim3(256), 0, s, n, rows, arpt, crpt, chunk, nz_lo, nz_hi, tasks->as<long long>(), items->as<long long>());
         G4S_TRY(g4s::prims::exclusive_scan(tasks->as<long long>(), toff->as<long long>(), (long long)n + 1, s));
         G4S_TRY(g4s::prims::exclusive_scan(items->as<long long>(), ioff->as<long long>(), (long long)n + 1, s));
         g4s::ReadScope reads(s);                                    // (the lambda's own: its destinations are its locals)
-        long long totals[2] = {0, 0};
-        G4S_HIP_TRY(reads.note(totals[0], toff->as<long long>() + n));
-        G4S_HIP_TRY(reads.fetch(totals[1], ioff->as<long long>() + n));
-        const long long ntask = totals[0], nitem = totals[1];
+        long long ntask = 0, nitem = 0;
+        G4S_HIP_TRY(reads.note(ntask, toff->as<long long>() + n));
+        G4S_HIP_TRY(reads.fetch(nitem, ioff->as<long long>() + n));
         if (ntask <= 0 || nitem <= 0 || nitem > (1ll << 28)) return G4S_OK;
         if (ctb->alloc(sizeof(int) * (size_t)std::max<long long>(nitem - ntask, 1)) != G4S_OK || ucnt->alloc(sizeof(int) * ((size_t)nitem + 1)) != G4S_OK ||
             uoff->alloc(sizeof(int) * ((size_t)nitem + 1)) != G4S_OK) { (void)hipGetLastError(); return G4S_OK; }
-        const unsigned grid = (unsigned)((ntask + 255) / 256);
-        // the splits: one thread per (entry, interior chunk boundary) — chunk_splits_kernel, its offsets = item_off − task_off (entries · (chunks − 1) per row)
-        const long long nct = nitem - ntask;
-        auto ctoff = std::make_unique<DevBuf>();
         G4S_TRY(ctoff->alloc(sizeof(long long) * ((size_t)n + 1)));
-        hipLaunchKernelGGL(diff_ll_kernel, dim3((n + 256) / 256), dim3(256), 0, s, n + 1, ioff->as<long long>(), toff->as<long long>(), ctoff->as<long long>());
-        if (nct > 0)
-            hipLaunchKernelGGL(chunk_splits_kernel, dim3((unsigned)((nct + 255) / 256)), dim3(256), 0, s, nct, n, rows, K, N2, wsplit, arpt, acol, brpt, wcol, crpt, pre_off, pre_cols, ccol, chunk,
-                               ctoff->as<long long>(), ctb->as<int>());
-        hipLaunchKernelGGL(unit_task_kernel<false>, dim3(grid), dim3(256), 0, s, ntask, n, rows, toff->as<long long>(), ioff->as<long long>(), arpt, acol, aval, brpt, wcol, crpt,
-                           pre_off, pre_cols, ccol, chunk, ctb->as<int>(), ucnt->as<int>(), (const int *)nullptr, (UnitDesc *)nullptr, 1);
-        G4S_TRY(g4s::prims::exclusive_scan(ucnt->as<int>(), uoff->as<int>(), nitem + 1, s));
+        const UnitWork w{n, rows, ntask, nitem, chunk, toff->as<long long>(), ioff->as<long long>(), ctoff->as<long long>(), ctb->as<int>(), ucnt->as<int>(), uoff->as<int>(),
+                         pre_off, pre_cols, ccol, nullptr, nullptr};
+        G4S_TRY(count_units(w));
         long long ubound = class_flop_bound >= 0 ? class_flop_bound / 64 + nitem : -1;
         if (ubound < 0 || ubound > (1ll << 27)) {                   // no bound from the caller (or a loose one): read the count
             int total_units = 0;
@@ -3186,11 +3251,10 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
             ubound = total_units;
         }
         if (ud->alloc(sizeof(UnitDesc) * (size_t)ubound) != G4S_OK) { (void)hipGetLastError(); return G4S_OK; }
-        hipLaunchKernelGGL(unit_task_kernel<true>, dim3(grid), dim3(256), 0, s, ntask, n, rows, toff->as<long long>(), ioff->as<long long>(), arpt, acol, aval, brpt, wcol, crpt,
-                           pre_off, pre_cols, ccol, chunk, ctb->as<int>(), (int *)nullptr, uoff->as<int>(), ud->as<UnitDesc>(), 1);
+        fill_units(w, ud->as<UnitDesc>());
         G4S_HIP_TRY(hipGetLastError());
         out->item_off = ioff->as<long long>(); out->uoff = uoff->as<int>(); out->U = ud->as<UnitDesc>();
-        for (auto *b : {&tasks, &toff, &items, &ioff, &ctb, &ucnt, &uoff, &ud, &ctoff}) ct_keep.push_back(std::move(*b));
+        for (auto *b : {&tasks, &toff, &items, &ioff, &ctb, &ucnt, &uoff, &ud, &ctoff}) keep.take(std::move(*b));
         return G4S_OK;
     };
     // The window kernels need every row's sorted distinct columns (window ids) before they start. The one-shot call carries them over from its symbolic
@@ -3198,89 +3262,58 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
     // into ccol at the row's own offset by the symbolic window kernel in its emit-only mode, in front of the launch that needs it (round 4: this used to be
     // phase 1 inside the numeric kernel itself).
     const bool carried_complete = pre && pre->complete;
-    auto emit_pass = [&](auto shape, const int *rows, int n, int nz_lo, int nz_hi) -> int {
-        constexpr int T = decltype(shape)::value;
-        auto k = spgemm_symbolic_window_kernel<T>;
-        const size_t lds = big_lds_bytes<T>();
-        G4S_TRY(allow_lds(k, lds));
-        hipLaunchKernelGGL(k, dim3(big_grid(n, BigCfg<T>::kPerCu)), dim3(T), lds, s, rows, n, (int *)nullptr, N2, K, wsplit, arpt, acol, brpt, wcol, (const long long *)nullptr, (int *)nullptr,
-                           pre_off, ccol, crpt, nz_lo, nz_hi);
-        return G4S_OK;
-    };
     auto big_t = [&](auto shape, const int *rows, int n, int nz_lo, int nz_hi, int *next_row) -> int {
         constexpr int T = decltype(shape)::value;
         if (!n) return G4S_OK;
         const size_t lds = big_lds_bytes<T>();   // value chunk (fp64 sums, columns, bucket index) + scan scratch + the flat lists
-        UnitLists ul;
-        if (!carried_complete) G4S_TRY(emit_pass(shape, rows, n, nz_lo, nz_hi));
-        if (use_units) G4S_TRY(unit_lists_by_tasks(T, rows, n, nz_lo, nz_hi, &ul));
         const dim3 grid(big_grid(n, BigCfg<T>::kPerCu));
-        auto rmeta = std::make_unique<DevBuf>();
-        G4S_TRY(rmeta->alloc(sizeof(NumRowMeta) * (size_t)n));
-        hipLaunchKernelGGL(num_row_meta_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, arpt, crpt, pre_off, ul.U ? ul.item_off : (const long long *)nullptr, ul.uoff, rmeta->as<NumRowMeta>());
-        if (ul.U) {
-            auto k = spgemm_numeric_big_kernel<T, true, SR>;
+        UnitLists ul;
+        if (!carried_complete) {                                    // the emit pass
+            auto k = spgemm_symbolic_window_kernel<T>;
             G4S_TRY(allow_lds(k, lds));
-            hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, nz_lo, nz_hi, next_row, N2, K, wsplit, arpt, acol, aval, brpt, wcol, winv, bval, row_flop.as<long long>(), crpt, ccol, cval, pre_off, pre_cols,
-                               ul.item_off, ul.uoff, ul.U, rmeta->as<NumRowMeta>());
-        } else {
-            auto k = spgemm_numeric_big_kernel<T, false, SR>;
-            G4S_TRY(allow_lds(k, lds));
-            hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, nz_lo, nz_hi, next_row, N2, K, wsplit, arpt, acol, aval, brpt, wcol, winv, bval, row_flop.as<long long>(), crpt, ccol, cval, pre_off, pre_cols,
-                               (const long long *)nullptr, (const int *)nullptr, (const UnitDesc *)nullptr, rmeta->as<NumRowMeta>());
+            hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, (int *)nullptr, N2, K, wsplit, arpt, acol, brpt, wcol, (const long long *)nullptr, (int *)nullptr, pre_off, ccol, crpt, nz_lo, nz_hi);
         }
-        ct_keep.push_back(std::move(rmeta));
-        return G4S_OK;
+        if (plan.use_units) G4S_TRY(unit_lists_by_tasks(T, rows, n, nz_lo, nz_hi, &ul));
+        DevBuf *rmeta = keep.buf();
+        G4S_TRY(rmeta->alloc(sizeof(NumRowMeta) * (size_t)n));
+        hipLaunchKernelGGL(num_row_meta_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, arpt, crpt, pre_off, ul.item_off, ul.uoff, rmeta->as<NumRowMeta>());
+        auto launch = [&](auto units) -> int {                      // (without unit lists ul holds three NULLs)
+            auto k = spgemm_numeric_big_kernel<T, decltype(units)::value, SR>;
+            G4S_TRY(allow_lds(k, lds));
+            hipLaunchKernelGGL(k, grid, dim3(T), lds, s, rows, n, nz_lo, nz_hi, next_row, N2, K, wsplit, arpt, acol, aval, brpt, wcol, winv, bval, row_size.as<long long>(), crpt, ccol, cval, pre_off, pre_cols,
+                               ul.item_off, ul.uoff, ul.U, rmeta->as<NumRowMeta>());
+            return G4S_OK;
+        };
+        return ul.U ? launch(std::true_type{}) : launch(std::false_type{});
     };
     auto big = [&](int threads, const int *rows, int n, int nz_lo = 0, int nz_hi = INT_MAX, int *next_row = nullptr) -> int {
-        if (threads == 256) return big_t(std::integral_constant<int, 256>{}, rows, n, nz_lo, nz_hi, next_row);
-        if (threads == 512) return big_t(std::integral_constant<int, 512>{}, rows, n, nz_lo, nz_hi, next_row);
-        return big_t(std::integral_constant<int, 1024>{}, rows, n, nz_lo, nz_hi, next_row);
+        return with_shape(threads, [&](auto shape) { return big_t(shape, rows, n, nz_lo, nz_hi, next_row); });
     };
-    const int t_large = shape_of("G4S_SPGEMM_T_NUM_LARGE", kShapeNumLarge), t_m2 = shape_of("G4S_SPGEMM_T_NUM_M2", kShapeNumM2),
-              t_m3 = shape_of("G4S_SPGEMM_T_NUM_M3", kShapeNumM3);
-    const int m3_cut = getenv("G4S_SPGEMM_M3_CUT") ? atoi(getenv("G4S_SPGEMM_M3_CUT")) : kNumM3Cut;
-    const char *e_med = getenv("G4S_SPGEMM_T_NUM_MED");
-    const int t_med = (mid_tables() & 1) ? 0 : e_med ? (atoi(e_med) ? shape_of("G4S_SPGEMM_T_NUM_MED", 1024) : 0) : kShapeNumMedium;   // 0: the table kernel
     dbg.mark("table-kernels+maps");
-    const bool one_mid_launch = t_med && xn_large && xn_m2 && t_med == t_large && t_large == t_m2;
-    if (one_mid_launch) {
-        // the three mid-size classes (512 < nz <= 4 096) share a shape and their lists are adjacent: one launch, one set of unit lists, one tail instead of three
-        G4S_TRY(big(t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM] + rc.count[CLS_LARGE] + rc.count[CLS_M2]));
+    if (plan.one_mid_launch) {
+        G4S_TRY(big(plan.t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM] + rc.count[CLS_LARGE] + rc.count[CLS_M2]));
     } else {
-    if (t_med && xn_large) { G4S_TRY(big(t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM])); }
-    else if (int n = rc.count[CLS_MEDIUM]) {
-        auto k = spgemm_numeric_lds_kernel<256, 256, 2048, SR>;
-        hipLaunchKernelGGL(k, dim3(n), dim3(256), num_lds_bytes(2048), s, rc.list(CLS_MEDIUM), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
-    }
-    if (xn_large) { G4S_TRY(big(t_large, rc.list(CLS_LARGE), rc.count[CLS_LARGE])); }
-    else if (int n = rc.count[CLS_LARGE]) {
-        auto k = spgemm_numeric_lds_kernel<512, 512, 4096, SR>;
-        G4S_TRY(allow_lds(k, num_lds_bytes(4096)));
-        hipLaunchKernelGGL(k, dim3(n), dim3(512), num_lds_bytes(4096), s, rc.list(CLS_LARGE), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
-    }
-    if (xn_m2) { G4S_TRY(big(t_m2, rc.list(CLS_M2), rc.count[CLS_M2])); }
-    else if (int n = rc.count[CLS_M2]) {
-        auto k = spgemm_numeric_lds_kernel<1024, 1024, 8192, SR>;
-        G4S_TRY(allow_lds(k, num_lds_bytes(8192)));
-        hipLaunchKernelGGL(k, dim3(n), dim3(1024), num_lds_bytes(8192), s, rc.list(CLS_M2), n, arpt, acol, aval, brpt, bcol, bval, row_flop.as<long long>(), crpt, ccol, cval, (const int *)nullptr);
-    }
+    if (plan.win_med) { G4S_TRY(big(plan.t_med, rc.list(CLS_MEDIUM), rc.count[CLS_MEDIUM])); }
+    else if (int n = rc.count[CLS_MEDIUM]) G4S_TRY(table(int_c<2048>{}, n, rc.list(CLS_MEDIUM), n, nullptr));
+    if (plan.win_large) { G4S_TRY(big(plan.t_large, rc.list(CLS_LARGE), rc.count[CLS_LARGE])); }
+    else if (int n = rc.count[CLS_LARGE]) G4S_TRY(table(int_c<4096>{}, n, rc.list(CLS_LARGE), n, nullptr));
+    if (plan.win_m2) { G4S_TRY(big(plan.t_m2, rc.list(CLS_M2), rc.count[CLS_M2])); }
+    else if (int n = rc.count[CLS_M2]) G4S_TRY(table(int_c<8192>{}, n, rc.list(CLS_M2), n, nullptr));
     }
     dbg.mark("mid-launch");
     if (rank_n) G4S_TRY(rank_stage2());                            // (its totals have arrived while the mid-size classes were being enqueued)
     dbg.mark("rank-launch");
     if (int n = rc.count[CLS_M3]) {
-        // the class spans 4 K … 128 K entries: its short rows go to the many-workgroups shape, the long ones keep 1 024 threads
-        if (t_m3 != 1024 && m3_cut > 0) { G4S_TRY(big(t_m3, rc.list(CLS_M3), n, 0, m3_cut)); G4S_TRY(big(1024, rc.list(CLS_M3), n, m3_cut, INT_MAX)); }
-        else if (getenv("G4S_SPGEMM_STATIC_ROWS")) G4S_TRY(big(1024, rc.list(CLS_M3), n));
+        if (plan.m3_form == M3_TWO_SHAPES) { G4S_TRY(big(plan.t_m3, rc.list(CLS_M3), n, 0, plan.m3_cut)); G4S_TRY(big(1024, rc.list(CLS_M3), n, plan.m3_cut, INT_MAX)); }
+        else if (plan.m3_form == M3_STATIC) G4S_TRY(big(1024, rc.list(CLS_M3), n));
         else {
             // The class spans 4 K … 1 M outputs per row (a 250-fold range of work): longest rows first, handed out one at a time.
             SortedRows sr;
             // (round 4 tried a clustered order instead — the rows past 64 K outputs longest first, the rest by their first column id, i.e. by the long B row most of
             // their products come from, so that consecutive tickets find it in L2: 14.62 against 14.74 ms for the kernel, nothing for the call. B-row misses are
             // not what this kernel waits for.)
-            G4S_TRY(sr.build(n, rc.list(CLS_M3), nullptr, crpt, N, s));   // a row has at most N outputs
-            G4S_TRY(big(m3_cut <= 0 ? t_m3 : 1024, sr.rows.as<int>(), n, 0, INT_MAX, sr.counter.as<int>()));   // (G4S_SPGEMM_M3_CUT=0 + G4S_SPGEMM_T_NUM_M3: the whole class in another shape)
+            G4S_TRY(sr.build(n, rc.list(CLS_M3), nullptr, crpt, s));
+            G4S_TRY(big(plan.t_m3_whole, sr.rows.as<int>(), n, 0, INT_MAX, sr.counter.as<int>()));
             // (the sorted list and the counter are released in stream order — or with the call's arena: no wait here)
         }
     }
@@ -3288,20 +3321,11 @@ int spgemm_numeric_run(int32_t M, int32_t K, int32_t N,
     dbg.mark("big-launch(+sync)");
     std::vector<int> hub, ranges;
     G4S_TRY(fetch_rows_and_ranges(rc.list(CLS_HUB), rc.count[CLS_HUB], arpt, hub, ranges, s));
-    G4S_TRY(run_hub_rows<SR>(true, hub, ranges, N, arpt, acol, aval, brpt, bcol, bval, nullptr, crpt, ccol, cval, s));
+    G4S_TRY(run_hub_rows<SR>(true, hub, ranges, N, acol, aval, brpt, bcol, bval, nullptr, crpt, ccol, cval, s));
     G4S_HIP_TRY(g4s::reads_sync(s));
     t_idle = true;                                                 // (cleared by the next call on this thread)
     dbg.mark("hub+sync");
     return G4S_OK;
-}
-int spgemm_numeric_impl(int32_t M, int32_t K, int32_t N,
-                        const int32_t *arpt, const int32_t *acol, const double *aval,
-                        const int32_t *brpt, const int32_t *bcol, const double *bval,
-                        const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream, const PreSorted *pre)
-{
-    return sr::dispatch(flags, [&](auto policy) {
-        return spgemm_numeric_run<decltype(policy)>(M, K, N, arpt, acol, aval, brpt, bcol, bval, crpt, ccol, cval, flags, stream, pre);
-    });
 }
 } // namespace
 
@@ -3310,6 +3334,7 @@ G4S_API g4s_status g4s_spgemm_numeric(int32_t M, int32_t K, int32_t N,
                                       const int32_t *brpt, const int32_t *bcol, const double *bval,
                                       const int32_t *crpt, int32_t *ccol, double *cval, unsigned flags, void *stream)
 {
+    const Switches sw{};
     std::shared_ptr<PreSorted> pre;                                // the state the symbolic call of THIS product left behind, if any — it stays for further numeric
     {                                                              // calls on the same pattern (new values of A or B, the time-stepping case) until something drops it
         std::lock_guard<std::mutex> lock(g_carried.m);
@@ -3317,6 +3342,10 @@ G4S_API g4s_status g4s_spgemm_numeric(int32_t M, int32_t K, int32_t N,
             g_carried.bcol == bcol && g_carried.crpt == crpt)
             pre = g_carried.pre;
     }
+    auto refuse = [&](const char *why) { if (sw.debug) fprintf(stderr, "g4s numeric: %s — its carried state is not used\n", why); pre.reset(); };
+    // G4S_SPGEMM_NO_RANK set after the symbolic call: its long rows carry cuts, which only the rank kernel reads, and no columns. This is an ordinary numeric call
+    // then (the state stays for later calls).
+    if (pre && pre->rank && sw.no_rank) refuse("G4S_SPGEMM_NO_RANK is set and the symbolic call wrote cuts");
     if (pre) {
         // The same pointers do not make it the same product: a caller may have refilled the buffers with another pattern, or brought its own crpt. The
         // state is taken over only while the five index arrays still hash to what the symbolic call saw (one pass over them, ≈ 30 µs on configs[2], one host wait);
@@ -3329,12 +3358,9 @@ G4S_API g4s_status g4s_spgemm_numeric(int32_t M, int32_t K, int32_t N,
             st = g4s::set_error(G4S_ERR_HIP, "g4s_spgemm_numeric: reading the pattern hash failed");
         g4s::scratch_free(d_hash, s);
         G4S_TRY(st);
-        if (h_hash != pre->key_hash) {
-            if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s numeric: the index arrays changed since the symbolic call — its carried state is not used\n");
-            pre.reset();
-        }
+        if (h_hash != pre->key_hash) refuse("the index arrays changed since the symbolic call");
     }
-    return spgemm_numeric_impl(M, K, N, arpt, acol, aval, brpt, bcol, bval, crpt, ccol, cval, flags, stream, pre.get());
+    return sr::dispatch(flags, [&](auto policy) { return spgemm_numeric_run<decltype(policy)>(sw, M, K, N, arpt, acol, aval, brpt, bcol, bval, crpt, ccol, cval, stream, pre.get()); });
 }
 
 G4S_API g4s_status g4s_spgemm_flop(int32_t M, const int32_t *arpt, const int32_t *acol, const int32_t *brpt,
@@ -3381,6 +3407,7 @@ G4S_API g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *ac
     G4S_REQUIRE(M >= 0 && K >= 0 && N >= 0 && arpt && brpt, "bad argument");
     *crpt_out = nullptr; *ccol_out = nullptr; *cval_out = nullptr; *cnnz_out = 0;
     g4s_timings t{};
+    const Switches sw{};                                           // one snapshot for both phases
     drop_carried();                                                // (a two-call product left unfinished holds the column scratch)
     const auto t_total = clk::now();
     ArenaScope arena;                                              // spans both phases: the carried state of the symbolic phase lives in it
@@ -3419,7 +3446,7 @@ G4S_API g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *ac
     int64_t cnnz = 0;
     const auto t_sym = clk::now();
     PreSorted pre;
-    G4S_TRY(spgemm_symbolic_impl(M, K, N, p_arpt, p_acol, p_brpt, p_bcol, d_crpt.as<int>(), &cnnz, nullptr, &pre));
+    G4S_TRY(spgemm_symbolic_impl(sw, M, K, N, p_arpt, p_acol, p_brpt, p_bcol, d_crpt.as<int>(), &cnnz, nullptr, &pre));
     *cnnz_out = cnnz;
     DevBuf d_ccol, d_cval;
     const double ms_sym = ms_since(t_sym);
@@ -3428,9 +3455,10 @@ G4S_API g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *ac
     G4S_TRY(d_ccol.alloc(sizeof(int) * (size_t)cnnz, dev));
     const double ms_alloc = ms_since(t_alloc);
     const auto t_num = clk::now();
-    G4S_TRY(spgemm_numeric_impl(M, K, N, p_arpt, p_acol, p_aval, p_brpt, p_bcol, p_bval, d_crpt.as<int>(), d_ccol.as<int>(), d_cval.as<double>(),
-                                flags, nullptr, &pre));
-    if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s one-call: symbolic %.1f ms, output allocation %.1f ms, numeric %.1f ms\n", ms_sym, ms_alloc, ms_since(t_num));
+    G4S_TRY(sr::dispatch(flags, [&](auto policy) {
+        return spgemm_numeric_run<decltype(policy)>(sw, M, K, N, p_arpt, p_acol, p_aval, p_brpt, p_bcol, p_bval, d_crpt.as<int>(), d_ccol.as<int>(), d_cval.as<double>(), nullptr, &pre);
+    }));
+    if (sw.debug) fprintf(stderr, "g4s one-call: symbolic %.1f ms, output allocation %.1f ms, numeric %.1f ms\n", ms_sym, ms_alloc, ms_since(t_num));
     t.spmm = ms_since(t0);
     t.convert = 0.0;
     t.order = 0.0;
@@ -3460,7 +3488,7 @@ G4S_API g4s_status g4s_spgemm_csr_i32_f64(const int32_t *arpt, const int32_t *ac
     t.destroy = ms_since(t0);
     t.total = ms_since(t_total);
     if (timings) *timings = t;
-    if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s one-call: create %.2f spmm %.2f export %.2f destroy %.2f total %.2f ms (the carried state of the two phases is released after this line)\n",
+    if (sw.debug) fprintf(stderr, "g4s one-call: create %.2f spmm %.2f export %.2f destroy %.2f total %.2f ms (the carried state of the two phases is released after this line)\n",
                                      t.create, t.spmm, t.export_csr, t.destroy, t.total);
     return G4S_OK;
 }

@@ -16,7 +16,7 @@ import numpy as np
 SYM_LIMITS = (32, 512, 4096, 32768, 2097152)     # `constexpr ClassLimits kSymLimits{{32, 512, G4S_SPGEMM_SYM_MEDIUM, 32768, 2097152, -1}, {0, 0, 0, 1, 1, 0}};`
 SYM_RAW = (False, False, False, True, True)      # … its second brace: the last two limits look at the unclipped bound; the sixth (−1) takes no row
 NUM_LIMITS = (32, 512, 1024, 2048, 4096, 1048576)   # `constexpr ClassLimits kNumLimits{{32, 512, 1024, 2048, 4096, G4S_SPGEMM_BIG_LIMIT}, …};`
-NUM_LIMIT_RANK = 8192                            # spgemm_numeric_run: `if (rank && m2_windows) num_limits.lim[4] = 8192;`
+NUM_LIMIT_RANK = 8192                            # num_classing: `c.fifth_limit = c.rank && windows_take(sw, pre->cmap.width(N), 4) ? 8192 : kNumLimits.lim[4];`
 SMALL_CAP = 512                                  # `constexpr int kSmallCap = 512;` — spgemm_small_wave_kernel: `if (na > 64 || flop > CAP)` hands the row back
 TINY_CAP = 64                                    # `constexpr int kTinyCap = 64;` — the same test in the form that takes the symbolic tiny class
 LANES = 64                                       # … and its `na > 64`: one lane per A-entry

@@ -47,9 +47,9 @@ def _oracle_pattern(name):
     return orpt, ocol
 
 
-def _two_call(a, b, semiring):
+def _two_call(a, b, semiring, between=None):
     """g4s_spgemm_symbolic + g4s_spgemm_numeric into arrays this test owns: ccol and cval are filled with sentinels first, so that an entry the numeric phase
-    leaves unwritten shows as a difference, not as stale memory that happens to be right"""
+    leaves unwritten shows as a difference, not as stale memory that happens to be right. between: called after the symbolic call has returned"""
     from g4s_amd import capi, host
     lib = capi.load()
     crpt = torch.full((a.rows + 1,), -7, dtype=torch.int32, device="cuda")
@@ -60,6 +60,8 @@ def _two_call(a, b, semiring):
     ccol = torch.full((cnnz.value,), -7, dtype=torch.int32, device="cuda")
     cval = torch.full((cnnz.value,), float("nan"), dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
+    if between:
+        between()
     capi.check(lib.g4s_spgemm_numeric(a.rows, a.cols, b.cols, host._ptr(a.rowptr), host._ptr(a.colids), host._ptr(a.values), host._ptr(b.rowptr), host._ptr(b.colids),
                                       host._ptr(b.values), host._ptr(crpt), host._ptr(ccol), host._ptr(cval),
                                       capi.DEVICE_POINTERS | capi.SORT_OUTPUT | host.SEMIRINGS[semiring], None))
@@ -114,3 +116,30 @@ def test_spgemm_rows_on_the_class_limits(name, mode, one_call, semiring, monkeyp
     8 192 outputs came back with 4 096 entries written and the rest of ccol / cval untouched. The limit now moves only while the window kernel takes the class."""
     assert semiring in sc.build(name).semirings
     _run(name, mode, one_call, semiring, monkeypatch, capfd)
+
+
+@pytest.mark.parametrize("semiring", ["plus_times", "min_plus"])
+def test_no_rank_set_between_the_two_calls(semiring, monkeypatch, capfd):
+    """g4s_spgemm_symbolic under the default environment writes cuts for the long rows of `long`; G4S_SPGEMM_NO_RANK is set before the g4s_spgemm_numeric call on
+    the same arrays. Cuts are read by the rank kernel alone: the numeric call must not take the carried state over (it used to, and handed the rows with cuts to
+    the window kernel without columns) — it runs as an uncarried numeric call, rank 0 and the rows classed by outputs with the 4 096 limit."""
+    c = sc.build("long")
+    a, b = _on_device("long")
+    monkeypatch.setenv("G4S_DEBUG", "1")
+    capfd.readouterr()
+    got = _two_call(a, b, semiring, between=lambda: monkeypatch.setenv("G4S_SPGEMM_NO_RANK", "1"))
+    err = capfd.readouterr().err
+    monkeypatch.delenv("G4S_DEBUG")
+
+    want = _want("long", semiring)
+    assert np.array_equal(got[0], want[0]), "row pointer differs"
+    assert np.array_equal(got[1], want[1]), f"{np.count_nonzero(got[1] != want[1])} column ids differ"
+    assert np.array_equal(_bits(got[2]), _bits(want[2])), f"{np.count_nonzero(_bits(got[2]) != _bits(want[2]))} values differ"
+    sym, num = SYM_LINE.findall(err), NUM_LINE.findall(err)
+    assert len(sym) == 1 and len(num) == 1, err
+    sym_got = dict(zip(sc.SYM_CLASSES, map(int, sym[0][:7])))
+    num_got = dict(zip(sc.NUM_CLASSES, map(int, num[0])))
+    print(f"long, NO_RANK set between the calls, {semiring}: symbolic {sym_got}; numeric {num_got}")
+    assert sc.rank_on(c, "default") and sym_got == sc.expected_histograms(c, "default", False)[0], f"symbolic classes {sym_got}"
+    assert num_got == sc.expected_histograms(c, "no_rank", False)[1] and num_got["rank"] == 0, f"numeric classes {num_got}"
+    assert "its carried state is not used" in err
