@@ -18,6 +18,7 @@ PAGERANK_SYMMETRIC, PAGERANK_WARM_START, PAGERANK_BATCH = 65536, 131072, 8      
 BC_ACCUMULATE, BC_BATCH = 262144, 16                                     # g4s_betweenness (g4s.h)
 CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
 KCORE_BATCH, KCORE_FULL = 16, 2**31 - 1                                  # g4s_kcore: launches per state read at least; max_k of the full decomposition (g4s.h)
+KTRUSS_BATCH, KTRUSS_FULL = 16, 2**31 - 1                                # g4s_ktruss: launches per state read at least; max_k of the full decomposition (g4s.h)
 COLOR_LARGEST_FIRST, COLOR_BATCH, COLOR_MASK_COLORS, COLOR_WINDOW = 524288, 16, 64, 256   # g4s_color: key := degree; launches per state read; mask width; scan window (g4s.h)
 EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
 COMBINE_PLUS, COMBINE_TIMES, COMBINE_MIN, COMBINE_MAX, COMBINE_FIRST, COMBINE_SECOND = 0, 1, 2, 3, 4, 5
@@ -77,6 +78,13 @@ class KCoreInfo(C.Structure):
     """g4s_kcore_info: what a g4s_kcore call found and did."""
     _fields_ = [("edges_walked", C.c_int64), ("top_core_size", C.c_int64), ("degeneracy", C.c_int32), ("levels", C.c_int32), ("rounds", C.c_int32),
                 ("scans", C.c_int32), ("launches", C.c_int32), ("resumes", C.c_int32), ("host_waits", C.c_int32), ("capped", C.c_int32)]
+
+
+class KTrussInfo(C.Structure):
+    """g4s_ktruss_info: what a g4s_ktruss call found and did."""
+    _fields_ = [("triangles", C.c_int64), ("edges_walked", C.c_int64), ("support_walked", C.c_int64), ("top_truss_edges", C.c_int64),
+                ("max_truss", C.c_int32), ("levels", C.c_int32), ("rounds", C.c_int32), ("scans", C.c_int32), ("launches", C.c_int32),
+                ("resumes", C.c_int32), ("host_waits", C.c_int32), ("capped", C.c_int32)]
 
 
 class ColorInfo(C.Structure):
@@ -230,6 +238,7 @@ SIGNATURES = {
     "g4s_triangle_count": (C.c_int, [C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(CCInfo), vp]),
     "g4s_kcore": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_uint, C.POINTER(KCoreInfo), vp]),
+    "g4s_ktruss": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(KTrussInfo), vp]),
     "g4s_color": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint, C.POINTER(ColorInfo), vp]),
     "g4s_csr_ewise_symbolic": (C.c_int, [C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64p, C.c_uint, C.POINTER(EwiseInfo), vp]),
     "g4s_csr_ewise_numeric": (C.c_int, [C.c_int, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),

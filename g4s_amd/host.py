@@ -13,6 +13,7 @@ Names and argument meaning follow the reference so that tests read like tests of
                    mm/inc/CSC.h:513-690); csr_permute, csr_induced_subgraph and csr_submatrix are compositions of it
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
+  ktruss         — truss numbers, peel rounds and supports of the edges of a symmetric pattern (g4s_ktruss); ktruss_subgraph is a composition of it
   kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
   color          — greedy colouring in a priority order (g4s_color); color_smallest_last, maximal_independent_set and color_classes go with it
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
@@ -221,6 +222,11 @@ class CSR:
     def kcore(self, max_k=None, return_round=False, return_info=False):
         """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
         return kcore(self, max_k, return_round, return_info)
+
+    def ktruss(self, max_k=None, return_round=False, return_support=False, return_info=False):
+        """Truss numbers (and the peel rounds and supports) of the edges of the graph whose symmetric pattern this matrix stores, one per stored entry —
+        ktruss(self, …). Needs no plan."""
+        return ktruss(self, max_k, return_round, return_support, return_info)
 
     def color(self, key=None, seed=0, largest_first=False, return_round=False, return_info=False):
         """The first-fit colouring in decreasing priority (key, hash) of the graph whose symmetric pattern this matrix stores — color(self, …)."""
@@ -727,6 +733,66 @@ def kcore(A, max_k=None, return_round=False, return_info=False):
         rnd = torch.from_numpy(out_r[:n]).cuda() if return_round else None
     res = (core,) + ((rnd,) if return_round else ()) + (({n_: getattr(info, n_) for n_, _ in capi.KCoreInfo._fields_},) if return_info else ())
     return res[0] if len(res) == 1 else res
+
+
+def _is_truss(v):
+    return _is_count(v) and 2 <= v <= capi.KTRUSS_FULL
+
+
+def ktruss(A, max_k=None, return_round=False, return_support=False, return_info=False):
+    """truss (int32 device tensor of nnz, one per stored entry): truss[p] = the largest k such that the edge stored at entry p belongs to a subgraph in
+    which every edge lies in at least k − 2 triangles (g4s_ktruss) — the edges with truss >= k are networkx.k_truss(G, k) of the graph without
+    self-loops. A is a CSR, or a (rowptr, colids) pair of int32 device tensors or of numpy arrays (host pointers; the results come back on the device
+    all the same), and holds the SYMMETRIC pattern of a simple undirected graph with strictly ascending rows (csr_symmetrise gives one); both copies of
+    an edge get the same values, a stored diagonal entry gets truss 0, round −1 and support 0. max_k: peel the levels below it only — the edges of the
+    max_k-truss then get truss = max_k and round = −1; None is the full decomposition. return_round=True adds round (the index of the peel frontier
+    that removed each edge), return_support=True adds support (the triangles through each edge in A), both int32 device tensors of nnz and functions
+    of the graph alone. return_info=True adds the dict of g4s_ktruss_info. Synchronous; no plan is built. ValueError (before any GPU call) for a CSR
+    that is not square, a max_k that is not an integer in [2, 2^31), and return_round / return_support / return_info that are not bools."""
+    if max_k is not None and not _is_truss(max_k):
+        raise ValueError(f"max_k must be None or an integer in [2, 2^31), not {max_k!r}")
+    for name, v in (("return_round", return_round), ("return_support", return_support), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    rowptr, colids, n = _pattern_of(A, "a k-truss decomposition")
+    _require_gpu()
+    cap = capi.KTRUSS_FULL if max_k is None else int(max_k)
+    info, null = capi.KTrussInfo(), C.c_void_p(0)
+    if isinstance(rowptr, torch.Tensor):
+        assert rowptr.is_cuda and colids.is_cuda and rowptr.dtype == torch.int32 and colids.dtype == torch.int32
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        nnz = int(colids.numel())
+        truss = torch.empty(nnz, dtype=torch.int32, device=rowptr.device)
+        rnd = torch.empty(nnz, dtype=torch.int32, device=rowptr.device) if return_round else None
+        sup = torch.empty(nnz, dtype=torch.int32, device=rowptr.device) if return_support else None
+        capi.check(capi.load().g4s_ktruss(n, _ptr_nn(rowptr), _ptr_nn(colids), cap, _ptr_nn(truss), _ptr_nn(rnd) if return_round else null,
+                                          _ptr_nn(sup) if return_support else null, capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        nnz = int(colids.size)
+        out, out_r, out_s = (np.empty(max(nnz, 1), np.int32) for _ in range(3))
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        capi.check(capi.load().g4s_ktruss(n, P(rowptr), P(colids if colids.size else out), cap, P(out), P(out_r) if return_round else null,
+                                          P(out_s) if return_support else null, capi.HOST_POINTERS, C.byref(info), _stream()))
+        truss = torch.from_numpy(out[:nnz]).cuda()
+        rnd = torch.from_numpy(out_r[:nnz]).cuda() if return_round else None
+        sup = torch.from_numpy(out_s[:nnz]).cuda() if return_support else None
+    res = ((truss,) + ((rnd,) if return_round else ()) + ((sup,) if return_support else ())
+           + (({n_: getattr(info, n_) for n_, _ in capi.KTrussInfo._fields_},) if return_info else ()))
+    return res[0] if len(res) == 1 else res
+
+
+def ktruss_subgraph(A, k):
+    """The k-truss of the square device CSR A — its largest subgraph in which every edge lies in at least k − 2 triangles — as a CSR on the same n
+    vertices whose values are the truss numbers capped at k (so every stored value is k). A composition: ktruss with max_k = k, which peels the levels
+    below k only, then csr_select("ge", thr=k) on a CSR that shares A's pattern and carries the truss numbers as values; stored diagonal entries
+    (truss 0) go. ValueError (before any GPU call) for a matrix that is not square and a k that is not an integer in [2, 2^31)."""
+    if not _is_truss(k):
+        raise ValueError(f"k must be an integer in [2, 2^31), not {k!r}")
+    if A.rows != A.cols:
+        raise ValueError(f"a k-truss subgraph needs a square matrix, not {A.rows} x {A.cols}")
+    truss = ktruss(A, max_k=int(k))
+    return csr_select(CSR(A.rowptr, A.colids, truss.to(torch.float64), A.rows, A.cols), "ge", thr=float(k))
 
 
 def degeneracy_order(A):

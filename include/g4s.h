@@ -112,9 +112,9 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
- * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py —, every result compared bit for bit):
+ * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py, for g4s_ktruss tests/test_ktruss_threads_gpu.py —, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_kcore, g4s_color, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_kcore, g4s_color, g4s_ktruss, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -800,6 +800,71 @@ typedef struct g4s_color_info {
 g4s_status g4s_color(int32_t n, const int32_t *rowptr, const int32_t *colids, const int32_t *key /* may be NULL */, uint32_t seed,
                      int32_t *color, int32_t *round /* may be NULL */, unsigned flags,
                      g4s_color_info *info /* may be NULL */, void *stream);
+
+/* k-truss decomposition: truss[p] (one int32 per STORED ENTRY, device or host like the other arrays, only written) = the truss number of the edge
+ * that entry p stores — the largest k such that the edge belongs to a subgraph in which every edge lies in at least k − 2 triangles of the subgraph;
+ * the k-truss of the graph is the edges with truss >= k, what networkx.k_truss(G, k) keeps. Every edge has truss >= 2. Raw arrays, no handle, no
+ * plan, no values.
+ *   Pattern: exactly g4s_kcore's. The adjacency of a simple undirected graph, rows strictly ascending with ids in [0, n), rowptr non-decreasing from
+ *     0: all of it checked on the device before any id is an index (G4S_ERR_INVALID, outputs unspecified afterwards). The caller declares the pattern
+ *     symmetric; symmetry is not checked. On a pattern that is not, the call still terminates and indexes nothing out of bounds — an entry left of the
+ *     diagonal without a mirror is treated like a diagonal entry — but the values are outside the contract. A stored diagonal entry is ignored and gets
+ *     truss = 0, round = −1, support = 0. Both stored copies of an edge carry the same values.
+ *   support[p] (nnz int32, may be NULL): the triangles through the edge in the INPUT graph — the values of C<A> = A·A on the pattern without its
+ *     diagonal (g4s_spgemm_masked).
+ *   round[p] (nnz int32, may be NULL): the graph is peeled level by level — j = the smallest remaining support, never decreasing — and inside a level
+ *     frontier by frontier: a frontier is ALL remaining edges of support <= j, removed at once, each with truss = j + 2. A triangle all of whose edges
+ *     were present before the removal and which holds at least one frontier edge dies ONCE: each of its edges outside the frontier loses exactly 1,
+ *     whether one or two of its edges are in the frontier. The next frontier is the edges that this removal brought to <= j. round[p] is the 0-based
+ *     index, over the whole call, of the non-empty frontier that removed the edge. That partition is a function of the graph alone, so truss, round
+ *     and support are the same on every run, stream, pointer kind and launch grid and are compared with ==.
+ *   max_k (>= 2): only the levels with truss < max_k are peeled. The edges still present afterwards — exactly the max_k-truss — get truss = max_k and
+ *     round = −1, and info.capped = 1: truss == min(full truss, max_k). INT32_MAX asks for the full decomposition; max_k < 2 is G4S_ERR_INVALID.
+ *   Checks before any HIP call (G4S_ERR_INVALID): any flag bit other than G4S_DEVICE_POINTERS, a NULL rowptr or truss, a NULL colids with n > 0, a
+ *     negative n, max_k < 2, and with host pointers outputs that overlap the inputs or each other. n == 0 is valid and writes nothing; nnz == 0 is
+ *     valid and writes nothing either. info may be NULL.
+ *   Algorithm: every undirected edge gets a compact id — the rank of its entry right of the diagonal (one scan) — and every stored entry
+ *     the id of its edge (the entry left of the diagonal finds its mirror by a binary search). An edge is walked along the SHORTER of its endpoints'
+ *     rows, balanced over entries (rows above 4096 entries in chunks of 1024 over all workgroups); each entry is searched in the other row, a hit is a
+ *     triangle. The support pass walks all edges once. A scan over the edges collects those with support <= j; when it collects none it raises j to the
+ *     smallest remaining support, so a non-empty level costs at most two scans. A peel walks the frontier's edges: per triangle two plain loads of the
+ *     other edges' rounds decide whether it is dead, and who decrements whom (of two frontier edges in one triangle the one with the smaller id); a
+ *     decrement is one atomic, and the lane that brings an edge from j + 1 to j appends it. Every edge is queued once: one array holds all frontiers.
+ *   Synchronous: runs on `stream` and returns when the outputs and info are complete. With device pointers the call waits once behind the row check
+ *     (it sizes its scratch from rowptr[n]). Scans and peels are enqueued blind in batches of at least G4S_KTRUSS_BATCH launches (doubling to 64) with
+ *     one read of the 128-byte state per batch: info.host_waits <= info.launches / 16 + 2. The peel grid follows the frontier seen at the last read; a
+ *     frontier that outgrows it stops the batch, which resumes on a larger grid (info.resumes). On a capturing stream it returns G4S_ERR_INVALID and
+ *     enqueues nothing. Scratch — a 256-byte state block, eight arrays of 4·nnz bytes (rank, edge of an entry, the two endpoints, support, round,
+ *     truss, queue), two lists of 4·min(nnz, 2^19) for long rows, plus device copies of the arrays with host pointers — comes from the library's
+ *     caching allocator and is released before the call returns. No process-wide state: different host threads may call at the same time. A graph
+ *     with more than 2^19 edges BOTH of whose endpoints have rows above 4096 entries is refused (G4S_ERR_INVALID).
+ *   Environment: G4S_KTRUSS_SCAN_WGS (the cap on the scan's workgroups, default one per CU), G4S_KTRUSS_MIN_GRID (the smallest peel grid,
+ *     default 8). The outputs do not depend on them.
+ *   Where it loses (profiles/ktruss.txt, one MI355X): against the host loop of INTEGRATION.md — supports by g4s_spgemm_masked on the remaining graph, a select,
+ *     an intersect, repeated level by level to the same truss numbers — it wins on all three graphs measured (tools/bench_ktruss.py): 52.9 ms against
+ *     1641 ms on the 1000 x 1000 grid with one diagonal per cell (1000 rounds), 122.9 against 3356 ms on the symmetrised R-MAT-16 (923 rounds), 330.6
+ *     against 36 125 ms on the symmetrised R-MAT-18 (1267 rounds). It loses against itself: the support pass walks the 163 M entries of R-MAT-16 in
+ *     3.3 ms, the peels walk the same entries once more in 104 ms, 2186 dependent kernels of 47 us on average, and the scans add 16 ms (two per level,
+ *     each over all edges). On the grid a peel is 50 us for 18 000 entries: the call is bound by the number of dependent kernels, as g4s_kcore is. A
+ *     graph of few rounds and one level is the case in which the loop comes closest; none was measured. */
+#define G4S_KTRUSS_BATCH 16         /* step launches enqueued behind one read of the state, at least (doubles up to 64 within a call) */
+typedef struct g4s_ktruss_info {
+    int64_t triangles;       /* triangles of the input graph                                          */
+    int64_t edges_walked;    /* stored entries walked by peel rounds (the shorter row of each edge)   */
+    int64_t support_walked;  /* stored entries walked by the support pass                             */
+    int64_t top_truss_edges; /* undirected edges whose truss equals `max_truss`                       */
+    int32_t max_truss;       /* the largest truss written (max_k when capped; 0 without any edge)     */
+    int32_t levels;          /* distinct truss values below max_k at which an edge was removed        */
+    int32_t rounds;          /* non-empty frontiers peeled = 1 + the largest value written to `round` */
+    int32_t scans;           /* passes over all edges that did work                                   */
+    int32_t launches;        /* kernels enqueued, those that returned at once included                */
+    int32_t resumes;         /* batches restarted because the frontier outgrew the launch grid        */
+    int32_t host_waits;      /* times the call waited for the device                                  */
+    int32_t capped;          /* 1: max_k ended the peeling with edges left                            */
+} g4s_ktruss_info;           /* 64 bytes */
+g4s_status g4s_ktruss(int32_t n, const int32_t *rowptr, const int32_t *colids, int32_t max_k,
+                      int32_t *truss, int32_t *round /* may be NULL */, int32_t *support /* may be NULL */, unsigned flags,
+                      g4s_ktruss_info *info /* may be NULL */, void *stream);
 
 /* Element-wise combination of two CSR matrices of the same shape, and filtering of one, on the device. Two calls each, on the model of
  * g4s_spgemm_symbolic / g4s_spgemm_numeric, with caller-allocated outputs: the symbolic call writes crpt (rows + 1) and *cnnz, the caller allocates

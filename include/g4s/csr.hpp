@@ -8,6 +8,7 @@
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
+//   KTruss(a,truss,round,support,max_k)   per stored entry: the truss number of its edge in the symmetric pattern `a`, the peel frontier that removed it, its triangles (g4s_ktruss)
 //   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
 //   EWiseAdd / EWiseMult / EWiseDifference(a,b,c), Select(a,c,pred,k,thr), Symmetrise(a,c)   A ∪ B, A ∩ B, A ∖ B, a filter, A ∪ Aᵀ (g4s_csr_ewise_*, g4s_csr_select_*)
@@ -216,6 +217,21 @@ void KCore(const CSR<IT, NT> &a, int32_t *core, int32_t *round = nullptr, int32_
     int32_t none = 0;
     check(g4s_kcore(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, max_k, a.rows ? core : &none, a.rows ? round : nullptr, G4S_HOST_POINTERS, info, nullptr),
           "KCore");
+}
+
+// truss[p] (a.nnz values, one per stored entry) = the largest k such that the edge stored at entry p belongs to a subgraph of the simple undirected graph
+// `a` in which every edge lies in at least k − 2 triangles (g4s_ktruss, host arrays): `a` holds the graph's symmetric pattern with ascending rows
+// (Symmetrise gives one); both copies of an edge get the same values, a stored diagonal entry gets truss 0, round −1, support 0. round (may be NULL): the
+// index of the peel frontier that removed the edge. support (may be NULL): the triangles through the edge in `a`. max_k (>= 2): only the levels below it
+// are peeled, what is left — the max_k-truss — gets truss = max_k and round = −1 (info->capped).
+template <typename IT, typename NT>
+void KTruss(const CSR<IT, NT> &a, int32_t *truss, int32_t *round = nullptr, int32_t *support = nullptr, int32_t max_k = INT32_MAX, g4s_ktruss_info *info = nullptr)
+{
+    if (a.rows != a.cols) throw std::runtime_error("KTruss: the pattern is not square");
+    const IT zero = 0;                                      // an empty CSR holds no arrays: nothing is read or written for rows == 0
+    int32_t none = 0;
+    check(g4s_ktruss(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, max_k, a.rows ? truss : &none, a.rows ? round : nullptr, a.rows ? support : nullptr,
+                     G4S_HOST_POINTERS, info, nullptr), "KTruss");
 }
 
 // color[v] (a.rows values) = the first-fit colour of v in the simple undirected graph `a`: the smallest colour not held by a neighbour of higher
