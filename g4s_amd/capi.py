@@ -18,6 +18,7 @@ PAGERANK_SYMMETRIC, PAGERANK_WARM_START, PAGERANK_BATCH = 65536, 131072, 8      
 BC_ACCUMULATE, BC_BATCH = 262144, 16                                     # g4s_betweenness (g4s.h)
 CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
 KCORE_BATCH, KCORE_FULL = 16, 2**31 - 1                                  # g4s_kcore: launches per state read at least; max_k of the full decomposition (g4s.h)
+SCC_BATCH = 16                                                           # g4s_strongly_connected_components: launches per state read at least (g4s.h)
 KTRUSS_BATCH, KTRUSS_FULL = 16, 2**31 - 1                                # g4s_ktruss: launches per state read at least; max_k of the full decomposition (g4s.h)
 COLOR_LARGEST_FIRST, COLOR_BATCH, COLOR_MASK_COLORS, COLOR_WINDOW = 524288, 16, 64, 256   # g4s_color: key := degree; launches per state read; mask width; scan window (g4s.h)
 EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
@@ -72,6 +73,13 @@ class CCInfo(C.Structure):
     """g4s_cc_info: what a g4s_connected_components call found and did."""
     _fields_ = [("components", C.c_int64), ("largest", C.c_int64), ("edges_linked", C.c_int64), ("largest_label", C.c_int32),
                 ("sample_rounds", C.c_int32), ("skipped", C.c_int32), ("host_waits", C.c_int32)]
+
+
+class SCCInfo(C.Structure):
+    """g4s_scc_info: what a g4s_strongly_connected_components call found and did."""
+    _fields_ = [("components", C.c_int64), ("largest", C.c_int64), ("largest_label", C.c_int32), ("trimmed", C.c_int32), ("pivot", C.c_int32),
+                ("pivot_size", C.c_int32), ("color_rounds", C.c_int32), ("reserved", C.c_int32), ("edges_walked", C.c_int64), ("launches", C.c_int32),
+                ("resumes", C.c_int32), ("host_waits", C.c_int32), ("built_transpose", C.c_int32)]
 
 
 class KCoreInfo(C.Structure):
@@ -237,6 +245,7 @@ SIGNATURES = {
     "g4s_spgemm_masked": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_triangle_count": (C.c_int, [C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(CCInfo), vp]),
+    "g4s_strongly_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(SCCInfo), vp]),
     "g4s_kcore": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_uint, C.POINTER(KCoreInfo), vp]),
     "g4s_ktruss": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(KTrussInfo), vp]),
     "g4s_color": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint, C.POINTER(ColorInfo), vp]),

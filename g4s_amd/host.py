@@ -13,6 +13,8 @@ Names and argument meaning follow the reference so that tests read like tests of
                    mm/inc/CSC.h:513-690); csr_permute, csr_induced_subgraph and csr_submatrix are compositions of it
   spgemm_masked  — C⟨M⟩ = A ⊗ B at the positions of a given pattern M only (g4s_spgemm_masked); triangle_count: Σ (L·L⟨L⟩) of the lower triangle
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
+  strongly_connected_components — canonical labels of the strongly connected components of a directed pattern (g4s_strongly_connected_components);
+                   compact_labels (labels → 0 … k−1) and condensation (the DAG of the components) are compositions of existing device calls
   ktruss         — truss numbers, peel rounds and supports of the edges of a symmetric pattern (g4s_ktruss); ktruss_subgraph is a composition of it
   kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
   color          — greedy colouring in a priority order (g4s_color); color_smallest_last, maximal_independent_set and color_classes go with it
@@ -218,6 +220,11 @@ class CSR:
         """Canonical labels of the weakly connected components of this square pattern — connected_components(self). Needs no plan: the handle
         is not touched."""
         return connected_components(self, symmetric, return_info)
+
+    def strongly_connected_components(self, transpose=None, return_info=False):
+        """Canonical labels of the strongly connected components of the directed graph this matrix stores by out-edges —
+        strongly_connected_components(self, …). Needs no plan."""
+        return strongly_connected_components(self, transpose, return_info)
 
     def kcore(self, max_k=None, return_round=False, return_info=False):
         """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
@@ -692,6 +699,86 @@ def _pattern_of(A, what):
     if A.rows != A.cols:
         raise ValueError(f"{what} needs a square pattern, not {A.rows} x {A.cols}")
     return A.rowptr, A.colids, int(A.rows)
+
+
+def strongly_connected_components(A, transpose=None, return_info=False):
+    """labels (int32 device tensor of n) = the smallest vertex id of each vertex's STRONGLY connected component (g4s_strongly_connected_components):
+    every stored entry (u, v) of the square pattern is an edge u → v, whatever its value. A is a CSR, or a (rowptr, colids) pair of int32 device
+    tensors or of numpy arrays (host pointers; the labels come back on the device all the same). transpose: the (trowptr, tcolids) pair of Aᵀ's
+    pattern, of the same kind as A's arrays, for a caller who has it (csr_transpose gives one); None lets the call build it. Synchronous; no plan is
+    built. return_info=True adds the dict of g4s_scc_info. ValueError (before any GPU call) for a CSR that is not square, a transpose that is not a
+    pair, whose trowptr does not have n + 1 entries or whose arrays are not of A's kind, and a return_info that is not a bool."""
+    if not isinstance(return_info, (bool, np.bool_)):
+        raise ValueError(f"return_info must be a bool, not {return_info!r}")
+    rowptr, colids, n = _pattern_of(A, "strongly connected components")
+    on_device = isinstance(rowptr, torch.Tensor)
+    trp = tci = None
+    if transpose is not None:
+        if not isinstance(transpose, (tuple, list)) or len(transpose) != 2:
+            raise ValueError("transpose must be None or a (trowptr, tcolids) pair")
+        trp, tci = transpose
+        if isinstance(trp, torch.Tensor) != on_device or isinstance(tci, torch.Tensor) != on_device:
+            raise ValueError("transpose must be of the same kind as the pattern: device tensors with device tensors, numpy arrays with numpy arrays")
+        size = (lambda a: int(a.numel())) if on_device else (lambda a: int(np.asarray(a).size))
+        if size(trp) != n + 1 or size(tci) != size(colids):
+            raise ValueError(f"transpose has the wrong length: trowptr needs {n + 1} entries and tcolids {size(colids)}, not {size(trp)} and {size(tci)}")
+    _require_gpu()
+    info, null = capi.SCCInfo(), C.c_void_p(0)
+    fn = capi.load().g4s_strongly_connected_components
+    if on_device:
+        assert rowptr.is_cuda and colids.is_cuda and rowptr.dtype == torch.int32 and colids.dtype == torch.int32
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        if trp is not None:
+            assert trp.is_cuda and tci.is_cuda and trp.dtype == torch.int32 and tci.dtype == torch.int32
+            trp, tci = trp.contiguous(), tci.contiguous()
+        labels = torch.empty(n, dtype=torch.int32, device=rowptr.device)
+        capi.check(fn(n, _ptr_nn(rowptr), _ptr_nn(colids), null if trp is None else _ptr_nn(trp), null if trp is None else _ptr_nn(tci), _ptr_nn(labels),
+                      capi.DEVICE_POINTERS, C.byref(info), _stream()))
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        out = np.empty(max(n, 1), np.int32)
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        if trp is not None:
+            trp, tci = np.ascontiguousarray(trp, np.int32), np.ascontiguousarray(tci, np.int32)
+        spare = np.zeros(1, np.int32)                                   # an empty array is passed as a pointer that is not read
+        capi.check(fn(n, P(rowptr), P(colids if colids.size else spare), null if trp is None else P(trp), null if trp is None else P(tci if tci.size else spare),
+                      P(out), capi.HOST_POINTERS, C.byref(info), _stream()))
+        labels = torch.from_numpy(out[:n]).cuda()
+    inf = {n_: getattr(info, n_) for n_, _ in capi.SCCInfo._fields_ if n_ != "reserved"}
+    return (labels, inf) if return_info else labels
+
+
+def compact_labels(labels):
+    """(index, roots) of canonical component labels — those of connected_components or of strongly_connected_components (an int32 device tensor with
+    labels[labels[v]] == labels[v]): roots (int32, ascending) = the k distinct labels, index[v] (int32) = the rank of labels[v] among them, so
+    roots[index] == labels and component a of the numbering 0 … k−1 is the one whose smallest vertex is roots[a]. A composition of device calls
+    (a compare, a prefix sum, a gather): no new kernel."""
+    _require_gpu()
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.dim() == 1
+    n = labels.numel()
+    is_root = labels == torch.arange(n, dtype=torch.int32, device=labels.device)
+    rank = torch.cumsum(is_root, 0, dtype=torch.int32) - 1             # rank[r] of a root r: the roots below it
+    roots = torch.nonzero(is_root).flatten().to(torch.int32)
+    return rank[labels.long()], roots
+
+
+def condensation(A, labels=None):
+    """(C, index): the condensation of the directed graph A (a CSR) by its strongly connected components — C is the k × k device CSR (values 1.0)
+    with an entry (a, b) where some stored edge of A runs from component a to a DIFFERENT component b, rows ascending, repeats merged; index[v] is
+    v's component in the numbering of compact_labels. labels: the result of strongly_connected_components(A), computed when None. C is acyclic. A
+    composition: csr_row_indices, a gather through index, csr_from_coo (repeats merged) and csr_select dropping the diagonal."""
+    rowptr, colids, n = _pattern_of(A, "a condensation")
+    if isinstance(A, (tuple, list)):
+        raise ValueError("condensation needs a CSR, not a (rowptr, colids) pair")
+    if labels is None:
+        labels = strongly_connected_components(A)
+    index, roots = compact_labels(labels)
+    k = int(roots.numel())
+    src = index[csr_row_indices(rowptr, int(colids.numel())).long()]
+    dst = index[colids.long()]
+    crp, cci, _ = csr_from_coo(src, dst, None, k, k, dup="first")
+    c = CSR(crp, cci, torch.ones(cci.numel(), dtype=torch.float64, device=cci.device), k, k)
+    return csr_select(c, "offdiag"), index
 
 
 def _is_count(v):

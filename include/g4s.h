@@ -112,9 +112,9 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
- * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py, for g4s_ktruss tests/test_ktruss_threads_gpu.py —, every result compared bit for bit):
+ * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py, for g4s_ktruss tests/test_ktruss_threads_gpu.py, for g4s_strongly_connected_components tests/test_scc_threads_gpu.py —, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_kcore, g4s_color, g4s_ktruss, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_connected_components, g4s_strongly_connected_components, g4s_kcore, g4s_color, g4s_ktruss, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -736,6 +736,70 @@ typedef struct g4s_kcore_info {
 g4s_status g4s_kcore(int32_t n, const int32_t *rowptr, const int32_t *colids, int32_t max_k,
                      int32_t *core, int32_t *round /* may be NULL */, unsigned flags,
                      g4s_kcore_info *info /* may be NULL */, void *stream);
+
+/* Strongly connected components: labels[v] (n int32, device or host like the other arrays, only written) = the smallest vertex id in v's strongly
+ * connected component, for the directed graph on vertices 0 … n−1 in which every stored entry (u, v) of the n×n pattern is an edge u → v — the
+ * directed counterpart of g4s_connected_components, and scipy.sparse.csgraph.connected_components(connection="strong") with canonical labels. Raw
+ * arrays, no handle, no plan, no values: a stored entry is an edge whatever its value.
+ *   Self-loops, repeated columns, unsorted rows and empty rows are valid and change nothing; a vertex on no cycle through another vertex is a
+ *     component of its own, with or without a self-loop.
+ *   Labels are canonical as g4s_connected_components': labels[v] <= v, labels[labels[v]] == labels[v]. They are the same on every run, stream, launch
+ *     grid and tuning switch, and are compared with ==, never up to a relabelling.
+ *   trowptr / tcolids: the pattern of Aᵀ (n + 1 and rowptr[n] entries), for a caller who has it — from g4s_csr_transpose, or because the same graph
+ *     is used again. Both given or both NULL; one without the other is G4S_ERR_INVALID. With both NULL the call builds them itself through
+ *     g4s_csr_transpose on device arrays (info.built_transpose = 1): 4·(n + 1) + 4·nnz bytes for the result plus that call's own scratch (about
+ *     28·nnz + 4·n bytes) and its three waits. A given pair that is NOT the transpose of the pattern is outside the contract: the call still
+ *     terminates, indexes nothing out of bounds and writes ids in [0, n).
+ *   Checks before any HIP call (G4S_ERR_INVALID, g4s_last_error names the argument): any flag bit other than G4S_DEVICE_POINTERS, a NULL rowptr or
+ *     labels, a NULL colids with n > 0, a negative n, one of trowptr / tcolids without the other, and with host pointers a labels array that overlaps
+ *     an input. On the device, for both patterns and before any id is an index: rowptr[0] == 0, rowptr non-decreasing, ids in [0, n), and
+ *     trowptr[n] == rowptr[n] — G4S_ERR_INVALID, outputs unspecified afterwards. n == 0 is valid and writes nothing; nnz == 0 is valid: labels[v] = v.
+ *     info may be NULL.
+ *   Algorithm (the Multistep shape of Slota, Rajamanickam, Madduri 2014). din[v] / dout[v] = the stored off-diagonal entries of v's row
+ *     in Aᵀ / in A. (1) Trim to the fixpoint: every live vertex with din == 0 or dout == 0 is a component of its own; removing it walks its two rows
+ *     with one atomic decrement per entry, and the lane that brings a counter to 0 claims that vertex: g4s_kcore's peel. (2) One pivot: the live
+ *     vertex with the largest din·dout (64 bits; the smallest id at ties); forward reach over A, backward reach over Aᵀ inside the forward set; what
+ *     the backward reach enters is the pivot's component and gets its smallest id; it is removed through the same peel. (3) Colouring rounds until
+ *     nobody is live: colour[v] = v, atomicMin along live out-edges to the fixpoint; the vertices that kept their own id are roots, and from all of
+ *     them at once a backward reach through vertices of the root's colour claims labels = colour — a root is the smallest id of everything that
+ *     reaches it, hence of its component; removal and trimming as before. The smallest live id is always a root, so every round removes a component.
+ *     The route is fixed, so components, largest, largest_label, trimmed, pivot, pivot_size and color_rounds are functions of the graph alone.
+ *   Synchronous: runs on `stream` and returns when labels and info are complete. Which phase runs next is decided on the device; the host enqueues
+ *     phase kernels blind in batches of at least G4S_SCC_BATCH launches (doubling to 64) with one read of the 208-byte state per batch, and a kernel
+ *     whose phase it is not returns at once. Hence info.host_waits <= info.launches / 16 + 5: one wait per batch of the loop, one for the statistics,
+ *     one for the copy to host arrays, three when the call builds the transpose — and no term in the number of steps, rounds or phases. The grid of
+ *     the stepped kernels follows the frontier seen at the last read; a frontier that outgrows it stops the batch, which resumes on a larger grid
+ *     (info.resumes). On a capturing stream the call returns G4S_ERR_INVALID and enqueues nothing. Scratch — a 256-byte state block, 28·n bytes
+ *     (two counters, the queue, the colours, the stamps, two work queues), four lists of 4·min(n, 2^19) for long rows, the transpose when it is built,
+ *     plus device copies of the arrays with host pointers — comes from the library's caching allocator and is released before the call returns. No
+ *     process-wide state: different host threads may call at the same time.
+ *   Environment: G4S_SCC_MIN_GRID (the smallest grid of a stepped kernel, default 8). The outputs do not depend on it.
+ *   Where it loses (profiles/scc.txt, one MI355X, tools/bench_scc.py): with a given transpose it takes 51.8 ms on configs[1] as given (98.7 M edges) and
+ *     8.3 ms on the directed R-MAT-20 against 2660 and 101 ms for scipy on the host with its copies (74.6 and 11.4 ms when it builds the transpose),
+ *     and 1.8x / 1.5x the time of two g4s_bfs calls that find the giant component alone. It LOSES on long acyclic chains, which are trimmed one
+ *     level per kernel: the 1000 × 1000 grid with every edge stored one way is 1999 dependent peels of at most 1000 vertices — 19.4 ms, 2.1x slower
+ *     than scipy on the host (9.1 ms). From the algorithm alone, not measured at size: a chain of small components whose ids ascend downstream costs
+ *     one colouring round per component, because each round's only root is the chain's first live component, and a long cycle costs one forward and
+ *     one backward step per vertex. A host algorithm (Tarjan) is linear in all three. */
+#define G4S_SCC_BATCH 16            /* phase launches enqueued behind one read of the state, at least (doubles up to 64 within a call) */
+typedef struct g4s_scc_info {
+    int64_t components;      /* number of distinct labels                                                       */
+    int64_t largest;         /* vertices in the largest component                                                */
+    int32_t largest_label;   /* its label (the smallest one among components of that size)                       */
+    int32_t trimmed;         /* vertices labelled by trimming, over the whole call                               */
+    int32_t pivot;           /* the pivot vertex; −1 when trimming left nobody                                   */
+    int32_t pivot_size;      /* vertices in the pivot's component (0 without a pivot)                            */
+    int32_t color_rounds;    /* colouring rounds run                                                             */
+    int32_t reserved;
+    int64_t edges_walked;    /* stored entries walked by peels, reaches and colour pushes                        */
+    int32_t launches;        /* kernels enqueued, those that returned at once included                           */
+    int32_t resumes;         /* batches restarted because the frontier outgrew the launch grid                   */
+    int32_t host_waits;      /* times the call waited for the device                                             */
+    int32_t built_transpose; /* 1: the call built the pattern of Aᵀ itself                                       */
+} g4s_scc_info;              /* 64 bytes */
+g4s_status g4s_strongly_connected_components(int32_t n, const int32_t *rowptr, const int32_t *colids,
+                                             const int32_t *trowptr /* may be NULL */, const int32_t *tcolids /* may be NULL */,
+                                             int32_t *labels, unsigned flags, g4s_scc_info *info /* may be NULL */, void *stream);
 
 /* Greedy colouring and independent sets: color[v] (n int32, device or host like the other arrays, only written) = the first-fit colour of v — the
  * smallest colour >= 0 not held by a neighbour of higher priority — i.e. sequential greedy colouring of the vertices in decreasing priority: what

@@ -7,6 +7,7 @@
 //   SpMVSemiring(a,x,y,multop,addop)   the same over min-plus, max-plus or or-and (y := A ⊗ x, or y ⊕ (A ⊗ x))
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
+//   StronglyConnectedComponents(a,labels)  labels[v] = the smallest vertex id of v's strongly connected component of the directed pattern `a` (g4s_strongly_connected_components)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
 //   KTruss(a,truss,round,support,max_k)   per stored entry: the truss number of its edge in the symmetric pattern `a`, the peel frontier that removed it, its triangles (g4s_ktruss)
 //   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
@@ -203,6 +204,18 @@ void ConnectedComponents(const CSR<IT, NT> &a, int32_t *labels, bool symmetric =
     int32_t none = 0;
     check(g4s_connected_components(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, a.rows ? labels : &none,
                                    G4S_HOST_POINTERS | (symmetric ? G4S_CC_SYMMETRIC : 0u), info, nullptr), "ConnectedComponents");
+}
+
+// labels[v] (a.rows values) = the smallest vertex id in v's STRONGLY connected component of the square pattern `a` — every stored entry (u, v) a directed
+// edge u → v, whatever its value (g4s_strongly_connected_components, host arrays; the call builds the transpose it needs).
+template <typename IT, typename NT>
+void StronglyConnectedComponents(const CSR<IT, NT> &a, int32_t *labels, g4s_scc_info *info = nullptr)
+{
+    if (a.rows != a.cols) throw std::runtime_error("StronglyConnectedComponents: the pattern is not square");
+    const IT zero = 0;                                      // an empty CSR holds no arrays: nothing is read or written for rows == 0
+    int32_t none = 0;
+    check(g4s_strongly_connected_components(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, nullptr, nullptr, a.rows ? labels : &none, G4S_HOST_POINTERS, info,
+                                            nullptr), "StronglyConnectedComponents");
 }
 
 // core[v] (a.rows values) = the largest k such that v belongs to a subgraph of the simple undirected graph `a` in which every vertex has at least k
