@@ -1,9 +1,12 @@
 // call_util.hpp — what the entry points that take host or device arrays and read a verdict back share (ewise.hip, extract.hip, coo.hip, spgemm_masked.hip,
-// components.hip, transpose.hip's g4s_csr_row_indices): an owned block of the caching allocator, the carver of a work block, the staging frame of a call with
-// host pointers, the overlap check of host arrays, the capture refusal, the capped grid and the combiners.
+// transpose.hip's g4s_csr_row_indices, pagerank.hip, traverse.hip, betweenness.hip and the graph calls on raw CSR arrays: components.hip, kcore.hip, color.hip,
+// ktruss.hip, scc.hip): an owned block of the caching allocator, the carver of a work block, the staging frame of a call with host pointers, the overlap
+// check of host arrays, the capture refusal, the capped grid, the combiners, and for the graph calls the environment switch, the launch counts and the
+// text of a refused pattern.
 #pragma once
 #include "common.hpp"
 #include <algorithm>
+#include <cstdlib>
 
 namespace {   // (one copy per translation unit, as the kernels of prims.hpp)
 
@@ -63,9 +66,29 @@ inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
 template <int WG_>
 inline int grid_for(long long n, long long cap) { return (int)std::max(1LL, std::min((n + WG_ - 1) / WG_, cap)); }
 
+// an A/B switch of the environment clamped to [lo, hi]; dflt when it is not set
+inline int env_int(const char *name, int dflt, int lo, int hi)
+{
+    const char *e = getenv(name);
+    if (!e || !*e) return dflt;
+    return std::max(lo, std::min(hi, atoi(e)));
+}
+
+// what a stepped graph call reports of its own host loop (g4s_*_info: launches, resumes, host_waits)
+struct Counts {
+    int launches = 0, resumes = 0, waits = 0;
+};
+
+// The bits an opening pass (frontier.hpp) leaves in a state block's `invalid` word, as the refusal's text: 1 rowptr, 2 an id, 4 the order inside a row.
+// NULL when none of them is set: the caller's own bits.
+inline const char *csr_invalid_text(int bits)
+{
+    return (bits & 1) ? "rowptr must start at 0 and never decrease" : (bits & 2) ? "a column id is outside [0, n)" : (bits & 4) ? "a row is not strictly ascending" : nullptr;
+}
+
 // One work block cut into arrays. piece() declares them in order, each padded to 256 bytes (tail(): unpadded, for the last one); alloc() makes the one
 // big_alloc of their sum and sets the pointers. idle(): the stream that used the block has been synchronised — without it the block is released behind a
-// device-wide wait, which is what an early return gets.
+// device-wide wait, which is what an early return gets. A call with a staging frame says it right behind Staged::finish, whatever the status.
 class Carver {
     struct Piece {
         void *slot;
@@ -99,8 +122,8 @@ public:
 
 // The device copies of a call with host pointers. The rule it owns: a block may go back to the cache as idle only after the stream that used it has been
 // synchronised — otherwise the next caller of big_alloc gets memory with a copy still in flight. finish() is the only place that marks the blocks idle, and
-// it synchronises first unless the status says that the device form already has. A frame destroyed without finish() leaves its blocks not idle: they are
-// released behind a device-wide wait.
+// it synchronises first unless the status says that the device form already has — so behind it the stream is idle whatever the status, and the caller's
+// own work blocks (Carver::idle) are too. A frame destroyed without finish() leaves its blocks not idle: they are released behind a device-wide wait.
 class Staged {
     static constexpr int kMax = 12;
     BigBuf b_[kMax];

@@ -41,7 +41,6 @@ namespace {
 using g4s::ClState;
 
 constexpr int kBatch = G4S_COLOR_BATCH;      // step launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
-constexpr int kHubCap = 1 << 19;             // rows above kHubCut entries: fewer than 2^31 / 4096
 constexpr int kMaskColors = G4S_COLOR_MASK_COLORS;
 constexpr int kWindow = G4S_COLOR_WINDOW;
 constexpr int kWindowWords = kWindow / 32;
@@ -60,10 +59,6 @@ struct StepArgs {
     int scan_follows;      // a scan kernel is enqueued behind every step of this batch
     int expect;            // scan only: the page turns behind which it runs; a scan behind a step that returned at once returns at once too
     unsigned seed;
-};
-
-struct RowRef {
-    int u, start;
 };
 
 // What travels with a row's entries in the walks: the vertex, its key and (steps only) the colour it has just been given.
@@ -88,19 +83,6 @@ __device__ __forceinline__ bool above(int ka, int a, int kb, int b, unsigned see
 
 // the lowest colour < 64 that the mask leaves free, 64 when there is none
 __device__ __forceinline__ int first_fit(unsigned long long m) { return m == ~0ull ? kMaskColors : __ffsll((long long)~m) - 1; }
-
-// A vertex for the frontier being built: behind the tail of the queue (one atomicAdd per wave), and into the hub list when its row is long. Called by
-// every lane that is active at the call site.
-__device__ __forceinline__ void append(bool want, int v, int len, const StepArgs &a, int *__restrict__ queue, int *__restrict__ hubs_next, ClState *st, long long &len_sum)
-{
-    const int idx = wave_append(want, &st->tail);
-    if ((unsigned)idx < (unsigned)a.n) queue[idx] = v;             // a vertex is appended once per call: idx < n by construction
-    if (want && len > kHubCut) {
-        const int h = atomicAdd(&st->n_hub_next, 1);
-        if ((unsigned)h < (unsigned)a.hub_cap) hubs_next[h] = v;   // fewer than 2^31 / kHubCut such rows exist
-    }
-    if (want) len_sum += len;
-}
 
 // The end of the seed and of a step kernel: the block's shares of the sums and of the largest colour, then the ticket; the last block to arrive turns
 // the page (turn_page).
@@ -142,59 +124,27 @@ __device__ __forceinline__ void finish(ClState *st, long long len_sum, long long
 __global__ __launch_bounds__(WG) void cl_open_rows_kernel(int n, const int *__restrict__ rowptr, int *__restrict__ pred, unsigned long long *__restrict__ mask,
                                                           int *__restrict__ deg, ClState *st)
 {
-    int bad = 0;
-    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
-        const int rb = rowptr[i], re = rowptr[i + 1];
-        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
+    open_rows(n, rowptr, &st->invalid, 1, [&](long long i, int rb, int re) {
         pred[i] = 0;
         mask[i] = 0ull;
         if (deg) deg[i] = re - rb;
-    }
-    if (bad) atomicOr(&st->invalid, 1);
+    });
     if (blockIdx.x == 0 && threadIdx.x == 0) st->max_color = -1;
 }
 
-// One entry of row u in the opening pass: the id in range, larger than the one before it; the diagonal does not count in the degree.
-__device__ __forceinline__ void open_entry(bool valid, int k, RowRef r, int n, const int *__restrict__ colids, int *deg, int &bad)
-{
-    if (!valid) return;
-    const int v = colids[k];
-    if ((unsigned)v >= (unsigned)n) bad |= 2;
-    else if (k > r.start && colids[k - 1] >= v) bad |= 4;
-    else if (v == r.u && deg) atomicSub(deg + r.u, 1);
-}
-
+// The column ids (open_ids / open_hubs, strictly ascending rows); the diagonal does not count in the degree, where the call keeps one.
 __global__ __launch_bounds__(WG) void cl_open_ids_kernel(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, int *deg,
                                                          int *__restrict__ hubs, ClState *st)
 {
     if (st->invalid) return;                                       // rowptr is monotone from 0 beyond this line: [0, rowptr[n]) is the colids array
-    int bad = 0;
-    walk_tiles<RowRef>(n, [&](int i, int &start, int &len, RowRef &r) {
-        const int rb = rowptr[i], l = rowptr[i + 1] - rb;
-        r.u = i;
-        r.start = rb;
-        if (l > kHubCut) {
-            const int h = atomicAdd(&st->n_hub_cur, 1);
-            if ((unsigned)h < (unsigned)hub_cap) hubs[h] = i;
-            return;
-        }
-        start = rb;
-        len = l;
-    }, [&](bool valid, int k, RowRef r) { open_entry(valid, k, r, n, colids, deg, bad); });
-    if (bad) atomicOr(&st->invalid, bad);
+    open_ids<true>(n, hub_cap, rowptr, colids, hubs, &st->n_hub_cur, &st->invalid, 2, [&](int, int u, int v) { if (v == u && deg) atomicSub(deg + u, 1); });
 }
 
 __global__ __launch_bounds__(WG) void cl_open_hubs_kernel(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, int *deg,
                                                           const int *__restrict__ hubs, ClState *st)
 {
     if (st->invalid) return;
-    int bad = 0;
-    walk_hubs<RowRef>(st->n_hub_cur < hub_cap ? st->n_hub_cur : hub_cap, [&](int h, int &start, int &len, RowRef &r) {
-        r.u = hubs[h];
-        r.start = start = rowptr[r.u];
-        len = rowptr[r.u + 1] - start;
-    }, [&](bool valid, int k, RowRef r) { open_entry(valid, k, r, n, colids, deg, bad); });
-    if (bad) atomicOr(&st->invalid, bad);
+    open_hubs<true>(n, hub_cap, rowptr, colids, hubs, &st->n_hub_cur, &st->invalid, 2, [&](int, int u, int v) { if (v == u && deg) atomicSub(deg + u, 1); });
 }
 
 // pred[w] = the stored entries u → w, u != w, with u above w: on a symmetric pattern the higher-priority neighbours of w. The hub list is the opening
@@ -235,7 +185,7 @@ __global__ __launch_bounds__(WG) void cl_seed_kernel(const int *__restrict__ row
         const long long i = i0 + threadIdx.x;
         const bool want = i < a.n && pred[i] == 0;
         const int len = want ? rowptr[i + 1] - rowptr[i] : 0;
-        append(want, (int)i, len, a, queue, hubs_next, st, len_sum);
+        append_frontier(want, (int)i, len, a.n, a.hub_cap, queue, hubs_next, &st->tail, &st->n_hub_next, len_sum);   // appended once per call: the slot is below n
     }
     finish(st, len_sum, 0, 0, -1, KIND_SEED, a);
 }
@@ -265,7 +215,7 @@ __global__ __launch_bounds__(WG) void cl_step_kernel(const int *__restrict__ row
                 }
             }
         }
-        append(want, w, len, a, queue, hubs_next, st, len_sum);
+        append_frontier(want, w, len, a.n, a.hub_cap, queue, hubs_next, &st->tail, &st->n_hub_next, len_sum);
     };
     walk_tiles<Pay>(st->end - head, [&](int i, int &start, int &len, Pay &p) {
         const int v = queue[head + i];
@@ -359,15 +309,8 @@ __global__ __launch_bounds__(WG) void cl_scan_kernel(const int *__restrict__ row
     }
 }
 
-int env_int(const char *name, int dflt, int lo, int hi)
-{
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    return std::max(lo, std::min(hi, atoi(e)));
-}
-
-struct Counts {
-    int launches = 0, resumes = 0, scan_resumes = 0, waits = 0;
+struct ColorCounts : Counts {
+    int scan_resumes = 0;
 };
 
 struct Work {
@@ -378,7 +321,7 @@ struct Work {
 
 // The whole colouring on device arrays; returns behind a wait on `s` with *h the final state.
 int run(int n, const int *rowptr, const int *colids, const int *key, unsigned seed, int *color, int *round, const Work &w, int hub_cap, int cus, ClState *h,
-        Counts *cnt, hipStream_t s)
+        ColorCounts *cnt, hipStream_t s)
 {
     // G4S_COLOR_MIN_GRID is an A/B switch: the outputs do not depend on it.
     const g4s::StepGrid sized(env_int("G4S_COLOR_MIN_GRID", g4s::kMinGrid, 1, 2 * cus), 2 * cus);
@@ -477,7 +420,7 @@ G4S_API g4s_status g4s_color(int32_t n, const int32_t *rowptr, const int32_t *co
     work.piece(&w.hubs[0], sizeof(int) * (size_t)hub_cap);
     work.tail(&w.hubs[1], sizeof(int) * (size_t)hub_cap);
     Staged stage(s);
-    Counts cnt;
+    ColorCounts cnt;
     int status = work.alloc();
     const int *rp = rowptr, *ci = colids, *ke = key;
     int *co = color, *ro = round;
@@ -500,8 +443,7 @@ G4S_API g4s_status g4s_color(int32_t n, const int32_t *rowptr, const int32_t *co
     status = stage.finish(status);                                 // the caller's host arrays and the blocks: nothing in flight touches them
     work.idle();
     if (status == G4S_OK && h.invalid)
-        status = g4s::set_error(G4S_ERR_INVALID, "g4s_color: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"
-                                                                  : (h.invalid & 2) ? "a column id is outside [0, n)" : "a row is not strictly ascending");
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_color: %s", csr_invalid_text(h.invalid));
     if (status == G4S_OK && info) {
         info->edges_walked = (int64_t)h.edges_walked;
         info->class0 = (int64_t)h.class0;

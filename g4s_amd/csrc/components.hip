@@ -35,7 +35,6 @@
 
 namespace {
 
-constexpr int kHubCap = 1 << 19;     // rows above kHubCut entries: fewer than 2^31 / 4096
 constexpr int kMaxRounds = 4;
 constexpr int kRoundsDefault = 2;
 constexpr int kJumpHops = 16;        // a pass moves a vertex this many hops up
@@ -56,7 +55,6 @@ struct CcState {
 };
 static_assert(sizeof(CcState) <= kStateBytes, "state block");
 
-__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ void st_(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 
 // Union of the trees of a and b (ancestors, possibly former ones, of the edge's two ends). max(a, b) strictly decreases: bounded, wait-free.
@@ -77,14 +75,10 @@ __device__ __forceinline__ void link_from(int a, int b, int *parent)
 
 __global__ __launch_bounds__(WG) void cc_open_rows_kernel(int n, const int *__restrict__ rowptr, int *__restrict__ parent, int *__restrict__ count, CcState *st)
 {
-    int bad = 0;
-    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
-        const int rb = rowptr[i], re = rowptr[i + 1];
-        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
+    open_rows(n, rowptr, &st->invalid, 1, [&](long long i, int, int) {
         parent[i] = (int)i;
         count[i] = 0;
-    }
-    if (bad) atomicOr(&st->invalid, 1);
+    });
 }
 
 __global__ __launch_bounds__(WG) void cc_open_ids_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ colids, CcState *st)
@@ -259,13 +253,6 @@ __global__ __launch_bounds__(WG) void cc_largest_kernel(int n, const int *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int env_int(const char *name, int dflt, int lo, int hi)
-{
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    return std::max(lo, std::min(hi, atoi(e)));
-}
-
 // Enqueues the whole labelling on device arrays. `st` has room for kStateBytes, `count` for n ints, `hubs` for min(n, kHubCap).
 int enqueue(int n, const int *rowptr, const int *colids, int *labels, bool symmetric, int rounds, bool no_skip, CcState *st, int *count, int *hubs, hipStream_t s)
 {
@@ -341,8 +328,7 @@ G4S_API g4s_status g4s_connected_components(int32_t n, const int32_t *rowptr, co
     status = stage.finish(status);                                 // the caller's host arrays and the blocks: nothing in flight touches them
     work.idle();
     if (status == G4S_OK && h.invalid)
-        status = g4s::set_error(G4S_ERR_INVALID, "g4s_connected_components: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"
-                                                                                                  : "a column id is outside [0, n)");
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_connected_components: %s", csr_invalid_text(h.invalid));
     if (status == G4S_OK && info) {
         info->components = (int64_t)h.components;
         info->largest = (int64_t)(h.best >> 32);

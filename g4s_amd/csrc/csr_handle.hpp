@@ -1,6 +1,7 @@
 // csr_handle.hpp — the CSR handle behind g4s_csr_t, for the files of the library that work on one: csr.hip (life cycle, SpMV), spmm.hip, transpose.hip,
 // traverse.hip, pagerank.hip, betweenness.hip. The device arrays of the last three's workspaces have one owner, DevicePieces below. What
-// traverse.hip and betweenness.hip share with kcore.hip and components.hip, which have no handle, is frontier.hpp (device) and step_batch.hpp (host).
+// traverse.hip and betweenness.hip share with the calls on raw CSR arrays, which have no handle (components.hip, kcore.hip, color.hip, ktruss.hip,
+// scc.hip), is frontier.hpp (device) and step_batch.hpp (host).
 #pragma once
 #include "common.hpp"
 #include "spmv_stream.hpp"

@@ -1,12 +1,15 @@
-// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, kcore.hip, components.hip): the walk over the entries
-// of a level's rows, balanced over entries (walk_tiles for ordinary rows, walk_hubs for long ones), the one-atomicAdd-per-wave append, the two ends of
-// a step kernel (step_runs; turn_page: the last workgroup to take a ticket turns the page of the state block), the scan for stored zeros and the row
-// grid; what a row is, its payload, what happens per entry and what a page turn writes stay with the caller, as callables. It brings along WG and the
-// wave reductions (wave_reduce.hpp, which pagerank.hip takes alone) and the host side of the stepped loop (step_batch.hpp).
+// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, components.hip, kcore.hip, color.hip, ktruss.hip, scc.hip; DESIGN
+// §4.11): the walk over the entries of a level's rows, balanced over entries (walk_tiles for ordinary rows, walk_hubs for long ones), the opening pass
+// of the calls on raw CSR arrays (open_rows: the row check; open_ids / open_hubs: the check of the column ids), the one-atomicAdd-per-wave append and
+// the append to a frontier that keeps a hub list (append_frontier), the two ends of a step kernel (step_runs; turn_page: the last workgroup to take a
+// ticket turns the page of the state block), the scan for stored zeros and the row grid; what a row is, its payload, what happens per entry and what a
+// page turn writes stay with the caller, as callables. It brings along WG and the wave reductions (wave_reduce.hpp, which pagerank.hip takes alone) and
+// the host side of the stepped loop (step_batch.hpp). level_peel.hpp puts the page turn and the host loop of kcore.hip and ktruss.hip on top of it.
 #pragma once
 #include "readback.hpp"
 #include "step_batch.hpp"
 #include "wave_reduce.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -16,6 +19,10 @@ namespace {
 // (2^20) far inside an int.
 constexpr int kHubCut = 4096;
 constexpr int kHubChunk = 1024;   // entries of a hub per workgroup visit
+constexpr int kHubCap = 1 << 19;  // room in a hub list: rows above kHubCut entries are fewer than 2^31 / 4096
+
+// a load that may be stale, which the compiler may neither tear nor assume race-free: a plain global load
+__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 
 inline int grid_rows(long long n, int cus)
 {
@@ -101,6 +108,79 @@ __device__ __forceinline__ void walk_hubs(int nh, Hub hub, Entry entry)
     }
 }
 
+// The opening pass of a call on raw CSR arrays, in kernels of the caller's (their names, their guards and whatever else they do stay with it). First
+// the rows: *invalid |= bit unless rowptr[0] == 0 and rowptr never decreases over rows 0 … n − 1; fill(i, rb, re) per row is the caller's.
+template <typename Fill>
+__device__ __forceinline__ void open_rows(int n, const int *__restrict__ rowptr, int *invalid, int bit, Fill fill)
+{
+    int bad = 0;
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
+        const int rb = rowptr[i], re = rowptr[i + 1];
+        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
+        fill(i, rb, re);
+    }
+    if (bad) atomicOr(invalid, bit);
+}
+
+// Then the column ids, behind a kernel boundary and the caller's `if (*invalid) return` ([0, rowptr[n]) is the colids array beyond it):
+// *invalid |= bit for an id outside [0, n) and, with kAscending, |= 2 · bit for one that is not above the id before it in its row;
+// accept(k, u, v) for every other entry k of row u, v its id. open_ids walks the ordinary rows and collects the rows above kHubCut entries in hubs[]
+// behind the counter *n_hubs; open_hubs, a kernel later, walks those (the count clamped to hub_cap: fewer than 2^31 / kHubCut such rows exist).
+struct OpenRow {
+    int u, start;                                                  // the order check wants to know where the row begins
+};
+template <bool kAscending> using OpenPay = std::conditional_t<kAscending, OpenRow, int>;
+
+template <bool kAscending, typename Accept>
+__device__ __forceinline__ void open_entry(bool valid, int k, OpenPay<kAscending> p, int n, const int *__restrict__ colids, int bit, int &bad, Accept accept)
+{
+    if (!valid) return;
+    const int v = colids[k];
+    if ((unsigned)v >= (unsigned)n) {
+        bad |= bit;
+    } else if constexpr (kAscending) {
+        if (k > p.start && colids[k - 1] >= v) bad |= 2 * bit;
+        else accept(k, p.u, v);
+    } else {
+        accept(k, p, v);
+    }
+}
+
+template <bool kAscending, typename Accept>
+__device__ __forceinline__ void open_ids(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, int *__restrict__ hubs, int *n_hubs,
+                                         int *invalid, int bit, Accept accept)
+{
+    int bad = 0;
+    walk_tiles<OpenPay<kAscending>>(n, [&](int i, int &start, int &len, OpenPay<kAscending> &p) {
+        const int rb = rowptr[i], l = rowptr[i + 1] - rb;
+        if constexpr (kAscending) p = OpenRow{i, rb};
+        else p = i;
+        if (l > kHubCut) {
+            const int h = atomicAdd(n_hubs, 1);
+            if ((unsigned)h < (unsigned)hub_cap) hubs[h] = i;
+            return;
+        }
+        start = rb;
+        len = l;
+    }, [&](bool valid, int k, OpenPay<kAscending> p) { open_entry<kAscending>(valid, k, p, n, colids, bit, bad, accept); });
+    if (bad) atomicOr(invalid, bad);
+}
+
+template <bool kAscending, typename Accept>
+__device__ __forceinline__ void open_hubs(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, const int *__restrict__ hubs,
+                                          const int *n_hubs, int *invalid, int bit, Accept accept)
+{
+    int bad = 0;
+    walk_hubs<OpenPay<kAscending>>(*n_hubs < hub_cap ? *n_hubs : hub_cap, [&](int h, int &start, int &len, OpenPay<kAscending> &p) {
+        const int u = hubs[h];
+        start = rowptr[u];
+        len = rowptr[u + 1] - start;
+        if constexpr (kAscending) p = OpenRow{u, start};
+        else p = u;
+    }, [&](bool valid, int k, OpenPay<kAscending> p) { open_entry<kAscending>(valid, k, p, n, colids, bit, bad, accept); });
+    if (bad) atomicOr(invalid, bad);
+}
+
 // The slot of each wanting lane behind *counter, by one atomicAdd per wave: ballot, the first wanting lane adds the popcount, every lane takes its
 // rank among the wanting lanes below it. −1 for a lane that does not want. Call with every lane that is active at the call site. Where the
 // vertex then goes (a queue's front, `order`, a hub list) is the caller's business, and so is the bound on the slot.
@@ -114,6 +194,24 @@ __device__ __forceinline__ int wave_append(bool want, int *counter)
     if (lane == leader) base = atomicAdd(counter, __popcll(m));
     base = __shfl(base, leader);
     return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// An item v (a vertex, an edge) whose row has `len` entries, for the frontier being built: behind *tail in the queue (an item is appended once per call,
+// so its slot is below `bound` by construction), into the next hub list behind *n_hub_next when the row is long, and len onto the lane's share of
+// the frontier's entries. Called by every lane that is active at the call site. False when the hub list had no room for v.
+__device__ __forceinline__ bool append_frontier(bool want, int v, int len, int bound, int hub_cap, int *__restrict__ queue, int *__restrict__ hubs_next, int *tail,
+                                                int *n_hub_next, long long &len_sum)
+{
+    const int idx = wave_append(want, tail);
+    if ((unsigned)idx < (unsigned)bound) queue[idx] = v;
+    bool room = true;
+    if (want && len > kHubCut) {
+        const int h = atomicAdd(n_hub_next, 1);
+        room = (unsigned)h < (unsigned)hub_cap;
+        if (room) hubs_next[h] = v;
+    }
+    if (want) len_sum += len;
+    return room;
 }
 
 // May a resumable step kernel run? `stop` is the state's word, the same for every block (it changes only after the last ticket): 0 goes on, 4 (the

@@ -23,8 +23,7 @@
 // A vertex whose degree has fallen to k or below is never appended again: later atomics on it return at most k. core[v] and round[v] are written by the
 // one appending lane and read only behind a kernel boundary. Nothing spins; every loop is bounded by the queue or a row length.
 #include "common.hpp"
-#include "frontier.hpp"
-#include "call_util.hpp"
+#include "level_peel.hpp"
 #include "kcore.hpp"
 #include <algorithm>
 #include <climits>
@@ -34,12 +33,9 @@ namespace {
 using g4s::KcState;
 
 constexpr int kBatch = G4S_KCORE_BATCH;      // step launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
-constexpr int kHubCap = 1 << 19;             // rows above kHubCut entries: fewer than 2^31 / 4096
 constexpr int kScanUnroll = 4;                // vertices per thread and trip of a scan
 constexpr size_t kStateBytes = 256;
 static_assert(sizeof(KcState) <= kStateBytes, "state block");
-
-enum { KIND_SCAN = 0, KIND_PEEL = 1 };
 
 struct StepArgs {
     long long grid_cap;    // a frontier with more entries than this asks for a larger peel grid
@@ -49,135 +45,40 @@ struct StepArgs {
     int resume;            // peel only: the first launch of a batch goes on from stop == 4
 };
 
-struct RowRef {
-    int u, start;
-};
-
-__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-
-// A vertex for the frontier being built: behind the tail of the queue (one atomicAdd per wave), and into the hub list when its row is long. Called by
-// every lane that is active at the call site.
-__device__ __forceinline__ void append(bool want, int v, int len, const StepArgs &a, int *__restrict__ queue, int *__restrict__ hubs_next, KcState *st, long long &len_sum)
-{
-    const int idx = wave_append(want, &st->tail);
-    if ((unsigned)idx < (unsigned)a.n) queue[idx] = v;             // a vertex is appended once per call: idx < n by construction
-    if (want && len > kHubCut) {
-        const int h = atomicAdd(&st->n_hub_next, 1);
-        if ((unsigned)h < (unsigned)a.hub_cap) hubs_next[h] = v;   // fewer than 2^31 / kHubCut such rows exist
-    }
-    if (want) len_sum += len;
-}
-
-// The end of a step kernel: the block's shares of the sums and of the minimum, then the ticket; the last block to arrive turns the page (turn_page).
-__device__ __forceinline__ void finish(KcState *st, long long len_sum, long long walked, int mn, int kind, const StepArgs a)
-{
-    __shared__ long long s_len[WG / 64], s_walk[WG / 64];
-    __shared__ int s_min[WG / 64];
-    len_sum = wave_sum(len_sum);
-    walked = wave_sum(walked);
-    mn = wave_min(mn);
-    if ((threadIdx.x & 63) == 0) { s_len[threadIdx.x >> 6] = len_sum; s_walk[threadIdx.x >> 6] = walked; s_min[threadIdx.x >> 6] = mn; }
-    if (!turn_page(&st->tickets, [&] {
-        long long ls = 0, ws = 0;
-        int m = INT_MAX;
-        for (int w = 0; w < WG / 64; ++w) { ls += s_len[w]; ws += s_walk[w]; m = s_min[w] < m ? s_min[w] : m; }
-        if (ls) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)ls);
-        if (ws) atomicAdd(&st->edges_walked, (unsigned long long)ws);
-        // the word only decreases while the kernel runs, so a value read earlier is too large and costs one atomic; read at agent scope, past the
-        // copy of the state line this CU has held since the kernel's first lines
-        if (m < __hip_atomic_load(&st->min_deg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&st->min_deg, m);
-    })) return;
-    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0), m = atomicAdd(&st->min_deg, 0);
-    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
-    const int got = tail - st->end;                                // what this kernel appended
-    st->head = st->end; st->end = tail;
-    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
-    st->edges_cur = e; st->edges_next = 0;
-    st->min_deg = INT_MAX;
-    st->tickets = 0;
-    int stop = e > a.grid_cap ? 4 : 0;
-    if (kind == KIND_SCAN) {
-        st->scans += 1;
-        if (got == 0) {                                            // vertices are left (a scan does not run otherwise), all above k: m is a degree
-            st->k = m;
-            if (m >= a.max_k) stop = 2;
-        } else {
-            st->levels += 1;
-            st->top_k = st->k;
-        }
-    } else {
-        st->round += 1;
-        if (got == 0 && tail >= a.n) stop = 1;
-    }
-    st->stop = stop;
-}
-
 __global__ __launch_bounds__(WG) void kc_open_rows_kernel(int n, int max_k, const int *__restrict__ rowptr, int *__restrict__ deg, int *__restrict__ core,
                                                           int *__restrict__ round, KcState *st)
 {
-    int bad = 0;
-    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
-        const int rb = rowptr[i], re = rowptr[i + 1];
-        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
+    open_rows(n, rowptr, &st->invalid, 1, [&](long long i, int rb, int re) {
         deg[i] = re - rb;
         core[i] = -1;
         if (round) round[i] = -1;
-    }
-    if (bad) atomicOr(&st->invalid, 1);
+    });
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        st->min_deg = INT_MAX;
+        st->min_left = INT_MAX;
         if (max_k == 0) st->stop = 2;                              // no level is below the cap: every vertex is left
     }
 }
 
-// One entry of row u in the opening pass: the id in range, larger than the one before it; the diagonal does not count in the degree.
-__device__ __forceinline__ void open_entry(bool valid, int k, RowRef r, int n, const int *__restrict__ colids, int *deg, int &bad)
-{
-    if (!valid) return;
-    const int v = colids[k];
-    if ((unsigned)v >= (unsigned)n) bad |= 2;
-    else if (k > r.start && colids[k - 1] >= v) bad |= 4;
-    else if (v == r.u) atomicSub(deg + r.u, 1);
-}
-
+// The column ids (open_ids / open_hubs, strictly ascending rows); the diagonal does not count in the degree.
 __global__ __launch_bounds__(WG) void kc_open_ids_kernel(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, int *deg,
                                                          int *__restrict__ hubs, KcState *st)
 {
     if (st->invalid) return;                                       // rowptr is monotone from 0 beyond this line: [0, rowptr[n]) is the colids array
-    int bad = 0;
-    walk_tiles<RowRef>(n, [&](int i, int &start, int &len, RowRef &r) {
-        const int rb = rowptr[i], l = rowptr[i + 1] - rb;
-        r.u = i;
-        r.start = rb;
-        if (l > kHubCut) {
-            const int h = atomicAdd(&st->n_hub_cur, 1);
-            if ((unsigned)h < (unsigned)hub_cap) hubs[h] = i;
-            return;
-        }
-        start = rb;
-        len = l;
-    }, [&](bool valid, int k, RowRef r) { open_entry(valid, k, r, n, colids, deg, bad); });
-    if (bad) atomicOr(&st->invalid, bad);
+    open_ids<true>(n, hub_cap, rowptr, colids, hubs, &st->n_hub_cur, &st->invalid, 2, [&](int, int u, int v) { if (v == u) atomicSub(deg + u, 1); });
 }
 
 __global__ __launch_bounds__(WG) void kc_open_hubs_kernel(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, int *deg,
                                                           const int *__restrict__ hubs, KcState *st)
 {
     if (st->invalid) return;
-    int bad = 0;
-    walk_hubs<RowRef>(st->n_hub_cur < hub_cap ? st->n_hub_cur : hub_cap, [&](int h, int &start, int &len, RowRef &r) {
-        r.u = hubs[h];
-        r.start = start = rowptr[r.u];
-        len = rowptr[r.u + 1] - start;
-    }, [&](bool valid, int k, RowRef r) { open_entry(valid, k, r, n, colids, deg, bad); });
-    if (bad) atomicOr(&st->invalid, bad);
+    open_hubs<true>(n, hub_cap, rowptr, colids, hubs, &st->n_hub_cur, &st->invalid, 2, [&](int, int u, int v) { if (v == u) atomicSub(deg + u, 1); });
 }
 
 __global__ __launch_bounds__(WG) void kc_scan_kernel(const int *__restrict__ rowptr, const int *__restrict__ deg, int *__restrict__ core, int *__restrict__ round,
                                                      int *__restrict__ queue, int *hubs0, int *hubs1, KcState *st, const StepArgs a)
 {
     if (st->invalid || st->stop != 0 || st->end != st->head) return;   // the same words for every block: they change only after the last ticket
-    const int kk = st->k, r = st->round;
+    const int kk = st->level, r = st->round;
     int *hubs_next = st->hub_cur ? hubs0 : hubs1;
     long long len_sum = 0;
     int mn = INT_MAX;
@@ -205,17 +106,17 @@ __global__ __launch_bounds__(WG) void kc_scan_kernel(const int *__restrict__ row
             } else if (c[j] == -1) {
                 mn = d[j] < mn ? d[j] : mn;
             }
-            append(want, (int)i, len, a, queue, hubs_next, st, len_sum);
+            append_frontier(want, (int)i, len, a.n, a.hub_cap, queue, hubs_next, &st->tail, &st->n_hub_next, len_sum);   // appended once per call: the slot is below n
         }
     }
-    finish(st, len_sum, 0, mn, KIND_SCAN, a);
+    finish_step(st, len_sum, 0, mn, KIND_SCAN, a.grid_cap, a.max_k, [&] { return a.n; });
 }
 
 __global__ __launch_bounds__(WG) void kc_peel_kernel(const int *__restrict__ rowptr, const int *__restrict__ colids, int *deg, int *core, int *round, int *queue,
                                                      int *hubs0, int *hubs1, KcState *st, const StepArgs a)
 {
     if (st->invalid || st->end == st->head || !step_runs(st->stop, a.resume)) return;
-    const int kk = st->k, r = st->round + 1, head = st->head;
+    const int kk = st->level, r = st->round + 1, head = st->head;
     const int *hubs_cur = st->hub_cur ? hubs1 : hubs0;
     int *hubs_next = st->hub_cur ? hubs0 : hubs1;
     long long len_sum = 0, walked = 0;
@@ -236,7 +137,7 @@ __global__ __launch_bounds__(WG) void kc_peel_kernel(const int *__restrict__ row
                 }
             }
         }
-        append(want, v, len, a, queue, hubs_next, st, len_sum);
+        append_frontier(want, v, len, a.n, a.hub_cap, queue, hubs_next, &st->tail, &st->n_hub_next, len_sum);
     };
     walk_tiles<int>(st->end - head, [&](int i, int &start, int &len, int &u) {
         u = queue[head + i];
@@ -250,7 +151,7 @@ __global__ __launch_bounds__(WG) void kc_peel_kernel(const int *__restrict__ row
         start = rowptr[u];
         len = rowptr[u + 1] - start;
     }, entry);
-    finish(st, len_sum, walked, INT_MAX, KIND_PEEL, a);
+    finish_step(st, len_sum, walked, INT_MAX, KIND_PEEL, a.grid_cap, a.max_k, [&] { return a.n; });
 }
 
 // Once the peeling has ended (stop 1 or 2; a no-op before): what max_k left gets core = max_k, and the vertices of the top core are counted.
@@ -258,7 +159,7 @@ __global__ __launch_bounds__(WG) void kc_finish_kernel(int n, int max_k, int *__
 {
     __shared__ int s_red[WG / 64];
     if (st->invalid || (st->stop != 1 && st->stop != 2)) return;
-    const int top = st->stop == 2 ? max_k : st->top_k;
+    const int top = st->stop == 2 ? max_k : st->top_level;
     int c = 0;
     for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
         int x = core[i];
@@ -274,17 +175,6 @@ __global__ __launch_bounds__(WG) void kc_finish_kernel(int n, int max_k, int *__
         if (sum) atomicAdd(&st->top_core, (unsigned long long)sum);
     }
 }
-
-int env_int(const char *name, int dflt, int lo, int hi)
-{
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    return std::max(lo, std::min(hi, atoi(e)));
-}
-
-struct Counts {
-    int launches = 0, resumes = 0, waits = 0;
-};
 
 // The whole decomposition on device arrays; returns behind a wait on `s` with *h the final state. `st` has room for kStateBytes, `deg` and `queue` for
 // n ints, hubs[0] and hubs[1] for hub_cap ints each.
@@ -309,39 +199,15 @@ int run(int n, const int *rowptr, const int *colids, int max_k, int *core, int *
     cnt->launches += 3;
 
     g4s::ReadScope reads(s);
-    bool know = false;                                             // *h is the device's state
-    int batch = kBatch, peels = 2;                                 // a batch is units of two scans (the level jump, the collect) and `peels` peels
-    int levels_seen = 0, rounds_seen = 0;
-    for (;;) {
-        const int grid = know ? sized.grid(h->edges_cur + (h->end - h->head) + h->n_hub_cur) : sized.max_grid;
-        a.grid_cap = sized.cap(grid);
-        int pos = know && h->end != h->head ? 2 : 0;               // a frontier is waiting: begin with the peels
-        for (int b = 0; b < batch; ++b) {
-            if (pos < 2) {
-                hipLaunchKernelGGL(kc_scan_kernel, dim3(g_scan), dim3(WG), 0, s, rowptr, deg, core, round, queue, hubs[0], hubs[1], st, a);
-            } else {
-                a.resume = b == 0 && know && h->stop == 4;
-                hipLaunchKernelGGL(kc_peel_kernel, dim3(grid), dim3(WG), 0, s, rowptr, colids, deg, core, round, queue, hubs[0], hubs[1], st, a);
-                a.resume = 0;
-            }
-            pos = pos + 1 == 2 + peels ? 0 : pos + 1;
-        }
-        hipLaunchKernelGGL(kc_finish_kernel, dim3(g_rows), dim3(WG), 0, s, n, max_k, core, st);
-        G4S_HIP_TRY(hipGetLastError());
-        cnt->launches += batch + 1;
-        if (know && h->stop == 4) cnt->resumes += 1;
-        G4S_HIP_TRY(reads.fetch(*h, st));
-        cnt->waits += 1;
-        if (h->invalid || h->stop == 1 || h->stop == 2) break;
-        // the next batch follows what this one showed: rounds per level, rounded up, and one to spare
-        const int dl = std::max(h->levels - levels_seen, 1), dr = h->round - rounds_seen;
-        levels_seen = h->levels;
-        rounds_seen = h->round;
-        if (know) batch = sized.next_batch(batch);
-        peels = std::max(2, std::min(batch - 2, (dr + dl - 1) / dl + 1));
-        know = true;
-    }
-    return G4S_OK;
+    return run_level_peel(sized, kBatch, 1, [&](long long grid_cap) {
+        a.grid_cap = grid_cap;
+        hipLaunchKernelGGL(kc_scan_kernel, dim3(g_scan), dim3(WG), 0, s, rowptr, deg, core, round, queue, hubs[0], hubs[1], st, a);
+    }, [&](int grid, long long grid_cap, int resume) {
+        a.grid_cap = grid_cap;
+        a.resume = resume;
+        hipLaunchKernelGGL(kc_peel_kernel, dim3(grid), dim3(WG), 0, s, rowptr, colids, deg, core, round, queue, hubs[0], hubs[1], st, a);
+        a.resume = 0;
+    }, [&] { hipLaunchKernelGGL(kc_finish_kernel, dim3(g_rows), dim3(WG), 0, s, n, max_k, core, st); }, reads, st, h, cnt);
 }
 
 } // namespace
@@ -401,12 +267,11 @@ G4S_API g4s_status g4s_kcore(int32_t n, const int32_t *rowptr, const int32_t *co
     status = stage.finish(status);                                 // the caller's host arrays and the blocks: nothing in flight touches them
     work.idle();
     if (status == G4S_OK && h.invalid)
-        status = g4s::set_error(G4S_ERR_INVALID, "g4s_kcore: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"
-                                                                  : (h.invalid & 2) ? "a column id is outside [0, n)" : "a row is not strictly ascending");
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_kcore: %s", csr_invalid_text(h.invalid));
     if (status == G4S_OK && info) {
         info->edges_walked = (int64_t)h.edges_walked;
         info->top_core_size = (int64_t)h.top_core;
-        info->degeneracy = h.stop == 2 ? max_k : h.top_k;
+        info->degeneracy = h.stop == 2 ? max_k : h.top_level;
         info->levels = h.levels;
         info->rounds = h.round;
         info->scans = h.scans;

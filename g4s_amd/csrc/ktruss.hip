@@ -37,8 +37,7 @@
 // only decrease; an edge appended in this kernel may take further decrements, which nobody reads again (it is in the next frontier, whose members are
 // never decremented, and its tr and rnd are already written by the one appending lane). Nothing spins; every loop is bounded by a queue or a row length.
 #include "common.hpp"
-#include "frontier.hpp"
-#include "call_util.hpp"
+#include "level_peel.hpp"
 #include "prims.hpp"
 #include "ktruss.hpp"
 #include <algorithm>
@@ -49,13 +48,10 @@ namespace {
 using g4s::KtState;
 
 constexpr int kBatch = G4S_KTRUSS_BATCH;     // step launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
-constexpr int kHubCap = 1 << 19;             // room in a hub list: rows above kHubCut entries are fewer than 2^31 / 4096; more hub EDGES than this are refused
 constexpr int kScanUnroll = 4;                // edges per thread and trip of a scan
 constexpr long long kEntryWeight = 16;        // a walk entry is a binary search in the other row — a dozen dependent loads — where StepGrid counts plain entries
 constexpr size_t kStateBytes = 256;
 static_assert(sizeof(KtState) <= kStateBytes, "state block");
-
-enum { KIND_SCAN = 0, KIND_PEEL = 1 };
 
 struct StepArgs {
     long long grid_cap;    // a frontier with more walk entries than this asks for a larger peel grid
@@ -71,16 +67,10 @@ struct Graph {
     int *hubs0, *hubs1;
 };
 
-struct RowRef {
-    int u, start;
-};
-
 struct EdgeRef {
     int c, u, v;           // the edge and its endpoints
     int ob, oe;            // the other (longer) row
 };
-
-__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 
 // the position of w in the ascending colids[lo, hi), −1 when it is not there
 __device__ __forceinline__ int find(const int *__restrict__ colids, int lo, int hi, int w)
@@ -111,118 +101,36 @@ __device__ __forceinline__ int walk_len(int c, const Graph &g)
     return ul <= vl ? ul : vl;
 }
 
-// An edge for the frontier being built: behind the tail of the queue (one atomicAdd per wave), and into the hub list when its walk row is long. Called
-// by every lane that is active at the call site.
-__device__ __forceinline__ void append(bool want, int c, int len, const StepArgs &a, const Graph &g, int *__restrict__ hubs_next, KtState *st, long long &len_sum)
+// An edge for the frontier being built (append_frontier). An edge is appended once per call: its slot is below m, which the kernel reads once and hands
+// down (a load of st->m per entry waits behind the atomics on its neighbours in the state block). Unlike rows, the edges whose walk row is long have no
+// bound below kHubCap (kHubCap of them is the limit of the call): a full hub list refuses the pattern.
+__device__ __forceinline__ void append(bool want, int c, int len, int m, const StepArgs &a, const Graph &g, int *__restrict__ hubs_next, KtState *st, long long &len_sum)
 {
-    const int idx = wave_append(want, &st->tail);
-    if ((unsigned)idx < (unsigned)st->m) g.queue[idx] = c;         // an edge is appended once per call: idx < m by construction
-    if (want && len > kHubCut) {
-        const int h = atomicAdd(&st->n_hub_next, 1);
-        if ((unsigned)h < (unsigned)a.hub_cap) hubs_next[h] = c;
-        else atomicOr(&st->invalid, 8);
-    }
-    if (want) len_sum += len;
-}
-
-// The end of a step kernel: the block's shares of the sums and of the minimum, then the ticket; the last block to arrive turns the page (turn_page).
-__device__ __forceinline__ void finish(KtState *st, long long len_sum, long long walked, int mn, int kind, const StepArgs a)
-{
-    __shared__ long long s_len[WG / 64], s_walk[WG / 64];
-    __shared__ int s_min[WG / 64];
-    len_sum = wave_sum(len_sum);
-    walked = wave_sum(walked);
-    mn = wave_min(mn);
-    if ((threadIdx.x & 63) == 0) { s_len[threadIdx.x >> 6] = len_sum; s_walk[threadIdx.x >> 6] = walked; s_min[threadIdx.x >> 6] = mn; }
-    if (!turn_page(&st->tickets, [&] {
-        long long ls = 0, ws = 0;
-        int m = INT_MAX;
-        for (int w = 0; w < WG / 64; ++w) { ls += s_len[w]; ws += s_walk[w]; m = s_min[w] < m ? s_min[w] : m; }
-        if (ls) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)ls);
-        if (ws) atomicAdd(&st->edges_walked, (unsigned long long)ws);
-        // the word only decreases while the kernel runs, so a value read earlier is too large and costs one atomic; read at agent scope, past the
-        // copy of the state line this CU has held since the kernel's first lines
-        if (m < __hip_atomic_load(&st->min_sup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&st->min_sup, m);
-    })) return;
-    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0), m = atomicAdd(&st->min_sup, 0);
-    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
-    const int got = tail - st->end;                                // what this kernel appended
-    st->head = st->end; st->end = tail;
-    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
-    st->edges_cur = e; st->edges_next = 0;
-    st->min_sup = INT_MAX;
-    st->tickets = 0;
-    int stop = e > a.grid_cap ? 4 : 0;
-    if (kind == KIND_SCAN) {
-        st->scans += 1;
-        if (got == 0) {                                            // edges are left (a scan does not run otherwise), all above j: m is a support
-            st->j = m;
-            if (m >= a.max_k - 2) stop = 2;
-        } else {
-            st->levels += 1;
-            st->top_j = st->j;
-        }
-    } else {
-        st->round += 1;
-        if (got == 0 && tail >= st->m) stop = 1;
-    }
-    st->stop = stop;
+    if (!append_frontier(want, c, len, m, a.hub_cap, g.queue, hubs_next, &st->tail, &st->n_hub_next, len_sum)) atomicOr(&st->invalid, 8);
 }
 
 __global__ __launch_bounds__(WG) void kt_open_rows_kernel(int n, const int *__restrict__ rowptr, KtState *st)
 {
-    int bad = 0;
-    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
-        const int rb = rowptr[i], re = rowptr[i + 1];
-        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
-    }
-    if (bad) atomicOr(&st->invalid, 1);
+    open_rows(n, rowptr, &st->invalid, 1, [](long long, int, int) {});
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         st->nnz = rowptr[n];
-        st->min_sup = INT_MAX;
+        st->min_left = INT_MAX;
     }
 }
 
-// One entry of row u in the opening pass: the id in range, larger than the one before it; up[k] = 1 for an entry right of the diagonal.
-__device__ __forceinline__ void open_entry(bool valid, int k, RowRef r, int n, const int *__restrict__ colids, int *__restrict__ up, int &bad)
-{
-    if (!valid) return;
-    const int v = colids[k];
-    if ((unsigned)v >= (unsigned)n) bad |= 2;
-    else if (k > r.start && colids[k - 1] >= v) bad |= 4;
-    up[k] = v > r.u;
-}
-
+// The column ids (open_ids / open_hubs, strictly ascending rows): up[k] = 1 for an entry right of the diagonal, in rank's array; the rows above kHubCut
+// entries stay in hubs1 for the building pass.
 __global__ __launch_bounds__(WG) void kt_open_ids_kernel(int n, int nnz, int hub_cap, const Graph g, KtState *st)
 {
     if (st->invalid || st->nnz != nnz) return;                     // rowptr is monotone from 0 to nnz beyond this line: [0, nnz) is the colids array
-    int bad = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) g.rank[nnz] = 0;      // the scan's total lands here
-    walk_tiles<RowRef>(n, [&](int i, int &start, int &len, RowRef &r) {
-        const int rb = g.rowptr[i], l = g.rowptr[i + 1] - rb;
-        r.u = i;
-        r.start = rb;
-        if (l > kHubCut) {
-            const int h = atomicAdd(&st->n_hub_rows, 1);
-            if ((unsigned)h < (unsigned)hub_cap) g.hubs1[h] = i;   // fewer than 2^31 / kHubCut such rows exist, and fewer than nnz
-            return;
-        }
-        start = rb;
-        len = l;
-    }, [&](bool valid, int k, RowRef r) { open_entry(valid, k, r, n, g.colids, g.rank, bad); });
-    if (bad) atomicOr(&st->invalid, bad);
+    open_ids<true>(n, hub_cap, g.rowptr, g.colids, g.hubs1, &st->n_hub_rows, &st->invalid, 2, [&](int k, int u, int v) { g.rank[k] = v > u; });
 }
 
 __global__ __launch_bounds__(WG) void kt_open_hubs_kernel(int n, int nnz, int hub_cap, const Graph g, KtState *st)
 {
     if (st->invalid || st->nnz != nnz) return;
-    int bad = 0;
-    walk_hubs<RowRef>(st->n_hub_rows < hub_cap ? st->n_hub_rows : hub_cap, [&](int h, int &start, int &len, RowRef &r) {
-        r.u = g.hubs1[h];
-        r.start = start = g.rowptr[r.u];
-        len = g.rowptr[r.u + 1] - start;
-    }, [&](bool valid, int k, RowRef r) { open_entry(valid, k, r, n, g.colids, g.rank, bad); });
-    if (bad) atomicOr(&st->invalid, bad);
+    open_hubs<true>(n, hub_cap, g.rowptr, g.colids, g.hubs1, &st->n_hub_rows, &st->invalid, 2, [&](int k, int u, int v) { g.rank[k] = v > u; });
 }
 
 // Behind the scan of up: m, and the two ends that need no step (no edge at all; max_k == 2, under which no level lies).
@@ -236,7 +144,7 @@ __global__ void kt_open_m_kernel(int nnz, int max_k, const int *__restrict__ ran
 }
 
 // One entry of row u in the building pass (see the head of the file).
-__device__ __forceinline__ void build_entry(bool valid, int k, RowRef r, int hub_cap, const Graph &g, KtState *st)
+__device__ __forceinline__ void build_entry(bool valid, int k, OpenRow r, int hub_cap, const Graph &g, KtState *st)
 {
     if (!valid) return;
     const int v = g.colids[k], u = r.u;
@@ -262,8 +170,8 @@ __device__ __forceinline__ void build_entry(bool valid, int k, RowRef r, int hub
 __global__ __launch_bounds__(WG) void kt_build_kernel(int n, int hub_cap, const Graph g, KtState *st)
 {
     if (st->invalid) return;
-    auto entry = [&](bool valid, int k, RowRef r) { build_entry(valid, k, r, hub_cap, g, st); };
-    walk_tiles<RowRef>(n, [&](int i, int &start, int &len, RowRef &r) {
+    auto entry = [&](bool valid, int k, OpenRow r) { build_entry(valid, k, r, hub_cap, g, st); };
+    walk_tiles<OpenRow>(n, [&](int i, int &start, int &len, OpenRow &r) {
         const int rb = g.rowptr[i], l = g.rowptr[i + 1] - rb;
         r.u = i;
         r.start = rb;
@@ -271,7 +179,7 @@ __global__ __launch_bounds__(WG) void kt_build_kernel(int n, int hub_cap, const 
         start = rb;
         len = l;
     }, entry);
-    walk_hubs<RowRef>(st->n_hub_rows < hub_cap ? st->n_hub_rows : hub_cap, [&](int h, int &start, int &len, RowRef &r) {
+    walk_hubs<OpenRow>(st->n_hub_rows < hub_cap ? st->n_hub_rows : hub_cap, [&](int h, int &start, int &len, OpenRow &r) {
         r.u = g.hubs1[h];
         r.start = start = g.rowptr[r.u];
         len = g.rowptr[r.u + 1] - start;
@@ -345,7 +253,7 @@ __global__ __launch_bounds__(WG) void kt_support_out_kernel(int nnz, const Graph
 __global__ __launch_bounds__(WG) void kt_scan_kernel(const Graph g, KtState *st, const StepArgs a)
 {
     if (st->invalid || st->stop != 0 || st->end != st->head) return;   // the same words for every block: they change only after the last ticket
-    const int jj = st->j, r = st->round, m = st->m;
+    const int jj = st->level, r = st->round, m = st->m;
     int *hubs_next = st->hub_cur ? g.hubs0 : g.hubs1;
     long long len_sum = 0;
     int mn = INT_MAX;
@@ -373,16 +281,16 @@ __global__ __launch_bounds__(WG) void kt_scan_kernel(const Graph g, KtState *st,
             } else if (x[q] == -1) {
                 mn = d[q] < mn ? d[q] : mn;
             }
-            append(want, (int)i, len, a, g, hubs_next, st, len_sum);
+            append(want, (int)i, len, m, a, g, hubs_next, st, len_sum);
         }
     }
-    finish(st, len_sum, 0, mn, KIND_SCAN, a);
+    finish_step(st, len_sum, 0, mn, KIND_SCAN, a.grid_cap, a.max_k - 2, [&] { return st->m; });   // level j is truss j + 2: the levels end at max_k − 2
 }
 
 __global__ __launch_bounds__(WG) void kt_peel_kernel(const Graph g, KtState *st, const StepArgs a)
 {
     if (st->invalid || st->end == st->head || !step_runs(st->stop, a.resume)) return;
-    const int jj = st->j, r = st->round, head = st->head;
+    const int jj = st->level, r = st->round, head = st->head, m = st->m;
     const int *hubs_cur = st->hub_cur ? g.hubs1 : g.hubs0;
     int *hubs_next = st->hub_cur ? g.hubs0 : g.hubs1;
     long long len_sum = 0, walked = 0;
@@ -398,7 +306,7 @@ __global__ __launch_bounds__(WG) void kt_peel_kernel(const Graph g, KtState *st,
                 len = walk_len(c, g);
             }
         }
-        append(want, c, len, a, g, hubs_next, st, len_sum);
+        append(want, c, len, m, a, g, hubs_next, st, len_sum);
     };
     // an entry whose own edge left in an earlier round closes no live triangle: two loads instead of the search (late in a peel most of a long row is gone)
     auto live = [&](int k) {
@@ -430,7 +338,7 @@ __global__ __launch_bounds__(WG) void kt_peel_kernel(const Graph g, KtState *st,
         lose(df, f);
         lose(dh, h);
     });
-    finish(st, len_sum, walked, INT_MAX, KIND_PEEL, a);
+    finish_step(st, len_sum, walked, INT_MAX, KIND_PEEL, a.grid_cap, a.max_k - 2, [&] { return st->m; });
 }
 
 // Once the peeling has ended (stop 1 or 2; a no-op before): the edges left by max_k get truss = max_k, the edges of the top truss are counted, and
@@ -439,7 +347,7 @@ __global__ __launch_bounds__(WG) void kt_finish_kernel(int nnz, int max_k, const
 {
     __shared__ int s_red[WG / 64];
     if (st->invalid || (st->stop != 1 && st->stop != 2)) return;
-    const int top = st->stop == 2 ? max_k : st->top_j + 2, m = st->m;
+    const int top = st->stop == 2 ? max_k : st->top_level + 2, m = st->m;
     int cnt = 0;
     for (long long c = (long long)blockIdx.x * WG + threadIdx.x; c < m; c += (long long)gridDim.x * WG) cnt += (g.rnd[c] == -1 ? max_k : g.tr[c]) == top;
     cnt = wave_sum(cnt);
@@ -457,17 +365,6 @@ __global__ __launch_bounds__(WG) void kt_finish_kernel(int nnz, int max_k, const
         if (round) round[p] = rc;
     }
 }
-
-int env_int(const char *name, int dflt, int lo, int hi)
-{
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    return std::max(lo, std::min(hi, atoi(e)));
-}
-
-struct Counts {
-    int launches = 0, resumes = 0, waits = 0;
-};
 
 // Everything behind the opening read on device arrays; returns behind a wait on `s` with *h the final state.
 int run(int n, int nnz, int max_k, const Graph &g, int *truss, int *round, int *support, KtState *st, int hub_cap, int cus, KtState *h, Counts *cnt, hipStream_t s)
@@ -492,39 +389,15 @@ int run(int n, int nnz, int max_k, const Graph &g, int *truss, int *round, int *
     cnt->launches += 9;                                            // the scan is three
 
     g4s::ReadScope reads(s);
-    bool know = false;                                             // *h is the device's state
-    int batch = kBatch, peels = 2;                                 // a batch is units of two scans (the level jump, the collect) and `peels` peels
-    int levels_seen = 0, rounds_seen = 0;
-    for (;;) {
-        const int grid = know ? sized.grid(kEntryWeight * (h->edges_cur + (h->end - h->head) + h->n_hub_cur)) : sized.max_grid;
-        a.grid_cap = sized.cap(grid) / kEntryWeight;
-        int pos = know && h->end != h->head ? 2 : 0;               // a frontier is waiting: begin with the peels
-        for (int b = 0; b < batch; ++b) {
-            if (pos < 2) {
-                hipLaunchKernelGGL(kt_scan_kernel, dim3(g_scan), dim3(WG), 0, s, g, st, a);
-            } else {
-                a.resume = b == 0 && know && h->stop == 4;
-                hipLaunchKernelGGL(kt_peel_kernel, dim3(grid), dim3(WG), 0, s, g, st, a);
-                a.resume = 0;
-            }
-            pos = pos + 1 == 2 + peels ? 0 : pos + 1;
-        }
-        hipLaunchKernelGGL(kt_finish_kernel, dim3(g_rows), dim3(WG), 0, s, nnz, max_k, g, truss, round, st);
-        G4S_HIP_TRY(hipGetLastError());
-        cnt->launches += batch + 1;
-        if (know && h->stop == 4) cnt->resumes += 1;
-        G4S_HIP_TRY(reads.fetch(*h, st));
-        cnt->waits += 1;
-        if (h->invalid || h->stop == 1 || h->stop == 2) break;
-        // the next batch follows what this one showed: rounds per level, rounded up, and one to spare
-        const int dl = std::max(h->levels - levels_seen, 1), dr = h->round - rounds_seen;
-        levels_seen = h->levels;
-        rounds_seen = h->round;
-        if (know) batch = sized.next_batch(batch);
-        peels = std::max(2, std::min(batch - 2, (dr + dl - 1) / dl + 1));
-        know = true;
-    }
-    return G4S_OK;
+    return run_level_peel(sized, kBatch, kEntryWeight, [&](long long grid_cap) {
+        a.grid_cap = grid_cap;
+        hipLaunchKernelGGL(kt_scan_kernel, dim3(g_scan), dim3(WG), 0, s, g, st, a);
+    }, [&](int grid, long long grid_cap, int resume) {
+        a.grid_cap = grid_cap;
+        a.resume = resume;
+        hipLaunchKernelGGL(kt_peel_kernel, dim3(grid), dim3(WG), 0, s, g, st, a);
+        a.resume = 0;
+    }, [&] { hipLaunchKernelGGL(kt_finish_kernel, dim3(g_rows), dim3(WG), 0, s, nnz, max_k, g, truss, round, st); }, reads, st, h, cnt);
 }
 
 } // namespace
@@ -616,18 +489,18 @@ G4S_API g4s_status g4s_ktruss(int32_t n, const int32_t *rowptr, const int32_t *c
         }
     }
     status = stage.finish(status);                                 // the caller's host arrays and the blocks: nothing in flight touches them
-    if (status == G4S_OK) { head.idle(); work.idle(); }
-    if (status == G4S_OK && h.invalid)
-        status = g4s::set_error(G4S_ERR_INVALID, "g4s_ktruss: %s", (h.invalid & 1) ? "rowptr must start at 0 and never decrease"
-                                                                   : (h.invalid & 2) ? "a column id is outside [0, n)"
-                                                                   : (h.invalid & 4) ? "a row is not strictly ascending"
-                                                                                     : "more than 524288 edges join two rows above 4096 entries");
+    head.idle();
+    work.idle();
+    if (status == G4S_OK && h.invalid) {
+        const char *text = csr_invalid_text(h.invalid);
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_ktruss: %s", text ? text : "more than 524288 edges join two rows above 4096 entries");
+    }
     if (status == G4S_OK && info) {
         info->triangles = (int64_t)(h.support_sum / 3);
         info->edges_walked = (int64_t)h.edges_walked;
         info->support_walked = (int64_t)h.support_walked;
         info->top_truss_edges = (int64_t)h.top_edges;
-        info->max_truss = h.stop == 2 ? max_k : h.m ? h.top_j + 2 : 0;
+        info->max_truss = h.stop == 2 ? max_k : h.m ? h.top_level + 2 : 0;
         info->levels = h.levels;
         info->rounds = h.round;
         info->scans = h.scans;

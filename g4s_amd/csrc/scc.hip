@@ -49,7 +49,6 @@ using namespace g4s;   // ScState, SC_*
 
 constexpr int kBatch = G4S_SCC_BATCH;        // launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
 constexpr int kReps = 3;                     // launches of a stepped phase the host guesses before it moves on
-constexpr int kHubCap = 1 << 19;             // rows above kHubCut entries: fewer than 2^31 / 4096
 constexpr size_t kStateBytes = 256;
 static_assert(sizeof(ScState) <= kStateBytes, "state block");
 
@@ -72,8 +71,6 @@ struct Tally {
     int cnt = 0, mn = INT_MAX;
     unsigned long long mx = 0;
 };
-
-__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 
 // A vertex that dies, or that a backward reach enters: behind the tail of the queue, and into the hub lists when its rows are long. Called by every
 // lane that is active at the call site. A vertex is queued once per call: idx < n by construction.
@@ -235,13 +232,7 @@ __device__ __forceinline__ bool my_turn(const ScState *st, const StepArgs &a) { 
 // ------------------------------------------------------------------------------------------------ open
 __global__ __launch_bounds__(WG) void sc_check_rows_kernel(int n, const int *__restrict__ rowptr, int slot, ScState *st)
 {
-    int bad = 0;
-    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
-        const int rb = rowptr[i], re = rowptr[i + 1];
-        bad |= rb < 0 || re < rb || (i == 0 && rb != 0);
-        if (i == n - 1) st->nnz[slot] = re;
-    }
-    if (bad) atomicOr(&st->invalid, slot ? 4 : 1);
+    open_rows(n, rowptr, &st->invalid, slot ? 4 : 1, [&](long long i, int, int re) { if (i == n - 1) st->nnz[slot] = re; });
 }
 
 __global__ __launch_bounds__(WG) void sc_open_kernel(int n, const Arrays g, ScState *st)
@@ -261,50 +252,20 @@ __global__ __launch_bounds__(WG) void sc_open_kernel(int n, const Arrays g, ScSt
     if (blockIdx.x == 0 && threadIdx.x == 0) st->mn_acc = INT_MAX;
 }
 
-struct RowRef {
-    int u;
-};
-
-// One entry of row u of a pattern in the opening pass: the id in range; the diagonal does not count in the row's counter.
-__device__ __forceinline__ void open_entry(bool valid, int k, int u, int n, const int *__restrict__ colids, int *counter, int &bad)
-{
-    if (!valid) return;
-    const int v = colids[k];
-    if ((unsigned)v >= (unsigned)n) bad = 1;
-    else if (v == u) atomicSub(counter + u, 1);
-}
-
+// The column ids of a pattern (open_ids / open_hubs; rows in any order): the diagonal does not count in the row's counter.
 // `which`: 0 the pattern of A (counter = dout), 1 of Aᵀ (counter = din)
 __global__ __launch_bounds__(WG) void sc_open_ids_kernel(int n, int hub_cap, int which, const int *__restrict__ rowptr, const int *__restrict__ colids, int *counter,
                                                          int *__restrict__ hubs, ScState *st)
 {
     if (st->invalid) return;                                       // [0, rowptr[n]) is the colids array
-    int bad = 0;
-    walk_tiles<int>(n, [&](int i, int &start, int &len, int &u) {
-        const int rb = rowptr[i], l = rowptr[i + 1] - rb;
-        u = i;
-        if (l > kHubCut) {
-            const int h = atomicAdd(&st->open_hubs[which], 1);
-            if ((unsigned)h < (unsigned)hub_cap) hubs[h] = i;
-            return;
-        }
-        start = rb;
-        len = l;
-    }, [&](bool valid, int k, int u) { open_entry(valid, k, u, n, colids, counter, bad); });
-    if (bad) atomicOr(&st->invalid, which ? 8 : 2);
+    open_ids<false>(n, hub_cap, rowptr, colids, hubs, &st->open_hubs[which], &st->invalid, which ? 8 : 2, [&](int, int u, int v) { if (v == u) atomicSub(counter + u, 1); });
 }
 
 __global__ __launch_bounds__(WG) void sc_open_hubs_kernel(int n, int hub_cap, int which, const int *__restrict__ rowptr, const int *__restrict__ colids, int *counter,
                                                           const int *__restrict__ hubs, ScState *st)
 {
     if (st->invalid) return;
-    int bad = 0;
-    walk_hubs<int>(st->open_hubs[which] < hub_cap ? st->open_hubs[which] : hub_cap, [&](int h, int &start, int &len, int &u) {
-        u = hubs[h];
-        start = rowptr[u];
-        len = rowptr[u + 1] - start;
-    }, [&](bool valid, int k, int u) { open_entry(valid, k, u, n, colids, counter, bad); });
-    if (bad) atomicOr(&st->invalid, which ? 8 : 2);
+    open_hubs<false>(n, hub_cap, rowptr, colids, hubs, &st->open_hubs[which], &st->invalid, which ? 8 : 2, [&](int, int u, int v) { if (v == u) atomicSub(counter + u, 1); });
 }
 
 // ------------------------------------------------------------------------------------------------ kernels over all vertices
@@ -598,17 +559,6 @@ __global__ __launch_bounds__(WG) void sc_largest_kernel(int n, const int *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int env_int(const char *name, int dflt, int lo, int hi)
-{
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    return std::max(lo, std::min(hi, atoi(e)));
-}
-
-struct Counts {
-    int launches = 0, resumes = 0, waits = 0;
-};
-
 bool stepped(int ph) { return ph == SC_PEEL || ph == SC_FWD || ph == SC_BWD || ph == SC_CPUSH || ph == SC_CBWD; }
 
 // The phase the host expects behind `ph`. Only a guess: the device decides.
@@ -714,8 +664,9 @@ int run(int n, const Arrays &g, ScState *st, int hub_cap, int cus, ScState *h, C
 
 const char *invalid_text(int bits)
 {
-    return (bits & 1) ? "rowptr must start at 0 and never decrease" : (bits & 4) ? "trowptr must start at 0 and never decrease"
-         : (bits & 16) ? "trowptr[n] differs from rowptr[n]" : (bits & 2) ? "a column id is outside [0, n)" : "a column id of the transpose is outside [0, n)";
+    // bits 1 and 2 are the opening pass's on A (csr_invalid_text), 4 and 8 the same two on Aᵀ
+    return (bits & 1) ? csr_invalid_text(1) : (bits & 4) ? "trowptr must start at 0 and never decrease"
+         : (bits & 16) ? "trowptr[n] differs from rowptr[n]" : (bits & 2) ? csr_invalid_text(2) : "a column id of the transpose is outside [0, n)";
 }
 
 } // namespace
