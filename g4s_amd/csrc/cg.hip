@@ -14,10 +14,12 @@
 #include "common.hpp"
 #include "readback.hpp"
 #include "cg_async.hpp"
+#include "block_sum.hpp"
 namespace g4s { int64_t dist_smallest_slab(g4s_spmv_dist_t h); }   // dist.hip
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <new>
 
 // opaque handle types of the two operators, defined in graph.hip / csr_handle.hpp
 extern "C" g4s_status g4s_elem_op_apply(g4s_elem_op_t op, const double *u_dev, double *Au_dev, void *stream);
@@ -33,16 +35,7 @@ inline int dot_blocks(int n) { const int b = (n + 255) / 256; return b < 1 ? 1 :
 
 struct CgState { double r1z1, r0z0, residual, residual0; int count, done; };   // residual0 = |F|, kept for the host's batch-size fit
 
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return s;
-}
+using g4s::block_sum;
 
 // Σ of the kDotBlocks partial sums, identical in every workgroup: thread t takes partial t, then the fixed-shape block reduction
 // (a serial loop per thread, the first version, is 256 dependent L2 round trips: ≈15 µs per dot product on an idle GPU)
@@ -177,18 +170,6 @@ __global__ __launch_bounds__(kThreads) void elem_inverse_diagonal_finish_kernel(
     if (i < n) BI[i] = BI[i] != 0.0 ? 1.0 / BI[i] : 0.0;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        hipError_t e = g4s::device_malloc(&p, n);
-        if (e != hipSuccess) return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "hipMalloc(%zu): %s", n, hipGetErrorString(e));
-        return G4S_OK;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 } // namespace
 
 // defined in graph.hip (needs the operator's node→term map)
@@ -209,11 +190,12 @@ G4S_API g4s_status g4s_elem_op_inverse_diagonal(g4s_elem_op_t op, double *BI_dev
 }
 
 namespace g4s {
-// One conjugate-gradient solve as an object, so that a caller can enqueue its first batch of iterations, go on enqueuing work that uses the
-// result SPECULATIVELY, and read the solve's state together with its own scalars in one host synchronisation (stokes.hip: the Uzawa loop was two
+// The conjugate-gradient solves of one caller as an object, so that the caller can enqueue a solve's first batch of iterations, go on enqueuing work that
+// uses the result SPECULATIVELY, and read the solve's state together with its own scalars in one host synchronisation (stokes.hip: the Uzawa loop was two
 // synchronisations per outer iteration — this one and its nine scalars — with the host's launches and the device's execution taking turns).
-//   start(batch)  arena, boundary mask, r/z/d0 initialised, `batch` iterations and the loop test enqueued; no synchronisation
-//   read_state_async(&h) copies the state to the host (caller synchronises); complete(h) runs further batches (synchronising) until done;
+//   start(F, d0, batch)  r/z/d0 initialised, `batch` iterations and the loop test enqueued; no synchronisation. The first start of the object takes the arena and
+//                  builds the boundary mask; later ones reuse both (the kernels reset what they use).
+//   read() notes the copy of the state into h (the caller synchronises); complete() runs further batches (synchronising) until done;
 //   finish() strips the boundary rows of d0 (conj_grad :409) — harmless to enqueue speculatively, enqueued again after a continued solve.
 // Iterations past the one that meets the test are no-ops on the device, so a batch that overshoots costs launches, never results.
 using MatVec = std::function<int(const double *, double *, const int *, hipStream_t)>;   // matvec(p, Ap, done_flag, stream); free to return at once when *done_flag != 0
@@ -228,16 +210,22 @@ int cg_build_mask(int32_t neq, const int32_t *zero_resid, int32_t n_zero, unsign
 }
 
 struct CgRun {
-    MatVec matvec;
-    int neq = 0, n_zero = 0, steps = 0, enqueued = 0;
-    const double *BI = nullptr;
-    const int32_t *zero_resid = nullptr;
-    double *d0 = nullptr, acc = 0.0;
-    hipStream_t s = nullptr;
+    const MatVec matvec;
+    const int neq, n_zero, steps;
+    const double *const BI;
+    const int32_t *const zero_resid;
+    const double acc;
+    const hipStream_t s;
+    int enqueued = 0;
+    double *d0 = nullptr;
     void *arena = nullptr;
     double *r1 = nullptr, *r2 = nullptr, *z = nullptr, *p1 = nullptr, *p2 = nullptr, *Ap = nullptr, *part_rz = nullptr, *part_pAp = nullptr, *part_rr = nullptr;
     CgState *st = nullptr;
     unsigned char *bc_mask = nullptr;
+    CgState h{};                 // the state after the batches enqueued so far, once a read has been waited for
+    g4s::ReadScope reads;        // owns the read into h: an object freed between read and settle waits for the copy and takes the note with it
+    CgRun(const MatVec &mv, int32_t neq, const double *BI, const int32_t *zero_resid, int32_t n_zero, double acc, int32_t steps, hipStream_t s)
+        : matvec(mv), neq(neq), n_zero(n_zero), steps(steps), BI(BI), zero_resid(zero_resid), acc(acc), s(s), reads(s) {}
     ~CgRun() { g4s::scratch_free(arena, s); }
 
     int enqueue(int todo)
@@ -256,38 +244,37 @@ struct CgRun {
         return G4S_OK;
     }
 
-    int start(const MatVec &mv, int32_t neq_, const double *BI_, const int32_t *zero_resid_, int32_t n_zero_, const double *F, double *d0_, double acc_, int32_t steps_,
-              int batch, hipStream_t stream, const unsigned char *shared_mask = nullptr)
+    int start(const double *F, double *d0_, int batch)
     {
-        G4S_REQUIRE(neq_ > 0 && BI_ && F && d0_, "bad argument");
-        G4S_REQUIRE(n_zero_ >= 0 && (n_zero_ == 0 || zero_resid_), "zero_resid is NULL");
-        matvec = mv; neq = neq_; BI = BI_; zero_resid = zero_resid_; n_zero = n_zero_; d0 = d0_; acc = acc_; steps = steps_; s = stream;
-        const size_t nb = sizeof(double) * (size_t)neq;
-        // one stream-ordered arena for the six work vectors, the partial sums, the state and the boundary mask: after the first solve
-        // the pool hands the same pages back without a driver call (nine hipMalloc/hipFree pairs cost more than a short solve)
-        const size_t nbp = (nb + 255) / 256 * 256;
-        const size_t arena_bytes = 6 * nbp + sizeof(double) * 3 * kDotBlocks + 256 + (n_zero ? ((size_t)neq + 255) / 256 * 256 : 0);
-        G4S_TRY(g4s::scratch_alloc(&arena, arena_bytes, s));
-        char *base = static_cast<char *>(arena);
-        r1 = reinterpret_cast<double *>(base); r2 = reinterpret_cast<double *>(base + nbp); z = reinterpret_cast<double *>(base + 2 * nbp);
-        p1 = reinterpret_cast<double *>(base + 3 * nbp); p2 = reinterpret_cast<double *>(base + 4 * nbp); Ap = reinterpret_cast<double *>(base + 5 * nbp);
-        part_rz = reinterpret_cast<double *>(base + 6 * nbp); part_pAp = part_rz + kDotBlocks; part_rr = part_pAp + kDotBlocks;
-        st = reinterpret_cast<CgState *>(part_rr + kDotBlocks);
-        static_assert(sizeof(CgState) <= 256, "state slot");
+        G4S_REQUIRE(neq > 0 && BI && F && d0_, "bad argument");
+        G4S_REQUIRE(n_zero >= 0 && (n_zero == 0 || zero_resid), "zero_resid is NULL");
+        d0 = d0_; enqueued = 0; h = CgState{};
+        if (!arena) {
+            // one stream-ordered arena for the six work vectors, the partial sums, the state and the boundary mask (nine hipMalloc/hipFree pairs cost more
+            // than a short solve)
+            const size_t nbp = (sizeof(double) * (size_t)neq + 255) / 256 * 256;
+            const size_t arena_bytes = 6 * nbp + sizeof(double) * 3 * kDotBlocks + 256 + (n_zero ? ((size_t)neq + 255) / 256 * 256 : 0);
+            G4S_TRY(g4s::scratch_alloc(&arena, arena_bytes, s));
+            char *base = static_cast<char *>(arena);
+            r1 = reinterpret_cast<double *>(base); r2 = reinterpret_cast<double *>(base + nbp); z = reinterpret_cast<double *>(base + 2 * nbp);
+            p1 = reinterpret_cast<double *>(base + 3 * nbp); p2 = reinterpret_cast<double *>(base + 4 * nbp); Ap = reinterpret_cast<double *>(base + 5 * nbp);
+            part_rz = reinterpret_cast<double *>(base + 6 * nbp); part_pAp = part_rz + kDotBlocks; part_rr = part_pAp + kDotBlocks;
+            st = reinterpret_cast<CgState *>(part_rr + kDotBlocks);
+            static_assert(sizeof(CgState) <= 256, "state slot");
+        }
         // no memset: cg_init_kernel resets the state, and every kernel that writes partial sums zeroes the slots of workgroups that do not exist
-        if (n_zero && shared_mask) bc_mask = const_cast<unsigned char *>(shared_mask);   // built once by the caller for all its solves (cg_build_mask)
-        else if (n_zero) {
+        if (n_zero && !bc_mask) {
+            G4S_TRY(cg_build_mask(neq, zero_resid, n_zero, reinterpret_cast<unsigned char *>(st) + 256, s));
             bc_mask = reinterpret_cast<unsigned char *>(st) + 256;
-            G4S_TRY(cg_build_mask(neq, zero_resid, n_zero, bc_mask, s));
         }
         hipLaunchKernelGGL(cg_init_kernel, dim3(dot_blocks(neq)), dim3(kThreads), 0, s, neq, F, BI, r1, d0, z, part_rr, part_rz, st);
         return enqueue(std::max(1, std::min(batch, steps + 1)));
     }
 
-    int read_state_async(g4s::ReadScope &reads, CgState &h) { G4S_HIP_TRY(reads.note(h, st)); return G4S_OK; }   // (a scope on this run's stream)
+    int read() { G4S_HIP_TRY(reads.note(h, st)); return G4S_OK; }
 
-    // h: the state after the batches enqueued so far (read by the caller after a synchronisation). Runs on until the loop test is met.
-    int complete(g4s::ReadScope &reads, CgState &h)
+    // After a read has been waited for: runs on until the loop test is met.
+    int complete()
     {
         int batch = std::min(32, std::max(2, enqueued * 2));
         while (!h.done) {
@@ -298,7 +285,7 @@ struct CgRun {
                 if (left > 0.0 && left < 1e6) batch = std::max(2, std::min(32, (int)std::ceil(left) + 1));
             }
             G4S_TRY(enqueue(std::max(1, std::min(batch, steps - enqueued + 1))));
-            G4S_TRY(read_state_async(reads, h));
+            G4S_TRY(read());
             G4S_HIP_TRY(reads.wait());
             batch = std::min(32, batch * 2);
         }
@@ -333,19 +320,17 @@ int conj_grad_impl(const MatVec &matvec, int32_t neq, const double *BI, const in
                    const double *F, double *d0, double acc, int32_t *cycles, double *residual_out, void *stream)
 {
     G4S_REQUIRE(cycles, "cycles is NULL");
-    hipStream_t s = g4s::as_stream(stream);
-    CgRun run;
-    G4S_TRY(run.start(matvec, neq, BI, zero_resid, n_zero, F, d0, acc, *cycles, cg_first_batch(), s));
-    g4s::ReadScope reads(s);
-    CgState h{};
-    G4S_TRY(run.read_state_async(reads, h));
-    G4S_HIP_TRY(reads.wait());
-    G4S_TRY(run.complete(reads, h));
+    CgRun run(matvec, neq, BI, zero_resid, n_zero, acc, *cycles, g4s::as_stream(stream));
+    G4S_TRY(run.start(F, d0, cg_first_batch()));
+    G4S_TRY(run.read());
+    G4S_HIP_TRY(run.reads.wait());
+    G4S_TRY(run.complete());
+    const CgState &h = run.h;
     if (getenv("G4S_DEBUG")) fprintf(stderr, "g4s conj_grad: %d iterations, %d enqueued, residual %.3e (acc %.3e)\n", h.count, run.enqueued, h.residual, acc);
     cg_last_iterations() = h.count;
     *cycles = h.count;
     G4S_TRY(run.finish());
-    G4S_HIP_TRY(reads.wait());
+    G4S_HIP_TRY(run.reads.wait());
     if (residual_out) *residual_out = h.residual;
     return G4S_OK;
 }
@@ -355,46 +340,6 @@ namespace {
 using g4s::MatVec;
 using g4s::conj_grad_impl;
 } // namespace
-namespace g4s {
-struct CgAsync {
-    explicit CgAsync(hipStream_t s) : reads(s) {}
-    CgRun run;
-    CgState h{};
-    g4s::ReadScope reads;        // owns the read into h: an object freed between read and settle waits for the copy and takes the note with it
-};
-
-int cg_async_start(CgAsync **out, g4s_elem_op_t op, g4s_csr_t A, int32_t neq, const double *BI, const int32_t *zero_resid, int32_t n_zero,
-                   const double *F, double *d0, double acc, int32_t steps, hipStream_t s, const unsigned char *bc_mask)
-{
-    *out = nullptr;
-    G4S_REQUIRE((op != nullptr) != (A != nullptr), "exactly one of op / A must be given");
-    auto c = new (std::nothrow) CgAsync(s);
-    if (!c) return set_error(G4S_ERR_NOMEM, "host allocation failed");
-    int st = c->run.start(cg_matvec_for(op, A), neq, BI, zero_resid, n_zero, F, d0, acc, steps, cg_first_batch(), s, bc_mask);
-    if (st == G4S_OK) st = c->run.finish();
-    if (st != G4S_OK) { delete c; return st; }
-    *out = c;
-    return G4S_OK;
-}
-
-int cg_async_read(CgAsync *c) { return c->run.read_state_async(c->reads, c->h); }
-
-int cg_async_settle(CgAsync *c, bool *speculation_held, int32_t *cycles, double *residual)
-{
-    *speculation_held = c->h.done != 0;                            // (the caller has synchronised with reads_sync: that is the contract of settle)
-    if (!c->h.done) {
-        G4S_TRY(c->run.complete(c->reads, c->h));
-        G4S_TRY(c->run.finish());
-    }
-    cg_last_iterations() = c->h.count;
-    if (cycles) *cycles = c->h.count;
-    if (residual) *residual = c->h.residual;
-    return G4S_OK;
-}
-
-void cg_async_free(CgAsync *c) { delete c; }
-} // namespace g4s
-
 
 G4S_API g4s_status g4s_conj_grad(g4s_elem_op_t op, g4s_csr_t A, int32_t neq, const double *BI, const int32_t *zero_resid, int32_t n_zero,
                                  const double *F, double *d0, double acc, int32_t *cycles, double *residual_out, void *stream)
@@ -427,7 +372,7 @@ struct g4s_cg_ws_s {
     CgState *st = nullptr;
     unsigned char *mask = nullptr;
     bool use_mask = false;
-    // the boundary mask of the last g4s_cg_begin and what it was built from; hold_mask (g4s::cg_ws_hold_mask): the owner promises that list keeps its contents
+    // the boundary mask of the last g4s_cg_begin and what it was built from; hold_mask (set by DistCgAsync): the owner promises that list keeps its contents
     // for the workspace's life, so a begin with the same list does not rebuild it (a memset and a launch per solve of an Uzawa iteration)
     const int32_t *mask_src = nullptr;
     int mask_n = -1;
@@ -471,8 +416,7 @@ G4S_API g4s_status g4s_cg_begin(g4s_cg_ws_t ws, const double *F_dev, const doubl
     hipStream_t s = g4s::as_stream(stream);
     ws->use_mask = n_zero > 0;
     if (n_zero && !(ws->hold_mask && ws->mask_src == zero_resid_dev && ws->mask_n == n_zero)) {
-        G4S_HIP_TRY(hipMemsetAsync(ws->mask, 0, (size_t)ws->n, s));
-        hipLaunchKernelGGL(cg_mask_kernel, dim3((n_zero + kThreads - 1) / kThreads), dim3(kThreads), 0, s, n_zero, zero_resid_dev, ws->mask);
+        G4S_TRY(g4s::cg_build_mask(ws->n, zero_resid_dev, n_zero, ws->mask, s));
         ws->mask_src = zero_resid_dev; ws->mask_n = n_zero;
     }
     hipLaunchKernelGGL(cg_init_kernel, dim3(dot_blocks(ws->n)), dim3(kThreads), 0, s, ws->n, F_dev, BI_dev, ws->r1, d0_dev, ws->z, ws->part + 2 * kDotBlocks, ws->part, ws->st);
@@ -571,22 +515,26 @@ int dist_product(g4s_spmv_dist_t A, const g4s_transport *tr, const double *x, do
 } // namespace g4s
 
 namespace g4s {
-// The partitioned solve as an object (the counterpart of CgRun above): start() enqueues the set-up, the first batch of iterations and the loop test
-// without a host wait; the caller may go on enqueuing work that uses d0 speculatively and read the state together with its own scalars
-// (stokes.hip: g4s_stokes_uzawa_cg_dist — one host wait per outer iteration). Every rank reads the same all-reduced sums, so every rank sees
-// the same (count, done, residual) and takes the same turn.
+// The partitioned solves of one caller as an object (the counterpart of CgRun above): start() enqueues the set-up, the first batch of iterations and the loop
+// test without a host wait; the caller may go on enqueuing work that uses d0 speculatively and read the state together with its own scalars
+// (stokes.hip: one host wait per outer iteration). Every rank reads the same all-reduced sums, so every rank sees the same (count, done, residual) and
+// takes the same turn. The first start creates the workspace, which holds its boundary mask from then on.
 struct DistCgAsync {
-    g4s_spmv_dist_t A = nullptr;
-    const g4s_transport *tr = nullptr;
-    g4s_cg_ws_t ws = nullptr;
-    const double *BI = nullptr;
-    const int32_t *zero_resid = nullptr;
-    double *d0 = nullptr, *part = nullptr, acc = 0.0;
-    int n_zero = 0, steps = 0, enqueued = 0;
-    void *stream = nullptr;
+    const g4s_spmv_dist_t A;
+    const g4s_transport *const tr;
+    const int n_local, n_zero, steps;
+    const double *const BI;
+    const int32_t *const zero_resid;
+    const double acc;
+    void *const stream;
+    int enqueued = 0;
+    double *d0 = nullptr, *part = nullptr;
+    struct Ws { g4s_cg_ws_t w = nullptr; ~Ws() { (void)g4s_cg_ws_destroy(w); } } ws;        // (ends after `reads`, which may still wait for a copy out of it)
     CgState h{};
-    g4s::ReadScope reads;                                                                   // see CgAsync
-    explicit DistCgAsync(void *stream) : stream(stream), reads(g4s::as_stream(stream)) {}
+    g4s::ReadScope reads;                                                                   // see CgRun
+    DistCgAsync(g4s_spmv_dist_t A, const g4s_transport *tr, int32_t n_local, const double *BI, const int32_t *zero_resid, int32_t n_zero, double acc, int32_t steps,
+                void *stream)
+        : A(A), tr(tr), n_local(n_local), n_zero(n_zero), steps(steps), BI(BI), zero_resid(zero_resid), acc(acc), stream(stream), reads(g4s::as_stream(stream)) {}
 
     // Iterations past the one that meets the test are no-ops in the CG kernels; their product and all-reduces still run, on data nothing
     // reads again (the partial sums are rewritten by the next solve's first kernel).
@@ -594,26 +542,31 @@ struct DistCgAsync {
     {
         double *p = nullptr, *Ap = nullptr;
         for (int it = 0; it < todo; ++it) {
-            G4S_TRY(g4s_cg_direction(ws, steps, acc, stream));
-            G4S_TRY(g4s_cg_buffers(ws, &p, &Ap, nullptr));
+            G4S_TRY(g4s_cg_direction(ws.w, steps, acc, stream));
+            G4S_TRY(g4s_cg_buffers(ws.w, &p, &Ap, nullptr));
             G4S_TRY(g4s::dist_product(A, tr, p, Ap, stream));
-            G4S_TRY(g4s_cg_reduce_pAp(ws, stream));
+            G4S_TRY(g4s_cg_reduce_pAp(ws.w, stream));
             G4S_TRY(tr->allreduce_sum_f64(tr->ctx, part + kDotBlocks, kDotBlocks, stream));
-            G4S_TRY(g4s_cg_update(ws, BI, d0, stream));
+            G4S_TRY(g4s_cg_update(ws.w, BI, d0, stream));
             G4S_TRY(tr->allreduce_sum_f64(tr->ctx, part, 3 * kDotBlocks, stream));          // [0, 256) r·z and [512, 768) r·r; the middle third is rewritten before its next use
         }
         enqueued += todo;
-        return g4s_cg_direction(ws, steps, acc, stream);                                    // the loop test behind the batch (a no-op once done)
+        return g4s_cg_direction(ws.w, steps, acc, stream);                                  // the loop test behind the batch (a no-op once done)
     }
-    int start(int batch, const double *F)
+    int start(const double *F, double *d0_, int batch)
     {
-        G4S_TRY(g4s_cg_begin(ws, F, BI, d0, zero_resid, n_zero, stream));
-        G4S_TRY(g4s_cg_buffers(ws, nullptr, nullptr, &part));
+        if (!ws.w) {
+            G4S_TRY(g4s_cg_ws_create(&ws.w, n_local));
+            ws.w->hold_mask = true;                                                         // zero_resid is the same list for every solve of this object
+        }
+        d0 = d0_; enqueued = 0; h = CgState{};
+        G4S_TRY(g4s_cg_begin(ws.w, F, BI, d0, zero_resid, n_zero, stream));
+        G4S_TRY(g4s_cg_buffers(ws.w, nullptr, nullptr, &part));
         G4S_TRY(tr->allreduce_sum_f64(tr->ctx, part, 3 * kDotBlocks, stream));              // r·z and r·r of the start vector
         return enqueue(std::max(1, std::min(batch, steps + 1)));
     }
-    int read() { G4S_HIP_TRY(reads.note(h, ws->st)); return G4S_OK; }
-    int complete()                                                                          // h: read after a synchronisation
+    int read() { G4S_HIP_TRY(reads.note(h, ws.w->st)); return G4S_OK; }
+    int complete()                                                                          // after a read has been waited for
     {
         int batch = std::min(32, std::max(2, enqueued * 2));
         while (!h.done) {
@@ -632,34 +585,36 @@ struct DistCgAsync {
     }
 };
 
-int dist_cg_async_start(DistCgAsync **out, g4s_cg_ws_t ws, g4s_spmv_dist_t A, const g4s_transport *tr, const double *BI, const int32_t *zero_resid, int32_t n_zero,
-                        const double *F, double *d0, double acc, int32_t steps, void *stream)
+// ---- the one face of the two solves (cg_async.hpp)
+template <typename Run> CgSolve<Run>::~CgSolve() { delete run_; }
+template <typename Run> int CgSolve<Run>::start(const double *rhs, double *d0)
 {
-    *out = nullptr;
-    auto c = new (std::nothrow) DistCgAsync(stream);
-    if (!c) return set_error(G4S_ERR_NOMEM, "host allocation failed");
-    c->A = A; c->tr = tr; c->ws = ws; c->BI = BI; c->zero_resid = zero_resid; c->n_zero = n_zero; c->d0 = d0; c->acc = acc; c->steps = steps;
-    int st = c->start(cg_first_batch(), F);
-    if (st == G4S_OK) st = c->finish();
-    if (st != G4S_OK) { delete c; return st; }
-    *out = c;
-    return G4S_OK;
+    if (!run_) return set_error(G4S_ERR_NOMEM, "host allocation failed");
+    G4S_TRY(run_->start(rhs, d0, cg_first_batch()));
+    return run_->finish();
 }
-void cg_ws_hold_mask(g4s_cg_ws_t ws, bool hold) { if (ws) { ws->hold_mask = hold; if (!hold) { ws->mask_src = nullptr; ws->mask_n = -1; } } }
-int dist_cg_async_read(DistCgAsync *c) { return c->read(); }
-int dist_cg_async_settle(DistCgAsync *c, bool *speculation_held, int32_t *cycles, double *residual)
+template <typename Run> int CgSolve<Run>::read() { return run_->read(); }
+template <typename Run> int CgSolve<Run>::settle(bool *speculation_held, int32_t *cycles, double *residual)
 {
-    *speculation_held = c->h.done != 0;
-    if (!c->h.done) {
-        G4S_TRY(c->complete());
-        G4S_TRY(c->finish());
+    const CgState &h = run_->h;                                    // (the caller has synchronised with reads_sync: that is the contract of settle)
+    *speculation_held = h.done != 0;
+    if (!h.done) {
+        G4S_TRY(run_->complete());
+        G4S_TRY(run_->finish());
     }
-    cg_last_iterations() = c->h.count;
-    if (cycles) *cycles = c->h.count;
-    if (residual) *residual = c->h.residual;
+    cg_last_iterations() = h.count;
+    if (cycles) *cycles = h.count;
+    if (residual) *residual = h.residual;
     return G4S_OK;
 }
-void dist_cg_async_free(DistCgAsync *c) { delete c; }
+template class CgSolve<CgRun>;
+template class CgSolve<DistCgAsync>;
+
+LocalCgSolve::LocalCgSolve(g4s_elem_op_t op, g4s_csr_t A, int32_t neq, const double *BI, const int32_t *zero_resid, int32_t n_zero, double acc, int32_t steps, void *stream)
+    : CgSolve(new (std::nothrow) CgRun(cg_matvec_for(op, A), neq, BI, zero_resid, n_zero, acc, steps, as_stream(stream))) {}
+DistCgSolve::DistCgSolve(g4s_spmv_dist_t A, const g4s_transport *tr, int32_t n_local, const double *BI, const int32_t *zero_resid, int32_t n_zero, double acc,
+                         int32_t steps, void *stream)
+    : CgSolve(new (std::nothrow) DistCgAsync(A, tr, n_local, BI, zero_resid, n_zero, acc, steps, stream)) {}
 } // namespace g4s
 
 G4S_API g4s_status g4s_conj_grad_dist_tr(g4s_spmv_dist_t A, const g4s_transport *tr, int32_t n_local, const double *BI_dev, const int32_t *zero_resid_dev,
@@ -672,24 +627,16 @@ G4S_API g4s_status g4s_conj_grad_dist_tr(g4s_spmv_dist_t A, const g4s_transport 
     G4S_REQUIRE(g4s::dist_smallest_slab(A) > 0, "every rank of the partition must own at least one row");
     G4S_REQUIRE(BI_dev && F_dev && d0_dev, "NULL argument");
     G4S_REQUIRE(n_local > 0 && n_zero >= 0 && (n_zero == 0 || zero_resid_dev), "bad size");
-    g4s_cg_ws_t ws = nullptr;
-    G4S_TRY(g4s_cg_ws_create(&ws, n_local));
     // Iterations are enqueued in batches with ONE read of (count, done, residual) behind each batch — the first as long as the previous solve of
     // this thread plus one (g4s::cg_first_batch, as the single-GPU solve): with an RCCL transport nothing inside a batch waits for the host.
-    auto run = [&]() -> int {
-        g4s::DistCgAsync *c = nullptr;
-        G4S_TRY(g4s::dist_cg_async_start(&c, ws, A, tr, BI_dev, zero_resid_dev, n_zero, F_dev, d0_dev, acc, steps, stream));
-        struct Free { g4s::DistCgAsync *c; ~Free() { g4s::dist_cg_async_free(c); } } guard{c};
-        G4S_TRY(g4s::dist_cg_async_read(c));
-        G4S_HIP_TRY(g4s::reads_sync(g4s::as_stream(stream)));
-        bool held = true;
-        G4S_TRY(g4s::dist_cg_async_settle(c, &held, cycles, residual));
-        G4S_HIP_TRY(g4s::reads_sync(g4s::as_stream(stream)));
-        return G4S_OK;
-    };
-    const int st = run();
-    (void)g4s_cg_ws_destroy(ws);
-    return st;
+    g4s::DistCgSolve cg(A, tr, n_local, BI_dev, zero_resid_dev, n_zero, acc, steps, stream);
+    G4S_TRY(cg.start(F_dev, d0_dev));
+    G4S_TRY(cg.read());
+    G4S_HIP_TRY(g4s::reads_sync(g4s::as_stream(stream)));
+    bool held = true;
+    G4S_TRY(cg.settle(&held, cycles, residual));
+    G4S_HIP_TRY(g4s::reads_sync(g4s::as_stream(stream)));
+    return G4S_OK;
 }
 
 G4S_API g4s_status g4s_conj_grad_dist(g4s_spmv_dist_t A, void *comm, int32_t n_local, const double *BI_dev, const int32_t *zero_resid_dev, int32_t n_zero,

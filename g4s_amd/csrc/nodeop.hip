@@ -16,18 +16,6 @@ namespace {
 constexpr int kSlots = 27;        // neighbour slots per node in the expanded form
 constexpr int kLanes = 32;        // lanes per node (27 active)
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        hipError_t e = g4s::device_malloc(&p, n);
-        if (e != hipSuccess) return g4s::set_error(e == hipErrorOutOfMemory ? G4S_ERR_NOMEM : G4S_ERR_HIP, "hipMalloc(%zu): %s", n, hipGetErrorString(e));
-        return G4S_OK;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // Au[eq(node, d)] = Σ_s Σ_c block[node][s][d][c] · u[eq(nbr[node][s], c)]
 __global__ __launch_bounds__(256) void node_blocks_matvec_kernel(int nno, const int *__restrict__ nbr, const double *__restrict__ blocks,
                                                                   const int *__restrict__ node_eq, const double *__restrict__ u,
@@ -71,7 +59,7 @@ __global__ __launch_bounds__(256) void node_zero_rows_kernel(int n_zero, const i
 
 struct g4s_node_op_s {
     int nno = 0, neq = 0;
-    DevBuf nbr, blocks, node_eq;
+    g4s::DevBuf nbr, blocks, node_eq;
 };
 
 G4S_API g4s_status g4s_node_op_create(g4s_node_op_t *out, int32_t nno, int32_t neq, int32_t max_eqn, const int32_t *node_map,

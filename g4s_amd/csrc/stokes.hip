@@ -2,7 +2,8 @@
 //
 // Follows solve_Ahat_p_fhat_CG, citcoms/lib/Stokes_flow_Incomp.c:188-452, in its update order, for the incompressible case
 // (inv_gruneisen == 0, so initial_vel_residual :839-881 runs) with solve_del2_u's conjugate-gradient branch
-// (General_matrix_functions.c:89-94) as the velocity solve — that is g4s_conj_grad (cg.hip) on the element-by-element operator.
+// (General_matrix_functions.c:89-94) as the velocity solve — the loop of g4s_conj_grad (cg.hip), held as a CgSolve (cg_async.hpp) on the element-by-element
+// operator, the assembled matrix or a row-partitioned one. The iteration is written once (uzawa_loop) for g4s_stokes_uzawa_cg and g4s_stokes_uzawa_cg_dist.
 // Operators: assemble_div_u / assemble_grad_p (Element_calculations.c:701-779) on the per-element gradient vectors
 // g[e][p] = elt_del[e].g[p][0]; norms: global_v_norm2 / global_p_norm2 / global_div_norm2 / global_pdot
 // (Global_operations.c:565-656), one process. Every vector stays in HBM; the host owns the outer loop's scalar logic
@@ -11,80 +12,67 @@
 #include "common.hpp"
 #include "readback.hpp"
 #include "cg_async.hpp"
+#include "block_sum.hpp"
 #include <algorithm>
 #include <cmath>
-#include <vector>
+#include <type_traits>
 
 namespace {
 
 constexpr int kBlocks = 256, kThreads = 256;
 
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return s;
-}
+using g4s::block_sum;
 
-struct Sum3 { double a, b, c; };
-struct Sum6 { double v[6]; };
+// A reduction of K sums at once. f(i) does the element-wise work of index i and returns its K terms; the sums have a fixed two-level shape (grid-stride
+// partials per workgroup → one workgroup adds the kBlocks partials of each sum): reproducible, on one device and on every rank alike. K = 6 carries
+// everything an outer iteration can sum once its new V, P and r are known in one pass (and, partitioned, in ONE all-reduce message: Global_operations.c:534-656
+// reduces each norm on its own).
+template <int K> struct Sums { double v[K]; };
 
-// f(i) does the element-wise work of index i and returns up to three terms to be summed over i. Two-level sums with a fixed
-// shape (grid-stride partials per workgroup → finish_sums_kernel): reproducible.
-template <typename F>
+template <int K, typename F>
 __global__ __launch_bounds__(kThreads) void map_sum_kernel(int n, F f, double *__restrict__ part)
 {
     __shared__ double sh[4];
-    Sum3 acc{0.0, 0.0, 0.0};
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += kBlocks * kThreads) {
-        const Sum3 v = f(i);
-        acc.a += v.a; acc.b += v.b; acc.c += v.c;
-    }
-    const double a = block_sum(acc.a, sh), b = block_sum(acc.b, sh), c = block_sum(acc.c, sh);
-    if (threadIdx.x == 0) { part[blockIdx.x] = a; part[kBlocks + blockIdx.x] = b; part[2 * kBlocks + blockIdx.x] = c; }
-}
-
-// One workgroup: the three sums in a fixed shape, then ep(s0, s1, s2) on one thread — the scalar algebra of the outer loop (δ, α,
-// the norms) stays on the device, in the slots of a small scalar array the following kernels read.
-template <typename E>
-__global__ __launch_bounds__(kThreads) void finish_sums_kernel(const double *__restrict__ part, E ep)
-{
-    __shared__ double sh[4];
-    static_assert(kBlocks == kThreads, "one partial per thread");
-    double r[3];
-    for (int k = 0; k < 3; ++k) r[k] = block_sum(part[k * kBlocks + threadIdx.x], sh);
-    if (threadIdx.x == 0) ep(r[0], r[1], r[2]);
-}
-
-// the same with six terms (the five norms at the end of an outer iteration in one pass instead of two)
-template <typename F>
-__global__ __launch_bounds__(kThreads) void map_sum6_kernel(int n, F f, double *__restrict__ part)
-{
-    __shared__ double sh[4];
-    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += kBlocks * kThreads) {
-        const Sum6 v = f(i);
+    double acc[K];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) acc[k] += v.v[k];
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += kBlocks * kThreads) {
+        const Sums<K> v = f(i);
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] += v.v[k];
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < K; ++k) {
         const double t = block_sum(acc[k], sh);
         if (threadIdx.x == 0) part[k * kBlocks + blockIdx.x] = t;
     }
 }
-template <typename E>
-__global__ __launch_bounds__(kThreads) void finish_sums6_kernel(const double *__restrict__ part, E ep)
+
+// One workgroup closes the reduction on one device: the K sums, then the epilogue ep(r) on one thread — the scalar algebra of the outer loop (δ, α, the
+// norms) stays on the device, in the slots of a small scalar array the following kernels read.
+template <int K, typename E>
+__global__ __launch_bounds__(kThreads) void finish_sums_kernel(const double *__restrict__ part, E ep)
 {
     __shared__ double sh[4];
-    double r[6];
-    for (int k = 0; k < 6; ++k) r[k] = block_sum(part[k * kBlocks + threadIdx.x], sh);
+    static_assert(kBlocks == kThreads, "one partial per thread");
+    double r[K];
+    for (int k = 0; k < K; ++k) r[k] = block_sum(part[k * kBlocks + threadIdx.x], sh);
     if (threadIdx.x == 0) ep(r);
 }
+
+// On a partitioned operator it closes in three steps: the rank's own K sums go to raw, the caller all-reduces raw, and one thread runs the same epilogue on it.
+template <int K>
+__global__ __launch_bounds__(kThreads) void finish_raw_kernel(const double *__restrict__ part, double *__restrict__ raw)
+{
+    __shared__ double sh[4];
+    static_assert(kBlocks == kThreads, "one partial per thread");
+    for (int k = 0; k < K; ++k) {
+        const double r = block_sum(part[k * kBlocks + threadIdx.x], sh);
+        if (threadIdx.x == 0) raw[k] = r;
+    }
+}
+template <typename E>
+__global__ void scalar_kernel(E ep, const double *r) { if (threadIdx.x == 0 && blockIdx.x == 0) ep(r); }
 
 template <typename F>
 __global__ __launch_bounds__(kThreads) void map_kernel(int n, F f)
@@ -162,9 +150,22 @@ __global__ __launch_bounds__(kThreads) void pressure_precond_kernel(int nel, int
 
 inline int grid_for(int n) { return (n + kThreads - 1) / kThreads; }
 
+inline void strip_rows(int n_zero, const int32_t *rows, double *x, hipStream_t s)
+{
+    if (n_zero) hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for(n_zero)), dim3(kThreads), 0, s, n_zero, rows, x);
+}
+
+// A block of the stream-ordered scratch pool, given back when its owner goes; take() hands out its pieces in order (sizes in bytes, multiples of 256).
 struct Scratch {
-    void *p = nullptr; hipStream_t s = nullptr;
+    explicit Scratch(hipStream_t s) : s(s) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
     ~Scratch() { g4s::scratch_free(p, s); }
+    int alloc(size_t bytes) { return g4s::scratch_alloc(&p, bytes, s); }
+    double *take(size_t bytes) { double *r = reinterpret_cast<double *>(static_cast<char *>(p) + used); used += bytes; return r; }
+    void *p = nullptr;
+    size_t used = 0;
+    const hipStream_t s;
 };
 
 } // namespace
@@ -206,106 +207,144 @@ G4S_API g4s_status g4s_elem_op_pressure_preconditioner(g4s_elem_op_t op, const d
     return G4S_OK;
 }
 
-G4S_API g4s_status g4s_stokes_uzawa_cg(g4s_elem_op_t op, g4s_csr_t K_csr, const double *g, const double *BI, const double *BPI, const double *nmass,
-                                       const double *area, double volume, const int32_t *zero_resid, int32_t n_zero, const double *FF,
-                                       double *V, double *P, const g4s_stokes_params *prm, g4s_stokes_result *res, double *hist,
-                                       int32_t hist_lines, void *stream)
+// ------------------------------------------------------------------------------------------------ the outer iteration, once for both operators
+namespace g4s { int dist_product(g4s_spmv_dist_t A, const g4s_transport *tr, const double *x, double *y, void *stream); }   // cg.hip
+
+namespace {
+
+// What uzawa_loop asks of an operator (a policy object, passed by reference on the host; device code gets only `vnorm`, by value):
+//   grad_p(in, out)   assemble_grad_p + strip_bcs;   div_u(in, out)   assemble_div_u;   apply_K(in, out)   the stiffness product, not stripped
+//   vnorm(X, i), n_vnorm   the i-th summand of global_v_norm2 of X and how many there are
+//   solve(BI, acc, steps)  the velocity solves of the call (cg_async.hpp)
+//   close<K>(part, raw, ep, s)   the end of a reduction: the K sums of the partials in `part` reach ep(r) on one device thread
+struct LocalOps {                                                  // one device: the element operator, K through it or through g4s_spmv
+    g4s_elem_op_t op; g4s_csr_t K_csr; const double *g; const int32_t *zero_resid; int n_zero; void *stream;
+    struct VNorm {                                                 // (Σ_d X[eq(i,d)]²)·NMass[i] over the nodes
+        const int *node_eq; const double *nmass; int dof;
+        __device__ double operator()(const double *X, int i) const
+        {
+            double t = 0.0;
+            for (int d = 0; d < dof; ++d) { const double x = X[node_eq[i * dof + d]]; const double q = x * x; t = d == 0 ? q : t + q; }
+            return t * nmass[i];
+        }
+    } vnorm;
+    int n_vnorm, neq;
+    int grad_p(const double *in, double *out) const { return g4s_elem_op_grad_p(op, g, in, out, zero_resid, n_zero, stream); }
+    int div_u(const double *in, double *out) const { return g4s_elem_op_div_u(op, g, in, out, stream); }
+    int apply_K(const double *in, double *out) const { return K_csr ? g4s_spmv(K_csr, in, out, 1.0, 0.0, stream) : g4s_elem_op_apply(op, in, out, stream); }
+    g4s::LocalCgSolve solve(const double *BI, double acc, int steps) const   // General_matrix_functions.c:48-146, CG branch
+    {
+        return g4s::LocalCgSolve(K_csr ? nullptr : op, K_csr, neq, BI, zero_resid, n_zero, acc, steps, stream);
+    }
+    template <int K, typename E> int close(const double *part, double *, E ep, hipStream_t s) const   // one launch: the sums and the epilogue
+    {
+        hipLaunchKernelGGL((finish_sums_kernel<K, E>), dim3(1), dim3(kThreads), 0, s, part, ep);
+        return G4S_OK;
+    }
+};
+
+struct DistOps {                                                   // row-partitioned K, D, Dt; every sum goes over the ranks
+    g4s_spmv_dist_t K, D, Dt; const g4s_transport *tr; const int32_t *zero_resid; int n_zero; void *stream;
+    struct VNorm {                                                 // X[i]²·vmass[i] over this rank's equations
+        const double *vmass;
+        __device__ double operator()(const double *X, int i) const { return X[i] * X[i] * vmass[i]; }
+    } vnorm;
+    int n_vnorm, neq;
+    int grad_p(const double *in, double *out) const
+    {
+        G4S_TRY(g4s::dist_product(Dt, tr, in, out, stream));
+        strip_rows(n_zero, zero_resid, out, g4s::as_stream(stream));
+        return G4S_OK;
+    }
+    int div_u(const double *in, double *out) const { return g4s::dist_product(D, tr, in, out, stream); }
+    int apply_K(const double *in, double *out) const { return g4s::dist_product(K, tr, in, out, stream); }
+    g4s::DistCgSolve solve(const double *BI, double acc, int steps) const { return g4s::DistCgSolve(K, tr, neq, BI, zero_resid, n_zero, acc, steps, stream); }
+    template <int K_, typename E> int close(const double *part, double *raw, E ep, hipStream_t s) const   // raw local sums → summed over the ranks → the epilogue
+    {
+        hipLaunchKernelGGL((finish_raw_kernel<K_>), dim3(1), dim3(kThreads), 0, s, part, raw);
+        G4S_TRY(tr->allreduce_sum_f64(tr->ctx, raw, K_, stream));
+        hipLaunchKernelGGL((scalar_kernel<E>), dim3(1), dim3(64), 0, s, ep, raw);
+        return G4S_OK;
+    }
+};
+
+// solve_Ahat_p_fhat_CG from the workspace to *res. `entry` names the caller in the loop's one error message; the entry points have checked the arguments.
+template <typename Ops>
+int uzawa_loop(const char *entry, const Ops &ops, int neq, int nel, const double *BI, const double *BPI, const double *area, double volume, const int32_t *zero_resid,
+               int n_zero, const double *FF, double *V, double *P, const g4s_stokes_params *prm, g4s_stokes_result *res, double *hist, int hist_lines, hipStream_t s)
 {
-    g4s::ElemOpView v;
-    G4S_TRY(g4s_elem_op_view(op, &v));
-    G4S_REQUIRE(prm && res, "params / result is NULL");
-    G4S_REQUIRE(v.nel > 0 && v.neq > 0 && v.nno > 0, "empty operator");
-    G4S_REQUIRE(g && BI && BPI && nmass && area && FF && V && P, "NULL argument");
-    G4S_REQUIRE(volume > 0.0, "volume must be positive");
-    G4S_REQUIRE(n_zero >= 0 && (n_zero == 0 || zero_resid), "zero_resid is NULL");
-    G4S_REQUIRE(hist_lines >= 0 && (hist_lines == 0 || hist), "hist is NULL");
-    hipStream_t s = g4s::as_stream(stream);
-    const int neq = v.neq, nel = v.nel, nno = v.nno, dof = v.dof;
+    // sc: device scalars of the loop. A reduction = map_sum over the vectors + ops.close, whose epilogue writes the derived scalars; nothing comes to the
+    // host until fetch() at the end of an outer iteration. <r1, z1> of the NEXT outer iteration is formed in the closing reduction of the current one (r2 is
+    // final there; round 5): the two slots of R1Z1 / DELTA alternate by the iteration's parity — the closing step may run twice (a speculation that did not
+    // hold) and must find the current pair untouched.
+    enum { R1Z1_0, R1Z1_1, DELTA_0, DELTA_1, ALPHA, VDOTV, U1DOTU1, PDOTP, S2S2, DIVN, NSC };
+    static_assert(NSC <= 16, "scalar slots");
     const size_t nq = ((size_t)neq * 8 + 255) / 256 * 256, np = ((size_t)nel * 8 + 255) / 256 * 256;
-    Scratch scr; scr.s = s;
-    G4S_TRY(g4s::scratch_alloc(&scr.p, 3 * nq + 6 * np + sizeof(double) * (6 * kBlocks + 16), s));
-    char *base = static_cast<char *>(scr.p);
-    double *F = reinterpret_cast<double *>(base), *u1 = reinterpret_cast<double *>(base + nq), *tmp = reinterpret_cast<double *>(base + 2 * nq);
-    double *r1 = reinterpret_cast<double *>(base + 3 * nq), *r2 = reinterpret_cast<double *>(base + 3 * nq + np),
-           *z1 = reinterpret_cast<double *>(base + 3 * nq + 2 * np), *s1 = reinterpret_cast<double *>(base + 3 * nq + 3 * np),
-           *s2 = reinterpret_cast<double *>(base + 3 * nq + 4 * np), *Fp = reinterpret_cast<double *>(base + 3 * nq + 5 * np);
-    double *part = reinterpret_cast<double *>(base + 3 * nq + 6 * np), *sums_dev = part + 6 * kBlocks;
-    const int *node_eq = v.node_eq;
-    // V and P of the NEXT outer iteration are written beside the current ones (ping-pong): an iteration that was enqueued behind a velocity
-    // solve which turns out not to have met its test can then simply be enqueued again, from unchanged inputs
-    Scratch scr2; scr2.s = s;
-    const size_t nm = ((size_t)neq + 255) / 256 * 256;
-    G4S_TRY(g4s::scratch_alloc(&scr2.p, nq + np + nm, s));
-    unsigned char *bc_mask = reinterpret_cast<unsigned char *>(static_cast<char *>(scr2.p) + nq + np);   // boundary-equation mask of every velocity solve of this call
-    G4S_TRY(g4s::cg_build_mask(neq, zero_resid, n_zero, bc_mask, s));
-    double *Vc = V, *Vn = reinterpret_cast<double *>(scr2.p), *Pc = P, *Pn = reinterpret_cast<double *>(static_cast<char *>(scr2.p) + nq);
+    Scratch scr(s), scr2(s);
+    G4S_TRY(scr.alloc(3 * nq + 6 * np + sizeof(double) * (6 * kBlocks + 32)));
+    double *F = scr.take(nq), *u1 = scr.take(nq), *tmp = scr.take(nq);
+    double *r1 = scr.take(np), *r2 = scr.take(np), *z1 = scr.take(np), *s1 = scr.take(np), *s2 = scr.take(np), *Fp = scr.take(np);
+    double *part = scr.take(sizeof(double) * 6 * kBlocks), *sc = scr.take(sizeof(double) * 16), *raw = scr.take(sizeof(double) * 16);   // raw: sums on their way through an all-reduce
+    // V and P of the NEXT outer iteration are written beside the current ones (ping-pong): an iteration that was enqueued behind a velocity solve whose
+    // first batch turns out not to have met its test can then simply be enqueued again, from unchanged inputs
+    G4S_TRY(scr2.alloc(nq + np));
+    double *Vc = V, *Vn = scr2.take(nq), *Pc = P, *Pn = scr2.take(np);
     // G4S_STOKES_SYNC=1: wait for every velocity solve before enqueuing what follows it (the round-2 behaviour, for A/B)
     const bool speculate = !(getenv("G4S_STOKES_SYNC") && atoi(getenv("G4S_STOKES_SYNC")) != 0);
 
-    // sc: device scalars of the loop. A reduction = map_sum over the vectors + a one-workgroup finish whose epilogue writes the
-    // derived scalars; nothing comes to the host until fetch() at the end of an outer iteration.
-    // <r1, z1> of the NEXT outer iteration is formed in the closing reduction of the current one (r2 is final there; round 5, as in g4s_stokes_uzawa_cg_dist): the two
-    // slots of R1Z1 / DELTA alternate by the iteration's parity — the closing step may run twice (a speculation that did not hold) and must find the current pair untouched.
-    enum { R1Z1_0, R1Z1_1, DELTA_0, DELTA_1, ALPHA, VDOTV, U1DOTU1, PDOTP, S2S2, DIVN, NSC };
-    static_assert(NSC <= 16, "scalar slots");
-    double *sc = sums_dev;
     double hsc[NSC] = {0};
-    auto reduce = [&](int n, auto f, auto ep) {
-        hipLaunchKernelGGL(map_sum_kernel, dim3(kBlocks), dim3(kThreads), 0, s, n, f, part);
-        hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(kThreads), 0, s, part, ep);
+    auto reduce = [&](auto k, int n, auto f, auto ep) -> int {     // k: the number of sums, as a std::integral_constant
+        constexpr int K = decltype(k)::value;
+        hipLaunchKernelGGL((map_sum_kernel<K, decltype(f)>), dim3(kBlocks), dim3(kThreads), 0, s, n, f, part);
+        return ops.template close<K>(part, raw, ep, s);
     };
+    constexpr std::integral_constant<int, 1> one{};
+    constexpr std::integral_constant<int, 6> six{};
     auto fetch = [&]() -> int {
         G4S_HIP_TRY(hipGetLastError());
         G4S_HIP_TRY(g4s::ReadScope(s).fetch(hsc, sc));
         return G4S_OK;
     };
     auto each = [&](int n, auto f) { hipLaunchKernelGGL(map_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, n, f); };
-    auto strip = [&](double *x) { if (n_zero) hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for(n_zero)), dim3(kThreads), 0, s, n_zero, zero_resid, x); };
-    auto v_terms = [=] __device__(const double *X, int i) {        // (Σ_d X[eq(i,d)]²)·NMass[i], the summand of global_v_norm2
-        double t = 0.0;
-        for (int d = 0; d < dof; ++d) { const double x = X[node_eq[i * dof + d]]; const double q = x * x; t = d == 0 ? q : t + q; }
-        return t * nmass[i];
-    };
+    auto strip = [&](double *x) { strip_rows(n_zero, zero_resid, x, s); };
+    const auto vnorm = ops.vnorm;                                  // device lambdas take the functor, never the policy
+    const int n_norms = std::max(ops.n_vnorm, nel), n_vnorm = ops.n_vnorm;
     int64_t inner_total = 0;
     const double inner_acc = prm->imp * prm->inner_accuracy_scale * prm->v_res;
-    auto solve_del2_u = [&](const double *rhs, double *d0, int *valid) -> int {   // General_matrix_functions.c:48-146, CG branch
-        int32_t cycles = prm->v_steps_low;
-        double residual = 0.0;
-        G4S_TRY(g4s_conj_grad(K_csr ? nullptr : op, K_csr, neq, BI, zero_resid, n_zero, rhs, d0, inner_acc, &cycles, &residual, s));
-        inner_total += cycles;
-        *valid = residual < inner_acc ? 1 : 0;
-        return G4S_OK;
-    };
+    auto cg = ops.solve(BI, inner_acc, prm->v_steps_low);          // every velocity solve of the call: one workspace, one boundary mask
+    int32_t cycles = 0;
+    double residual = 0.0;
+    bool held = true;
 
     // ---- initial_vel_residual (:839-881): F = FF − grad(P) − K·V, stripped; K·u1 = F; V += u1
-    int valid = 0;
-    G4S_TRY(g4s_elem_op_grad_p(op, g, P, u1, zero_resid, n_zero, s));
+    G4S_TRY(ops.grad_p(P, u1));
     each(neq, [=] __device__(int i) { F[i] = FF[i] - u1[i]; });
-    if (K_csr) G4S_TRY(g4s_spmv(K_csr, V, u1, 1.0, 0.0, s));
-    else G4S_TRY(g4s_elem_op_apply(op, V, u1, s));
+    G4S_TRY(ops.apply_K(V, u1));
     strip(u1);
     each(neq, [=] __device__(int i) { F[i] = F[i] - u1[i]; });
     strip(F);
-    G4S_TRY(solve_del2_u(F, u1, &valid));
-    strip(u1);
+    // this solve's result feeds sums whose inputs it also writes in place (V += u1): waited for, not speculated on — once per call
+    G4S_TRY(cg.start(F, u1));
+    G4S_TRY(cg.read());
+    G4S_HIP_TRY(g4s::reads_sync(s));
+    G4S_TRY(cg.settle(&held, &cycles, &residual));
+    inner_total += cycles;
+    int valid = residual < inner_acc ? 1 : 0;
     each(neq, [=] __device__(int i) { V[i] = V[i] + u1[i]; });
 
     // ---- r1 = div(V); incompressibility = sqrt(|r1|²_div / (1e-32 + |V|²))
-    G4S_TRY(g4s_elem_op_div_u(op, g, V, r1, s));
+    G4S_TRY(ops.div_u(V, r1));
     G4S_HIP_TRY(hipMemsetAsync(sc, 0, sizeof(double) * NSC, s));
-    hipLaunchKernelGGL(map_sum6_kernel, dim3(kBlocks), dim3(kThreads), 0, s, std::max(nno, nel), [=] __device__(int i) {
-        Sum6 o{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
-        if (i < nno) o.v[0] = v_terms(V, i);
+    G4S_TRY(reduce(six, n_norms, [=] __device__(int i) {
+        Sums<6> o{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+        if (i < n_vnorm) o.v[0] = vnorm(V, i);
         if (i < nel) {
             o.v[1] = r1[i] * r1[i] / area[i]; o.v[2] = P[i] * P[i] * area[i];
             const double z = BPI[i] * r1[i];                          // z1 = BPI∘r1 and <r1, z1> of the first outer iteration (:296-318)
             z1[i] = z; o.v[3] = r1[i] * z;
         }
         return o;
-    }, part);
-    hipLaunchKernelGGL(finish_sums6_kernel, dim3(1), dim3(kThreads), 0, s, part, [=] __device__(const double (&r)[6]) {
-        sc[VDOTV] = r[0]; sc[DIVN] = r[1]; sc[PDOTP] = r[2]; sc[R1Z1_0] = r[3];
-    });
+    }, [=] __device__(const double *r) { sc[VDOTV] = r[0]; sc[DIVN] = r[1]; sc[PDOTP] = r[2]; sc[R1Z1_0] = r[3]; }));
     G4S_TRY(fetch());
     double vdotv = hsc[VDOTV] / volume, pdotp = hsc[PDOTP] / volume;
     double incompressibility = std::sqrt(hsc[DIVN] / volume / (1e-32 + vdotv));
@@ -319,62 +358,56 @@ G4S_API g4s_status g4s_stokes_uzawa_cg(g4s_elem_op_t op, g4s_csr_t K_csr, const 
     for (;;) {
         const bool keep = prm->check_continuity_convergence ? (incompressibility > prm->imp || converging < 2)
                                                             : (incompressibility > prm->imp && converging < 2);   // keep_iterating :150-162
-        if (!(count < prm->steps_max && keep)) break;
+        if (!(count < prm->steps_max && keep)) break;              // (partitioned: every rank holds the same all-reduced scalars — the same verdict everywhere)
         // z1 = BPI∘r1, <r1, z1> and δ = <r1, z1> / <r0, z0> (:296-318) sit in slot `cur`: written by the closing reduction of the previous iteration
         const int cur = count & 1, nxt = cur ^ 1;
-        if (hsc[R1Z1_0 + cur] == 0.0) return g4s::set_error(G4S_ERR_INVALID, "g4s_stokes_uzawa_cg: <r1, z1> = 0 at the head of iteration %d (the source asserts)", count);
+        if (hsc[R1Z1_0 + cur] == 0.0) return g4s::set_error(G4S_ERR_INVALID, "%s: <r1, z1> = 0 at the head of iteration %d (the source asserts)", entry, count);
         const bool first = count == 0;
         each(nel, [=] __device__(int i) { s2[i] = first ? z1[i] : z1[i] + sc[DELTA_0 + cur] * s1[i]; });
-        // K·u1 = grad(s2). The solve's first batch (one iteration more than the previous solve needed) is only enqueued; everything that follows it
-        // in this outer iteration is enqueued behind it at once, and ONE synchronisation brings back the solve's state and the nine scalars.
-        // Before round 3 the host waited for the solve, then enqueued the rest and waited again: at Cookbook2's size the loop was host-bound
-        // (38 launches of 3–11 µs and two read-backs per outer iteration: 0.21 ms, of which the device needs 0.13 — tools/uzawa_graph_probe.py).
-        G4S_TRY(g4s_elem_op_grad_p(op, g, s2, tmp, zero_resid, n_zero, s));
-        g4s::CgAsync *cg = nullptr;
-        G4S_TRY(g4s::cg_async_start(&cg, K_csr ? nullptr : op, K_csr, neq, BI, zero_resid, n_zero, tmp, u1, inner_acc, prm->v_steps_low, s, n_zero ? bc_mask : nullptr));
-        struct CgFree { g4s::CgAsync *c; ~CgFree() { g4s::cg_async_free(c); } } cg_guard{cg};
-        int32_t cycles = 0;
-        double residual = 0.0;
-        bool held = true;
+        // K·u1 = grad(s2). The solve's first batch (one iteration more than the previous solve needed) is only enqueued — partitioned: its products, exchanges
+        // and all-reduces included, with an RCCL transport none of them waits for the host; everything that follows it in this outer iteration is enqueued
+        // behind it at once, and ONE synchronisation brings back the solve's state and the nine scalars. Before round 3 the host waited for the solve, then
+        // enqueued the rest and waited again: at Cookbook2's size the loop was host-bound (38 launches of 3–11 µs and two read-backs per outer iteration:
+        // 0.21 ms, of which the device needs 0.13 — tools/uzawa_graph_probe.py).
+        G4S_TRY(ops.grad_p(s2, tmp));
+        G4S_TRY(cg.start(tmp, u1));
+        held = true;
         if (!speculate) {
-            G4S_TRY(g4s::cg_async_read(cg));
+            G4S_TRY(cg.read());
             G4S_HIP_TRY(g4s::reads_sync(s));
-            G4S_TRY(g4s::cg_async_settle(cg, &held, &cycles, &residual));
+            G4S_TRY(cg.settle(&held, &cycles, &residual));
         }
         auto rest_of_iteration = [&]() -> int {
-            G4S_TRY(g4s_elem_op_div_u(op, g, u1, Fp, s));
+            G4S_TRY(ops.div_u(u1, Fp));
             // α = <r1, z1> / <s2, div(u1)>; r2, P, V (:336-354)
-            reduce(nel, [=] __device__(int i) { return Sum3{s2[i] * Fp[i], 0.0, 0.0}; },
-                   [=] __device__(double a, double, double) { sc[ALPHA] = sc[R1Z1_0 + cur] / a; });
+            G4S_TRY(reduce(one, nel, [=] __device__(int i) { return Sums<1>{{s2[i] * Fp[i]}}; }, [=] __device__(const double *r) { sc[ALPHA] = sc[R1Z1_0 + cur] / r[0]; }));
             each(std::max(nel, neq), [=] __device__(int i) {        // one launch for the three updates
                 const double alpha = sc[ALPHA];
                 if (i < nel) { r2[i] = r1[i] - alpha * Fp[i]; Pn[i] = Pc[i] + alpha * s2[i]; }
                 if (i < neq) Vn[i] = Vc[i] - alpha * u1[i];
             });
-            G4S_TRY(g4s_elem_op_div_u(op, g, Vn, Fp, s));           // (Fp = div(u1) has gone into r2: the buffer is free)
+            G4S_TRY(ops.div_u(Vn, Fp));                             // (Fp = div(u1) has gone into r2: the buffer is free)
             // the five norms of the iteration and, since r2 is final, z1 = BPI∘r2 and <r1, z1> of the NEXT one, in one two-level pass
-            hipLaunchKernelGGL(map_sum6_kernel, dim3(kBlocks), dim3(kThreads), 0, s, std::max(nno, nel), [=] __device__(int i) {
-                Sum6 o{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
-                if (i < nno) { o.v[0] = v_terms(Vn, i); o.v[1] = v_terms(u1, i); }
+            return reduce(six, n_norms, [=] __device__(int i) {
+                Sums<6> o{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+                if (i < n_vnorm) { o.v[0] = vnorm(Vn, i); o.v[1] = vnorm(u1, i); }
                 if (i < nel) {
                     o.v[2] = Pn[i] * Pn[i] * area[i]; o.v[3] = s2[i] * s2[i] * area[i]; o.v[4] = Fp[i] * Fp[i] / area[i];
                     const double z = BPI[i] * r2[i];
                     z1[i] = z; o.v[5] = r2[i] * z;
                 }
                 return o;
-            }, part);
-            hipLaunchKernelGGL(finish_sums6_kernel, dim3(1), dim3(kThreads), 0, s, part, [=] __device__(const double (&r)[6]) {
+            }, [=] __device__(const double *r) {
                 sc[VDOTV] = r[0]; sc[U1DOTU1] = r[1]; sc[PDOTP] = r[2]; sc[S2S2] = r[3]; sc[DIVN] = r[4];
                 sc[R1Z1_0 + nxt] = r[5]; sc[DELTA_0 + nxt] = r[5] / sc[R1Z1_0 + cur];      // δ of the next iteration = its <r1, z1> over this one's (:296-318, :405)
             });
-            return G4S_OK;
         };
         G4S_TRY(rest_of_iteration());
         if (speculate) {
-            G4S_TRY(g4s::cg_async_read(cg));
+            G4S_TRY(cg.read());
             G4S_TRY(fetch());
-            G4S_TRY(g4s::cg_async_settle(cg, &held, &cycles, &residual));
-            if (!held) G4S_TRY(rest_of_iteration());              // the first batch did not meet the test: u1 is final only now — once more, from the same V, P, r1, s2
+            G4S_TRY(cg.settle(&held, &cycles, &residual));
+            if (!held) G4S_TRY(rest_of_iteration());              // the first batch did not meet the test: u1 is final only now — once more, from the same V, P, r1, s2 (all ranks alike)
         }
         inner_total += cycles;
         valid = residual < inner_acc ? 1 : 0;
@@ -412,30 +445,26 @@ G4S_API g4s_status g4s_stokes_uzawa_cg(g4s_elem_op_t op, g4s_csr_t K_csr, const 
     return G4S_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ the same iteration on a partitioned operator
-namespace g4s { int dist_product(g4s_spmv_dist_t A, const g4s_transport *tr, const double *x, double *y, void *stream); }   // cg.hip
-
-namespace {
-// the raw local sums of a reduction, before the all-reduce (the derived scalars are formed after it, by one thread)
-__global__ __launch_bounds__(kThreads) void finish_raw_kernel(const double *__restrict__ part, double *__restrict__ raw)
-{
-    __shared__ double sh[4];
-    double r[3];
-    for (int k = 0; k < 3; ++k) r[k] = block_sum(part[k * kBlocks + threadIdx.x], sh);
-    if (threadIdx.x == 0) { raw[0] = r[0]; raw[1] = r[1]; raw[2] = r[2]; }
-}
-__global__ __launch_bounds__(kThreads) void finish_raw6_kernel(const double *__restrict__ part, double *__restrict__ raw)
-{
-    __shared__ double sh[4];
-    for (int k = 0; k < 6; ++k) {
-        const double r = block_sum(part[k * kBlocks + threadIdx.x], sh);
-        if (threadIdx.x == 0) raw[k] = r;
-    }
-}
-template <typename E>
-__global__ void scalar_kernel(E ep) { if (threadIdx.x == 0 && blockIdx.x == 0) ep(); }
 } // namespace
 
+G4S_API g4s_status g4s_stokes_uzawa_cg(g4s_elem_op_t op, g4s_csr_t K_csr, const double *g, const double *BI, const double *BPI, const double *nmass,
+                                       const double *area, double volume, const int32_t *zero_resid, int32_t n_zero, const double *FF,
+                                       double *V, double *P, const g4s_stokes_params *prm, g4s_stokes_result *res, double *hist,
+                                       int32_t hist_lines, void *stream)
+{
+    g4s::ElemOpView v;
+    G4S_TRY(g4s_elem_op_view(op, &v));
+    G4S_REQUIRE(prm && res, "params / result is NULL");
+    G4S_REQUIRE(v.nel > 0 && v.neq > 0 && v.nno > 0, "empty operator");
+    G4S_REQUIRE(g && BI && BPI && nmass && area && FF && V && P, "NULL argument");
+    G4S_REQUIRE(volume > 0.0, "volume must be positive");
+    G4S_REQUIRE(n_zero >= 0 && (n_zero == 0 || zero_resid), "zero_resid is NULL");
+    G4S_REQUIRE(hist_lines >= 0 && (hist_lines == 0 || hist), "hist is NULL");
+    const LocalOps ops{op, K_csr, g, zero_resid, n_zero, stream, {v.node_eq, nmass, v.dof}, v.nno, v.neq};
+    return uzawa_loop(__func__, ops, v.neq, v.nel, BI, BPI, area, volume, zero_resid, n_zero, FF, V, P, prm, res, hist, hist_lines, g4s::as_stream(stream));
+}
+
+// the same iteration on a partitioned operator: this rank's neq equations and nel elements
 G4S_API g4s_status g4s_stokes_uzawa_cg_dist(g4s_spmv_dist_t K, g4s_spmv_dist_t D, g4s_spmv_dist_t Dt, const g4s_transport *tr, int32_t neq, int32_t nel,
                                             const double *BI, const double *BPI, const double *vmass, const double *area, double volume,
                                             const int32_t *zero_resid, int32_t n_zero, const double *FF, double *V, double *P,
@@ -447,194 +476,6 @@ G4S_API g4s_status g4s_stokes_uzawa_cg_dist(g4s_spmv_dist_t K, g4s_spmv_dist_t D
     G4S_REQUIRE(volume > 0.0, "volume must be positive");
     G4S_REQUIRE(n_zero >= 0 && (n_zero == 0 || zero_resid), "zero_resid is NULL");
     G4S_REQUIRE(hist_lines >= 0 && (hist_lines == 0 || hist), "hist is NULL");
-    hipStream_t s = g4s::as_stream(stream);
-    const size_t nq = ((size_t)neq * 8 + 255) / 256 * 256, np = ((size_t)nel * 8 + 255) / 256 * 256;
-    Scratch scr; scr.s = s;
-    G4S_TRY(g4s::scratch_alloc(&scr.p, 3 * nq + 6 * np + sizeof(double) * (6 * kBlocks + 32), s));
-    char *base = static_cast<char *>(scr.p);
-    double *F = reinterpret_cast<double *>(base), *u1 = reinterpret_cast<double *>(base + nq), *tmp = reinterpret_cast<double *>(base + 2 * nq);
-    double *r1 = reinterpret_cast<double *>(base + 3 * nq), *r2 = reinterpret_cast<double *>(base + 3 * nq + np),
-           *z1 = reinterpret_cast<double *>(base + 3 * nq + 2 * np), *s1 = reinterpret_cast<double *>(base + 3 * nq + 3 * np),
-           *s2 = reinterpret_cast<double *>(base + 3 * nq + 4 * np), *Fp = reinterpret_cast<double *>(base + 3 * nq + 5 * np);
-    double *part = reinterpret_cast<double *>(base + 3 * nq + 6 * np), *sc = part + 6 * kBlocks, *raw = sc + 16;
-    // Round 5: <r1, z1> of the NEXT outer iteration is formed in the closing reduction of the current one (r2 is final there), so the two slots of R1Z1 / DELTA
-    // alternate by the iteration's parity — the closing step may run twice (a speculation that did not hold) and must find the current pair untouched.
-    enum { R1Z1_0, R1Z1_1, DELTA_0, DELTA_1, ALPHA, VDOTV, U1DOTU1, PDOTP, S2S2, DIVN, NSC };
-    double hsc[NSC] = {0};
-    // a reduction: local partial sums in the fixed two-level shape → three raw sums → summed over the ranks → the derived scalars
-    auto reduce = [&](int n, auto f, auto ep) -> int {
-        hipLaunchKernelGGL(map_sum_kernel, dim3(kBlocks), dim3(kThreads), 0, s, n, f, part);
-        hipLaunchKernelGGL(finish_raw_kernel, dim3(1), dim3(kThreads), 0, s, part, raw);
-        G4S_TRY(tr->allreduce_sum_f64(tr->ctx, raw, 3, stream));
-        hipLaunchKernelGGL(scalar_kernel, dim3(1), dim3(64), 0, s, ep);
-        return G4S_OK;
-    };
-    // the same with six sums in ONE all-reduce message: everything an outer iteration can sum once its new V, P and r are known (round 5: was two reductions
-    // at its end and one at the head of the next — three all-reduces, now one; Global_operations.c:534-656 reduces each norm on its own)
-    auto reduce6 = [&](int n, auto f, auto ep) -> int {
-        hipLaunchKernelGGL(map_sum6_kernel, dim3(kBlocks), dim3(kThreads), 0, s, n, f, part);
-        hipLaunchKernelGGL(finish_raw6_kernel, dim3(1), dim3(kThreads), 0, s, part, raw);
-        G4S_TRY(tr->allreduce_sum_f64(tr->ctx, raw, 6, stream));
-        hipLaunchKernelGGL(scalar_kernel, dim3(1), dim3(64), 0, s, ep);
-        return G4S_OK;
-    };
-    auto fetch = [&]() -> int {
-        G4S_HIP_TRY(hipGetLastError());
-        G4S_HIP_TRY(g4s::ReadScope(s).fetch(hsc, sc));
-        return G4S_OK;
-    };
-    auto each = [&](int n, auto f) { hipLaunchKernelGGL(map_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, n, f); };
-    auto strip = [&](double *x) { if (n_zero) hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for(n_zero)), dim3(kThreads), 0, s, n_zero, zero_resid, x); };
-    auto grad_p = [&](const double *p_in, double *out) -> int { G4S_TRY(g4s::dist_product(Dt, tr, p_in, out, stream)); strip(out); return G4S_OK; };   // assemble_grad_p + strip_bcs
-    auto div_u = [&](const double *u_in, double *out) -> int { return g4s::dist_product(D, tr, u_in, out, stream); };                                   // assemble_div_u
-    int64_t inner_total = 0;
-    const double inner_acc = prm->imp * prm->inner_accuracy_scale * prm->v_res;
-    // one CG workspace for every velocity solve of the call
-    struct Ws { g4s_cg_ws_t w = nullptr; ~Ws() { (void)g4s_cg_ws_destroy(w); } } ws;
-    G4S_TRY(g4s_cg_ws_create(&ws.w, neq));
-    g4s::cg_ws_hold_mask(ws.w, true);                              // zero_resid is this call's own argument: the same list for every velocity solve
-    // V and P of the NEXT outer iteration are written beside the current ones (ping-pong), as in g4s_stokes_uzawa_cg: an iteration enqueued behind a
-    // velocity solve whose first batch turns out not to have met its test is enqueued again, from unchanged inputs
-    Scratch scr2; scr2.s = s;
-    G4S_TRY(g4s::scratch_alloc(&scr2.p, nq + np, s));
-    double *Vc = V, *Vn = reinterpret_cast<double *>(scr2.p), *Pc = P, *Pn = reinterpret_cast<double *>(static_cast<char *>(scr2.p) + nq);
-    const bool speculate = !(getenv("G4S_STOKES_SYNC") && atoi(getenv("G4S_STOKES_SYNC")) != 0);
-    struct CgFree { g4s::DistCgAsync *c; ~CgFree() { g4s::dist_cg_async_free(c); } };
-
-    // ---- initial_vel_residual (:839-881): F = FF − grad(P) − K·V, stripped; K·u1 = F; V += u1
-    int valid = 0;
-    G4S_TRY(grad_p(P, u1));
-    each(neq, [=] __device__(int i) { F[i] = FF[i] - u1[i]; });
-    G4S_TRY(g4s::dist_product(K, tr, V, u1, stream));
-    strip(u1);
-    each(neq, [=] __device__(int i) { F[i] = F[i] - u1[i]; });
-    strip(F);
-    {
-        // this solve's result feeds sums whose inputs it also writes in place (V += u1): waited for, not speculated on — once per call
-        g4s::DistCgAsync *cg = nullptr;
-        G4S_TRY(g4s::dist_cg_async_start(&cg, ws.w, K, tr, BI, zero_resid, n_zero, F, u1, inner_acc, prm->v_steps_low, stream));
-        CgFree guard{cg};
-        G4S_TRY(g4s::dist_cg_async_read(cg));
-        G4S_HIP_TRY(g4s::reads_sync(s));
-        bool held = true;
-        int32_t cycles = 0;
-        double residual = 0.0;
-        G4S_TRY(g4s::dist_cg_async_settle(cg, &held, &cycles, &residual));
-        inner_total += cycles;
-        valid = residual < inner_acc ? 1 : 0;
-    }
-    each(neq, [=] __device__(int i) { V[i] = V[i] + u1[i]; });
-
-    G4S_TRY(div_u(V, r1));
-    G4S_HIP_TRY(hipMemsetAsync(sc, 0, sizeof(double) * NSC, s));
-    G4S_TRY(reduce6(std::max(neq, nel), [=] __device__(int i) {
-        Sum6 o{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
-        if (i < neq) o.v[0] = V[i] * V[i] * vmass[i];
-        if (i < nel) {
-            o.v[1] = r1[i] * r1[i] / area[i]; o.v[2] = P[i] * P[i] * area[i];
-            const double z = BPI[i] * r1[i];                          // z1 = BPI·r1 and <r1, z1> of the first outer iteration (:263-273)
-            z1[i] = z; o.v[3] = r1[i] * z;
-        }
-        return o;
-    }, [=] __device__() { sc[VDOTV] = raw[0]; sc[DIVN] = raw[1]; sc[PDOTP] = raw[2]; sc[R1Z1_0] = raw[3]; }));
-    G4S_TRY(fetch());
-    double vdotv = hsc[VDOTV] / volume, pdotp = hsc[PDOTP] / volume;
-    double incompressibility = std::sqrt(hsc[DIVN] / volume / (1e-32 + vdotv));
-    double dvelocity = 1.0, dpressure = 1.0;
-    int count = 0, converging = 0, lines = 0;
-    auto record = [&]() {
-        if (lines < hist_lines) { double *h = hist + 5 * (size_t)lines; h[0] = std::sqrt(vdotv); h[1] = std::sqrt(pdotp); h[2] = dvelocity; h[3] = dpressure; h[4] = incompressibility; }
-        ++lines;
-    };
-    record();
-    for (;;) {
-        const bool keep = prm->check_continuity_convergence ? (incompressibility > prm->imp || converging < 2)
-                                                            : (incompressibility > prm->imp && converging < 2);   // keep_iterating :150-162
-        if (!(count < prm->steps_max && keep)) break;              // every rank holds the same all-reduced scalars: the same verdict everywhere
-        const int cur = count & 1, nxt = cur ^ 1;                  // this iteration's <r1, z1> and δ sit in slot `cur` (written by the closing reduction of the previous one)
-        if (hsc[R1Z1_0 + cur] == 0.0) return g4s::set_error(G4S_ERR_INVALID, "g4s_stokes_uzawa_cg_dist: <r1, z1> = 0 at the head of iteration %d (the source asserts)", count);
-        const bool first = count == 0;
-        each(nel, [=] __device__(int i) { s2[i] = first ? z1[i] : z1[i] + sc[DELTA_0 + cur] * s1[i]; });
-        G4S_TRY(grad_p(s2, tmp));
-        // K·u1 = grad(s2): the solve's first batch is only enqueued (products, exchanges and all-reduces included — with an RCCL transport none of them
-        // waits for the host); the rest of the outer iteration goes behind it at once and ONE synchronisation brings back the solve's state and the
-        // nine scalars. Until round 4 this loop waited three times per outer iteration (the solve's state, the solve's end, the scalars).
-        g4s::DistCgAsync *cg = nullptr;
-        G4S_TRY(g4s::dist_cg_async_start(&cg, ws.w, K, tr, BI, zero_resid, n_zero, tmp, u1, inner_acc, prm->v_steps_low, stream));
-        CgFree guard{cg};
-        int32_t cycles = 0;
-        double residual = 0.0;
-        bool held = true;
-        if (!speculate) {
-            G4S_TRY(g4s::dist_cg_async_read(cg));
-            G4S_HIP_TRY(g4s::reads_sync(s));
-            G4S_TRY(g4s::dist_cg_async_settle(cg, &held, &cycles, &residual));
-        }
-        auto rest_of_iteration = [&]() -> int {
-            G4S_TRY(div_u(u1, Fp));
-            G4S_TRY(reduce(nel, [=] __device__(int i) { return Sum3{s2[i] * Fp[i], 0.0, 0.0}; }, [=] __device__() { sc[ALPHA] = sc[R1Z1_0 + cur] / raw[0]; }));
-            each(std::max(nel, neq), [=] __device__(int i) {
-                const double alpha = sc[ALPHA];
-                if (i < nel) { r2[i] = r1[i] - alpha * Fp[i]; Pn[i] = Pc[i] + alpha * s2[i]; }
-                if (i < neq) Vn[i] = Vc[i] - alpha * u1[i];
-            });
-            G4S_TRY(div_u(Vn, Fp));                                 // (Fp = D·u1 has gone into r2: the buffer is free)
-            // the five norms of this iteration and, since r2 is final, z1 = BPI·r2 and <r1, z1> of the NEXT one — one all-reduce message of six sums
-            G4S_TRY(reduce6(std::max(neq, nel), [=] __device__(int i) {
-                Sum6 o{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
-                if (i < neq) { o.v[0] = Vn[i] * Vn[i] * vmass[i]; o.v[1] = u1[i] * u1[i] * vmass[i]; }
-                if (i < nel) {
-                    o.v[2] = Pn[i] * Pn[i] * area[i]; o.v[3] = s2[i] * s2[i] * area[i]; o.v[4] = Fp[i] * Fp[i] / area[i];
-                    const double z = BPI[i] * r2[i];
-                    z1[i] = z; o.v[5] = r2[i] * z;
-                }
-                return o;
-            }, [=] __device__() {
-                sc[VDOTV] = raw[0]; sc[U1DOTU1] = raw[1]; sc[PDOTP] = raw[2]; sc[S2S2] = raw[3]; sc[DIVN] = raw[4];
-                sc[R1Z1_0 + nxt] = raw[5]; sc[DELTA_0 + nxt] = raw[5] / sc[R1Z1_0 + cur];
-            }));
-            return G4S_OK;
-        };
-        G4S_TRY(rest_of_iteration());
-        if (speculate) {
-            G4S_TRY(g4s::dist_cg_async_read(cg));
-            G4S_TRY(fetch());
-            G4S_TRY(g4s::dist_cg_async_settle(cg, &held, &cycles, &residual));
-            if (!held) G4S_TRY(rest_of_iteration());              // u1 is final only now: once more, from the same V, P, r1, s2 (all ranks alike)
-        }
-        inner_total += cycles;
-        valid = residual < inner_acc ? 1 : 0;
-        if (!speculate || !held) G4S_TRY(fetch());
-        const double alpha = hsc[ALPHA];
-        vdotv = hsc[VDOTV] / volume;
-        pdotp = hsc[PDOTP] / volume;
-        dvelocity = alpha * std::sqrt(hsc[U1DOTU1] / volume / (1e-32 + vdotv));
-        dpressure = alpha * std::sqrt(hsc[S2S2] / volume / (1e-32 + pdotp));
-        incompressibility = std::sqrt(hsc[DIVN] / volume / (1e-32 + vdotv));
-        ++count;
-        record();
-        if (!valid) converging = 0;
-        else if (prm->check_pressure_convergence) converging = (dvelocity < prm->imp && dpressure < prm->imp) ? converging + 1 : 0;
-        else converging = dvelocity < prm->imp ? converging + 1 : 0;
-        std::swap(s1, s2);
-        std::swap(r1, r2);
-        std::swap(Vc, Vn);
-        std::swap(Pc, Pn);
-    }
-    if (Vc != V) {                                                 // an odd number of iterations: the result sits in the scratch pair
-        G4S_HIP_TRY(hipMemcpyAsync(V, Vc, sizeof(double) * (size_t)neq, hipMemcpyDeviceToDevice, s));
-        G4S_HIP_TRY(hipMemcpyAsync(P, Pc, sizeof(double) * (size_t)nel, hipMemcpyDeviceToDevice, s));
-    }
-    G4S_HIP_TRY(hipGetLastError());
-    G4S_HIP_TRY(g4s::reads_sync(s));
-    res->outer_iterations = count;
-    res->inner_iterations = inner_total;
-    res->last_solve_valid = valid;
-    res->incompressibility = incompressibility;
-    res->v_norm = std::sqrt(vdotv);
-    res->p_norm = std::sqrt(pdotp);
-    res->dvelocity = dvelocity;
-    res->dpressure = dpressure;
-    return G4S_OK;
+    const DistOps ops{K, D, Dt, tr, zero_resid, n_zero, stream, {vmass}, neq, neq};
+    return uzawa_loop(__func__, ops, neq, nel, BI, BPI, area, volume, zero_resid, n_zero, FF, V, P, prm, res, hist, hist_lines, g4s::as_stream(stream));
 }
-

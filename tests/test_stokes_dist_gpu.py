@@ -120,6 +120,19 @@ def test_uzawa_on_the_partitioned_operator_matches_oracle(tmp_path, oracle, monk
     assert np.isclose(metas[0][2], inc_o, rtol=1e-4, atol=1e-14)
 
 
+def _one_rank_over_rccl(pr, neq, nel):
+    """K, D, Dt of the whole problem on the library's own communicator of one rank."""
+    from g4s_amd import dist as gdist
+    ien, idmap = pr["ien"], pr["id"]
+    Kc = assemble_csr(ien, idmap, pr["K"], neq)
+    Dc, Dtc = div_grad_csr(ien, idmap, pr["g"], neq)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    K = gdist.DistSpMV([0, neq], 0, 1, *[dev(a) for a in Kc], neq, loopback=True)           # half of the slab travels rank 0 → rank 0 through RCCL
+    D = gdist.DistSpMV([0, nel], 0, 1, *[dev(a) for a in Dc], neq, col_offsets=[0, neq])
+    Dt = gdist.DistSpMV([0, neq], 0, 1, *[dev(a) for a in Dtc], nel, col_offsets=[0, nel])
+    return K, D, Dt
+
+
 def test_uzawa_dist_over_rccl_one_rank(oracle):
     """The RCCL half on one GPU: the library's own communicator of one rank, g4s_transport_rccl (ncclAllReduce for every norm and dot
     product, the handles' RCCL wiring for the products). Same bar as above."""
@@ -127,12 +140,8 @@ def test_uzawa_dist_over_rccl_one_rank(oracle):
     shape = (6, 6, 4, 1)
     pr, BI, BPI = _setup(*shape, oracle)
     ien, idmap, nno, neq, nel = pr["ien"], pr["id"], pr["nno"], pr["neq"], len(pr["ien"])
-    Kc = assemble_csr(ien, idmap, pr["K"], neq)
-    Dc, Dtc = div_grad_csr(ien, idmap, pr["g"], neq)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    K = gdist.DistSpMV([0, neq], 0, 1, *[dev(a) for a in Kc], neq, loopback=True)           # half of the slab travels rank 0 → rank 0 through RCCL
-    D = gdist.DistSpMV([0, nel], 0, 1, *[dev(a) for a in Dc], neq, col_offsets=[0, neq])
-    Dt = gdist.DistSpMV([0, neq], 0, 1, *[dev(a) for a in Dtc], nel, col_offsets=[0, nel])
+    K, D, Dt = _one_rank_over_rccl(pr, neq, nel)
     imp, scale, vlow, steps = 1e-6, 1.0, 500, 40
     v_res = float(np.linalg.norm(pr["F"]))
     prm = capi.StokesParams(imp, scale, v_res, vlow, steps, 0, 0)
@@ -143,5 +152,41 @@ def test_uzawa_dist_over_rccl_one_rank(oracle):
                                                                        pr["bc"], pr["F"], np.zeros(neq), np.zeros(nel), imp, scale, v_res, vlow, steps, 0, 0)
     assert res.outer_iterations == cnt_o
     assert np.allclose(V.cpu().numpy(), Vo, rtol=0, atol=1e-8 * np.abs(Vo).max()) and np.allclose(P.cpu().numpy(), Po, rtol=0, atol=1e-7 * np.abs(Po).max())
+    for h in (K, D, Dt):
+        h.close()
+
+
+def test_uzawa_dist_speculation_and_its_fallback_are_bit_identical(oracle, monkeypatch):
+    """The partitioned loop's three ways through the same arithmetic — speculation that holds (default), speculation that never holds
+    (G4S_CG_FIRST_BATCH=1: every solve is continued and the rest of the iteration enqueued twice), no speculation (G4S_STOKES_SYNC=1) — give the
+    same outer and inner counts and bit-identical V, P and history, for an odd and an even number of outer iterations (the ping-pong copy-back
+    runs and is skipped) and for a converged run. One rank over the library's RCCL loopback; the pin the single-device loop has in
+    test_stokes_gpu.py."""
+    from g4s_amd import capi, dist as gdist
+    pr, BI, BPI = _setup(6, 6, 4, 1, oracle)
+    neq, nel = pr["neq"], len(pr["ien"])
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    K, D, Dt = _one_rank_over_rccl(pr, neq, nel)
+    tr = gdist.rccl_transport(K.comm)
+    BId, BPId, vmd, ard, bcd, Fd = dev(BI), dev(BPI), dev(np.repeat(pr["nmass"], 3)), dev(pr["area"]), dev(pr["bc"]), dev(pr["F"])
+    v_res = float(np.linalg.norm(pr["F"]))
+    outs = {}
+    for steps in (3, 4, 40):                                       # capped at an odd and at an even count, converged
+        for mode in ("default", "never_holds", "sync"):
+            monkeypatch.delenv("G4S_CG_FIRST_BATCH", raising=False)
+            monkeypatch.delenv("G4S_STOKES_SYNC", raising=False)
+            if mode == "never_holds":
+                monkeypatch.setenv("G4S_CG_FIRST_BATCH", "1")
+            if mode == "sync":
+                monkeypatch.setenv("G4S_STOKES_SYNC", "1")
+            prm = capi.StokesParams(1e-6, 1.0, v_res, 500, steps, 0, 0)
+            V, P = torch.zeros(neq, dtype=torch.float64, device="cuda"), torch.zeros(nel, dtype=torch.float64, device="cuda")
+            res, hist = gdist.stokes_uzawa_dist(K, D, Dt, tr, BId, BPId, vmd, ard, pr["volume"], bcd, Fd, V, P, prm, hist_lines=steps + 1)
+            outs[(steps, mode)] = (res.outer_iterations, res.inner_iterations, V.cpu().numpy(), P.cpu().numpy(), hist)
+        a, b, c = outs[(steps, "default")], outs[(steps, "never_holds")], outs[(steps, "sync")]
+        assert a[0] == b[0] == c[0] and a[1] == b[1] == c[1], (steps, a[:2], b[:2], c[:2])
+        for k in (2, 3, 4):
+            assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], c[k]), (steps, k)
+    assert outs[(3, "default")][0] == 3 and outs[(4, "default")][0] == 4 and outs[(40, "default")][0] > 4
     for h in (K, D, Dt):
         h.close()
