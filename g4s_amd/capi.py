@@ -19,6 +19,7 @@ BC_ACCUMULATE, BC_BATCH = 262144, 16                                     # g4s_b
 CC_SYMMETRIC = 32768                                                     # g4s_connected_components: the pattern is declared symmetric (g4s.h)
 KCORE_BATCH, KCORE_FULL = 16, 2**31 - 1                                  # g4s_kcore: launches per state read at least; max_k of the full decomposition (g4s.h)
 SCC_BATCH = 16                                                           # g4s_strongly_connected_components: launches per state read at least (g4s.h)
+MSF_MAXIMUM, MSF_BATCH = 1048576, 16                                     # g4s_minimum_spanning_forest: the maximum forest; launches per state read at least (g4s.h)
 KTRUSS_BATCH, KTRUSS_FULL = 16, 2**31 - 1                                # g4s_ktruss: launches per state read at least; max_k of the full decomposition (g4s.h)
 COLOR_LARGEST_FIRST, COLOR_BATCH, COLOR_MASK_COLORS, COLOR_WINDOW = 524288, 16, 64, 256   # g4s_color: key := degree; launches per state read; mask width; scan window (g4s.h)
 EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
@@ -80,6 +81,12 @@ class SCCInfo(C.Structure):
     _fields_ = [("components", C.c_int64), ("largest", C.c_int64), ("largest_label", C.c_int32), ("trimmed", C.c_int32), ("pivot", C.c_int32),
                 ("pivot_size", C.c_int32), ("color_rounds", C.c_int32), ("reserved", C.c_int32), ("edges_walked", C.c_int64), ("launches", C.c_int32),
                 ("resumes", C.c_int32), ("host_waits", C.c_int32), ("built_transpose", C.c_int32)]
+
+
+class MSFInfo(C.Structure):
+    """g4s_msf_info: what a g4s_minimum_spanning_forest call found and did."""
+    _fields_ = [("components", C.c_int64), ("edges", C.c_int64), ("weight", C.c_double), ("entries_walked", C.c_int64), ("rounds", C.c_int32),
+                ("launches", C.c_int32), ("resumes", C.c_int32), ("host_waits", C.c_int32)]
 
 
 class KCoreInfo(C.Structure):
@@ -246,6 +253,7 @@ SIGNATURES = {
     "g4s_triangle_count": (C.c_int, [C.c_int32, vp, vp, i64p, C.c_uint, C.POINTER(MaskedInfo), vp]),
     "g4s_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(CCInfo), vp]),
     "g4s_strongly_connected_components": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(SCCInfo), vp]),
+    "g4s_minimum_spanning_forest": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(MSFInfo), vp]),
     "g4s_kcore": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_uint, C.POINTER(KCoreInfo), vp]),
     "g4s_ktruss": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(KTrussInfo), vp]),
     "g4s_color": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint, C.POINTER(ColorInfo), vp]),

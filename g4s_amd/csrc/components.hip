@@ -7,7 +7,7 @@
 //              `if (st->invalid) return`, so an id is never dereferenced before it has been checked. Nothing is read back in between.
 //   sample     round r = 0 … rounds − 1: vertex v links itself to its r-th stored neighbour; a compress after every round (without it the second
 //              round walks the first round's chains: 1000 hops per vertex on the 1000 × 1000 grid).
-//   link(u,v)  a, b = parent[u], parent[v]; while a != b: high / low = max / min; if parent[high] == low, done; if parent[high] == high, one
+//   link(u,v)  (link_from of union_find.hpp, shared with msf.hip) a, b = parent[u], parent[v]; while a != b: high / low = max / min; if parent[high] == low, done; if parent[high] == high, one
 //              atomicCAS(parent + high, high, low) — done when it succeeds; otherwise go on from (parent[p], parent[low]) where p is what the load or
 //              the FAILED CAS returned (p < high). parent[x] <= x always holds, so max(a, b) strictly decreases: at most `high` turns, no lane ever
 //              waits for another, nothing spins. The smaller id wins every hook, so the final root is the minimum id: the canonical label.
@@ -30,6 +30,7 @@
 #include "common.hpp"
 #include "frontier.hpp"
 #include "call_util.hpp"
+#include "union_find.hpp"
 #include <algorithm>
 #include <climits>
 
@@ -37,8 +38,6 @@ namespace {
 
 constexpr int kMaxRounds = 4;
 constexpr int kRoundsDefault = 2;
-constexpr int kJumpHops = 16;        // a pass moves a vertex this many hops up
-constexpr int kJumpPasses = 8;       // 16^8 = 2^32 > any depth
 constexpr int kCompressions = kMaxRounds + 1;
 constexpr int kSamples = 1024;       // vertices looked at by the pick
 constexpr size_t kStateBytes = 512;
@@ -54,24 +53,6 @@ struct CcState {
     int pending[kCompressions * (kJumpPasses + 1)];
 };
 static_assert(sizeof(CcState) <= kStateBytes, "state block");
-
-__device__ __forceinline__ void st_(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-
-// Union of the trees of a and b (ancestors, possibly former ones, of the edge's two ends). max(a, b) strictly decreases: bounded, wait-free.
-__device__ __forceinline__ void link_from(int a, int b, int *parent)
-{
-    while (a != b) {
-        const int high = a > b ? a : b, low = a < b ? a : b;
-        int p = ld(parent + high);
-        if (p == low) return;
-        if (p == high) {
-            p = (int)atomicCAS(parent + high, high, low);
-            if (p == high) return;                                 // hooked: high was a root
-        }
-        a = ld(parent + p);                                        // p < high: what the load or the failed CAS returned
-        b = ld(parent + low);
-    }
-}
 
 __global__ __launch_bounds__(WG) void cc_open_rows_kernel(int n, const int *__restrict__ rowptr, int *__restrict__ parent, int *__restrict__ count, CcState *st)
 {
@@ -104,15 +85,7 @@ __global__ __launch_bounds__(WG) void cc_sample_kernel(int n, int r, const int *
 __global__ __launch_bounds__(WG) void cc_jump_kernel(int n, int *parent, CcState *st, int slot, int first)
 {
     if (st->invalid || (!first && !st->pending[slot])) return;
-    int more = 0;
-    for (long long v = (long long)blockIdx.x * WG + threadIdx.x; v < n; v += (long long)gridDim.x * WG) {
-        const int p0 = ld(parent + v);
-        int p = p0, g = ld(parent + p);
-        for (int h = 1; h < kJumpHops && g != p; ++h) { p = g; g = ld(parent + p); }
-        if (p != p0) st_(parent + v, p);
-        more |= g != p;
-    }
-    if (more) atomicOr(&st->pending[slot + 1], 1);
+    if (jump_pass(n, parent)) atomicOr(&st->pending[slot + 1], 1);
 }
 
 __global__ __launch_bounds__(WG) void cc_pick_kernel(int n, const int *__restrict__ parent, CcState *st, int allow_skip)

@@ -15,6 +15,8 @@ Names and argument meaning follow the reference so that tests read like tests of
   connected_components — canonical labels (smallest member id) of the weakly connected components of a pattern (g4s_connected_components)
   strongly_connected_components — canonical labels of the strongly connected components of a directed pattern (g4s_strongly_connected_components);
                    compact_labels (labels → 0 … k−1) and condensation (the DAG of the components) are compositions of existing device calls
+  minimum_spanning_forest — the positions of the entries of the minimum / maximum spanning forest of a weighted undirected graph
+                   (g4s_minimum_spanning_forest); spanning_forest_csr (the forest as a CSR) is a composition of existing device calls
   ktruss         — truss numbers, peel rounds and supports of the edges of a symmetric pattern (g4s_ktruss); ktruss_subgraph is a composition of it
   kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
   color          — greedy colouring in a priority order (g4s_color); color_smallest_last, maximal_independent_set and color_classes go with it
@@ -225,6 +227,11 @@ class CSR:
         """Canonical labels of the strongly connected components of the directed graph this matrix stores by out-edges —
         strongly_connected_components(self, …). Needs no plan."""
         return strongly_connected_components(self, transpose, return_info)
+
+    def minimum_spanning_forest(self, maximum=False, return_labels=False):
+        """The positions of the entries of the minimum (maximum) spanning forest of the undirected graph this matrix stores, weights = values —
+        minimum_spanning_forest(self, …). Needs no plan."""
+        return minimum_spanning_forest(self, maximum, return_labels)
 
     def kcore(self, max_k=None, return_round=False, return_info=False):
         """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
@@ -746,6 +753,77 @@ def strongly_connected_components(A, transpose=None, return_info=False):
         labels = torch.from_numpy(out[:n]).cuda()
     inf = {n_: getattr(info, n_) for n_, _ in capi.SCCInfo._fields_ if n_ != "reserved"}
     return (labels, inf) if return_info else labels
+
+
+def minimum_spanning_forest(A, maximum=False, return_labels=False):
+    """(positions, info) of the minimum spanning forest of the undirected graph whose edges are the stored off-diagonal entries of the square matrix A
+    (g4s_minimum_spanning_forest): positions (int32 device tensor of info["edges"]) = the ascending indices k into colids / values of the forest's
+    entries, under the strict order (w, min(i,j), max(i,j), k) — the forest Kruskal builds scanning the entries in that order, the same on every run.
+    A is a CSR (the weights are its values), or a (rowptr, colids) pair (all weights equal: a spanning forest) or a (rowptr, colids, values) triple of
+    device tensors or of numpy arrays (host pointers; the results come back on the device all the same). maximum=True gives the maximum spanning forest
+    (only the weight is reversed). return_labels=True returns (positions, labels, info), labels being those of connected_components. info is the dict
+    of g4s_msf_info. Synchronous; no plan is built. ValueError (before any GPU call) for a CSR that is not square, a tuple of the wrong length, values
+    that do not match colids, and flags that are not bools."""
+    for name, v in (("maximum", maximum), ("return_labels", return_labels)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    if isinstance(A, (tuple, list)):
+        if len(A) not in (2, 3):
+            raise ValueError("expected a CSR, a (rowptr, colids) pair or a (rowptr, colids, values) triple")
+        rowptr, colids, n = _pattern_of(tuple(A[:2]), "a spanning forest")
+        values = A[2] if len(A) == 3 else None
+    else:
+        rowptr, colids, n = _pattern_of(A, "a spanning forest")
+        values = A.values
+    on_device = isinstance(rowptr, torch.Tensor)
+    size = (lambda a: int(a.numel())) if on_device else (lambda a: int(np.asarray(a).size))
+    if values is not None and (isinstance(values, torch.Tensor) != on_device or size(values) != size(colids)):
+        raise ValueError("values must be of the same kind and length as colids")
+    _require_gpu()
+    info, null = capi.MSFInfo(), C.c_void_p(0)
+    flags = capi.MSF_MAXIMUM if maximum else 0
+    fn = capi.load().g4s_minimum_spanning_forest
+    if on_device:
+        assert rowptr.is_cuda and colids.is_cuda and rowptr.dtype == torch.int32 and colids.dtype == torch.int32
+        assert values is None or (values.is_cuda and values.dtype == torch.float64)
+        rowptr, colids = rowptr.contiguous(), colids.contiguous()
+        values = None if values is None else values.contiguous()
+        edges = torch.empty(max(n - 1, 0), dtype=torch.int32, device=rowptr.device)
+        labels = torch.empty(n, dtype=torch.int32, device=rowptr.device) if return_labels else None
+        capi.check(fn(n, _ptr_nn(rowptr), _ptr_nn(colids), null if values is None else _ptr_nn(values), _ptr_nn(edges), null if labels is None else _ptr_nn(labels),
+                      flags | capi.DEVICE_POINTERS, C.byref(info), _stream()))
+        positions = edges[:info.edges]
+    else:
+        rowptr, colids = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32)
+        values = None if values is None else np.ascontiguousarray(values, np.float64)
+        out, lab = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32)
+        spare = np.zeros(1, np.float64)                                 # an empty array is passed as a pointer that is not read
+        P = lambda a: C.c_void_p(a.ctypes.data if a.size else spare.ctypes.data)
+        capi.check(fn(n, P(rowptr), P(colids), null if values is None else P(values), P(out), P(lab) if return_labels else null, flags | capi.HOST_POINTERS,
+                      C.byref(info), _stream()))
+        positions = torch.from_numpy(out[:info.edges]).cuda()
+        labels = torch.from_numpy(lab[:n]).cuda() if return_labels else None
+    inf = {n_: getattr(info, n_) for n_, _ in capi.MSFInfo._fields_}
+    return (positions, labels, inf) if return_labels else (positions, inf)
+
+
+def spanning_forest_csr(A, positions, symmetric=True):
+    """The forest that minimum_spanning_forest(A) found, as a device CSR of A's shape: the entries of the CSR A at `positions` (an int32 device tensor
+    of indices into A.colids), rows ascending; with symmetric=True (the default) every edge is stored in both directions — 2 · len(positions) entries
+    — as connected_components(…, symmetric=True), bfs and sssp want an undirected graph. A composition of existing device calls: csr_row_indices, two
+    gathers, csr_from_coo and, for symmetric=True, csr_symmetrise. No new kernel. ValueError (before any GPU call) for an A that is not a square CSR
+    and a `symmetric` that is not a bool."""
+    if not isinstance(symmetric, (bool, np.bool_)):
+        raise ValueError(f"symmetric must be a bool, not {symmetric!r}")
+    if not isinstance(A, CSR) or A.rows != A.cols:
+        raise ValueError("spanning_forest_csr needs the square CSR the positions point into")
+    _require_gpu()
+    assert positions.is_cuda and positions.dtype == torch.int32 and positions.dim() == 1
+    n, at = int(A.rows), positions.long()
+    row = csr_row_indices(A.rowptr, A.nnz)[at]
+    rp, ci, va = csr_from_coo(row, A.colids[at], A.values[at], n, n, dup="first")
+    f = CSR(rp, ci, va, n, n)
+    return csr_symmetrise(f, "first") if symmetric else f
 
 
 def compact_labels(labels):

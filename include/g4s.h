@@ -112,9 +112,9 @@ typedef struct g4s_csr_info {
  * Concurrency: a handle supports ONE product in flight at a time — g4s_spmv uses per-handle workspaces (the partial sums of split long
  * rows on the streaming path, the product buffer and the gathered hot columns on the blocked path), so two g4s_spmv calls on the same
  * handle must be ordered (same stream, or an event between them); different handles are independent.
- * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py, for g4s_ktruss tests/test_ktruss_threads_gpu.py, for g4s_strongly_connected_components tests/test_scc_threads_gpu.py —, every result compared bit for bit):
+ * Threads and streams (what tests/test_concurrency_gpu.py pins — for g4s_csr_extract_* tests/test_extract_threads_gpu.py, for g4s_kcore tests/test_kcore_threads_gpu.py, for g4s_color tests/test_color_threads_gpu.py, for g4s_ktruss tests/test_ktruss_threads_gpu.py, for g4s_strongly_connected_components tests/test_scc_threads_gpu.py, for g4s_minimum_spanning_forest tests/test_msf_threads_gpu.py —, every result compared bit for bit):
  *   Different host threads may call at the same time: the one-call and the two-call SpGEMM, g4s_spgemm_masked, g4s_triangle_count,
- *     g4s_connected_components, g4s_strongly_connected_components, g4s_kcore, g4s_color, g4s_ktruss, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
+ *     g4s_minimum_spanning_forest, g4s_connected_components, g4s_strongly_connected_components, g4s_kcore, g4s_color, g4s_ktruss, g4s_csr_transpose, the four g4s_csr_ewise_* / g4s_csr_select_* calls, g4s_csr_from_coo_symbolic / _numeric, g4s_csr_row_indices, g4s_csr_extract_symbolic / _numeric, the one-shot g4s_spmv_csr_i32_f64, g4s_csr_create / g4s_csr_destroy of their own handles,
  *     g4s_sssp / g4s_bfs and the products on a handle the thread owns, g4s_free / g4s_dev_free of their outputs and g4s_trim. Each thread
  *     passes a stream of its own (or the NULL stream); inputs that are only read may be shared. The library's scratch is per thread and per call; the
  *     freed blocks it caches per process are handed to another thread only after the stream that used them has been synchronised.
@@ -800,6 +800,68 @@ typedef struct g4s_scc_info {
 g4s_status g4s_strongly_connected_components(int32_t n, const int32_t *rowptr, const int32_t *colids,
                                              const int32_t *trowptr /* may be NULL */, const int32_t *tcolids /* may be NULL */,
                                              int32_t *labels, unsigned flags, g4s_scc_info *info /* may be NULL */, void *stream);
+
+/* Minimum (or maximum) spanning forest: edges[0 … info.edges) (int32, device or host like the other arrays, only written) = the positions k in colids
+ * of the forest's entries, ascending, for the undirected weighted graph on vertices 0 … n−1 in which every stored entry (i, j) with i != j of the n×n
+ * CSR is an edge {i, j} of weight values[k], direction ignored — scipy.sparse.csgraph.minimum_spanning_tree and networkx's minimum_spanning_edges with
+ * one fixed answer. Raw arrays, no handle, no plan.
+ *   Graph: the rule of g4s_connected_components. Self-loops (never chosen), repeated columns, unsorted rows, empty rows, an upper triangle alone and a
+ *     fully symmetric pattern are all valid; a symmetric pattern and its upper triangle give the same forest as sets of vertex pairs. values == NULL: all
+ *     weights equal, which gives a spanning forest.
+ *   Order: entries are ordered by the strict total order (w, min(i,j), max(i,j), k), w compared as a double; −0.0 equals +0.0 (canonicalised before the
+ *     bit-ordered key), ±inf are ordinary weights, a NaN is found on the device and returns G4S_ERR_INVALID. The result is the forest Kruskal builds
+ *     when it scans the entries in that order: unique, so the outputs are the same integers and the same weight bits on every run, stream, launch grid,
+ *     batch size and tuning switch. G4S_MSF_MAXIMUM (no other entry point accepts it) orders by (−w, min, max, k): the maximum spanning forest; only
+ *     the weight is reversed, ties still go to the smaller pair and position.
+ *   Outputs: edges has room for max(n − 1, 0) values; info.edges of them are written, ascending, the rest is left untouched. labels (n int32, may be
+ *     NULL) = the canonical component labels, the integers g4s_connected_components writes on the same pattern. info.weight = the sum of the forest's
+ *     weights added in ascending position order in a shape fixed by info.edges alone (tiles of 2048, 8 consecutive values per lane, a shuffle ladder,
+ *     four waves left to right; then the tile sums the same way): the same bits on every run; 0.0 with values == NULL. info may be NULL.
+ *   Checks before any HIP call (G4S_ERR_INVALID, g4s_last_error names the argument): any flag bit other than G4S_DEVICE_POINTERS and G4S_MSF_MAXIMUM,
+ *     a NULL rowptr with n > 0, a NULL edges with n > 1, a NULL colids with n > 0, a negative n, and edges or labels that overlap an input or each
+ *     other (with device pointers, where rowptr[n] is not known yet, colids and values stand in with their first element). On the device, before any
+ *     id is an index: rowptr[0] == 0, rowptr non-decreasing, ids in [0, n), no NaN — G4S_ERR_INVALID, outputs unspecified afterwards. n == 0 and
+ *     nnz == 0 are valid (labels[v] = v, info.edges = 0). On a capturing stream the call returns G4S_ERR_INVALID and enqueues nothing.
+ *   Algorithm: Borůvka rounds on the union-find forest of g4s_connected_components. A round walks the live rows (rows above 4096 entries
+ *     by all workgroups) once per stage of the key — the 64-bit image of the weight, then (min << 32 | max) among the entries that have the winning
+ *     weight, then k among those that have both; two stages with values == NULL —, each a 64-bit (32-bit) atomicMin per root behind a reduction across
+ *     the wave where its lanes share the root; then one thread per root with a winner appends k to the forest (of two roots that chose the same entry
+ *     the smaller one) and hooks the two trees by compare-and-swap, the smaller id winning; pointer jumping flattens the forest; rows that saw no
+ *     outgoing entry leave the live list. rounds <= ceil(log2 n) + 1. Then the positions are sorted and the weights summed.
+ *   Synchronous: runs on `stream` and returns when the outputs and info are complete. The host enqueues whole rounds (13 or 14 launches) blind, at least
+ *     G4S_MSF_BATCH launches behind one read of the 120-byte state, doubling up to 64; every kernel returns at once when the stop word is set. Hence
+ *     info.host_waits <= info.launches / 16 + 3: one wait per batch, one behind the sort and the sum, one for the copy to host arrays. The grid of the
+ *     walks follows the live entries seen at the last read; live rows that outgrow the grid of the first batch stop it, and the next batch resumes on a
+ *     larger grid (info.resumes) — the live rows only shrink afterwards, and by default the first grid is large enough, so only G4S_MSF_FIRST_GRID
+ *     makes a resume happen. Scratch: a 256-byte state block, 36·n bytes (two 8-byte and one 4-byte key word per vertex, the stamps, two live lists, the
+ *     forest list; 40·n with labels == NULL), two hub lists of 4·min(n, 2^19), nothing of the size of nnz, plus device copies of the arrays with host
+ *     pointers; from the library's caching allocator, released before the call returns. No process-wide state: different host threads may call at the
+ *     same time (tests/test_msf_threads_gpu.py).
+ *   Environment: G4S_MSF_FIRST_GRID (workgroups of the first batch's walks; default 0 = automatic), G4S_MSF_WAVE_MIN (default 1; 0: every
+ *     lane sends its own atomic). The outputs do not depend on them.
+ *   Where it loses (profiles/msf.txt, one MI355X, tools/bench_msf.py, seeded symmetric integer weights): against scipy's minimum_spanning_tree on the
+ *     host with its copy, on none of the measured graphs — the configs[0] grid (5.0 M entries) takes 5.58 ms in 10 rounds (8.6 M entries walked per
+ *     round) against 297 ms, the symmetrised R-MAT-20 21.2 ms in 7 rounds against 2233 ms, configs[1] symmetrised (195.8 M entries) 147.0 ms in 6 rounds
+ *     (scipy not measured at that size). The expected bad case, a path of 4 M vertices with increasing weights — one round whose hooks form a single
+ *     chain of n − 1 — has the smallest margin: 6.0 ms against 75 ms, 12.5x; pointer jumping takes the chain 16 hops a pass. It loses to itself by 3x
+ *     when weights are given (three walks of the live entries per round instead of two, and more rounds: values == NULL takes 1.86 / 6.5 / 48.5 ms on
+ *     the three graphs), and every call pays 13 or 14 launches per round and at least two waits, which is all a tiny graph costs: a path of 1000
+ *     vertices takes 0.23 ms against 0.66 ms for scipy, 2.8x, a floor of about 0.2 ms below which a host algorithm is ahead. Per-kernel times and the two switches as A/B timings were not measured. */
+#define G4S_MSF_MAXIMUM 1048576u    /* the maximum spanning forest: the order is (−w, min, max, k) */
+#define G4S_MSF_BATCH 16            /* launches enqueued behind one read of the state, at least (whole rounds; doubles up to 64 within a call) */
+typedef struct g4s_msf_info {
+    int64_t components;      /* number of distinct labels: n − edges                                             */
+    int64_t edges;           /* positions written to `edges`                                                     */
+    double weight;           /* the sum of their weights; 0.0 with values == NULL                                */
+    int64_t entries_walked;  /* stored entries walked by the find stages, all rounds and stages                  */
+    int32_t rounds;          /* Borůvka rounds run, the last one (which may find nothing) included               */
+    int32_t launches;        /* kernels enqueued, those that returned at once included (the sort: 3 per pass)    */
+    int32_t resumes;         /* batches restarted because the live rows outgrew the launch grid                  */
+    int32_t host_waits;      /* times the call waited for the device                                             */
+} g4s_msf_info;              /* 48 bytes */
+g4s_status g4s_minimum_spanning_forest(int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values /* may be NULL */,
+                                       int32_t *edges, int32_t *labels /* may be NULL */, unsigned flags,
+                                       g4s_msf_info *info /* may be NULL */, void *stream);
 
 /* Greedy colouring and independent sets: color[v] (n int32, device or host like the other arrays, only written) = the first-fit colour of v — the
  * smallest colour >= 0 not held by a neighbour of higher priority — i.e. sequential greedy colouring of the vertices in decreasing priority: what

@@ -8,6 +8,7 @@
 //   MaskedSpGEMM(a,b,mask,c,multop,addop)   C⟨M⟩ = A ⊗ B at the positions of the pattern `mask` only; TriangleCount(a): Σ (L·L⟨L⟩) of the lower triangle
 //   ConnectedComponents(a,labels,symmetric)   labels[v] = the smallest vertex id of v's weakly connected component (every stored entry an edge)
 //   StronglyConnectedComponents(a,labels)  labels[v] = the smallest vertex id of v's strongly connected component of the directed pattern `a` (g4s_strongly_connected_components)
+//   MinimumSpanningForest(a,edges,labels), MaximumSpanningForest(…)   the positions of the entries of the minimum / maximum spanning forest of the weighted undirected graph `a` (g4s_minimum_spanning_forest)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
 //   KTruss(a,truss,round,support,max_k)   per stored entry: the truss number of its edge in the symmetric pattern `a`, the peel frontier that removed it, its triangles (g4s_ktruss)
 //   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
@@ -216,6 +217,29 @@ void StronglyConnectedComponents(const CSR<IT, NT> &a, int32_t *labels, g4s_scc_
     int32_t none = 0;
     check(g4s_strongly_connected_components(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, nullptr, nullptr, a.rows ? labels : &none, G4S_HOST_POINTERS, info,
                                             nullptr), "StronglyConnectedComponents");
+}
+
+// edges[0 … info->edges) = the ascending positions, in a.colids / a.values, of the entries of the minimum spanning forest of the undirected graph whose
+// edges are the stored off-diagonal entries of the square matrix `a`, weights = values, under the strict order (w, min, max, position) — the forest
+// Kruskal builds in that order (g4s_minimum_spanning_forest, host arrays). edges has room for max(a.rows − 1, 0) values. labels (a.rows values, may be
+// NULL): the canonical component labels. weighted = false reads no values: all weights equal, a spanning forest. Returns the number of positions.
+// MaximumSpanningForest is the same call with G4S_MSF_MAXIMUM: only the weight is reversed.
+template <typename IT, typename NT>
+int64_t MinimumSpanningForest(const CSR<IT, NT> &a, int32_t *edges, int32_t *labels = nullptr, g4s_msf_info *info = nullptr, bool weighted = true, unsigned flags = 0u)
+{
+    if (a.rows != a.cols) throw std::runtime_error("MinimumSpanningForest: the matrix is not square");
+    const IT zero = 0;                                      // an empty CSR holds no arrays: nothing is read or written for rows == 0
+    g4s_msf_info mine = {};
+    check(g4s_minimum_spanning_forest(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, weighted ? a.values : nullptr, edges, a.rows ? labels : nullptr,
+                                      G4S_HOST_POINTERS | flags, &mine, nullptr), "MinimumSpanningForest");
+    if (info) *info = mine;
+    return mine.edges;
+}
+
+template <typename IT, typename NT>
+int64_t MaximumSpanningForest(const CSR<IT, NT> &a, int32_t *edges, int32_t *labels = nullptr, g4s_msf_info *info = nullptr, bool weighted = true)
+{
+    return MinimumSpanningForest(a, edges, labels, info, weighted, G4S_MSF_MAXIMUM);
 }
 
 // core[v] (a.rows values) = the largest k such that v belongs to a subgraph of the simple undirected graph `a` in which every vertex has at least k
