@@ -22,6 +22,8 @@ SCC_BATCH = 16                                                           # g4s_s
 MSF_MAXIMUM, MSF_BATCH = 1048576, 16                                     # g4s_minimum_spanning_forest: the maximum forest; launches per state read at least (g4s.h)
 KTRUSS_BATCH, KTRUSS_FULL = 16, 2**31 - 1                                # g4s_ktruss: launches per state read at least; max_k of the full decomposition (g4s.h)
 COLOR_LARGEST_FIRST, COLOR_BATCH, COLOR_MASK_COLORS, COLOR_WINDOW = 524288, 16, 64, 256   # g4s_color: key := degree; launches per state read; mask width; scan window (g4s.h)
+TRSV_UPPER, TRSV_UNIT_DIAGONAL, TRSV_NO_CHAINS = 2097152, 4194304, 8388608   # g4s_sptrsv_analyse: the triangle, the diagonal, one launch per level (g4s.h)
+TRSV_WAVE_ROW, TRSV_CHAIN_WIDTH, TRSV_CHAIN_LEVELS, TRSV_HUB_ROW = 32, 256, 1024, 4096   # g4s_sptrsv: the row classes of the documented sum and the chaining rule (g4s.h)
 EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
 COMBINE_PLUS, COMBINE_TIMES, COMBINE_MIN, COMBINE_MAX, COMBINE_FIRST, COMBINE_SECOND = 0, 1, 2, 3, 4, 5
 DUP_KEEP = -1                                                            # g4s_csr_from_coo_*: dup is DUP_KEEP or a COMBINE_* value (g4s.h)
@@ -106,6 +108,13 @@ class ColorInfo(C.Structure):
     """g4s_color_info: what a g4s_color call found and did."""
     _fields_ = [("edges_walked", C.c_int64), ("class0", C.c_int64), ("colors", C.c_int32), ("rounds", C.c_int32), ("overflow", C.c_int32),
                 ("launches", C.c_int32), ("resumes", C.c_int32), ("scan_resumes", C.c_int32), ("host_waits", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TRSVInfo(C.Structure):
+    """g4s_trsv_info: what a g4s_sptrsv_analyse call found and did, and what a solve on its handle costs."""
+    _fields_ = [("nnz_triangle", C.c_int64), ("n", C.c_int32), ("levels", C.c_int32), ("widest_level", C.c_int32), ("launches_per_solve", C.c_int32),
+                ("chains", C.c_int32), ("bad_row", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32), ("resumes", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class EwiseInfo(C.Structure):
@@ -257,6 +266,11 @@ SIGNATURES = {
     "g4s_kcore": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_uint, C.POINTER(KCoreInfo), vp]),
     "g4s_ktruss": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(KTrussInfo), vp]),
     "g4s_color": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint, C.POINTER(ColorInfo), vp]),
+    "g4s_sptrsv_analyse": (C.c_int, [C.POINTER(vp), C.c_int32, vp, vp, vp, vp, C.c_uint, C.POINTER(TRSVInfo), vp]),
+    "g4s_sptrsv_solve": (C.c_int, [vp, vp, vp, vp]),
+    "g4s_sptrsv_update_values": (C.c_int, [vp, vp, C.c_uint, vp]),
+    "g4s_sptrsv_get_info": (C.c_int, [vp, C.POINTER(TRSVInfo)]),
+    "g4s_sptrsv_destroy": (C.c_int, [vp]),
     "g4s_csr_ewise_symbolic": (C.c_int, [C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64p, C.c_uint, C.POINTER(EwiseInfo), vp]),
     "g4s_csr_ewise_numeric": (C.c_int, [C.c_int, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
     "g4s_csr_select_symbolic": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, i64p, C.c_uint, vp]),

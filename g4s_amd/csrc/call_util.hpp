@@ -1,6 +1,6 @@
 // call_util.hpp — what the entry points that take host or device arrays and read a verdict back share (ewise.hip, extract.hip, coo.hip, spgemm_masked.hip,
 // transpose.hip's g4s_csr_row_indices, pagerank.hip, traverse.hip, betweenness.hip and the graph calls on raw CSR arrays: components.hip, kcore.hip, color.hip,
-// ktruss.hip, scc.hip, msf.hip): an owned block of the caching allocator, the carver of a work block, the staging frame of a call with host pointers, the overlap
+// ktruss.hip, scc.hip, msf.hip, and trsv.hip): an owned block of the caching allocator, the carver of a work block, the staging frame of a call with host pointers, the overlap
 // check of host arrays, the capture refusal, the capped grid, the combiners, and for the graph calls the environment switch, the launch counts and the
 // text of a refused pattern.
 #pragma once

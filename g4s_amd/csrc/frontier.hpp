@@ -1,4 +1,4 @@
-// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, components.hip, kcore.hip, color.hip, ktruss.hip, scc.hip, msf.hip; DESIGN
+// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, components.hip, kcore.hip, color.hip, ktruss.hip, scc.hip, msf.hip, trsv.hip; DESIGN
 // §4.11): the walk over the entries of a level's rows, balanced over entries (walk_tiles for ordinary rows, walk_hubs for long ones), the opening pass
 // of the calls on raw CSR arrays (open_rows: the row check; open_ids / open_hubs: the check of the column ids), the one-atomicAdd-per-wave append and
 // the append to a frontier that keeps a hub list (append_frontier), the two ends of a step kernel (step_runs; turn_page: the last workgroup to take a

@@ -1,4 +1,4 @@
-// step_batch.hpp — the host side of the stepped device loops (traverse.hip, betweenness.hip, kcore.hip, ktruss.hip, color.hip, scc.hip, msf.hip; pagerank.hip takes
+// step_batch.hpp — the host side of the stepped device loops (traverse.hip, betweenness.hip, kcore.hip, ktruss.hip, color.hip, scc.hip, msf.hip, trsv.hip; pagerank.hip takes
 // kBatchMax), in plain C++ (no HIP: tests/cpp/step_batch_test.cpp runs it on the host under a sanitizer). The host enqueues a batch of step launches
 // blind, reads the state once per batch and sizes the next batch's grid from the frontier it saw; a frontier that outgrows that grid stops the batch
 // (stop = 4, frontier.hpp). For the level peels (kcore.hip, ktruss.hip through level_peel.hpp): the words of their state blocks that the page turn and

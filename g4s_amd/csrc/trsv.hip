@@ -1,0 +1,723 @@
+// trsv.hip — g4s_sptrsv_* (include/g4s.h): a level-scheduled sparse triangular solve on the lower or upper triangle of an n × n CSR. DESIGN §4.20.
+//
+// The analysis is paid once. It is a Kahn peel of the dependency DAG on the stepped driver of the graph calls (frontier.hpp, step_batch.hpp), the
+// pred-count peel of color.hip on another DAG: row i depends on column c for every stored off-diagonal entry (i, c) of the triangle.
+//   open     tr_open_rows_kernel: rowptr[0] == 0, non-decreasing. tr_open_ids_kernel / tr_open_hubs_kernel (return at once when the rows were bad):
+//            ids in [0, n); per triangle entry (u, v): v == u counts in dcnt[u], else in ocnt[u] and in tcnt[v], the length of row v of the transposed
+//            pattern. tr_count_kernel: the totals and the smallest row without a diagonal. One read of the state: a refusal ends here.
+//   pattern  tptr = scan(tcnt); tr_scatter_kernel walks A once more and writes row u behind a cursor of column v: the rows that wait for v, in any
+//            order (the order decides which lane appends a row, never a level).
+//   peel     tr_seed_kernel: pred[i] = ocnt[i], the rows with pred == 0 are frontier 0 (level 0). tr_step_kernel: the frontier walk over the
+//            frontier's rows of the transposed pattern; per entry v → w one atomicSub on pred[w]; the lane that sees 1 appends w and writes
+//            level[w] = the step's index + 1. One launch per level; kBatch (doubling to kBatchMax) launches behind one read of the state.
+//   layout   a stable radix sort of the rows by level (prims.hpp) gives the (level, id) order; a histogram and a scan the level offsets; a scan of
+//            the row lengths the entry offsets; tr_gather_kernel (one wave per row, ballots keep the stored order) writes each row's off-diagonal
+//            entries and behind them its diagonal entries, with the position map update_values refreshes them through.
+// The solve enqueues the launch list (trsv.hpp) and waits for nothing. Every launch solves whole levels, so a row reads only x values written behind
+// a kernel boundary or — inside a chain — by its own workgroup behind a fence and a barrier. No wave waits for another workgroup; nothing spins.
+// Memory model: a chain's rows read x with agent-scope loads (performed in L2, past whatever copy the CU's vector cache holds from an earlier level,
+// DESIGN §4.8) and every level of a chain ends with __threadfence() and __syncthreads(); a level kernel reads x with plain loads.
+// The arithmetic shape of a row (g4s.h) depends on its own entry count alone: solve_tile is the one place that computes it, for both kernels.
+#include "common.hpp"
+#include "frontier.hpp"
+#include "call_util.hpp"
+#include "prims.hpp"
+#include "trsv.hpp"
+#include <algorithm>
+#include <climits>
+#include <new>
+#include <vector>
+
+struct g4s_trsv_s {
+    int n = 0;
+    unsigned flags = 0;
+    long long nnz_in = 0;               // entries of the arrays the handle was analysed from: what update_values reads
+    long long nnz_tri = 0;
+    g4s::DevBuf block;                  // the (level, row) layout, one allocation
+    int *rowid = nullptr, *ebeg = nullptr, *noff = nullptr, *lcol = nullptr, *emap = nullptr, *loff = nullptr;
+    double *diag = nullptr, *lval = nullptr;
+    std::vector<int> loff_host;         // the level offsets, for the grids of the level launches
+    std::vector<int> lent_host;         // the entry offsets of the levels, for their strides
+    std::vector<g4s::TrLaunch> launches;
+    g4s_trsv_info info{};
+};
+
+namespace {
+
+using g4s::TrState;
+
+constexpr int kBatch = 16;                    // step launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
+constexpr int kWaveRow = G4S_TRSV_WAVE_ROW;
+constexpr int kChainWidth = G4S_TRSV_CHAIN_WIDTH;
+constexpr int kChainLevels = G4S_TRSV_CHAIN_LEVELS;
+constexpr size_t kStateBytes = 256;
+constexpr unsigned kFlagMask = G4S_DEVICE_POINTERS | G4S_TRSV_UPPER | G4S_TRSV_UNIT_DIAGONAL | G4S_TRSV_NO_CHAINS;
+static_assert(sizeof(TrState) <= kStateBytes, "state block");
+static_assert(kChainWidth == WG, "a level of a chain is one tile of the workgroup");
+static_assert(kWaveRow >= 1 && kWaveRow < kHubCut, "the three row classes");
+
+enum { KIND_SEED = 0, KIND_STEP = 1 };
+
+struct StepArgs {
+    long long grid_cap;    // a frontier with more entries than this asks for a larger grid
+    int n;
+    int hub_cap;
+    int resume;            // the first step of a batch goes on from stop == 4
+};
+
+__device__ __forceinline__ bool in_triangle(int upper, int u, int v) { return upper ? v >= u : v <= u; }
+
+// ------------------------------------------------------------------------------------------------------------------------------ the analysis
+__global__ __launch_bounds__(WG) void tr_open_rows_kernel(int n, const int *__restrict__ rowptr, TrState *st)
+{
+    open_rows(n, rowptr, &st->invalid, 1, [](long long, int, int) {});
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->bad_row = n;
+        st->nnz_in = rowptr[n];                                    // means something only on a valid rowptr, and is used only then
+    }
+}
+
+struct Counting {
+    int upper, unit;
+    int *ocnt, *dcnt, *tcnt;
+    __device__ void operator()(int, int u, int v) const
+    {
+        if (!in_triangle(upper, u, v)) return;
+        if (v == u) { if (!unit) atomicAdd(dcnt + u, 1); }
+        else { atomicAdd(ocnt + u, 1); atomicAdd(tcnt + v, 1); }
+    }
+};
+
+__global__ __launch_bounds__(WG) void tr_open_ids_kernel(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids, int *__restrict__ hubs,
+                                                         TrState *st, const Counting c)
+{
+    if (st->invalid) return;                                       // rowptr is monotone from 0 beyond this line: [0, rowptr[n]) is the colids array
+    open_ids<false>(n, hub_cap, rowptr, colids, hubs, &st->n_hub_open, &st->invalid, 2, c);
+}
+
+__global__ __launch_bounds__(WG) void tr_open_hubs_kernel(int n, int hub_cap, const int *__restrict__ rowptr, const int *__restrict__ colids,
+                                                          const int *__restrict__ hubs, TrState *st, const Counting c)
+{
+    if (st->invalid) return;
+    open_hubs<false>(n, hub_cap, rowptr, colids, hubs, &st->n_hub_open, &st->invalid, 2, c);
+}
+
+// the totals, and the smallest row that stores no diagonal entry (unit: dcnt is all zero and nobody asks)
+__global__ __launch_bounds__(WG) void tr_count_kernel(int n, int unit, const int *__restrict__ ocnt, const int *__restrict__ dcnt, TrState *st)
+{
+    if (st->invalid) return;
+    long long so = 0, sd = 0;
+    int bad = n;
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
+        const int d = dcnt[i];
+        so += ocnt[i];
+        sd += d;
+        if (!unit && d == 0 && (int)i < bad) bad = (int)i;
+    }
+    so = wave_sum(so);
+    sd = wave_sum(sd);
+    bad = wave_min(bad);
+    if ((threadIdx.x & 63) == 0) {
+        if (so) atomicAdd(&st->nnz_off, (unsigned long long)so);
+        if (sd) atomicAdd(&st->nnz_diag, (unsigned long long)sd);
+        if (bad < n) atomicMin(&st->bad_row, bad);
+    }
+}
+
+// The transposed pattern: row u behind column v's cursor, for every off-diagonal entry (u, v) of the triangle. The hub list is the opening pass's.
+__global__ __launch_bounds__(WG) void tr_scatter_kernel(int n, int hub_cap, int upper, const int *__restrict__ rowptr, const int *__restrict__ colids,
+                                                        const int *__restrict__ hubs, const int *__restrict__ tptr, int *fill, int *__restrict__ trows,
+                                                        const TrState *st)
+{
+    auto entry = [&](bool valid, int k, int u) {
+        if (!valid) return;
+        const int v = colids[k];
+        if (v != u && in_triangle(upper, u, v)) trows[tptr[v] + atomicAdd(fill + v, 1)] = u;
+    };
+    walk_tiles<int>(n, [&](int i, int &start, int &len, int &u) {
+        const int rb = rowptr[i], l = rowptr[i + 1] - rb;
+        if (l > kHubCut) return;
+        u = i;
+        start = rb;
+        len = l;
+    }, entry);
+    walk_hubs<int>(st->n_hub_open < hub_cap ? st->n_hub_open : hub_cap, [&](int h, int &start, int &len, int &u) {
+        u = hubs[h];
+        start = rowptr[u];
+        len = rowptr[u + 1] - start;
+    }, entry);
+}
+
+// The end of the seed and of a step kernel: the block's share of the built frontier's entries, then the ticket; the last block to arrive turns the
+// page (turn_page).
+__device__ __forceinline__ void finish(TrState *st, long long len_sum, int kind, const StepArgs a)
+{
+    __shared__ long long s_len[WG / 64];
+    len_sum = wave_sum(len_sum);
+    if ((threadIdx.x & 63) == 0) s_len[threadIdx.x >> 6] = len_sum;
+    if (!turn_page(&st->tickets, [&] {
+        long long ls = 0;
+        for (int w = 0; w < WG / 64; ++w) ls += s_len[w];
+        if (ls) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)ls);
+    })) return;
+    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0);
+    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
+    const int got = tail - st->end, had = st->end - st->head;      // what this kernel appended, what it walked
+    st->head = st->end; st->end = tail;
+    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
+    st->edges_cur = e; st->edges_next = 0;
+    st->tickets = 0;
+    if (kind == KIND_STEP && had > 0) st->round += 1;
+    st->stop = got == 0 ? 1 : e > a.grid_cap ? 4 : 0;
+}
+
+// Frontier 0: the rows that wait for nothing. Its page turn is a step's, without a round.
+__global__ __launch_bounds__(WG) void tr_seed_kernel(const int *__restrict__ tptr, const int *__restrict__ ocnt, int *__restrict__ pred, int *__restrict__ level,
+                                                     int *__restrict__ queue, int *hubs0, int *hubs1, TrState *st, const StepArgs a)
+{
+    int *hubs_next = st->hub_cur ? hubs0 : hubs1;
+    long long len_sum = 0;
+    for (long long i0 = (long long)blockIdx.x * WG; i0 < a.n; i0 += (long long)gridDim.x * WG) {
+        const long long i = i0 + threadIdx.x;
+        const int p = i < a.n ? ocnt[i] : -1;
+        const bool want = p == 0;
+        if (i < a.n) { pred[i] = p; level[i] = want ? 0 : -1; }
+        const int len = want ? tptr[i + 1] - tptr[i] : 0;
+        append_frontier(want, (int)i, len, a.n, a.hub_cap, queue, hubs_next, &st->tail, &st->n_hub_next, len_sum);   // appended once per call: the slot is below n
+    }
+    finish(st, len_sum, KIND_SEED, a);
+}
+
+__global__ __launch_bounds__(WG) void tr_step_kernel(const int *__restrict__ tptr, const int *__restrict__ trows, int *pred, int *level, int *queue, int *hubs0,
+                                                     int *hubs1, TrState *st, const StepArgs a)
+{
+    if (!step_runs(st->stop, a.resume)) return;                    // the same word for every block
+    const int r = st->round, head = st->head;
+    const int *hubs_cur = st->hub_cur ? hubs1 : hubs0;
+    int *hubs_next = st->hub_cur ? hubs0 : hubs1;
+    long long len_sum = 0;
+    auto entry = [&](bool valid, int k, int) {
+        bool want = false;
+        int w = 0, len = 0;
+        if (valid) {
+            w = trows[k];
+            want = atomicSub(pred + w, 1) == 1;                    // the atomic alone decides who appends w
+            if (want) {
+                level[w] = r + 1;                                  // the last column w waited for is in frontier r
+                len = tptr[w + 1] - tptr[w];
+            }
+        }
+        append_frontier(want, w, len, a.n, a.hub_cap, queue, hubs_next, &st->tail, &st->n_hub_next, len_sum);
+    };
+    walk_tiles<int>(st->end - head, [&](int i, int &start, int &len, int &u) {
+        u = queue[head + i];
+        const int rb = tptr[u], l = tptr[u + 1] - rb;
+        if (l > kHubCut) return;                                   // walked out of the hub list
+        start = rb;
+        len = l;
+    }, entry);
+    walk_hubs<int>(st->n_hub_cur < a.hub_cap ? st->n_hub_cur : a.hub_cap, [&](int h, int &start, int &len, int &u) {
+        u = hubs_cur[h];
+        start = tptr[u];
+        len = tptr[u + 1] - start;
+    }, entry);
+    finish(st, len_sum, KIND_STEP, a);
+}
+
+// keys of the stable descending sort: the level reversed, so that level 0 comes first and ids ascend inside a level; the level histogram beside it
+__global__ __launch_bounds__(WG) void tr_keys_kernel(int n, int levels, const int *__restrict__ level, int *__restrict__ keys, int *__restrict__ ids, int *lcnt)
+{
+    for (long long i = (long long)blockIdx.x * WG + threadIdx.x; i < n; i += (long long)gridDim.x * WG) {
+        const int l = level[i];
+        keys[i] = levels - 1 - l;
+        ids[i] = (int)i;
+        atomicAdd(lcnt + l, 1);
+    }
+}
+
+__global__ __launch_bounds__(WG) void tr_rowlen_kernel(int n, const int *__restrict__ rowid, const int *__restrict__ ocnt, const int *__restrict__ dcnt,
+                                                       int *__restrict__ noff, int *__restrict__ tot)
+{
+    for (long long p = (long long)blockIdx.x * WG + threadIdx.x; p < n; p += (long long)gridDim.x * WG) {
+        const int r = rowid[p], o = ocnt[r];
+        noff[p] = o;
+        tot[p] = o + dcnt[r];
+    }
+}
+
+// lent[l] = the entry offset of level l's first row, l = 0 … levels: the host sizes a level's launch from its rows and its entries
+__global__ __launch_bounds__(WG) void tr_level_entries_kernel(int levels, const int *__restrict__ loff, const int *__restrict__ ebeg, int *__restrict__ lent)
+{
+    for (int l = blockIdx.x * WG + threadIdx.x; l <= levels; l += gridDim.x * WG) lent[l] = ebeg[loff[l]];
+}
+
+// Row rowid[p] of A into the layout, one wave per row, 64 entries a trip: the off-diagonal entries of the triangle in stored order at ebeg[p], the
+// diagonal entries in stored order behind them; diag[p] = their sum from the left (1.0 with a unit diagonal, which keeps none).
+__global__ __launch_bounds__(WG) void tr_gather_kernel(int n, int upper, int unit, const int *__restrict__ rowptr, const int *__restrict__ colids,
+                                                       const double *__restrict__ values, const int *__restrict__ rowid, const int *__restrict__ ebeg,
+                                                       const int *__restrict__ noff, int *__restrict__ lcol, double *__restrict__ lval, int *__restrict__ emap,
+                                                       double *__restrict__ diag)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    for (long long p = (long long)blockIdx.x * (WG / 64) + (threadIdx.x >> 6); p < n; p += (long long)gridDim.x * (WG / 64)) {
+        const int r = rowid[p], rb = rowptr[r], re = rowptr[r + 1], e0 = ebeg[p], m = noff[p];
+        int ob = 0, db = 0;
+        double d = 1.0;
+        for (int k0 = rb; k0 < re; k0 += 64) {
+            const int k = k0 + lane;
+            const bool valid = k < re;
+            const int c = valid ? colids[k] : -1;
+            const double v = valid ? values[k] : 0.0;
+            const bool tri = valid && in_triangle(upper, r, c) && !(unit && c == r);
+            const bool isd = tri && c == r, iso = tri && c != r;
+            const unsigned long long mo = __ballot(iso);
+            unsigned long long md = __ballot(isd);
+            if (tri) {
+                const int pos = iso ? e0 + ob + __popcll(mo & below) : e0 + m + db + __popcll(md & below);
+                lcol[pos] = c;
+                lval[pos] = v;
+                emap[pos] = k;
+            }
+            ob += __popcll(mo);
+            while (md) {                                           // the same for every lane: the diagonal entries of this trip, from the left
+                const int j = __ffsll((long long)md) - 1;
+                md &= md - 1;
+                const double vj = __shfl(v, j);
+                d = db == 0 ? vj : d + vj;
+                db += 1;
+            }
+        }
+        if (lane == 0) diag[p] = d;
+    }
+}
+
+// New values through the position map: every kept entry, and every row's diagonal sum from the caller's array itself.
+__global__ __launch_bounds__(WG) void tr_update_kernel(int n, long long nnz_tri, const double *__restrict__ values, const int *__restrict__ emap,
+                                                       const int *__restrict__ ebeg, const int *__restrict__ noff, double *__restrict__ lval,
+                                                       double *__restrict__ diag)
+{
+    for (long long e = (long long)blockIdx.x * WG + threadIdx.x; e < nnz_tri; e += (long long)gridDim.x * WG) lval[e] = values[emap[e]];
+    for (long long p = (long long)blockIdx.x * WG + threadIdx.x; p < n; p += (long long)gridDim.x * WG) {
+        const int d0 = ebeg[p] + noff[p], d1 = ebeg[p + 1];
+        if (d0 == d1) continue;                                    // a unit diagonal keeps none
+        double d = values[emap[d0]];
+        for (int j = d0 + 1; j < d1; ++j) d = d + values[emap[j]];
+        diag[p] = d;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------- the solve
+struct TrView {
+    const int *rowid, *ebeg, *noff, *lcol, *loff;
+    const double *diag, *lval;
+    int unit;
+};
+
+template <bool kChain>
+__device__ __forceinline__ double ldx(const double *x, int c)
+{
+    if constexpr (kChain) return __hip_atomic_load(x + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return x[c];
+}
+
+// One lane's share of a row's sum: the entries first, first + kStride, … below m of the row whose entries begin at e, added left to right from +0.0.
+// kUnroll entries are loaded before the first of them is added — a lane has one dependent pair of loads (the column, then x) per entry, and a hub row
+// of 10⁵ entries is 400 such pairs per lane —; the additions keep their order, so the bits do not depend on kUnroll.
+template <bool kChain, int kStride, int kUnroll>
+__device__ __forceinline__ double strided_sum(const TrView &T, const double *x, int e, int first, int m)
+{
+    double s = 0.0;
+    int k = first;
+    for (; k + (kUnroll - 1) * kStride < m; k += kUnroll * kStride) {
+        int c[kUnroll];
+        double v[kUnroll], y[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) c[u] = T.lcol[e + k + u * kStride];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) v[u] = T.lval[e + k + u * kStride];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) y[u] = ldx<kChain>(x, c[u]);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) s = s + v[u] * y[u];
+    }
+    for (; k < m; k += kStride) s = s + T.lval[e + k] * ldx<kChain>(x, T.lcol[e + k]);
+    return s;
+}
+
+// Rows [lo, hi) of the layout, hi − lo <= WG / stride, all of one level; called by every thread of the workgroup. Thread t owns row lo + t / stride when
+// stride (a power of two up to 64) divides t, and writes its x: a wave takes its rows above kWaveRow entries one after another, so where rows are long
+// the launch gives a wave few of them. Who sums a row never changes how it is summed.
+//   m <= kWaveRow            the lane alone, left to right from +0.0
+//   kWaveRow < m <= kHubCut  the row's wave: lane l takes entries l, l + 64, … left to right from +0.0, then the wave_sum ladder
+//   m > kHubCut              the workgroup: thread t takes entries t, t + 256, …, a wave_sum ladder per wave, then ((w0 + w1) + w2) + w3
+// b and x may be the same array: row r is the only reader of b[r] and the only writer of x[r].
+template <bool kChain>
+__device__ __forceinline__ void solve_tile(const TrView &T, int lo, int hi, int stride, const double *b, double *x, int *s_hub, int *s_nh, double *s_part)
+{
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int p = lo + t / stride;
+    const bool have = t % stride == 0 && p < hi;
+    const int m = have ? T.noff[p] : 0, e0 = have ? T.ebeg[p] : 0;
+    double s = 0.0;
+    if (t == 0) *s_nh = 0;
+    __syncthreads();
+    if (m > kHubCut) s_hub[atomicAdd(s_nh, 1)] = t;                // in any order: a hub's sum does not depend on its turn
+    if (m <= kWaveRow) s = strided_sum<kChain, 1, 4>(T, x, e0, 0, m);
+    unsigned long long wm = __ballot(m > kWaveRow && m <= kHubCut);
+    while (wm) {                                                   // the same for every lane of the wave
+        const int j = __ffsll((long long)wm) - 1;
+        wm &= wm - 1;
+        const int mj = __shfl(m, j), ej = __shfl(e0, j);
+        const double part = __shfl(wave_sum(strided_sum<kChain, 64, 8>(T, x, ej, lane, mj)), 0);
+        if (lane == j) s = part;
+    }
+    __syncthreads();
+    const int nh = *s_nh;
+    for (int h = 0; h < nh; ++h) {
+        const int th = s_hub[h], mh = T.noff[lo + th / stride], eh = T.ebeg[lo + th / stride];
+        const double part = wave_sum(strided_sum<kChain, WG, 8>(T, x, eh, t, mh));
+        if (lane == 0) s_part[wave] = part;
+        __syncthreads();
+        if (t == th) s = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+        __syncthreads();
+    }
+    if (have) {
+        const int r = T.rowid[p];
+        double v = b[r] - s;
+        if (!T.unit) v = v / T.diag[p];
+        if (v != v) v = __longlong_as_double(0x7FF8000000000000ll);   // IEEE leaves a NaN's sign and payload open (b − s is b + (−s) here): the header fixes them
+        x[r] = v;
+    }
+}
+static_assert(WG / 64 == 4, "the hub shape adds four wave sums");
+
+// one level that is not in a chain: a tile of WG / stride rows per workgroup
+__global__ __launch_bounds__(WG) void tr_level_kernel(const TrView T, int lo, int hi, int stride, const double *b, double *x)
+{
+    __shared__ int s_hub[WG], s_nh;
+    __shared__ double s_part[WG / 64];
+    const long long t0 = (long long)lo + (long long)blockIdx.x * (WG / stride);
+    const int t1 = (int)std::min<long long>(hi, t0 + WG / stride);
+    solve_tile<false>(T, (int)t0, t1, stride, b, x, s_hub, &s_nh, s_part);
+}
+
+// a chain: one workgroup, levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one stored
+__global__ __launch_bounds__(WG) void tr_chain_kernel(const TrView T, int level_lo, int level_hi, const double *b, double *x)
+{
+    __shared__ int s_hub[WG], s_nh;
+    __shared__ double s_part[WG / 64];
+    for (int l = level_lo; l < level_hi; ++l) {
+        const int lo = T.loff[l], hi = T.loff[l + 1];
+        int stride = 64;                                           // the level's rows spread over the four waves: the largest stride that leaves room
+        while (stride > 1 && WG / stride < hi - lo) stride >>= 1;
+        solve_tile<true>(T, lo, hi, stride, b, x, s_hub, &s_nh, s_part);
+        __threadfence();                                           // this level's x in L2 before anybody passes the barrier
+        __syncthreads();
+    }
+}
+
+int bits_of(int v)
+{
+    int b = 1;
+    while (b < 31 && (v >> b) != 0) ++b;
+    return b;
+}
+
+struct Work {
+    TrState *st;
+    int *ocnt, *dcnt, *tcnt, *hubs_open;
+    int *trows, *tptr, *fill, *pred, *level, *queue, *hubs[2], *keys, *keys_out, *tmpk, *tmpv, *ids, *lcnt, *tot;
+};
+
+// Opening pass and the counts; returns behind a wait on `s` with *h the state.
+int open(int n, const int *rowptr, const int *colids, int upper, int unit, const Work &w, int hub_cap, int cus, TrState *h, Counts *cnt, hipStream_t s)
+{
+    const Counting c{upper, unit, w.ocnt, w.dcnt, w.tcnt};
+    const int g_rows = grid_rows(n, cus);
+    G4S_HIP_TRY(hipMemsetAsync(w.st, 0, kStateBytes, s));
+    G4S_HIP_TRY(hipMemsetAsync(w.ocnt, 0, sizeof(int) * (size_t)n, s));
+    G4S_HIP_TRY(hipMemsetAsync(w.dcnt, 0, sizeof(int) * (size_t)n, s));
+    G4S_HIP_TRY(hipMemsetAsync(w.tcnt, 0, sizeof(int) * ((size_t)n + 1), s));
+    hipLaunchKernelGGL(tr_open_rows_kernel, dim3(g_rows), dim3(WG), 0, s, n, rowptr, w.st);
+    hipLaunchKernelGGL(tr_open_ids_kernel, dim3(grid_for<WG>(n, 2048)), dim3(WG), 0, s, n, hub_cap, rowptr, colids, w.hubs_open, w.st, c);
+    hipLaunchKernelGGL(tr_open_hubs_kernel, dim3(1024), dim3(WG), 0, s, n, hub_cap, rowptr, colids, w.hubs_open, w.st, c);
+    hipLaunchKernelGGL(tr_count_kernel, dim3(g_rows), dim3(WG), 0, s, n, unit, w.ocnt, w.dcnt, w.st);
+    G4S_HIP_TRY(hipGetLastError());
+    cnt->launches += 4;
+    G4S_HIP_TRY(g4s::ReadScope(s).fetch(*h, w.st));
+    cnt->waits += 1;
+    return G4S_OK;
+}
+
+// The transposed pattern and the peel; returns behind a wait on `s` with *h the final state: h->round levels, level[] complete.
+int peel(int n, const int *rowptr, const int *colids, int upper, const Work &w, int hub_cap, int cus, TrState *h, Counts *cnt, hipStream_t s)
+{
+    const g4s::StepGrid sized(g4s::kMinGrid, 2 * cus);
+    const int g_rows = grid_rows(n, cus);
+    StepArgs a;
+    a.grid_cap = LLONG_MAX;                                        // the seed stops nothing: the first grid is sized behind it
+    a.n = n;
+    a.hub_cap = hub_cap;
+    a.resume = 0;
+    G4S_TRY(g4s::prims::exclusive_scan(w.tcnt, w.tptr, (long long)n + 1, s));
+    G4S_HIP_TRY(hipMemsetAsync(w.fill, 0, sizeof(int) * (size_t)n, s));
+    hipLaunchKernelGGL(tr_scatter_kernel, dim3(grid_for<WG>(n, 2048)), dim3(WG), 0, s, n, hub_cap, upper, rowptr, colids, w.hubs_open, w.tptr, w.fill, w.trows, w.st);
+    hipLaunchKernelGGL(tr_seed_kernel, dim3(g_rows), dim3(WG), 0, s, w.tptr, w.ocnt, w.pred, w.level, w.queue, w.hubs[0], w.hubs[1], w.st, a);
+    G4S_HIP_TRY(hipGetLastError());
+    cnt->launches += 5;                                            // the scan counts as three
+    g4s::ReadScope reads(s);
+    G4S_HIP_TRY(reads.fetch(*h, w.st));
+    cnt->waits += 1;
+    int batch = kBatch;
+    while (h->stop != 1) {
+        const int grid = sized.grid(h->edges_cur + (h->end - h->head) + h->n_hub_cur);
+        const bool resumed = h->stop == 4;
+        a.grid_cap = sized.cap(grid);
+        if (resumed) cnt->resumes += 1;
+        for (int b = 0; b < batch; ++b) {
+            a.resume = b == 0 && resumed;
+            hipLaunchKernelGGL(tr_step_kernel, dim3(grid), dim3(WG), 0, s, w.tptr, w.trows, w.pred, w.level, w.queue, w.hubs[0], w.hubs[1], w.st, a);
+        }
+        a.resume = 0;
+        G4S_HIP_TRY(hipGetLastError());
+        cnt->launches += batch;
+        G4S_HIP_TRY(reads.fetch(*h, w.st));
+        cnt->waits += 1;
+        batch = sized.next_batch(batch);
+    }
+    return G4S_OK;
+}
+
+// The (level, row) layout into the handle's arrays, and the level offsets to the host; returns behind a wait on `s`.
+int layout(g4s_trsv_s *T, int levels, const int *rowptr, const int *colids, const double *values, int upper, int unit, const Work &w, int cus,
+           std::vector<int> *loff_host, Counts *cnt, hipStream_t s)
+{
+    const int n = T->n, g_rows = grid_rows(n, cus);
+    G4S_HIP_TRY(hipMemsetAsync(w.lcnt, 0, sizeof(int) * ((size_t)levels + 1), s));
+    G4S_HIP_TRY(hipMemsetAsync(w.tot + n, 0, sizeof(int), s));
+    hipLaunchKernelGGL(tr_keys_kernel, dim3(g_rows), dim3(WG), 0, s, n, levels, w.level, w.keys, w.ids, w.lcnt);
+    G4S_TRY(g4s::prims::sort_pairs_descending(w.keys, w.ids, w.keys_out, T->rowid, w.tmpk, w.tmpv, n, bits_of(levels - 1), s));
+    G4S_TRY(g4s::prims::exclusive_scan(w.lcnt, T->loff, (long long)levels + 1, s));
+    hipLaunchKernelGGL(tr_rowlen_kernel, dim3(g_rows), dim3(WG), 0, s, n, T->rowid, w.ocnt, w.dcnt, T->noff, w.tot);
+    G4S_TRY(g4s::prims::exclusive_scan(w.tot, T->ebeg, (long long)n + 1, s));
+    hipLaunchKernelGGL(tr_gather_kernel, dim3(grid_for<WG / 64>(n, 16LL * cus)), dim3(WG), 0, s, n, upper, unit, rowptr, colids, values, T->rowid, T->ebeg, T->noff,
+                       T->lcol, T->lval, T->emap, T->diag);
+    G4S_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tr_level_entries_kernel, dim3(grid_for<WG>((long long)levels + 1, 64)), dim3(WG), 0, s, levels, T->loff, T->ebeg, w.lcnt);   // lcnt is free again
+    G4S_HIP_TRY(hipGetLastError());
+    cnt->launches += 4 + 3 * ((bits_of(levels - 1) + 3) / 4) + 6;  // a scan counts as three, a sort pass as three
+    loff_host->resize((size_t)levels + 1);
+    T->lent_host.resize((size_t)levels + 1);
+    G4S_HIP_TRY(hipMemcpyAsync(loff_host->data(), T->loff, sizeof(int) * ((size_t)levels + 1), hipMemcpyDeviceToHost, s));
+    G4S_HIP_TRY(hipMemcpyAsync(T->lent_host.data(), w.lcnt, sizeof(int) * ((size_t)levels + 1), hipMemcpyDeviceToHost, s));
+    G4S_HIP_TRY(hipStreamSynchronize(s));
+    cnt->waits += 1;
+    return G4S_OK;
+}
+
+void plan_launches(g4s_trsv_s *T, const int *loff, int levels)
+{
+    T->launches = g4s::trsv_launches(loff, levels, kChainWidth, kChainLevels, (T->flags & G4S_TRSV_NO_CHAINS) != 0);
+    int widest = 0, chains = 0;
+    for (int l = 0; l < levels; ++l) widest = std::max(widest, loff[l + 1] - loff[l]);
+    for (const g4s::TrLaunch &L : T->launches) chains += L.chain;
+    T->info.levels = levels;
+    T->info.widest_level = widest;
+    T->info.launches_per_solve = (int)T->launches.size();
+    T->info.chains = chains;
+}
+
+} // namespace
+
+G4S_API g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values, int32_t *level,
+                                      unsigned flags, g4s_trsv_info *info, void *stream)
+{
+    G4S_REQUIRE((flags & ~kFlagMask) == 0u, "flags other than G4S_HOST_POINTERS / G4S_DEVICE_POINTERS and the G4S_TRSV_* bits");
+    G4S_REQUIRE(out, "out is NULL");
+    G4S_REQUIRE(n >= 0, "negative dimension");
+    G4S_REQUIRE(rowptr, "rowptr is NULL");
+    G4S_REQUIRE((colids && values) || n == 0, "colids or values is NULL");
+    const bool device = (flags & G4S_DEVICE_POINTERS) != 0;
+    const int upper = (flags & G4S_TRSV_UPPER) != 0, unit = (flags & G4S_TRSV_UNIT_DIAGONAL) != 0;
+    long long nnz = 0;
+    if (!device) {
+        nnz = rowptr[n];
+        G4S_REQUIRE(nnz >= 0, "rowptr[n] is negative");
+        const size_t nb = sizeof(int32_t) * (size_t)n;
+        const Span outs[] = {{level, nb}}, ins[] = {{rowptr, nb + sizeof(int32_t)}, {colids, sizeof(int32_t) * (size_t)nnz}, {values, sizeof(double) * (size_t)nnz}};
+        G4S_REQUIRE(!any_overlap(outs, ins), "level must not overlap the inputs");
+    }
+    const hipStream_t s = g4s::as_stream(stream);
+    G4S_TRY(not_capturing(__func__, s, "its state"));
+    if (info) { *info = g4s_trsv_info{}; info->n = n; info->bad_row = -1; }
+    g4s_trsv_s *T = new (std::nothrow) g4s_trsv_s;
+    if (!T) return g4s::set_error(G4S_ERR_NOMEM, "g4s_sptrsv_analyse: no memory for the handle");
+    T->n = n;
+    T->flags = flags;
+    T->info.n = n;
+    T->info.bad_row = -1;
+    if (n == 0) {
+        if (info) *info = T->info;
+        *out = T;
+        return G4S_OK;
+    }
+
+    int cus = 1;
+    int status = G4S_OK;
+    if (g4s::device_cus(&cus) != hipSuccess) status = g4s::set_error(G4S_ERR_HIP, "g4s_sptrsv_analyse: no device");
+    const int hub_cap = std::min(n, kHubCap);
+    TrState h{};
+    Work w{};
+    Carver first, second;
+    first.piece(&w.st, kStateBytes);
+    first.piece(&w.ocnt, sizeof(int) * (size_t)n);
+    first.piece(&w.dcnt, sizeof(int) * (size_t)n);
+    first.piece(&w.tcnt, sizeof(int) * ((size_t)n + 1));
+    first.tail(&w.hubs_open, sizeof(int) * (size_t)hub_cap);
+    Staged stage(s);
+    Counts cnt;
+    if (status == G4S_OK) status = first.alloc();
+    const int *rp = rowptr, *ci = colids;
+    const double *va = values;
+    int *lv = level;
+    if (status == G4S_OK && !device) {
+        rp = stage.in(rowptr, sizeof(int) * ((size_t)n + 1));
+        ci = stage.in(colids, sizeof(int) * (size_t)nnz);
+        va = stage.in(values, sizeof(double) * (size_t)nnz);
+        status = stage.error();
+    }
+    if (status == G4S_OK) status = open(n, rp, ci, upper, unit, w, hub_cap, cus, &h, &cnt, s);
+    const bool refused = status == G4S_OK && (h.invalid || h.bad_row < n);
+    int levels = 0;
+    std::vector<int> &loff_host = T->loff_host;
+    if (status == G4S_OK && !refused) {
+        const size_t ni = sizeof(int) * (size_t)n;
+        second.piece(&w.trows, sizeof(int) * (size_t)h.nnz_off);
+        second.piece(&w.tptr, ni + sizeof(int));
+        second.piece(&w.fill, ni);
+        second.piece(&w.pred, ni);
+        second.piece(&w.level, ni);
+        second.piece(&w.queue, ni);
+        second.piece(&w.hubs[0], sizeof(int) * (size_t)hub_cap);
+        second.piece(&w.hubs[1], sizeof(int) * (size_t)hub_cap);
+        second.piece(&w.keys, ni);
+        second.piece(&w.keys_out, ni);
+        second.piece(&w.tmpk, ni);
+        second.piece(&w.tmpv, ni);
+        second.piece(&w.ids, ni);
+        second.piece(&w.lcnt, ni + sizeof(int));
+        second.tail(&w.tot, ni + sizeof(int));
+        status = second.alloc();
+        if (status == G4S_OK) status = peel(n, rp, ci, upper, w, hub_cap, cus, &h, &cnt, s);
+        if (status == G4S_OK) {
+            levels = h.round;
+            T->nnz_in = device ? (long long)h.nnz_in : nnz;
+            T->nnz_tri = (long long)(h.nnz_off + h.nnz_diag);
+            const size_t nt = (size_t)T->nnz_tri;
+            const size_t o_rowid = 0, o_ebeg = o_rowid + pad256(ni), o_noff = o_ebeg + pad256(ni + sizeof(int)), o_loff = o_noff + pad256(ni),
+                         o_lcol = o_loff + pad256(sizeof(int) * ((size_t)levels + 1)), o_emap = o_lcol + pad256(sizeof(int) * nt),
+                         o_diag = o_emap + pad256(sizeof(int) * nt), o_lval = o_diag + pad256(sizeof(double) * (size_t)n),
+                         total = o_lval + pad256(sizeof(double) * nt);
+            status = T->block.alloc(total);
+            char *base = T->block.as<char>();
+            T->rowid = reinterpret_cast<int *>(base + o_rowid);
+            T->ebeg = reinterpret_cast<int *>(base + o_ebeg);
+            T->noff = reinterpret_cast<int *>(base + o_noff);
+            T->loff = reinterpret_cast<int *>(base + o_loff);
+            T->lcol = reinterpret_cast<int *>(base + o_lcol);
+            T->emap = reinterpret_cast<int *>(base + o_emap);
+            T->diag = reinterpret_cast<double *>(base + o_diag);
+            T->lval = reinterpret_cast<double *>(base + o_lval);
+        }
+        if (status == G4S_OK) status = layout(T, levels, rp, ci, va, upper, unit, w, cus, &loff_host, &cnt, s);
+        if (status == G4S_OK && level) {
+            if (!device) status = stage.to_host(level, w.level, ni);
+            else if (hipMemcpyAsync(lv, w.level, ni, hipMemcpyDeviceToDevice, s) != hipSuccess) status = g4s::set_error(G4S_ERR_HIP, "g4s_sptrsv_analyse: the copy of level failed");
+            if (status == G4S_OK) status = stage.wait();
+            cnt.waits += 1;
+        }
+    }
+    status = stage.finish(status);                                 // the caller's host arrays and the blocks: nothing in flight touches them
+    first.idle();
+    second.idle();
+    if (status == G4S_OK && h.invalid)
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_sptrsv_analyse: %s", csr_invalid_text(h.invalid));
+    if (status == G4S_OK && h.bad_row < n) {
+        if (info) info->bad_row = h.bad_row;
+        status = g4s::set_error(G4S_ERR_INVALID, "g4s_sptrsv_analyse: row %d stores no diagonal entry in the triangle", h.bad_row);
+    }
+    if (status != G4S_OK) {
+        delete T;
+        return status;
+    }
+    plan_launches(T, loff_host.data(), levels);
+    T->info.nnz_triangle = T->nnz_tri;
+    T->info.launches = cnt.launches;
+    T->info.host_waits = cnt.waits;
+    T->info.resumes = cnt.resumes;
+    if (info) *info = T->info;
+    *out = T;
+    return G4S_OK;
+}
+
+G4S_API g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x_dev, void *stream)
+{
+    G4S_REQUIRE(T, "the handle is NULL");
+    if (T->n == 0) return G4S_OK;
+    G4S_REQUIRE(b_dev && x_dev, "b or x is NULL");
+    const hipStream_t s = g4s::as_stream(stream);
+    const TrView V{T->rowid, T->ebeg, T->noff, T->lcol, T->loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
+    for (const g4s::TrLaunch &L : T->launches) {
+        if (L.chain) {
+            hipLaunchKernelGGL(tr_chain_kernel, dim3(1), dim3(WG), 0, s, V, L.level_lo, L.level_hi, b_dev, x_dev);
+        } else {                                                   // one level
+            const int lo = T->loff_host[L.level_lo], hi = T->loff_host[L.level_hi];
+            const int rows = WG / g4s::trsv_stride(hi - lo, T->lent_host[L.level_hi] - T->lent_host[L.level_lo]);
+            hipLaunchKernelGGL(tr_level_kernel, dim3((unsigned)((hi - lo + rows - 1) / rows)), dim3(WG), 0, s, V, lo, hi, WG / rows, b_dev, x_dev);
+        }
+    }
+    G4S_HIP_TRY(hipGetLastError());
+    return G4S_OK;
+}
+
+G4S_API g4s_status g4s_sptrsv_update_values(g4s_trsv_t T, const double *values, unsigned flags, void *stream)
+{
+    G4S_REQUIRE(T, "the handle is NULL");
+    G4S_REQUIRE((flags & ~G4S_DEVICE_POINTERS) == 0u, "flags other than G4S_HOST_POINTERS / G4S_DEVICE_POINTERS");
+    if (T->n == 0 || T->nnz_tri == 0) return G4S_OK;
+    G4S_REQUIRE(values, "values is NULL");
+    const hipStream_t s = g4s::as_stream(stream);
+    const bool device = (flags & G4S_DEVICE_POINTERS) != 0;
+    int cus = 1;
+    G4S_HIP_TRY(g4s::device_cus(&cus));
+    const int grid = grid_rows(std::max<long long>(T->nnz_tri, T->n), cus);
+    if (device) {
+        hipLaunchKernelGGL(tr_update_kernel, dim3(grid), dim3(WG), 0, s, T->n, T->nnz_tri, values, T->emap, T->ebeg, T->noff, T->lval, T->diag);
+        G4S_HIP_TRY(hipGetLastError());
+        return G4S_OK;
+    }
+    G4S_TRY(not_capturing(__func__, s, "nothing back, but copies a host array in and waits for it"));
+    Staged stage(s);
+    const double *va = stage.in(values, sizeof(double) * (size_t)T->nnz_in);
+    int status = stage.error();
+    if (status == G4S_OK) {
+        hipLaunchKernelGGL(tr_update_kernel, dim3(grid), dim3(WG), 0, s, T->n, T->nnz_tri, va, T->emap, T->ebeg, T->noff, T->lval, T->diag);
+        if (hipGetLastError() != hipSuccess) status = g4s::set_error(G4S_ERR_HIP, "g4s_sptrsv_update_values: the launch failed");
+    }
+    if (status == G4S_OK) status = stage.wait();
+    return stage.finish(status);
+}
+
+G4S_API g4s_status g4s_sptrsv_get_info(g4s_trsv_t T, g4s_trsv_info *info)
+{
+    G4S_REQUIRE(T && info, "the handle or info is NULL");
+    *info = T->info;
+    return G4S_OK;
+}
+
+G4S_API g4s_status g4s_sptrsv_destroy(g4s_trsv_t T)
+{
+    delete T;                                                      // hipFree waits for whatever still reads the layout
+    return G4S_OK;
+}

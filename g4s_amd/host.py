@@ -18,6 +18,8 @@ Names and argument meaning follow the reference so that tests read like tests of
   minimum_spanning_forest — the positions of the entries of the minimum / maximum spanning forest of a weighted undirected graph
                    (g4s_minimum_spanning_forest); spanning_forest_csr (the forest as a CSR) is a composition of existing device calls
   ktruss         — truss numbers, peel rounds and supports of the edges of a symmetric pattern (g4s_ktruss); ktruss_subgraph is a composition of it
+  sptrsv_analyse — the plan of a level-scheduled triangular solve on the lower or upper triangle of a square CSR (g4s_sptrsv_*): solve, update_values;
+                   spsolve_triangular is the one-shot form with scipy's meaning, gauss_seidel a sweep built from two plans and g4s_spmv
   kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
   color          — greedy colouring in a priority order (g4s_color); color_smallest_last, maximal_independent_set and color_classes go with it
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
@@ -232,6 +234,10 @@ class CSR:
         """The positions of the entries of the minimum (maximum) spanning forest of the undirected graph this matrix stores, weights = values —
         minimum_spanning_forest(self, …). Needs no plan."""
         return minimum_spanning_forest(self, maximum, return_labels)
+
+    def triangular_plan(self, lower=True, unit_diagonal=False, return_level=False):
+        """The plan of a triangular solve on this matrix's lower or upper triangle — sptrsv_analyse(self, …). It keeps its own copy of the triangle."""
+        return sptrsv_analyse(self, lower, unit_diagonal, return_level)
 
     def kcore(self, max_k=None, return_round=False, return_info=False):
         """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
@@ -898,6 +904,166 @@ def kcore(A, max_k=None, return_round=False, return_info=False):
         rnd = torch.from_numpy(out_r[:n]).cuda() if return_round else None
     res = (core,) + ((rnd,) if return_round else ()) + (({n_: getattr(info, n_) for n_, _ in capi.KCoreInfo._fields_},) if return_info else ())
     return res[0] if len(res) == 1 else res
+
+
+class TriangularPlan:
+    """A g4s_trsv_t: the (level, row) copy of a triangle and its launch list. solve(b, out=None) enqueues on the current torch stream and waits for
+    nothing (it can be captured into a graph); out may be b. info: the dict of g4s_trsv_info. close() releases the handle."""
+
+    def __init__(self, handle, n, nnz, info):
+        self._handle, self.n, self.nnz = handle, int(n), int(nnz)
+        self.info = {n_: getattr(info, n_) for n_, _ in capi.TRSVInfo._fields_ if n_ != "reserved"}
+
+    def solve(self, b, out=None):
+        if self._handle is None:
+            raise ValueError("the plan is closed")
+        if not (isinstance(b, torch.Tensor) and b.dtype == torch.float64 and b.dim() == 1 and b.numel() == self.n and b.is_contiguous()):
+            raise ValueError(f"b must be a contiguous float64 tensor of {self.n} entries")
+        if out is None:
+            out = torch.empty_like(b)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.dim() == 1 and out.numel() == self.n and out.is_contiguous()
+                  and out.device == b.device):
+            raise ValueError(f"out must be a contiguous float64 tensor of {self.n} entries on b's device")
+        assert b.is_cuda
+        capi.check(capi.load().g4s_sptrsv_solve(self._handle, _ptr_nn(b), _ptr_nn(out), _stream()))
+        return out
+
+    def update_values(self, values):
+        """New values in the layout of the arrays the plan was analysed from (all nnz of them): a device tensor (refreshed on the current torch
+        stream, asynchronous) or a numpy array (copied in, synchronous)."""
+        if self._handle is None:
+            raise ValueError("the plan is closed")
+        on_device = isinstance(values, torch.Tensor)
+        if (int(values.numel()) if on_device else int(np.asarray(values).size)) != self.nnz:
+            raise ValueError(f"values must have the {self.nnz} entries of the analysed arrays")
+        if on_device:
+            assert values.is_cuda and values.dtype == torch.float64
+            values = values.contiguous()
+            capi.check(capi.load().g4s_sptrsv_update_values(self._handle, _ptr_nn(values), capi.DEVICE_POINTERS, _stream()))
+        else:
+            values = np.ascontiguousarray(values, np.float64)
+            spare = np.zeros(1, np.float64)
+            capi.check(capi.load().g4s_sptrsv_update_values(self._handle, C.c_void_p((values if values.size else spare).ctypes.data), capi.HOST_POINTERS, _stream()))
+
+    def close(self):
+        if self._handle is not None:
+            capi.load().g4s_sptrsv_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _triangle_args(A, flags):
+    """(rowptr, colids, values, n) of a CSR or a (rowptr, colids, values) triple; ValueError for everything that can be refused without a device"""
+    for name, v in flags:
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    if isinstance(A, (tuple, list)):
+        if len(A) != 3:
+            raise ValueError("expected a CSR or a (rowptr, colids, values) triple")
+        rowptr, colids, n = _pattern_of(tuple(A[:2]), "a triangular solve")
+        values = A[2]
+    else:
+        rowptr, colids, n = _pattern_of(A, "a triangular solve")
+        values = A.values
+    on_device = isinstance(rowptr, torch.Tensor)
+    size = (lambda a: int(a.numel())) if on_device else (lambda a: int(np.asarray(a).size))
+    if isinstance(colids, torch.Tensor) != on_device or isinstance(values, torch.Tensor) != on_device or size(values) != size(colids):
+        raise ValueError("rowptr, colids and values must be of the same kind, and values of the same length as colids")
+    return rowptr, colids, values, n
+
+
+def sptrsv_analyse(A, lower=True, unit_diagonal=False, return_level=False, no_chains=False):
+    """The plan (TriangularPlan) of the solve T x = b with the lower (lower=False: upper) triangle T of the square matrix A (g4s_sptrsv_analyse):
+    only the entries of that triangle are read, so the (D + L) of a general A is solved from A itself. A is a CSR, or a (rowptr, colids, values)
+    triple of device tensors or of numpy arrays (host pointers). unit_diagonal=True ignores stored diagonal entries; without it a row that stores
+    none is refused (capi.G4SError; the message names the smallest such row). return_level=True returns (plan, level), level being the int32 device
+    tensor of the rows' depths in the dependency DAG. no_chains=True is the test switch G4S_TRSV_NO_CHAINS: one launch per level, the same bits.
+    Synchronous. ValueError (before any GPU call) for a CSR that is not square, a tuple of the wrong length, arrays of mixed kinds, values that do
+    not match colids, and flags that are not bools."""
+    rowptr, colids, values, n = _triangle_args(A, (("lower", lower), ("unit_diagonal", unit_diagonal), ("return_level", return_level), ("no_chains", no_chains)))
+    _require_gpu()
+    flags = (0 if lower else capi.TRSV_UPPER) | (capi.TRSV_UNIT_DIAGONAL if unit_diagonal else 0) | (capi.TRSV_NO_CHAINS if no_chains else 0)
+    info, null, handle = capi.TRSVInfo(), C.c_void_p(0), C.c_void_p()
+    fn = capi.load().g4s_sptrsv_analyse
+    if isinstance(rowptr, torch.Tensor):
+        assert rowptr.is_cuda and colids.is_cuda and values.is_cuda
+        assert rowptr.dtype == torch.int32 and colids.dtype == torch.int32 and values.dtype == torch.float64
+        rowptr, colids, values = rowptr.contiguous(), colids.contiguous(), values.contiguous()
+        level = torch.empty(n, dtype=torch.int32, device=rowptr.device) if return_level else None
+        capi.check(fn(C.byref(handle), n, _ptr_nn(rowptr), _ptr_nn(colids), _ptr_nn(values), _ptr_nn(level) if return_level else null,
+                      flags | capi.DEVICE_POINTERS, C.byref(info), _stream()))
+        nnz = int(colids.numel())
+    else:
+        rowptr, colids, values = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32), np.ascontiguousarray(values, np.float64)
+        lev = np.empty(max(n, 1), np.int32)
+        spare = np.zeros(1, np.float64)                                 # an empty array is passed as a pointer that is not read
+        P = lambda a: C.c_void_p(a.ctypes.data if a.size else spare.ctypes.data)
+        capi.check(fn(C.byref(handle), n, P(rowptr), P(colids), P(values), P(lev) if return_level else null, flags | capi.HOST_POINTERS, C.byref(info),
+                      _stream()))
+        level = torch.from_numpy(lev[:n]).cuda() if return_level else None
+        nnz = int(colids.size)
+    plan = TriangularPlan(handle, n, nnz, info)
+    return (plan, level) if return_level else plan
+
+
+def spsolve_triangular(A, b, lower=True, unit_diagonal=False):
+    """x (float64 device tensor) with T x = b for the lower / upper triangle T of A — scipy.sparse.linalg.spsolve_triangular's meaning for one
+    right-hand side, except that entries outside the triangle are ignored instead of refused. One analysis, one solve, the plan released.
+    A: as for sptrsv_analyse; b: a device tensor or a numpy array of n doubles."""
+    rowptr, colids, values, n = _triangle_args(A, (("lower", lower), ("unit_diagonal", unit_diagonal)))
+    if (int(b.numel()) if isinstance(b, torch.Tensor) else int(np.asarray(b).size)) != n:
+        raise ValueError(f"b must have {n} entries")
+    _require_gpu()
+    if not isinstance(b, torch.Tensor):
+        b = torch.from_numpy(np.ascontiguousarray(b, np.float64).reshape(-1)).cuda()
+    plan = sptrsv_analyse((rowptr, colids, values), lower, unit_diagonal)
+    try:
+        return plan.solve(b.contiguous())
+    finally:
+        torch.cuda.current_stream().synchronize()
+        plan.close()
+
+
+def gauss_seidel(A, b, x, sweeps=1, symmetric=False, plans=None):
+    """`sweeps` Gauss–Seidel sweeps on A x = b, in place on x (float64 device tensor; returned): x ← x + (D + L)⁻¹ (b − A x), and with
+    symmetric=True behind each of them the backward half x ← x + (D + U)⁻¹ (b − A x) — a symmetric Gauss–Seidel sweep. A is a CSR. Wiring, no kernel of
+    its own: the residual is g4s_spmv (r = −1·A·x + 1·b), the corrections are solves on the lower and upper plans of A, the rest torch vector
+    operations. plans: a (lower, upper or None) pair of TriangularPlans of A to reuse; without it they are analysed here and released at the end."""
+    if not isinstance(A, CSR):
+        raise ValueError("A must be a CSR")
+    if A.rows != A.cols:
+        raise ValueError(f"a Gauss–Seidel sweep needs a square matrix, not {A.rows} x {A.cols}")
+    if not (isinstance(sweeps, (int, np.integer)) and not isinstance(sweeps, (bool, np.bool_)) and sweeps >= 0):
+        raise ValueError(f"sweeps must be a non-negative integer, not {sweeps!r}")
+    if not isinstance(symmetric, (bool, np.bool_)):
+        raise ValueError(f"symmetric must be a bool, not {symmetric!r}")
+    for name, v in (("b", b), ("x", x)):
+        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.dim() == 1 and v.numel() == A.rows):
+            raise ValueError(f"{name} must be a float64 tensor of {A.rows} entries")
+    own = plans is None
+    lo, up = (A.triangular_plan(lower=True), A.triangular_plan(lower=False) if symmetric else None) if own else plans
+    if symmetric and up is None:
+        raise ValueError("a symmetric sweep needs the upper plan")
+    try:
+        r = torch.empty_like(b)
+        for _ in range(int(sweeps)):
+            for plan in (lo, up) if symmetric else (lo,):
+                r.copy_(b)
+                A.spmv(x, r, alpha=-1.0, beta=1.0)
+                plan.solve(r, out=r)
+                x.add_(r)
+    finally:
+        if own:
+            torch.cuda.current_stream().synchronize()
+            lo.close()
+            if up is not None:
+                up.close()
+    return x
 
 
 def _is_truss(v):

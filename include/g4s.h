@@ -992,6 +992,80 @@ g4s_status g4s_ktruss(int32_t n, const int32_t *rowptr, const int32_t *colids, i
                       int32_t *truss, int32_t *round /* may be NULL */, int32_t *support /* may be NULL */, unsigned flags,
                       g4s_ktruss_info *info /* may be NULL */, void *stream);
 
+/* Sparse triangular solve, level-scheduled: T x = b for the lower (default) or upper (G4S_TRSV_UPPER) triangle T of an n × n CSR with
+ * int32 indices and fp64 values — the kernel behind Gauss–Seidel and SSOR sweeps and IC(0) / ILU(0) preconditioners. An analysis that is paid once
+ * (g4s_sptrsv_analyse: the levels of the dependency DAG, the schedule, the handle) and a solve that is paid per right-hand side (g4s_sptrsv_solve).
+ *   Matrix: raw arrays on the host or the device (flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS), as g4s_kcore takes them. Only the entries of the
+ *     chosen triangle are read (col <= row for lower, col >= row for upper); everything else is ignored, values included, so (D + L) and (D + U) of a
+ *     general A are solved from A itself without a select. Columns inside a row need not ascend and may repeat: every stored off-diagonal entry
+ *     contributes its own product, in stored order; repeated diagonal entries are summed from the left, d = (d0 + d1) + …. With
+ *     G4S_TRSV_UNIT_DIAGONAL stored diagonal entries are ignored. Without it a row that stores no diagonal entry is G4S_ERR_INVALID, info.bad_row is
+ *     the smallest such row and no handle is made. A stored zero, inf or NaN on the diagonal is no error: the division is IEEE.
+ *   Checks: before any HIP call (G4S_ERR_INVALID) any flag bit other than G4S_DEVICE_POINTERS and the three G4S_TRSV_* bits, a NULL out or rowptr,
+ *     NULL colids or values with n > 0, a negative n, and with host pointers a level that overlaps the inputs. On the device, before any id is an
+ *     index: rowptr non-decreasing from 0 and ids in [0, n) (G4S_ERR_INVALID). After every refusal *out is untouched and level unspecified. n == 0 is
+ *     valid: a handle with no level, whose solve does nothing.
+ *   The handle keeps its own copy of the triangle, laid out by (level, row): the caller's arrays need not outlive the analysis.
+ *     g4s_sptrsv_update_values takes new values in the layout of the arrays the handle was analysed from (all of them, rowptr[n] entries; host or
+ *     device by its own flags) and refreshes the copy and the diagonal sums in one pass through a kept position map, on `stream`, asynchronous with
+ *     device pointers; with host pointers it copies the array in and waits (not capturable). The pattern is fixed for the handle's life.
+ *   level[i] (n int32, may be NULL, host or device like the inputs): 0 when row i has no off-diagonal entry in the triangle, else 1 + the largest
+ *     level among the columns of those entries. Exact integers, the same on every run; info.levels = 1 + the largest. Rows are scheduled by
+ *     (level, id).
+ *   Arithmetic, fixed so that the bits can be pinned: x[i] = (b[i] − s_i) / d_i, with a unit diagonal x[i] = b[i] − s_i. s_i sums the products
+ *     v·x[col] of row i's m off-diagonal triangle entries, in stored order, in a shape that depends on m alone — never on the level's width, the grid
+ *     or the kernel. Products and sums round separately (no FMA).
+ *       m <= G4S_TRSV_WAVE_ROW          s = +0.0; s = s + p_k for k = 0 … m − 1.
+ *       G4S_TRSV_WAVE_ROW < m <= 4096   64 partial sums: a_l = +0.0, a_l = a_l + p_k for k = l, l + 64, …; then for o = 32, 16, … 1:
+ *                                       a_l = a_l + a_(l+o) for l < o (the ladder of wave_reduce.hpp); s = a_0.
+ *       m > 4096                        256 partial sums over k = t, t + 256, …; the ladder over each 64 consecutive ones gives w0 … w3;
+ *                                       s = ((w0 + w1) + w2) + w3. One workgroup sums such a row, so it does not hold a level behind one wave.
+ *     An x[i] that is a NaN is stored as the quiet NaN 0x7FF8000000000000: IEEE leaves the sign and the payload of a NaN result open (the device
+ *     subtracts by adding the negated operand, which flips a NaN's sign), so the solve fixes them. ±0.0 and ±inf are what the operations give.
+ *   Solve: b_dev and x_dev are device arrays of n doubles; x_dev may be b_dev (row i is the only reader of b[i] and the only writer of x[i]). It
+ *     enqueues info.launches_per_solve kernels on `stream`, waits for nothing on the host and can be captured into a graph. No wave waits for a value
+ *     another workgroup produces in the same kernel: dependencies between workgroups are kernel boundaries on the stream, nothing spins.
+ *   Launches — the rule, restated by tests/trsv_ref.py: a level of at most G4S_TRSV_CHAIN_WIDTH rows is narrow. A maximal run of consecutive narrow
+ *     levels is cut, from its first level on, into pieces of at most G4S_TRSV_CHAIN_LEVELS levels; every piece (one of a single level included) is a
+ *     chain: ONE launch of ONE workgroup that steps through its levels behind a fence and a barrier, reading x with loads performed in L2. Every other
+ *     level is one launch over its rows alone, 256 rows a workgroup and fewer where the level's rows are long. info.chains counts the chains, info.launches_per_solve = chains + the other
+ *     levels. G4S_TRSV_NO_CHAINS (for tests) makes every level a launch of the second kind: chains = 0, launches_per_solve = levels, the same bits.
+ *   The analysis is synchronous and not capturable (G4S_ERR_INVALID on a capturing stream, nothing enqueued). It is a Kahn peel of the DAG on the
+ *     stepped driver of the graph calls — one step kernel per level, at least 16 (doubling to 64) behind one read of the state:
+ *     info.host_waits <= info.launches / 16 + 5 (the counts, the seed, the level offsets, level to the host, and the last batch). A deep DAG pays one
+ *     launch per level here too. Scratch is O(nnz_triangle + n + levels), released before it returns.
+ *   Threads and streams: a solve only reads the handle, so solves on ONE handle may be enqueued on different streams and from different threads at
+ *     the same time, given different x. g4s_sptrsv_update_values writes the handle: it must be ordered against every solve on it (same stream, or
+ *     an event). Different handles are independent; analyses may run in different host threads at the same time (tests/test_trsv_threads_gpu.py).
+ *   Out of scope: several right-hand sides per solve, a transposed solve (transpose with g4s_csr_transpose and solve the other triangle),
+ *     IC(0) / ILU(0) factorisation, a preconditioner slot in g4s_conj_grad, several devices. */
+#define G4S_TRSV_UPPER          2097152u /* solve with the upper triangle (default: lower) */
+#define G4S_TRSV_UNIT_DIAGONAL  4194304u /* the diagonal is 1: stored diagonal entries are ignored, none is required */
+#define G4S_TRSV_NO_CHAINS      8388608u /* tests: one launch per level */
+#define G4S_TRSV_WAVE_ROW     32         /* a row of more off-diagonal triangle entries is summed by a wave */
+#define G4S_TRSV_CHAIN_WIDTH  256        /* a level of at most this many rows is narrow */
+#define G4S_TRSV_CHAIN_LEVELS 1024       /* levels per chain, at most */
+typedef struct g4s_trsv_s *g4s_trsv_t;
+typedef struct g4s_trsv_info {
+    int64_t nnz_triangle;        /* entries kept: off-diagonal ones of the triangle and (without UNIT_DIAGONAL) diagonal ones */
+    int32_t n;
+    int32_t levels;              /* 1 + the largest level; 0 for n == 0                                   */
+    int32_t widest_level;        /* rows of the widest level                                              */
+    int32_t launches_per_solve;  /* kernels one g4s_sptrsv_solve enqueues                                 */
+    int32_t chains;              /* of them chains                                                        */
+    int32_t bad_row;             /* the smallest row without a stored diagonal entry, −1 when there is none */
+    int32_t launches;            /* the analysis: kernels enqueued, those that returned at once included  */
+    int32_t host_waits;          /* the analysis: times it waited for the device                          */
+    int32_t resumes;             /* the analysis: batches restarted because the frontier outgrew the grid */
+    int32_t reserved;
+} g4s_trsv_info;                 /* 48 bytes */
+g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values,
+                              int32_t *level /* n, may be NULL */, unsigned flags, g4s_trsv_info *info /* may be NULL */, void *stream);
+g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x_dev /* may be b_dev */, void *stream);
+g4s_status g4s_sptrsv_update_values(g4s_trsv_t T, const double *values, unsigned flags, void *stream);
+g4s_status g4s_sptrsv_get_info(g4s_trsv_t T, g4s_trsv_info *info);
+g4s_status g4s_sptrsv_destroy(g4s_trsv_t T);
+
 /* Element-wise combination of two CSR matrices of the same shape, and filtering of one, on the device. Two calls each, on the model of
  * g4s_spgemm_symbolic / g4s_spgemm_numeric, with caller-allocated outputs: the symbolic call writes crpt (rows + 1) and *cnnz, the caller allocates
  * ccol (and cval) of *cnnz entries, the numeric call fills them. Nothing is kept between the two calls — no process-wide state, so different host

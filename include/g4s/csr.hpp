@@ -10,6 +10,7 @@
 //   StronglyConnectedComponents(a,labels)  labels[v] = the smallest vertex id of v's strongly connected component of the directed pattern `a` (g4s_strongly_connected_components)
 //   MinimumSpanningForest(a,edges,labels), MaximumSpanningForest(…)   the positions of the entries of the minimum / maximum spanning forest of the weighted undirected graph `a` (g4s_minimum_spanning_forest)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
+//   TriangularSolve(a,lower,unit)    an RAII plan of the level-scheduled solve T x = b on the lower / upper triangle of `a`: solve, update_values (g4s_sptrsv_*)
 //   KTruss(a,truss,round,support,max_k)   per stored entry: the truss number of its edge in the symmetric pattern `a`, the peel frontier that removed it, its triangles (g4s_ktruss)
 //   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
@@ -255,6 +256,52 @@ void KCore(const CSR<IT, NT> &a, int32_t *core, int32_t *round = nullptr, int32_
     check(g4s_kcore(a.rows, a.rowptr ? a.rowptr : &zero, a.colids, max_k, a.rows ? core : &none, a.rows ? round : nullptr, G4S_HOST_POINTERS, info, nullptr),
           "KCore");
 }
+
+// The plan of the solve T x = b with the lower (lower = false: upper) triangle T of the square matrix `a` (g4s_sptrsv_analyse): only the entries of
+// that triangle are read, so the (D + L) of a general matrix is solved from the matrix itself. The plan keeps its own copy of the triangle on the
+// device; `a` need not outlive the constructor. unit_diagonal: stored diagonal entries are ignored; without it a row that stores none throws.
+// level (may be NULL): a.rows ints, the depth of every row in the dependency DAG. solve(b, x): host arrays of a.rows doubles, x may be b; copied
+// through a device buffer of the plan, synchronous. solve_device: device arrays, enqueued on `stream`, asynchronous. update_values: new values in
+// the layout of a.values, all a.nnz of them.
+class TriangularSolve {
+public:
+    template <typename IT, typename NT>
+    explicit TriangularSolve(const CSR<IT, NT> &a, bool lower = true, bool unit_diagonal = false, int32_t *level = nullptr) : n_(a.rows)
+    {
+        if (a.rows != a.cols) throw std::runtime_error("TriangularSolve: the matrix is not square");
+        const unsigned flags = G4S_HOST_POINTERS | (lower ? 0u : G4S_TRSV_UPPER) | (unit_diagonal ? G4S_TRSV_UNIT_DIAGONAL : 0u);
+        const IT zero = 0;                                  // an empty CSR holds no arrays: nothing is read for rows == 0 or nnz == 0
+        const NT none = 0;
+        check(g4s_sptrsv_analyse(&plan_, a.rows, a.rowptr ? a.rowptr : &zero, a.nnz ? a.colids : &zero, a.nnz ? a.values : &none, level, flags, &info_, nullptr),
+              "TriangularSolve");
+    }
+    TriangularSolve(const TriangularSolve &) = delete;
+    TriangularSolve &operator=(const TriangularSolve &) = delete;
+    TriangularSolve(TriangularSolve &&o) noexcept : plan_(o.plan_), buf_(o.buf_), n_(o.n_), info_(o.info_) { o.plan_ = nullptr; o.buf_ = nullptr; }
+    ~TriangularSolve()
+    {
+        if (buf_) (void)g4s_dev_free(buf_);
+        if (plan_) (void)g4s_sptrsv_destroy(plan_);
+    }
+    void solve(const double *b, double *x)
+    {
+        if (n_ == 0) return;
+        if (!buf_) check(g4s_dev_alloc(&buf_, sizeof(double) * (size_t)n_), "TriangularSolve::solve");
+        check(g4s_memcpy_h2d(buf_, b, sizeof(double) * (size_t)n_), "TriangularSolve::solve");
+        solve_device(static_cast<const double *>(buf_), static_cast<double *>(buf_));
+        check(g4s_device_synchronize(), "TriangularSolve::solve");
+        check(g4s_memcpy_d2h(x, buf_, sizeof(double) * (size_t)n_), "TriangularSolve::solve");
+    }
+    void solve_device(const double *b_dev, double *x_dev, void *stream = nullptr) { check(g4s_sptrsv_solve(plan_, b_dev, x_dev, stream), "TriangularSolve::solve"); }
+    void update_values(const double *values) { check(g4s_sptrsv_update_values(plan_, values, G4S_HOST_POINTERS, nullptr), "TriangularSolve::update_values"); }
+    const g4s_trsv_info &info() const { return info_; }
+
+private:
+    g4s_trsv_t plan_ = nullptr;
+    void *buf_ = nullptr;
+    int32_t n_;
+    g4s_trsv_info info_ = {};
+};
 
 // truss[p] (a.nnz values, one per stored entry) = the largest k such that the edge stored at entry p belongs to a subgraph of the simple undirected graph
 // `a` in which every edge lies in at least k − 2 triangles (g4s_ktruss, host arrays): `a` holds the graph's symmetric pattern with ascending rows
