@@ -24,7 +24,8 @@ KTRUSS_BATCH, KTRUSS_FULL = 16, 2**31 - 1                                # g4s_k
 COLOR_LARGEST_FIRST, COLOR_BATCH, COLOR_MASK_COLORS, COLOR_WINDOW = 524288, 16, 64, 256   # g4s_color: key := degree; launches per state read; mask width; scan window (g4s.h)
 TRSV_UPPER, TRSV_UNIT_DIAGONAL, TRSV_NO_CHAINS = 2097152, 4194304, 8388608   # g4s_sptrsv_analyse: the triangle, the diagonal, one launch per level (g4s.h)
 TRSV_WAVE_ROW, TRSV_CHAIN_WIDTH, TRSV_CHAIN_LEVELS, TRSV_HUB_ROW = 32, 256, 1024, 4096   # g4s_sptrsv: the row classes of the documented sum and the chaining rule (g4s.h)
-EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                   # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
+ILU0_NO_CHAINS, ILU0_LANE_ROW, ILU0_WAVE_ROW = 16777216, 8, 512            # g4s_ilu0_analyse: one launch per level; the row classes of the factorisation (g4s.h)
+EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                 # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
 COMBINE_PLUS, COMBINE_TIMES, COMBINE_MIN, COMBINE_MAX, COMBINE_FIRST, COMBINE_SECOND = 0, 1, 2, 3, 4, 5
 DUP_KEEP = -1                                                            # g4s_csr_from_coo_*: dup is DUP_KEEP or a COMBINE_* value (g4s.h)
 SELECT_TRIL, SELECT_TRIU, SELECT_OFFDIAG, SELECT_DIAG, SELECT_NONZERO, SELECT_GT, SELECT_GE, SELECT_LT, SELECT_LE = 0, 1, 2, 3, 4, 5, 6, 7, 8   # g4s_csr_select_*: pred
@@ -115,6 +116,13 @@ class TRSVInfo(C.Structure):
     _fields_ = [("nnz_triangle", C.c_int64), ("n", C.c_int32), ("levels", C.c_int32), ("widest_level", C.c_int32), ("launches_per_solve", C.c_int32),
                 ("chains", C.c_int32), ("bad_row", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32), ("resumes", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class ILU0Info(C.Structure):
+    """g4s_ilu0_info: what a g4s_ilu0_analyse call found and did, and what a factorisation and an apply on its handle cost."""
+    _fields_ = [("nnz", C.c_int64), ("n", C.c_int32), ("levels", C.c_int32), ("widest_level", C.c_int32), ("launches_per_factor", C.c_int32),
+                ("chains", C.c_int32), ("launches_per_apply", C.c_int32), ("bad_row", C.c_int32), ("bad_pivot", C.c_int32), ("launches", C.c_int32),
+                ("host_waits", C.c_int32)]
 
 
 class EwiseInfo(C.Structure):
@@ -271,6 +279,12 @@ SIGNATURES = {
     "g4s_sptrsv_update_values": (C.c_int, [vp, vp, C.c_uint, vp]),
     "g4s_sptrsv_get_info": (C.c_int, [vp, C.POINTER(TRSVInfo)]),
     "g4s_sptrsv_destroy": (C.c_int, [vp]),
+    "g4s_ilu0_analyse": (C.c_int, [C.POINTER(vp), C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(ILU0Info), vp]),
+    "g4s_ilu0_factor": (C.c_int, [vp, vp, C.c_uint, vp, vp]),
+    "g4s_ilu0_apply": (C.c_int, [vp, vp, vp, vp]),
+    "g4s_ilu0_get_factors": (C.c_int, [vp, vp, C.c_uint, vp]),
+    "g4s_ilu0_get_info": (C.c_int, [vp, C.POINTER(ILU0Info)]),
+    "g4s_ilu0_destroy": (C.c_int, [vp]),
     "g4s_csr_ewise_symbolic": (C.c_int, [C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64p, C.c_uint, C.POINTER(EwiseInfo), vp]),
     "g4s_csr_ewise_numeric": (C.c_int, [C.c_int, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint, vp]),
     "g4s_csr_select_symbolic": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, i64p, C.c_uint, vp]),

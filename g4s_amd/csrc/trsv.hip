@@ -530,6 +530,11 @@ void plan_launches(g4s_trsv_s *T, const int *loff, int levels)
 
 } // namespace
 
+g4s::TrSchedule g4s::trsv_schedule(const g4s_trsv_s *T)
+{
+    return TrSchedule{T->rowid, T->loff, T->loff_host.data(), T->lent_host.data(), &T->launches, T->info.levels};
+}
+
 G4S_API g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values, int32_t *level,
                                       unsigned flags, g4s_trsv_info *info, void *stream)
 {

@@ -2,6 +2,7 @@
 // level peel and the launch list of a solve — the chaining rule of include/g4s.h, which tests/trsv_ref.py restates.
 #pragma once
 #include <vector>
+struct g4s_trsv_s;
 namespace g4s {
 
 // The state block of the analysis: the words of a frontier walk (ClState's, color.hpp) and the counts the opening pass leaves.
@@ -55,5 +56,15 @@ inline int trsv_stride(int rows, long long entries)
     while (s < 64 && 2LL * s <= avg / 4) s *= 2;
     return s;
 }
+
+// What g4s_ilu0 (ilu.hip) takes from the plan of the lower triangle: the rows in (level, row) order and the level offsets on the device, the level
+// offsets, the entry offsets of the levels and the launch list on the host. All of it lives as long as the plan. A plan of n == 0 has no level.
+struct TrSchedule {
+    const int *rowid, *loff;
+    const int *loff_host, *lent_host;
+    const std::vector<TrLaunch> *launches;
+    int levels;
+};
+TrSchedule trsv_schedule(const g4s_trsv_s *T);
 
 } // namespace g4s

@@ -20,6 +20,8 @@ Names and argument meaning follow the reference so that tests read like tests of
   ktruss         — truss numbers, peel rounds and supports of the edges of a symmetric pattern (g4s_ktruss); ktruss_subgraph is a composition of it
   sptrsv_analyse — the plan of a level-scheduled triangular solve on the lower or upper triangle of a square CSR (g4s_sptrsv_*): solve, update_values;
                    spsolve_triangular is the one-shot form with scipy's meaning, gauss_seidel a sweep built from two plans and g4s_spmv
+  ilu0           — the ILU(0) factorisation of a square CSR with canonical rows and its apply z = U⁻¹ L⁻¹ r (g4s_ilu0_*): apply, factor, factors;
+                   pcg is a preconditioned CG wired from g4s_spmv, that apply and torch
   kcore          — core numbers and the peel order of a symmetric pattern (g4s_kcore); degeneracy_order and kcore_subgraph are compositions of it
   color          — greedy colouring in a priority order (g4s_color); color_smallest_last, maximal_independent_set and color_classes go with it
   sssp / bfs     — shortest paths / BFS levels from a set of sources on a graph stored by out-edges (g4s_sssp, g4s_bfs): one call, the loop on the device
@@ -238,6 +240,10 @@ class CSR:
     def triangular_plan(self, lower=True, unit_diagonal=False, return_level=False):
         """The plan of a triangular solve on this matrix's lower or upper triangle — sptrsv_analyse(self, …). It keeps its own copy of the triangle."""
         return sptrsv_analyse(self, lower, unit_diagonal, return_level)
+
+    def ilu0(self):
+        """The ILU(0) factorisation of this matrix (canonical rows, every diagonal entry stored) — ilu0(self). It keeps its own copy."""
+        return ilu0(self)
 
     def kcore(self, max_k=None, return_round=False, return_info=False):
         """Core numbers (and the peel rounds) of the graph whose symmetric pattern this matrix stores — kcore(self, …). Needs no plan."""
@@ -1064,6 +1070,152 @@ def gauss_seidel(A, b, x, sweeps=1, symmetric=False, plans=None):
             if up is not None:
                 up.close()
     return x
+
+
+class ILU0:
+    """A g4s_ilu0_t: the factors A ≈ L U on A's own pattern and the two solve plans on them. apply(r, out=None): z = U⁻¹ (L⁻¹ r) on the current torch
+    stream, waits for nothing (it can be captured into a graph); out may be r. factor(values=None): refactorise — new values in the layout of the
+    analysed arrays as a device tensor (asynchronous, capturable) or a numpy array (copied in, synchronous), None: the values the handle holds;
+    returns the int32 device word of the smallest row with a zero or non-finite pivot (−1: none), which the caller reads when they like. factors():
+    a device tensor of the nnz factor values, L strictly below the diagonal, U on and above it. info: the dict of g4s_ilu0_info. close() releases
+    the handle."""
+
+    def __init__(self, handle, n, nnz, info):
+        self._handle, self.n, self.nnz = handle, int(n), int(nnz)
+        self.info = {n_: getattr(info, n_) for n_, _ in capi.ILU0Info._fields_}
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the factorisation is closed")
+
+    def apply(self, r, out=None):
+        self._open()
+        if not (isinstance(r, torch.Tensor) and r.dtype == torch.float64 and r.dim() == 1 and r.numel() == self.n and r.is_contiguous()):
+            raise ValueError(f"r must be a contiguous float64 tensor of {self.n} entries")
+        if out is None:
+            out = torch.empty_like(r)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.dim() == 1 and out.numel() == self.n and out.is_contiguous()
+                  and out.device == r.device):
+            raise ValueError(f"out must be a contiguous float64 tensor of {self.n} entries on r's device")
+        assert r.is_cuda
+        capi.check(capi.load().g4s_ilu0_apply(self._handle, _ptr_nn(r), _ptr_nn(out), _stream()))
+        return out
+
+    def factor(self, values=None):
+        self._open()
+        on_device = isinstance(values, torch.Tensor)
+        if values is not None and (int(values.numel()) if on_device else int(np.asarray(values).size)) != self.nnz:
+            raise ValueError(f"values must have the {self.nnz} entries of the analysed arrays")
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        fn = capi.load().g4s_ilu0_factor
+        if values is None:
+            capi.check(fn(self._handle, C.c_void_p(0), capi.DEVICE_POINTERS, _ptr_nn(bad), _stream()))
+        elif on_device:
+            assert values.is_cuda and values.dtype == torch.float64
+            capi.check(fn(self._handle, _ptr_nn(values.contiguous()), capi.DEVICE_POINTERS, _ptr_nn(bad), _stream()))
+        else:
+            values = np.ascontiguousarray(values, np.float64)
+            spare = np.zeros(1, np.float64)
+            capi.check(fn(self._handle, C.c_void_p((values if values.size else spare).ctypes.data), capi.HOST_POINTERS, _ptr_nn(bad), _stream()))
+        return bad
+
+    def factors(self):
+        self._open()
+        out = torch.empty(self.nnz, dtype=torch.float64, device="cuda")
+        capi.check(capi.load().g4s_ilu0_get_factors(self._handle, _ptr_nn(out), capi.DEVICE_POINTERS, _stream()))
+        return out
+
+    def close(self):
+        if self._handle is not None:
+            capi.load().g4s_ilu0_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ilu0(A, no_chains=False):
+    """The ILU(0) factorisation (ILU0) of the square matrix A (g4s_ilu0_analyse): A ≈ L U with L and U on A's own pattern. A is a CSR, or a
+    (rowptr, colids, values) triple of device tensors or of numpy arrays (host pointers). Its rows must be canonical — columns strictly ascending,
+    every diagonal entry stored (csr_canonical gives such rows) —; anything else is refused (capi.G4SError; the message names the smallest offending
+    row). A zero or non-finite pivot is no error: info["bad_pivot"] names the smallest such row, −1 when there is none. no_chains=True is the test
+    switch G4S_ILU0_NO_CHAINS: one launch per level, the same bits. Synchronous. ValueError (before any GPU call) for a CSR that is not square, a
+    tuple of the wrong length, arrays of mixed kinds, values that do not match colids, and a no_chains that is not a bool."""
+    rowptr, colids, values, n = _triangle_args(A, (("no_chains", no_chains),))
+    _require_gpu()
+    flags = capi.ILU0_NO_CHAINS if no_chains else 0
+    info, handle = capi.ILU0Info(), C.c_void_p()
+    fn = capi.load().g4s_ilu0_analyse
+    if isinstance(rowptr, torch.Tensor):
+        assert rowptr.is_cuda and colids.is_cuda and values.is_cuda
+        assert rowptr.dtype == torch.int32 and colids.dtype == torch.int32 and values.dtype == torch.float64
+        rowptr, colids, values = rowptr.contiguous(), colids.contiguous(), values.contiguous()
+        capi.check(fn(C.byref(handle), n, _ptr_nn(rowptr), _ptr_nn(colids), _ptr_nn(values), flags | capi.DEVICE_POINTERS, C.byref(info), _stream()))
+        nnz = int(colids.numel())
+    else:
+        rowptr, colids, values = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colids, np.int32), np.ascontiguousarray(values, np.float64)
+        spare = np.zeros(1, np.float64)                                 # an empty array is passed as a pointer that is not read
+        P = lambda a: C.c_void_p(a.ctypes.data if a.size else spare.ctypes.data)
+        capi.check(fn(C.byref(handle), n, P(rowptr), P(colids), P(values), flags | capi.HOST_POINTERS, C.byref(info), _stream()))
+        nnz = int(colids.size)
+    return ILU0(handle, n, nnz, info)
+
+
+def pcg(A, b, M=None, x0=None, tol=1e-8, maxiter=None):
+    """Preconditioned conjugate gradients on A x = b: (x, iterations, relative residual). A is a square CSR (symmetric positive definite for the
+    method to mean anything), b a float64 device tensor of its rows, M an object with apply(r, out=None) — an ILU0 of A — or None (plain CG), x0 the
+    start (None: zero; it is not modified). Stops at the first iteration whose recurred residual has ‖r‖ <= tol · ‖b‖, or at maxiter (None: rows).
+    Wiring, no kernel of its own: the product is g4s_spmv, the preconditioner M.apply, the dots and vector updates torch. It reads two scalars per
+    iteration back, so it is synchronous and not capturable."""
+    if not isinstance(A, CSR):
+        raise ValueError("A must be a CSR")
+    if A.rows != A.cols:
+        raise ValueError(f"conjugate gradients need a square matrix, not {A.rows} x {A.cols}")
+    for name, v in (("b", b),) + ((("x0", x0),) if x0 is not None else ()):
+        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.dim() == 1 and v.numel() == A.rows):
+            raise ValueError(f"{name} must be a float64 tensor of {A.rows} entries")
+    if M is not None and not callable(getattr(M, "apply", None)):
+        raise ValueError("M must be None or have apply(r, out=None)")
+    if not (isinstance(tol, (float, np.floating)) and tol > 0.0):
+        raise ValueError(f"tol must be a positive float, not {tol!r}")
+    if maxiter is not None and not (isinstance(maxiter, (int, np.integer)) and not isinstance(maxiter, (bool, np.bool_)) and maxiter >= 0):
+        raise ValueError(f"maxiter must be None or a non-negative integer, not {maxiter!r}")
+    maxiter = A.rows if maxiter is None else int(maxiter)
+    b = b.contiguous()
+    x = torch.zeros_like(b) if x0 is None else x0.clone().contiguous()
+    r = b.clone()
+    if x0 is not None:
+        A.spmv(x, r, alpha=-1.0, beta=1.0)
+    bnorm = float(torch.linalg.vector_norm(b))
+    stop = tol * bnorm
+    rnorm = float(torch.linalg.vector_norm(r))
+    if bnorm == 0.0:
+        return torch.zeros_like(b), 0, 0.0
+    z = r.clone() if M is None else M.apply(r)
+    p = z.clone()
+    q = torch.empty_like(b)
+    rz = torch.dot(r, z)
+    it = 0
+    while rnorm > stop and it < maxiter:
+        A.spmv(p, q)
+        alpha = rz / torch.dot(p, q)
+        x.add_(p * alpha)
+        r.sub_(q * alpha)
+        rnorm = float(torch.linalg.vector_norm(r))
+        it += 1
+        if rnorm <= stop:
+            break
+        if M is None:
+            z.copy_(r)
+        else:
+            M.apply(r, out=z)
+        rz_new = torch.dot(r, z)
+        p.mul_(rz_new / rz).add_(z)
+        rz = rz_new
+    return x, it, rnorm / bnorm
 
 
 def _is_truss(v):

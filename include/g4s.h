@@ -1038,7 +1038,7 @@ g4s_status g4s_ktruss(int32_t n, const int32_t *rowptr, const int32_t *colids, i
  *     the same time, given different x. g4s_sptrsv_update_values writes the handle: it must be ordered against every solve on it (same stream, or
  *     an event). Different handles are independent; analyses may run in different host threads at the same time (tests/test_trsv_threads_gpu.py).
  *   Out of scope: several right-hand sides per solve, a transposed solve (transpose with g4s_csr_transpose and solve the other triangle),
- *     IC(0) / ILU(0) factorisation, a preconditioner slot in g4s_conj_grad, several devices. */
+ *     IC(0), ILU(k) (ILU(0) is g4s_ilu0 below), a preconditioner slot in g4s_conj_grad, several devices. */
 #define G4S_TRSV_UPPER          2097152u /* solve with the upper triangle (default: lower) */
 #define G4S_TRSV_UNIT_DIAGONAL  4194304u /* the diagonal is 1: stored diagonal entries are ignored, none is required */
 #define G4S_TRSV_NO_CHAINS      8388608u /* tests: one launch per level */
@@ -1065,6 +1065,77 @@ g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x_dev /* 
 g4s_status g4s_sptrsv_update_values(g4s_trsv_t T, const double *values, unsigned flags, void *stream);
 g4s_status g4s_sptrsv_get_info(g4s_trsv_t T, g4s_trsv_info *info);
 g4s_status g4s_sptrsv_destroy(g4s_trsv_t T);
+
+/* ILU(0), level-scheduled: the incomplete factorisation A ≈ L U on the pattern of A itself, and its apply z = U⁻¹ (L⁻¹ r) — the
+ * preconditioner g4s_sptrsv solves with. Factorise once per operator (g4s_ilu0_analyse), apply per Krylov iteration (g4s_ilu0_apply), refactorise when
+ * the values change (g4s_ilu0_factor).
+ *   Matrix: an n × n CSR with int32 ids and fp64 values, raw arrays on the host or the device (flags: G4S_HOST_POINTERS / G4S_DEVICE_POINTERS). Unlike
+ *     the solve, the factorisation needs canonical rows: columns strictly ascending inside a row, and every row stores its diagonal entry
+ *     (host.csr_canonical, g4s::SortAndMerge give such rows).
+ *   Checks: before any HIP call (G4S_ERR_INVALID) any flag bit other than G4S_DEVICE_POINTERS and G4S_ILU0_NO_CHAINS, a NULL out or rowptr, NULL
+ *     colids or values with n > 0, a negative n, with host pointers a negative rowptr[n]. On the device, before any id is an index: rowptr
+ *     non-decreasing from 0; then per row ids in [0, n), strictly ascending, the diagonal stored (G4S_ERR_INVALID). info.bad_row is the smallest row
+ *     that offends in one of the three ways (the message names what that row does; −1 for a bad rowptr) and *out is untouched. n == 0 is valid.
+ *   The handle keeps its own copy of the pattern and of the values it last factorised, the position of every diagonal entry, ONE array f of
+ *     rowptr[n] factor values in the layout of the input arrays — L strictly below the diagonal (its unit diagonal implied), U on and above it —
+ *     which g4s_ilu0_get_factors copies out (host or device by its flags; the host form waits), and two g4s_trsv_t plans analysed from
+ *     (rowptr, colids, f) through g4s_sptrsv_analyse: the lower one with G4S_TRSV_UNIT_DIAGONAL, the other G4S_TRSV_UPPER. The caller's arrays need
+ *     not outlive the analysis.
+ *   Arithmetic, fixed so that every stored double can be pinned. Row i has the columns c_0 < … < c_(m−1) and working values w, initialised from A.
+ *     For p = 0, 1, … while c_p = k < i, in that order: (1) w_p = w_p / u_kk, u_kk being row k's finished diagonal value; (2) for every entry (k, j)
+ *     of row k with j > k whose column j row i stores at position t: w_t = w_t − (w_p · u_kj), product and difference rounded separately (no FMA).
+ *     Updates for a j that row i does not store are dropped. Every w_t so receives its updates in ascending k whichever lane performs them: the
+ *     bits depend neither on the grid nor on the row class nor on chaining. When a row finishes, every value of it that is a NaN is stored as
+ *     0x7FF8000000000000 (the reason is the solve's: a − p is a + (−p) on the device); ±0.0 and ±inf are what the operations give.
+ *   Pivots: a zero, inf or NaN pivot is no error. bad_pivot is the smallest row whose finished u_ii is zero or not finite, −1 when there is none:
+ *     info.bad_pivot for the factorisation g4s_ilu0_analyse ends with; g4s_ilu0_factor writes it to the device word bad_pivot_dev (may be NULL; the
+ *     word is set to −1 and lowered by the factor kernels with a vector atomicMin on the stream) and the caller reads it when they like.
+ *   Launches: the dependency DAG of the row-wise factorisation is the DAG of the strictly lower triangle — row i waits for every k < i with a
+ *     stored (i, k) — so the factorisation runs on the lower plan's (level, row) schedule under the rule of g4s_sptrsv: one launch per wide level,
+ *     one workgroup per chain of narrow levels, behind every level of a chain a fence and a barrier, the values of rows finished earlier in the same
+ *     kernel read with loads performed in L2. No wave waits for another workgroup, nothing spins. info.launches_per_factor equals the lower
+ *     plan's launches_per_solve, info.chains its chains; info.launches_per_apply is the sum of the two plans' launches_per_solve.
+ *     G4S_ILU0_NO_CHAINS (for tests) makes every level one launch, in the factorisation and in both solves: the same bits.
+ *   Row classes, which never decide a bit: a row of at most G4S_ILU0_LANE_ROW stored entries is one lane's, w in registers; one of at most
+ *     G4S_ILU0_WAVE_ROW is one wave's, w and its columns in LDS, the k loop sequential, the j loop over the lanes with a binary search in the row's
+ *     columns; a longer one is one workgroup's, w in f itself, re-read with loads performed in L2 behind a fence and a barrier per k.
+ *   Synchrony: g4s_ilu0_analyse is synchronous and not capturable (G4S_ERR_INVALID on a capturing stream, nothing enqueued); it ends with the first
+ *     factorisation. info.launches / info.host_waits count the two inner analyses and its own work:
+ *     host_waits <= launches / 16 + 13 (the two solve analyses' 5 each, the row check, the id check and the pivot word). g4s_ilu0_factor copies `values` in (rowptr[n] doubles in the layout of the analysed arrays, host or device by its flags; NULL:
+ *     refactorise the values the handle holds), enqueues info.launches_per_factor factor kernels and refreshes both plans with
+ *     g4s_sptrsv_update_values. With device pointers (and with NULL) it waits for nothing and can be captured; with host pointers it copies in and
+ *     waits. g4s_ilu0_apply is two solves, L then U, with z as the intermediate (no scratch; z_dev may be r_dev); it never waits and can be captured.
+ *   Threads and streams: g4s_ilu0_apply only reads the handle, so applies on ONE handle may be enqueued on different streams and from different
+ *     threads at the same time, given different z. g4s_ilu0_factor writes the handle: it must be ordered against every apply and every
+ *     g4s_ilu0_get_factors on it (same stream, or an event). Different handles are independent; analyses may run in different host threads at the same
+ *     time (tests/test_ilu_threads_gpu.py).
+ *   Out of scope: IC(0), fill levels above 0, pivoting or a shift for a bad pivot, a preconditioner slot in g4s_conj_grad (host.pcg wires a
+ *     preconditioned CG from g4s_spmv, this apply and torch), several devices. */
+#define G4S_ILU0_NO_CHAINS 16777216u /* tests: one launch per level, in the factorisation and in both solves */
+#define G4S_ILU0_LANE_ROW  8         /* a row of more stored entries is factorised by a wave */
+#define G4S_ILU0_WAVE_ROW  512       /* a row of more stored entries is factorised by a workgroup */
+typedef struct g4s_ilu0_s *g4s_ilu0_t;
+typedef struct g4s_ilu0_info {
+    int64_t nnz;                 /* stored entries: rowptr[n]                                                 */
+    int32_t n;
+    int32_t levels;              /* of the lower DAG; 0 for n == 0                                            */
+    int32_t widest_level;        /* rows of its widest level                                                  */
+    int32_t launches_per_factor; /* factor kernels one g4s_ilu0_factor enqueues                               */
+    int32_t chains;              /* of them chains                                                            */
+    int32_t launches_per_apply;  /* kernels one g4s_ilu0_apply enqueues                                       */
+    int32_t bad_row;             /* the smallest row that is not canonical, −1 when there is none             */
+    int32_t bad_pivot;           /* the smallest row whose u_ii is zero or not finite in the analysis's factorisation, −1: none */
+    int32_t launches;            /* the analysis: kernels enqueued, the two inner analyses' included          */
+    int32_t host_waits;          /* the analysis: times it waited for the device                              */
+} g4s_ilu0_info;                 /* 48 bytes */
+g4s_status g4s_ilu0_analyse(g4s_ilu0_t *out, int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values, unsigned flags,
+                            g4s_ilu0_info *info /* may be NULL */, void *stream);
+g4s_status g4s_ilu0_factor(g4s_ilu0_t P, const double *values /* NULL: what is held */, unsigned flags, int32_t *bad_pivot_dev /* may be NULL */,
+                           void *stream);
+g4s_status g4s_ilu0_apply(g4s_ilu0_t P, const double *r_dev, double *z_dev /* may be r_dev */, void *stream);
+g4s_status g4s_ilu0_get_factors(g4s_ilu0_t P, double *values_out, unsigned flags, void *stream);
+g4s_status g4s_ilu0_get_info(g4s_ilu0_t P, g4s_ilu0_info *info);
+g4s_status g4s_ilu0_destroy(g4s_ilu0_t P);
 
 /* Element-wise combination of two CSR matrices of the same shape, and filtering of one, on the device. Two calls each, on the model of
  * g4s_spgemm_symbolic / g4s_spgemm_numeric, with caller-allocated outputs: the symbolic call writes crpt (rows + 1) and *cnnz, the caller allocates

@@ -11,6 +11,7 @@
 //   MinimumSpanningForest(a,edges,labels), MaximumSpanningForest(…)   the positions of the entries of the minimum / maximum spanning forest of the weighted undirected graph `a` (g4s_minimum_spanning_forest)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
 //   TriangularSolve(a,lower,unit)    an RAII plan of the level-scheduled solve T x = b on the lower / upper triangle of `a`: solve, update_values (g4s_sptrsv_*)
+//   ILU0<IT,NT>(a)                   an RAII handle of the ILU(0) factorisation of `a` (canonical rows): apply z = U⁻¹ L⁻¹ r, factor, factors (g4s_ilu0_*)
 //   KTruss(a,truss,round,support,max_k)   per stored entry: the truss number of its edge in the symmetric pattern `a`, the peel frontier that removed it, its triangles (g4s_ktruss)
 //   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
@@ -301,6 +302,66 @@ private:
     void *buf_ = nullptr;
     int32_t n_;
     g4s_trsv_info info_ = {};
+};
+
+// The ILU(0) factorisation of the square matrix `a` (g4s_ilu0_analyse): a ≈ L U on a's own pattern. The rows of `a` must be canonical — columns
+// strictly ascending, every diagonal entry stored (SortAndMerge gives such rows) —, anything else throws. The handle keeps its own copy on the
+// device; `a` need not outlive the constructor. apply(r, z): z = U⁻¹ (L⁻¹ r), host arrays of a.rows doubles, z may be r; copied through a device
+// buffer of the object, synchronous. apply_device: device arrays, enqueued on `stream`, asynchronous. factor(values): refactorise with new values
+// in the layout of a.values (all a.nnz of them; NULL: the values held); returns the smallest row whose pivot is zero or not finite, −1 when there
+// is none — which is no error. factors(out): a.nnz values in the layout of a.values, L strictly below the diagonal, U on and above it.
+template <typename IT, typename NT>
+class ILU0 {
+public:
+    explicit ILU0(const CSR<IT, NT> &a) : n_(a.rows)
+    {
+        if (a.rows != a.cols) throw std::runtime_error("ILU0: the matrix is not square");
+        const IT zero = 0;                                  // an empty CSR holds no arrays: nothing is read for rows == 0 or nnz == 0
+        const NT none = 0;
+        check(g4s_ilu0_analyse(&h_, a.rows, a.rowptr ? a.rowptr : &zero, a.nnz ? a.colids : &zero, a.nnz ? a.values : &none, G4S_HOST_POINTERS, &info_, nullptr),
+              "ILU0");
+    }
+    ILU0(const ILU0 &) = delete;
+    ILU0 &operator=(const ILU0 &) = delete;
+    ILU0(ILU0 &&o) noexcept : h_(o.h_), buf_(o.buf_), n_(o.n_), info_(o.info_) { o.h_ = nullptr; o.buf_ = nullptr; }
+    ~ILU0()
+    {
+        if (buf_) (void)g4s_dev_free(buf_);
+        if (h_) (void)g4s_ilu0_destroy(h_);
+    }
+    void apply(const double *r, double *z)
+    {
+        if (n_ == 0) return;
+        double *buf = buffer("ILU0::apply");
+        check(g4s_memcpy_h2d(buf, r, sizeof(double) * (size_t)n_), "ILU0::apply");
+        apply_device(buf, buf);
+        check(g4s_device_synchronize(), "ILU0::apply");
+        check(g4s_memcpy_d2h(z, buf, sizeof(double) * (size_t)n_), "ILU0::apply");
+    }
+    void apply_device(const double *r_dev, double *z_dev, void *stream = nullptr) { check(g4s_ilu0_apply(h_, r_dev, z_dev, stream), "ILU0::apply"); }
+    int32_t factor(const double *values = nullptr)
+    {
+        if (n_ == 0) return -1;
+        int32_t bad = -1;
+        int32_t *word = reinterpret_cast<int32_t *>(buffer("ILU0::factor") + n_);
+        check(g4s_ilu0_factor(h_, values, G4S_HOST_POINTERS, word, nullptr), "ILU0::factor");
+        check(g4s_device_synchronize(), "ILU0::factor");
+        check(g4s_memcpy_d2h(&bad, word, sizeof(bad)), "ILU0::factor");
+        return bad;
+    }
+    void factors(double *out) { check(g4s_ilu0_get_factors(h_, out, G4S_HOST_POINTERS, nullptr), "ILU0::factors"); }
+    const g4s_ilu0_info &info() const { return info_; }
+
+private:
+    double *buffer(const char *what)                        // n doubles for r / z and, behind them, the pivot word
+    {
+        if (!buf_) check(g4s_dev_alloc(&buf_, sizeof(double) * ((size_t)n_ + 1)), what);
+        return static_cast<double *>(buf_);
+    }
+    g4s_ilu0_t h_ = nullptr;
+    void *buf_ = nullptr;
+    int32_t n_;
+    g4s_ilu0_info info_ = {};
 };
 
 // truss[p] (a.nnz values, one per stored entry) = the largest k such that the edge stored at entry p belongs to a subgraph of the simple undirected graph
