@@ -106,19 +106,14 @@ __device__ __forceinline__ void finish(ClState *st, long long len_sum, long long
         // the state line this CU has held since the kernel's first lines
         if (m > __hip_atomic_load(&st->max_color, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&st->max_color, m);
     })) return;
-    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0), ot = atomicAdd(&st->over_tail, 0);
-    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
-    const int got = tail - st->end, had = st->end - st->head;      // what this kernel appended, what it coloured
-    st->head = st->end; st->end = tail;
-    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
-    st->edges_cur = e; st->edges_next = 0;
+    const int ot = atomicAdd(&st->over_tail, 0);
+    const QueueFlip f = flip_queue(st);                            // what this kernel appended, what it coloured
     const int pending = ot - st->over_end;                         // what this kernel sent to the overflow list
     st->over_head = st->over_end; st->over_end = ot;
-    st->tickets = 0;
     st->turns += 1;
-    if (kind == KIND_STEP && had > 0) st->round += 1;
+    if (kind == KIND_STEP && f.walked > 0) st->round += 1;
     // 5 before 1: the last frontier's overflow still wants its scan, and the step that resumes behind it finds an empty frontier and ends the call
-    st->stop = pending > 0 && !a.scan_follows ? 5 : got == 0 ? 1 : e > a.grid_cap ? 4 : 0;
+    st->stop = pending > 0 && !a.scan_follows ? 5 : f.appended == 0 ? 1 : f.entries > a.grid_cap ? 4 : 0;
 }
 
 __global__ __launch_bounds__(WG) void cl_open_rows_kernel(int n, const int *__restrict__ rowptr, int *__restrict__ pred, unsigned long long *__restrict__ mask,

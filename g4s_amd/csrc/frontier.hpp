@@ -1,10 +1,11 @@
-// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, components.hip, kcore.hip, color.hip, ktruss.hip, scc.hip, msf.hip, trsv.hip; DESIGN
+// frontier.hpp — what the frontier algorithms share (traverse.hip, betweenness.hip, components.hip, kcore.hip, color.hip, ktruss.hip, scc.hip, msf.hip, trsv.hip, ilu.hip; DESIGN
 // §4.11): the walk over the entries of a level's rows, balanced over entries (walk_tiles for ordinary rows, walk_hubs for long ones), the opening pass
 // of the calls on raw CSR arrays (open_rows: the row check; open_ids / open_hubs: the check of the column ids), the one-atomicAdd-per-wave append and
 // the append to a frontier that keeps a hub list (append_frontier), the two ends of a step kernel (step_runs; turn_page: the last workgroup to take a
-// ticket turns the page of the state block), the scan for stored zeros and the row grid; what a row is, its payload, what happens per entry and what a
-// page turn writes stay with the caller, as callables. It brings along WG and the wave reductions (wave_reduce.hpp, which pagerank.hip takes alone) and
-// the host side of the stepped loop (step_batch.hpp). level_peel.hpp puts the page turn and the host loop of kcore.hip and ktruss.hip on top of it.
+// ticket turns the page of the state block; flip_queue: what every page turn does to the queue words), the scan for stored zeros and the row grid;
+// what a row is, its payload, what happens per entry and what else a page turn writes stay with the caller, as callables. It brings along WG and the
+// wave reductions (wave_reduce.hpp, which pagerank.hip takes alone) and the host side of the stepped loop (step_batch.hpp). level_peel.hpp puts the
+// page turn and the host loop of kcore.hip and ktruss.hip on top of it.
 #pragma once
 #include "readback.hpp"
 #include "step_batch.hpp"
@@ -243,6 +244,26 @@ __device__ __forceinline__ bool turn_page(int *tickets, Publish publish)
     if (!s_last || threadIdx.x != 0) return false;
     __threadfence();
     return true;
+}
+
+// What the winner of turn_page does to the queue words that PeelState (step_batch.hpp), ClState (color.hpp) and TrState (trsv.hpp) name alike: the
+// frontier that was being built becomes the current one — queue[end, tail), its hub list, its entry sum —, an empty one is begun, and the tickets are
+// 0 for the next kernel. The totals are read back with atomics (turn_page says why). The caller's own words and its `stop` rule follow it.
+struct QueueFlip {
+    int appended, walked;                                          // items this kernel appended; items of the frontier it walked
+    long long entries;                                             // the entry sum of what it appended
+};
+template <typename State>
+__device__ __forceinline__ QueueFlip flip_queue(State *st)
+{
+    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0);
+    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
+    const QueueFlip f{tail - st->end, st->end - st->head, e};
+    st->head = st->end; st->end = tail;
+    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
+    st->edges_cur = e; st->edges_next = 0;
+    st->tickets = 0;
+    return f;
 }
 
 // *flag |= 1 when a stored value is 0.0: or-and takes a stored zero for no edge, so the kernels of such a matrix have to read the values

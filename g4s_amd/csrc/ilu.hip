@@ -9,11 +9,11 @@
 //   factor   per launch of the lower plan ilu_level_kernel (one wide level) or ilu_chain_kernel (one workgroup, a run of narrow levels, a fence and a
 //            barrier behind each); then g4s_sptrsv_update_values on both plans.
 //   apply    g4s_sptrsv_solve on the lower plan (r → z), then on the upper plan (z → z).
-// Memory model. A row reads the finished values of earlier rows: in a level kernel they were stored behind a kernel boundary and plain
-// loads do; in a chain they may be this workgroup's of a moment ago, and ldf<true> loads them in L2. A row's own working values w are shared between
-// the lanes that update them inside one kernel, so they live in registers (one lane's row), in LDS (one wave's row, behind a wave barrier per step) or
-// — the workgroup's row — in f itself, where every read of them is an agent-scope load behind __threadfence() and __syncthreads(). No row reads a
-// value of another row of its own level; no wave waits for another workgroup.
+// The frame — the launch walk, the deal of a tile's rows, the levels of a chain — is the solve's (level_schedule.hpp, level_tile.hpp), and so is the
+// memory model of the finished values of earlier rows (ld_prior<kChain>, for_chain_levels). A row's own working values w are shared
+// between the lanes that update them inside one kernel, so they live in registers (one lane's row), in LDS (one wave's row, behind a wave barrier per
+// step) or — the workgroup's row — in f itself, where every read of them is an agent-scope load (ld_prior<true>, whatever the kernel) behind
+// __threadfence() and __syncthreads(). No row reads a value of another row of its own level; no wave waits for another workgroup.
 // The arithmetic of g4s.h is factor_tile's three row functions and nothing else: each performs, per k ascending, w_p / u_kk and then w_t − (w_p · u_kj).
 #include "common.hpp"
 #include "frontier.hpp"
@@ -21,6 +21,7 @@
 #include "readback.hpp"
 #include "trsv.hpp"
 #include "ilu.hpp"
+#include "level_tile.hpp"
 #include <algorithm>
 #include <climits>
 #include <memory>
@@ -35,7 +36,6 @@ struct g4s_ilu0_s {
     unsigned *bad = nullptr;            // the pivot word of a factorisation whose caller passes none
     double *a = nullptr, *f = nullptr;  // the values last factorised; the factors
     g4s_trsv_t lower = nullptr, upper = nullptr;
-    g4s::TrSchedule sched{};
     g4s_ilu0_info info{};
     ~g4s_ilu0_s()
     {
@@ -50,12 +50,9 @@ using g4s::IluState;
 
 constexpr int kLaneRow = G4S_ILU0_LANE_ROW;
 constexpr int kWaveRow = G4S_ILU0_WAVE_ROW;
-constexpr int kChainWidth = G4S_TRSV_CHAIN_WIDTH;
 constexpr size_t kStateBytes = 256;
 constexpr unsigned kFlagMask = G4S_DEVICE_POINTERS | G4S_ILU0_NO_CHAINS;
 static_assert(sizeof(IluState) <= kStateBytes, "state block");
-static_assert(kChainWidth == WG, "a level of a chain is one tile of the workgroup");
-static_assert(kLaneRow >= 1 && kLaneRow < kWaveRow, "the three row classes");
 static_assert((G4S_ILU0_NO_CHAINS & (G4S_DEVICE_POINTERS | G4S_TRSV_UPPER | G4S_TRSV_UNIT_DIAGONAL | G4S_TRSV_NO_CHAINS)) == 0u, "a bit of its own");
 
 // ------------------------------------------------------------------------------------------------------------------------------- the check
@@ -103,19 +100,6 @@ struct IluView {
     unsigned *bad;
 };
 
-__device__ __forceinline__ double ld_l2(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// a finished value of an earlier row
-template <bool kChain>
-__device__ __forceinline__ double ldf(const double *f, int q)
-{
-    if constexpr (kChain) return ld_l2(f + q);
-    else return f[q];
-}
-
-// the stored form of a finished value: IEEE leaves a NaN's sign and payload open, the header fixes them
-__device__ __forceinline__ double finished(double v) { return v != v ? __longlong_as_double(0x7FF8000000000000ll) : v; }
-
 __device__ __forceinline__ void note_pivot(unsigned *bad, int i, double u)
 {
     if (u == 0.0 || !(fabs(u) < __longlong_as_double(0x7FF0000000000000ll))) atomicMin(bad, (unsigned)i);
@@ -143,11 +127,11 @@ __device__ __forceinline__ void lane_row(const IluView &V, int i, int rb, int m)
         const int k = c[p];
         if (k < i) {                                               // ascending: false from the diagonal on
             const int dk = V.dpos[k], ke = V.rowptr[k + 1];
-            const double wp = w[p] / ldf<kChain>(V.f, dk);
+            const double wp = w[p] / ld_prior<kChain>(V.f + dk);
             w[p] = wp;
             for (int q = dk + 1; q < ke; ++q) {
                 const int j = V.colids[q];
-                const double prod = wp * ldf<kChain>(V.f, q);
+                const double prod = wp * ld_prior<kChain>(V.f + q);
 #pragma unroll
                 for (int t = p + 1; t < kLaneRow; ++t)
                     if (c[t] == j) w[t] = w[t] - prod;
@@ -157,7 +141,7 @@ __device__ __forceinline__ void lane_row(const IluView &V, int i, int rb, int m)
 #pragma unroll
     for (int t = 0; t < kLaneRow; ++t) {
         if (t < m) {
-            const double v = finished(w[t]);
+            const double v = canonical_nan(w[t]);
             V.f[rb + t] = v;
             if (c[t] == i) note_pivot(V.bad, i, v);
         }
@@ -190,19 +174,19 @@ __device__ __forceinline__ void wave_row(const IluView &V, int i, int rb, int m,
     const int nlow = V.dpos[i] - rb;
     for (int p = 0; p < nlow; ++p) {
         const int k = sc[p], dk = V.dpos[k], ke = V.rowptr[k + 1];
-        const double wp = sw[p] / ldf<kChain>(V.f, dk);
+        const double wp = sw[p] / ld_prior<kChain>(V.f + dk);
         wave_sync();
         if (lane == 0) sw[p] = wp;
         for (int q = dk + 1 + lane; q < ke; q += 64) {
             const int j = V.colids[q];
-            const double u = ldf<kChain>(V.f, q);
+            const double u = ld_prior<kChain>(V.f + q);
             const int t = find_col([&](int x) { return sc[x]; }, p + 1, m, j);
             if (t < m) sw[t] = sw[t] - wp * u;
         }
         wave_sync();
     }
     for (int t = lane; t < m; t += 64) {
-        const double v = finished(sw[t]);
+        const double v = canonical_nan(sw[t]);
         V.f[rb + t] = v;
         if (t == nlow) note_pivot(V.bad, i, v);
     }
@@ -210,7 +194,7 @@ __device__ __forceinline__ void wave_row(const IluView &V, int i, int rb, int m,
 }
 
 // Row i of more than kWaveRow entries, by the workgroup (every thread calls): w is the row of f itself. A value of it is stored plainly by one thread
-// and read by others only with ld_l2 behind the __threadfence() and the __syncthreads() that end every step.
+// and read by others only with ld_prior<true> behind the __threadfence() and the __syncthreads() that end every step.
 template <bool kChain>
 __device__ __forceinline__ void hub_row(const IluView &V, int i, int t, double *s_wp)
 {
@@ -221,7 +205,7 @@ __device__ __forceinline__ void hub_row(const IluView &V, int i, int t, double *
     for (int p = 0; p < nlow; ++p) {
         const int k = V.colids[rb + p], dk = V.dpos[k], ke = V.rowptr[k + 1];
         if (t == 0) {
-            const double wp = ld_l2(V.f + rb + p) / ldf<kChain>(V.f, dk);
+            const double wp = ld_prior<true>(V.f + rb + p) / ld_prior<kChain>(V.f + dk);
             V.f[rb + p] = wp;
             *s_wp = wp;
         }
@@ -229,46 +213,38 @@ __device__ __forceinline__ void hub_row(const IluView &V, int i, int t, double *
         const double wp = *s_wp;
         for (int q = dk + 1 + t; q < ke; q += WG) {
             const int j = V.colids[q];
-            const double u = ldf<kChain>(V.f, q);
+            const double u = ld_prior<kChain>(V.f + q);
             const int x = find_col([&](int y) { return V.colids[rb + y]; }, p + 1, m, j);
-            if (x < m) V.f[rb + x] = ld_l2(V.f + rb + x) - wp * u;
+            if (x < m) V.f[rb + x] = ld_prior<true>(V.f + rb + x) - wp * u;
         }
         __threadfence();
         __syncthreads();
     }
     for (int q = t; q < m; q += WG) {
-        const double v = ld_l2(V.f + rb + q);
-        if (v != v) V.f[rb + q] = finished(v);
+        const double v = ld_prior<true>(V.f + rb + q);
+        if (v != v) V.f[rb + q] = canonical_nan(v);
         if (q == nlow) note_pivot(V.bad, i, v);
     }
 }
 
-// Rows [lo, hi) of the schedule, hi − lo <= WG / stride, all of one level; called by every thread of the workgroup. Thread t owns row lo + t / stride
-// when stride divides t — solve_tile's deal (trsv.hip): a lane's rows first, then each wave its wave rows one after another, then the workgroup
-// the longest ones. Who factorises a row never changes a bit of it.
+// Rows [lo, hi) of the schedule, all of one level, dealt by deal_tile (level_tile.hpp): a lane's rows first, then each wave its wave rows one after
+// another, then the workgroup the longest ones. Who factorises a row never changes a bit of it.
+struct IluRow {
+    int m, i, rb;                                                  // stored entries, the row, and where they begin
+};
+
 template <bool kChain>
 __device__ __forceinline__ void factor_tile(const IluView &V, int lo, int hi, int stride, int *s_hub, int *s_nh, double *s_w, int *s_c, double *s_wp)
 {
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int p = lo + t / stride;
-    const bool have = t % stride == 0 && p < hi;
-    const int i = have ? V.rowid[p] : 0, rb = have ? V.rowptr[i] : 0, m = have ? V.rowptr[i + 1] - rb : 0;
-    if (t == 0) *s_nh = 0;
-    __syncthreads();
-    if (m > kWaveRow) s_hub[atomicAdd(s_nh, 1)] = t;               // in any order: the rows of a level do not read each other
-    if (have && m <= kLaneRow) lane_row<kChain>(V, i, rb, m);
-    unsigned long long wm = __ballot(m > kLaneRow && m <= kWaveRow);
-    while (wm) {                                                   // the same for every lane of the wave
-        const int j = __ffsll((long long)wm) - 1;
-        wm &= wm - 1;
-        wave_row<kChain>(V, __shfl(i, j), __shfl(rb, j), __shfl(m, j), s_w + wave * kWaveRow, s_c + wave * kWaveRow, lane);
-    }
-    __syncthreads();
-    const int nh = *s_nh;
-    for (int h = 0; h < nh; ++h) {
-        hub_row<kChain>(V, V.rowid[lo + s_hub[h] / stride], t, s_wp);
-        __syncthreads();
-    }
+    deal_tile<kLaneRow, kWaveRow>(lo, hi, stride, s_hub, s_nh,
+        [&](int p) {
+            const int i = V.rowid[p], rb = V.rowptr[i];
+            return IluRow{V.rowptr[i + 1] - rb, i, rb};
+        },
+        [&](const IluRow &r) { lane_row<kChain>(V, r.i, r.rb, r.m); },
+        [&](const IluRow &r, int j) { wave_row<kChain>(V, __shfl(r.i, j), __shfl(r.rb, j), __shfl(r.m, j), s_w + wave * kWaveRow, s_c + wave * kWaveRow, lane); },
+        [&](const IluRow &r, int) { hub_row<kChain>(V, r.i, t, s_wp); });
 }
 
 // one level that is not in a chain: a tile of WG / stride rows per workgroup
@@ -276,24 +252,16 @@ __global__ __launch_bounds__(WG) void ilu_level_kernel(const IluView V, int lo, 
 {
     __shared__ int s_hub[WG], s_nh, s_c[(WG / 64) * kWaveRow];
     __shared__ double s_w[(WG / 64) * kWaveRow], s_wp;
-    const long long t0 = (long long)lo + (long long)blockIdx.x * (WG / stride);
-    const int t1 = (int)std::min<long long>(hi, t0 + WG / stride);
-    factor_tile<false>(V, (int)t0, t1, stride, s_hub, &s_nh, s_w, s_c, &s_wp);
+    const int2 tile = level_tile_bounds(lo, hi, stride);
+    factor_tile<false>(V, tile.x, tile.y, stride, s_hub, &s_nh, s_w, s_c, &s_wp);
 }
 
-// a chain: one workgroup, levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one stored
+// a chain: one workgroup, levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one stored (for_chain_levels)
 __global__ __launch_bounds__(WG) void ilu_chain_kernel(const IluView V, int level_lo, int level_hi)
 {
     __shared__ int s_hub[WG], s_nh, s_c[(WG / 64) * kWaveRow];
     __shared__ double s_w[(WG / 64) * kWaveRow], s_wp;
-    for (int l = level_lo; l < level_hi; ++l) {
-        const int lo = V.loff[l], hi = V.loff[l + 1];
-        int stride = 64;                                           // the level's rows spread over the four waves: the largest stride that leaves room
-        while (stride > 1 && WG / stride < hi - lo) stride >>= 1;
-        factor_tile<true>(V, lo, hi, stride, s_hub, &s_nh, s_w, s_c, &s_wp);
-        __threadfence();                                           // this level's rows in L2 before anybody passes the barrier
-        __syncthreads();
-    }
+    for_chain_levels(V.loff, level_lo, level_hi, [&](int lo, int hi, int stride) { factor_tile<true>(V, lo, hi, stride, s_hub, &s_nh, s_w, s_c, &s_wp); });
 }
 
 // −1, no bad pivot: the largest unsigned, which every row with one lowers. A kernel, not a memset: a factorisation is captured into graphs.
@@ -302,17 +270,12 @@ __global__ void ilu_begin_kernel(unsigned *bad) { *bad = ~0u; }
 // The factor launches on the values in P->a, the pivot word in front of them, and both plans refreshed from f. Enqueues only.
 int enqueue_factor(g4s_ilu0_s *P, unsigned *bad, hipStream_t s)
 {
-    const IluView V{P->rowptr, P->colids, P->dpos, P->sched.rowid, P->sched.loff, P->a, P->f, bad};
+    const g4s::LevelSchedule &S = g4s::trsv_schedule(P->lower);
+    const IluView V{P->rowptr, P->colids, P->dpos, S.rowid, S.loff, P->a, P->f, bad};
     hipLaunchKernelGGL(ilu_begin_kernel, dim3(1), dim3(1), 0, s, bad);
-    for (const g4s::TrLaunch &L : *P->sched.launches) {
-        if (L.chain) {
-            hipLaunchKernelGGL(ilu_chain_kernel, dim3(1), dim3(WG), 0, s, V, L.level_lo, L.level_hi);
-        } else {                                                   // one level
-            const int lo = P->sched.loff_host[L.level_lo], hi = P->sched.loff_host[L.level_hi];
-            const int rows = WG / g4s::ilu_stride(hi - lo, P->sched.lent_host[L.level_hi] - P->sched.lent_host[L.level_lo]);
-            hipLaunchKernelGGL(ilu_level_kernel, dim3((unsigned)((hi - lo + rows - 1) / rows)), dim3(WG), 0, s, V, lo, hi, WG / rows);
-        }
-    }
+    g4s::for_each_launch(S, g4s::ilu_stride,
+        [&](int level_lo, int level_hi) { hipLaunchKernelGGL(ilu_chain_kernel, dim3(1), dim3(WG), 0, s, V, level_lo, level_hi); },
+        [&](int lo, int hi, int stride, int grid) { hipLaunchKernelGGL(ilu_level_kernel, dim3((unsigned)grid), dim3(WG), 0, s, V, lo, hi, stride); });
     G4S_HIP_TRY(hipGetLastError());
     G4S_TRY(g4s_sptrsv_update_values(P->lower, P->f, G4S_DEVICE_POINTERS, s));
     G4S_TRY(g4s_sptrsv_update_values(P->upper, P->f, G4S_DEVICE_POINTERS, s));
@@ -377,7 +340,6 @@ int analyse(g4s_ilu0_s *P, const int32_t *rowptr, const int32_t *colids, const d
     g4s_trsv_info li{}, ui{};
     G4S_TRY(g4s_sptrsv_analyse(&P->lower, n, P->rowptr, P->colids, P->f, nullptr, G4S_DEVICE_POINTERS | G4S_TRSV_UNIT_DIAGONAL | chains, &li, s));
     G4S_TRY(g4s_sptrsv_analyse(&P->upper, n, P->rowptr, P->colids, P->f, nullptr, G4S_DEVICE_POINTERS | G4S_TRSV_UPPER | chains, &ui, s));
-    P->sched = g4s::trsv_schedule(P->lower);
 
     G4S_TRY(enqueue_factor(P, P->bad, s));
     int bad_pivot = -1;

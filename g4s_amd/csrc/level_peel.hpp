@@ -1,6 +1,7 @@
 // level_peel.hpp — what the level peels share (kcore.hip: vertices by degree; ktruss.hip: edges by triangle support) on top of frontier.hpp
-// and call_util.hpp: the end of their scan and peel kernels on the PeelState words of their state blocks (step_batch.hpp), and the host loop that
-// enqueues PeelSchedule's batches. The kernels themselves, what an item and its row are, and the opening launches stay with the two files.
+// and call_util.hpp: the end of their scan and peel kernels on the PeelState words of their state blocks (step_batch.hpp; the queue words are flipped by
+// flip_queue of frontier.hpp, as color.hip's and trsv.hip's are), and the host loop that enqueues PeelSchedule's batches. The kernels themselves, what
+// an item and its row are, and the opening launches stay with the two files.
 #pragma once
 #include "frontier.hpp"
 #include "call_util.hpp"
@@ -32,18 +33,13 @@ __device__ __forceinline__ void finish_step(g4s::PeelState *st, long long len_su
         // copy of the state line this CU has held since the kernel's first lines
         if (m < __hip_atomic_load(&st->min_left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&st->min_left, m);
     })) return;
-    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0), m = atomicAdd(&st->min_left, 0);
-    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
-    const int got = tail - st->end;                                // what this kernel appended
-    st->head = st->end; st->end = tail;
-    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
-    st->edges_cur = e; st->edges_next = 0;
+    const int m = atomicAdd(&st->min_left, 0);
+    const QueueFlip f = flip_queue(st);
     st->min_left = INT_MAX;
-    st->tickets = 0;
-    int stop = e > grid_cap ? 4 : 0;
+    int stop = f.entries > grid_cap ? 4 : 0;
     if (kind == KIND_SCAN) {
         st->scans += 1;
-        if (got == 0) {                                            // items are left (a scan does not run otherwise), all above the level: m is one's count
+        if (f.appended == 0) {                                     // items are left (a scan does not run otherwise), all above the level: m is one's count
             st->level = m;
             if (m >= level_cap) stop = 2;
         } else {
@@ -52,7 +48,7 @@ __device__ __forceinline__ void finish_step(g4s::PeelState *st, long long len_su
         }
     } else {
         st->round += 1;
-        if (got == 0 && tail >= items()) stop = 1;
+        if (f.appended == 0 && st->end >= items()) stop = 1;       // end: the append counter this kernel left
     }
     st->stop = stop;
 }

@@ -21,7 +21,8 @@ struct StepGrid {
 };
 
 // The head of the device-resident state of a level peel (KcState, KtState): items (vertices, edges) leave level by level and inside a level frontier
-// by frontier, through ONE queue that holds all frontiers one behind the other. The host reads the whole block once per batch of steps.
+// by frontier, through ONE queue that holds all frontiers one behind the other. The host reads the whole block once per batch of steps. The queue words
+// — edges_cur … hub_cur and tickets — carry the names flip_queue (frontier.hpp) turns them by, as in ClState (color.hpp) and TrState (trsv.hpp).
 struct PeelState {
     long long edges_cur;                // stored entries of the current frontier's rows: what the launch grid is sized from
     long long edges_next;               // of the frontier being built

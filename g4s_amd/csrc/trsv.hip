@@ -13,20 +13,19 @@
 //   layout   a stable radix sort of the rows by level (prims.hpp) gives the (level, id) order; a histogram and a scan the level offsets; a scan of
 //            the row lengths the entry offsets; tr_gather_kernel (one wave per row, ballots keep the stored order) writes each row's off-diagonal
 //            entries and behind them its diagonal entries, with the position map update_values refreshes them through.
-// The solve enqueues the launch list (trsv.hpp) and waits for nothing. Every launch solves whole levels, so a row reads only x values written behind
-// a kernel boundary or — inside a chain — by its own workgroup behind a fence and a barrier. No wave waits for another workgroup; nothing spins.
-// Memory model: a chain's rows read x with agent-scope loads (performed in L2, past whatever copy the CU's vector cache holds from an earlier level,
-// DESIGN §4.8) and every level of a chain ends with __threadfence() and __syncthreads(); a level kernel reads x with plain loads.
+// The solve enqueues the launch list (for_each_launch, level_schedule.hpp) and waits for nothing. Every launch solves whole levels, so a row reads only
+// x values written behind a kernel boundary or — inside a chain — by its own workgroup behind a fence and a barrier: the frame and its memory model
+// are level_tile.hpp's (deal_tile, for_chain_levels, ld_prior), shared with ilu.hip. No wave waits for another workgroup; nothing spins.
 // The arithmetic shape of a row (g4s.h) depends on its own entry count alone: solve_tile is the one place that computes it, for both kernels.
 #include "common.hpp"
 #include "frontier.hpp"
 #include "call_util.hpp"
 #include "prims.hpp"
 #include "trsv.hpp"
+#include "level_tile.hpp"
 #include <algorithm>
 #include <climits>
 #include <new>
-#include <vector>
 
 struct g4s_trsv_s {
     int n = 0;
@@ -34,11 +33,9 @@ struct g4s_trsv_s {
     long long nnz_in = 0;               // entries of the arrays the handle was analysed from: what update_values reads
     long long nnz_tri = 0;
     g4s::DevBuf block;                  // the (level, row) layout, one allocation
-    int *rowid = nullptr, *ebeg = nullptr, *noff = nullptr, *lcol = nullptr, *emap = nullptr, *loff = nullptr;
+    int *ebeg = nullptr, *noff = nullptr, *lcol = nullptr, *emap = nullptr;
     double *diag = nullptr, *lval = nullptr;
-    std::vector<int> loff_host;         // the level offsets, for the grids of the level launches
-    std::vector<int> lent_host;         // the entry offsets of the levels, for their strides
-    std::vector<g4s::TrLaunch> launches;
+    g4s::LevelSchedule sched;           // rowid and loff point into the block
     g4s_trsv_info info{};
 };
 
@@ -48,13 +45,9 @@ using g4s::TrState;
 
 constexpr int kBatch = 16;                    // step launches behind one state read, at least; doubles up to g4s::kBatchMax (step_batch.hpp)
 constexpr int kWaveRow = G4S_TRSV_WAVE_ROW;
-constexpr int kChainWidth = G4S_TRSV_CHAIN_WIDTH;
-constexpr int kChainLevels = G4S_TRSV_CHAIN_LEVELS;
 constexpr size_t kStateBytes = 256;
 constexpr unsigned kFlagMask = G4S_DEVICE_POINTERS | G4S_TRSV_UPPER | G4S_TRSV_UNIT_DIAGONAL | G4S_TRSV_NO_CHAINS;
 static_assert(sizeof(TrState) <= kStateBytes, "state block");
-static_assert(kChainWidth == WG, "a level of a chain is one tile of the workgroup");
-static_assert(kWaveRow >= 1 && kWaveRow < kHubCut, "the three row classes");
 
 enum { KIND_SEED = 0, KIND_STEP = 1 };
 
@@ -160,15 +153,9 @@ __device__ __forceinline__ void finish(TrState *st, long long len_sum, int kind,
         for (int w = 0; w < WG / 64; ++w) ls += s_len[w];
         if (ls) atomicAdd((unsigned long long *)&st->edges_next, (unsigned long long)ls);
     })) return;
-    const int tail = atomicAdd(&st->tail, 0), nh = atomicAdd(&st->n_hub_next, 0);
-    const long long e = (long long)atomicAdd((unsigned long long *)&st->edges_next, 0ull);
-    const int got = tail - st->end, had = st->end - st->head;      // what this kernel appended, what it walked
-    st->head = st->end; st->end = tail;
-    st->n_hub_cur = nh; st->n_hub_next = 0; st->hub_cur ^= 1;
-    st->edges_cur = e; st->edges_next = 0;
-    st->tickets = 0;
-    if (kind == KIND_STEP && had > 0) st->round += 1;
-    st->stop = got == 0 ? 1 : e > a.grid_cap ? 4 : 0;
+    const QueueFlip f = flip_queue(st);
+    if (kind == KIND_STEP && f.walked > 0) st->round += 1;
+    st->stop = f.appended == 0 ? 1 : f.entries > a.grid_cap ? 4 : 0;
 }
 
 // Frontier 0: the rows that wait for nothing. Its page turn is a step's, without a round.
@@ -314,13 +301,6 @@ struct TrView {
     int unit;
 };
 
-template <bool kChain>
-__device__ __forceinline__ double ldx(const double *x, int c)
-{
-    if constexpr (kChain) return __hip_atomic_load(x + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return x[c];
-}
-
 // One lane's share of a row's sum: the entries first, first + kStride, … below m of the row whose entries begin at e, added left to right from +0.0.
 // kUnroll entries are loaded before the first of them is added — a lane has one dependent pair of loads (the column, then x) per entry, and a hub row
 // of 10⁵ entries is 400 such pairs per lane —; the additions keep their order, so the bits do not depend on kUnroll.
@@ -337,84 +317,65 @@ __device__ __forceinline__ double strided_sum(const TrView &T, const double *x, 
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) v[u] = T.lval[e + k + u * kStride];
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) y[u] = ldx<kChain>(x, c[u]);
+        for (int u = 0; u < kUnroll; ++u) y[u] = ld_prior<kChain>(x + c[u]);
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) s = s + v[u] * y[u];
     }
-    for (; k < m; k += kStride) s = s + T.lval[e + k] * ldx<kChain>(x, T.lcol[e + k]);
+    for (; k < m; k += kStride) s = s + T.lval[e + k] * ld_prior<kChain>(x + T.lcol[e + k]);
     return s;
 }
 
-// Rows [lo, hi) of the layout, hi − lo <= WG / stride, all of one level; called by every thread of the workgroup. Thread t owns row lo + t / stride when
-// stride (a power of two up to 64) divides t, and writes its x: a wave takes its rows above kWaveRow entries one after another, so where rows are long
-// the launch gives a wave few of them. Who sums a row never changes how it is summed.
+// Rows [lo, hi) of the layout, all of one level, dealt by deal_tile (level_tile.hpp); the owner of a row keeps its sum s through the three classes and
+// writes its x. Who sums a row never changes how it is summed:
 //   m <= kWaveRow            the lane alone, left to right from +0.0
 //   kWaveRow < m <= kHubCut  the row's wave: lane l takes entries l, l + 64, … left to right from +0.0, then the wave_sum ladder
 //   m > kHubCut              the workgroup: thread t takes entries t, t + 256, …, a wave_sum ladder per wave, then ((w0 + w1) + w2) + w3
 // b and x may be the same array: row r is the only reader of b[r] and the only writer of x[r].
+struct TrRow {
+    int m, e;                                                      // off-diagonal entries, and where they begin
+};
+
 template <bool kChain>
 __device__ __forceinline__ void solve_tile(const TrView &T, int lo, int hi, int stride, const double *b, double *x, int *s_hub, int *s_nh, double *s_part)
 {
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int p = lo + t / stride;
-    const bool have = t % stride == 0 && p < hi;
-    const int m = have ? T.noff[p] : 0, e0 = have ? T.ebeg[p] : 0;
     double s = 0.0;
-    if (t == 0) *s_nh = 0;
-    __syncthreads();
-    if (m > kHubCut) s_hub[atomicAdd(s_nh, 1)] = t;                // in any order: a hub's sum does not depend on its turn
-    if (m <= kWaveRow) s = strided_sum<kChain, 1, 4>(T, x, e0, 0, m);
-    unsigned long long wm = __ballot(m > kWaveRow && m <= kHubCut);
-    while (wm) {                                                   // the same for every lane of the wave
-        const int j = __ffsll((long long)wm) - 1;
-        wm &= wm - 1;
-        const int mj = __shfl(m, j), ej = __shfl(e0, j);
-        const double part = __shfl(wave_sum(strided_sum<kChain, 64, 8>(T, x, ej, lane, mj)), 0);
-        if (lane == j) s = part;
-    }
-    __syncthreads();
-    const int nh = *s_nh;
-    for (int h = 0; h < nh; ++h) {
-        const int th = s_hub[h], mh = T.noff[lo + th / stride], eh = T.ebeg[lo + th / stride];
-        const double part = wave_sum(strided_sum<kChain, WG, 8>(T, x, eh, t, mh));
-        if (lane == 0) s_part[wave] = part;
-        __syncthreads();
-        if (t == th) s = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-        __syncthreads();
-    }
-    if (have) {
+    const int p = deal_tile<kWaveRow, kHubCut>(lo, hi, stride, s_hub, s_nh,
+        [&](int p) { return TrRow{T.noff[p], T.ebeg[p]}; },
+        [&](const TrRow &r) { s = strided_sum<kChain, 1, 4>(T, x, r.e, 0, r.m); },
+        [&](const TrRow &r, int j) {
+            const double part = __shfl(wave_sum(strided_sum<kChain, 64, 8>(T, x, __shfl(r.e, j), lane, __shfl(r.m, j))), 0);
+            if (lane == j) s = part;
+        },
+        [&](const TrRow &r, int th) {
+            const double part = wave_sum(strided_sum<kChain, WG, 8>(T, x, r.e, t, r.m));
+            if (lane == 0) s_part[wave] = part;
+            __syncthreads();
+            if (t == th) s = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+        });
+    if (p >= 0) {
         const int r = T.rowid[p];
         double v = b[r] - s;
         if (!T.unit) v = v / T.diag[p];
-        if (v != v) v = __longlong_as_double(0x7FF8000000000000ll);   // IEEE leaves a NaN's sign and payload open (b − s is b + (−s) here): the header fixes them
-        x[r] = v;
+        x[r] = canonical_nan(v);
     }
 }
-static_assert(WG / 64 == 4, "the hub shape adds four wave sums");
 
 // one level that is not in a chain: a tile of WG / stride rows per workgroup
 __global__ __launch_bounds__(WG) void tr_level_kernel(const TrView T, int lo, int hi, int stride, const double *b, double *x)
 {
     __shared__ int s_hub[WG], s_nh;
     __shared__ double s_part[WG / 64];
-    const long long t0 = (long long)lo + (long long)blockIdx.x * (WG / stride);
-    const int t1 = (int)std::min<long long>(hi, t0 + WG / stride);
-    solve_tile<false>(T, (int)t0, t1, stride, b, x, s_hub, &s_nh, s_part);
+    const int2 tile = level_tile_bounds(lo, hi, stride);
+    solve_tile<false>(T, tile.x, tile.y, stride, b, x, s_hub, &s_nh, s_part);
 }
 
-// a chain: one workgroup, levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one stored
+// a chain: one workgroup, levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one stored (for_chain_levels)
 __global__ __launch_bounds__(WG) void tr_chain_kernel(const TrView T, int level_lo, int level_hi, const double *b, double *x)
 {
     __shared__ int s_hub[WG], s_nh;
     __shared__ double s_part[WG / 64];
-    for (int l = level_lo; l < level_hi; ++l) {
-        const int lo = T.loff[l], hi = T.loff[l + 1];
-        int stride = 64;                                           // the level's rows spread over the four waves: the largest stride that leaves room
-        while (stride > 1 && WG / stride < hi - lo) stride >>= 1;
-        solve_tile<true>(T, lo, hi, stride, b, x, s_hub, &s_nh, s_part);
-        __threadfence();                                           // this level's x in L2 before anybody passes the barrier
-        __syncthreads();
-    }
+    for_chain_levels(T.loff, level_lo, level_hi, [&](int lo, int hi, int stride) { solve_tile<true>(T, lo, hi, stride, b, x, s_hub, &s_nh, s_part); });
 }
 
 int bits_of(int v)
@@ -489,51 +450,53 @@ int peel(int n, const int *rowptr, const int *colids, int upper, const Work &w, 
     return G4S_OK;
 }
 
-// The (level, row) layout into the handle's arrays, and the level offsets to the host; returns behind a wait on `s`.
-int layout(g4s_trsv_s *T, int levels, const int *rowptr, const int *colids, const double *values, int upper, int unit, const Work &w, int cus,
-           std::vector<int> *loff_host, Counts *cnt, hipStream_t s)
+// The (level, row) layout into the handle's arrays, and the level offsets and the levels' entry offsets to the host; returns behind a wait on `s`.
+int layout(g4s_trsv_s *T, int levels, const int *rowptr, const int *colids, const double *values, int upper, int unit, const Work &w, int cus, Counts *cnt,
+           hipStream_t s)
 {
+    g4s::LevelSchedule &S = T->sched;
     const int n = T->n, g_rows = grid_rows(n, cus);
     G4S_HIP_TRY(hipMemsetAsync(w.lcnt, 0, sizeof(int) * ((size_t)levels + 1), s));
     G4S_HIP_TRY(hipMemsetAsync(w.tot + n, 0, sizeof(int), s));
     hipLaunchKernelGGL(tr_keys_kernel, dim3(g_rows), dim3(WG), 0, s, n, levels, w.level, w.keys, w.ids, w.lcnt);
-    G4S_TRY(g4s::prims::sort_pairs_descending(w.keys, w.ids, w.keys_out, T->rowid, w.tmpk, w.tmpv, n, bits_of(levels - 1), s));
-    G4S_TRY(g4s::prims::exclusive_scan(w.lcnt, T->loff, (long long)levels + 1, s));
-    hipLaunchKernelGGL(tr_rowlen_kernel, dim3(g_rows), dim3(WG), 0, s, n, T->rowid, w.ocnt, w.dcnt, T->noff, w.tot);
+    G4S_TRY(g4s::prims::sort_pairs_descending(w.keys, w.ids, w.keys_out, S.rowid, w.tmpk, w.tmpv, n, bits_of(levels - 1), s));
+    G4S_TRY(g4s::prims::exclusive_scan(w.lcnt, S.loff, (long long)levels + 1, s));
+    hipLaunchKernelGGL(tr_rowlen_kernel, dim3(g_rows), dim3(WG), 0, s, n, S.rowid, w.ocnt, w.dcnt, T->noff, w.tot);
     G4S_TRY(g4s::prims::exclusive_scan(w.tot, T->ebeg, (long long)n + 1, s));
-    hipLaunchKernelGGL(tr_gather_kernel, dim3(grid_for<WG / 64>(n, 16LL * cus)), dim3(WG), 0, s, n, upper, unit, rowptr, colids, values, T->rowid, T->ebeg, T->noff,
+    hipLaunchKernelGGL(tr_gather_kernel, dim3(grid_for<WG / 64>(n, 16LL * cus)), dim3(WG), 0, s, n, upper, unit, rowptr, colids, values, S.rowid, T->ebeg, T->noff,
                        T->lcol, T->lval, T->emap, T->diag);
     G4S_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tr_level_entries_kernel, dim3(grid_for<WG>((long long)levels + 1, 64)), dim3(WG), 0, s, levels, T->loff, T->ebeg, w.lcnt);   // lcnt is free again
+    hipLaunchKernelGGL(tr_level_entries_kernel, dim3(grid_for<WG>((long long)levels + 1, 64)), dim3(WG), 0, s, levels, S.loff, T->ebeg, w.lcnt);   // lcnt is free again
     G4S_HIP_TRY(hipGetLastError());
     cnt->launches += 4 + 3 * ((bits_of(levels - 1) + 3) / 4) + 6;  // a scan counts as three, a sort pass as three
-    loff_host->resize((size_t)levels + 1);
-    T->lent_host.resize((size_t)levels + 1);
-    G4S_HIP_TRY(hipMemcpyAsync(loff_host->data(), T->loff, sizeof(int) * ((size_t)levels + 1), hipMemcpyDeviceToHost, s));
-    G4S_HIP_TRY(hipMemcpyAsync(T->lent_host.data(), w.lcnt, sizeof(int) * ((size_t)levels + 1), hipMemcpyDeviceToHost, s));
+    S.loff_host.resize((size_t)levels + 1);
+    S.lent_host.resize((size_t)levels + 1);
+    G4S_HIP_TRY(hipMemcpyAsync(S.loff_host.data(), S.loff, sizeof(int) * ((size_t)levels + 1), hipMemcpyDeviceToHost, s));
+    G4S_HIP_TRY(hipMemcpyAsync(S.lent_host.data(), w.lcnt, sizeof(int) * ((size_t)levels + 1), hipMemcpyDeviceToHost, s));
     G4S_HIP_TRY(hipStreamSynchronize(s));
     cnt->waits += 1;
     return G4S_OK;
 }
 
-void plan_launches(g4s_trsv_s *T, const int *loff, int levels)
+// the launch list from the level offsets on the host, and what the info says of it
+void plan_launches(g4s_trsv_s *T, int levels)
 {
-    T->launches = g4s::trsv_launches(loff, levels, kChainWidth, kChainLevels, (T->flags & G4S_TRSV_NO_CHAINS) != 0);
+    g4s::LevelSchedule &S = T->sched;
+    const int *loff = S.loff_host.data();
+    S.levels = levels;
+    S.launches = g4s::trsv_launches(loff, levels, G4S_TRSV_CHAIN_WIDTH, G4S_TRSV_CHAIN_LEVELS, (T->flags & G4S_TRSV_NO_CHAINS) != 0);
     int widest = 0, chains = 0;
     for (int l = 0; l < levels; ++l) widest = std::max(widest, loff[l + 1] - loff[l]);
-    for (const g4s::TrLaunch &L : T->launches) chains += L.chain;
+    for (const g4s::TrLaunch &L : S.launches) chains += L.chain;
     T->info.levels = levels;
     T->info.widest_level = widest;
-    T->info.launches_per_solve = (int)T->launches.size();
+    T->info.launches_per_solve = (int)S.launches.size();
     T->info.chains = chains;
 }
 
 } // namespace
 
-g4s::TrSchedule g4s::trsv_schedule(const g4s_trsv_s *T)
-{
-    return TrSchedule{T->rowid, T->loff, T->loff_host.data(), T->lent_host.data(), &T->launches, T->info.levels};
-}
+const g4s::LevelSchedule &g4s::trsv_schedule(const g4s_trsv_s *T) { return T->sched; }
 
 G4S_API g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values, int32_t *level,
                                       unsigned flags, g4s_trsv_info *info, void *stream)
@@ -595,7 +558,6 @@ G4S_API g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t 
     if (status == G4S_OK) status = open(n, rp, ci, upper, unit, w, hub_cap, cus, &h, &cnt, s);
     const bool refused = status == G4S_OK && (h.invalid || h.bad_row < n);
     int levels = 0;
-    std::vector<int> &loff_host = T->loff_host;
     if (status == G4S_OK && !refused) {
         const size_t ni = sizeof(int) * (size_t)n;
         second.piece(&w.trows, sizeof(int) * (size_t)h.nnz_off);
@@ -626,16 +588,16 @@ G4S_API g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t 
                          total = o_lval + pad256(sizeof(double) * nt);
             status = T->block.alloc(total);
             char *base = T->block.as<char>();
-            T->rowid = reinterpret_cast<int *>(base + o_rowid);
+            T->sched.rowid = reinterpret_cast<int *>(base + o_rowid);
             T->ebeg = reinterpret_cast<int *>(base + o_ebeg);
             T->noff = reinterpret_cast<int *>(base + o_noff);
-            T->loff = reinterpret_cast<int *>(base + o_loff);
+            T->sched.loff = reinterpret_cast<int *>(base + o_loff);
             T->lcol = reinterpret_cast<int *>(base + o_lcol);
             T->emap = reinterpret_cast<int *>(base + o_emap);
             T->diag = reinterpret_cast<double *>(base + o_diag);
             T->lval = reinterpret_cast<double *>(base + o_lval);
         }
-        if (status == G4S_OK) status = layout(T, levels, rp, ci, va, upper, unit, w, cus, &loff_host, &cnt, s);
+        if (status == G4S_OK) status = layout(T, levels, rp, ci, va, upper, unit, w, cus, &cnt, s);
         if (status == G4S_OK && level) {
             if (!device) status = stage.to_host(level, w.level, ni);
             else if (hipMemcpyAsync(lv, w.level, ni, hipMemcpyDeviceToDevice, s) != hipSuccess) status = g4s::set_error(G4S_ERR_HIP, "g4s_sptrsv_analyse: the copy of level failed");
@@ -656,7 +618,7 @@ G4S_API g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t 
         delete T;
         return status;
     }
-    plan_launches(T, loff_host.data(), levels);
+    plan_launches(T, levels);
     T->info.nnz_triangle = T->nnz_tri;
     T->info.launches = cnt.launches;
     T->info.host_waits = cnt.waits;
@@ -672,16 +634,10 @@ G4S_API g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x
     if (T->n == 0) return G4S_OK;
     G4S_REQUIRE(b_dev && x_dev, "b or x is NULL");
     const hipStream_t s = g4s::as_stream(stream);
-    const TrView V{T->rowid, T->ebeg, T->noff, T->lcol, T->loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
-    for (const g4s::TrLaunch &L : T->launches) {
-        if (L.chain) {
-            hipLaunchKernelGGL(tr_chain_kernel, dim3(1), dim3(WG), 0, s, V, L.level_lo, L.level_hi, b_dev, x_dev);
-        } else {                                                   // one level
-            const int lo = T->loff_host[L.level_lo], hi = T->loff_host[L.level_hi];
-            const int rows = WG / g4s::trsv_stride(hi - lo, T->lent_host[L.level_hi] - T->lent_host[L.level_lo]);
-            hipLaunchKernelGGL(tr_level_kernel, dim3((unsigned)((hi - lo + rows - 1) / rows)), dim3(WG), 0, s, V, lo, hi, WG / rows, b_dev, x_dev);
-        }
-    }
+    const TrView V{T->sched.rowid, T->ebeg, T->noff, T->lcol, T->sched.loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
+    g4s::for_each_launch(T->sched, g4s::trsv_stride,
+        [&](int level_lo, int level_hi) { hipLaunchKernelGGL(tr_chain_kernel, dim3(1), dim3(WG), 0, s, V, level_lo, level_hi, b_dev, x_dev); },
+        [&](int lo, int hi, int stride, int grid) { hipLaunchKernelGGL(tr_level_kernel, dim3((unsigned)grid), dim3(WG), 0, s, V, lo, hi, stride, b_dev, x_dev); });
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;
 }

@@ -186,6 +186,15 @@ def two_long_rows(base=WAVE_ROW + 8, seed=29):
     return tr.csr(dominant([[(j, float(rng.uniform(-1, 1))) for j in r] for r in rows]))
 
 
+def strided_tiles(base=16, rows=300, seed=30):
+    """the pattern of trsv_ref's strided_tiles made canonical: `base` short rows with a band at +1 and +3 and one column each among the later rows'
+    diagonals, then `rows` rows that store all of the first `base` columns and their own diagonal. One level of `rows` wave rows with `base` pivots
+    each: its launch gives a workgroup eight of them, two a wave, and the last workgroup four"""
+    rng = _rng(seed)
+    pat = [sorted({i, min(i + 1, base - 1), min(i + 3, base - 1), base + (rows // base) * i}) for i in range(base)] + [list(range(base)) + [base + h] for h in range(rows)]
+    return tr.csr(dominant([[(j, float(rng.uniform(-1, 1))) for j in r] for r in pat]))
+
+
 def row0_full(n=200, seed=25):
     """row 0 is full; every later row stores (i, 0), its diagonal and up to two more columns (every tenth row a dozen): the pivot step on row 0 walks
     n − 1 entries, mostly onto columns the row does not store"""
@@ -252,6 +261,7 @@ CASES = {
     "arrow_wave": lambda: arrow(WAVE_ROW),
     "arrow_wave_plus_1": lambda: arrow(WAVE_ROW + 1),
     "two_long_rows": lambda: two_long_rows(),
+    "strided_tiles": lambda: strided_tiles(),
     "row0_full": lambda: row0_full(),
     "messy": lambda: messy(),
     "zero_pivot": lambda: zero_pivot(),

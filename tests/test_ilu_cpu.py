@@ -103,6 +103,11 @@ def test_the_named_cases_reach_the_edges_they_are_named_for():
     (n, rp, ci, va), _, i, _, _ = ref.case("two_long_rows")
     assert np.diff(rp)[-2:].tolist() == [ref.WAVE_ROW + 9] * 2 and np.diff(rp)[:-2].max() <= 5 and (i["levels"], i["widest_level"]) == (2, ref.WAVE_ROW + 8)
     assert tr.levels(n, rp, ci, va, True, True)[-2:].tolist() == [1, 1]
+    (n, rp, ci, va), _, i, _, _ = ref.case("strided_tiles")
+    lev = tr.levels(n, rp, ci, va, True, True)
+    assert np.bincount(lev).tolist() == [16, 300] and np.diff(rp)[16:].tolist() == [17] * 300 and (i["launches_per_factor"], i["chains"]) == (2, 1)
+    assert ref.LANE_ROW < 17 <= ref.WAVE_ROW and 300 > ref.CHAIN_WIDTH and np.all(ci[rp[16:-1]] == 0) and np.all(ci[rp[17:] - 2] == 15)   # 16 pivots a row
+    assert np.diff(rp)[:16].max() == 4 and rp[16] > 3 * 16                    # the pivot rows have entries behind their diagonals
     n, rp, ci, va = ref.case("row0_full")[0]
     assert rp[1] == n == 200 and np.all(ci[rp[1:-1]] == 0) and np.diff(rp)[1:].max() > ref.LANE_ROW and np.diff(rp)[1:].min() == 2
     assert _dropped(n, rp, ci) > 150 * 190

@@ -111,6 +111,10 @@ def test_the_named_cases_reach_the_edges_they_are_named_for():
     assert [len(o) for o in off[70:]] == [31, 32, 33, 63, 64, 65]
     off, dia = ref.triangle(*ref.case("hub_row")[0])
     assert [len(o) for o in off[-2:]] == [ref.HUB_ROW + 1, ref.HUB_ROW]
+    for name, rows, m in (("strided_tiles", 300, 16), ("wave_tiles", 260, 256)):   # level 1 is one launch, with chains or without: wider than a chain
+        (n, rp, ci, va), lev, i, _, _ = ref.case(name)
+        assert np.bincount(lev).tolist() == [m, rows] and rows > ref.CHAIN_WIDTH and np.diff(rp)[m:].tolist() == [m + 1] * rows
+        assert (i["launches_per_solve"], i["chains"], i["nnz_triangle"] - m) == (2, 1, rows * (m + 1))
     mat = ref.case("messy")[0]
     off, dia = ref.triangle(*mat)
     assert max(len(d) for d in dia) == 3 and any(len({c for c, _, _ in o}) < len(o) for o in off)

@@ -296,6 +296,10 @@ CASES = {
     "blocks": lambda: blocks([CHAIN_WIDTH - 1, CHAIN_WIDTH, CHAIN_WIDTH + 1, CHAIN_WIDTH, CHAIN_WIDTH - 1, CHAIN_WIDTH + 1, 5]),
     "wave_row_edges": lambda: long_rows([WAVE_ROW - 1, WAVE_ROW, WAVE_ROW + 1, 63, 64, 65], 70),
     "hub_row": lambda: long_rows([HUB_ROW + 1, HUB_ROW], HUB_ROW + 3),
+    # a level launch of several workgroups whose threads own a row only every stride-th: 300 rows of 17 entries are 64 rows a workgroup (stride 4), the
+    # fifth workgroup 44; 260 rows of 257 entries are one row a wave (stride 64), 65 workgroups
+    "strided_tiles": lambda: long_rows([16] * 300, 16),
+    "wave_tiles": lambda: long_rows([256] * 260, 256),
     "messy": lambda: messy(60),
 }
 
