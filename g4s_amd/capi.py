@@ -24,6 +24,7 @@ KTRUSS_BATCH, KTRUSS_FULL = 16, 2**31 - 1                                # g4s_k
 COLOR_LARGEST_FIRST, COLOR_BATCH, COLOR_MASK_COLORS, COLOR_WINDOW = 524288, 16, 64, 256   # g4s_color: key := degree; launches per state read; mask width; scan window (g4s.h)
 TRSV_UPPER, TRSV_UNIT_DIAGONAL, TRSV_NO_CHAINS = 2097152, 4194304, 8388608   # g4s_sptrsv_analyse: the triangle, the diagonal, one launch per level (g4s.h)
 TRSV_WAVE_ROW, TRSV_CHAIN_WIDTH, TRSV_CHAIN_LEVELS, TRSV_HUB_ROW = 32, 256, 1024, 4096   # g4s_sptrsv: the row classes of the documented sum and the chaining rule (g4s.h)
+TRSV_COL_MAJOR, TRSV_RHS_TILE, TRSV_MAX_RHS = 33554432, 8, 32768          # g4s_sptrsv_solve_multi / g4s_ilu0_apply_multi: the layout flag, the column tile, the cap on k (g4s.h)
 ILU0_NO_CHAINS, ILU0_LANE_ROW, ILU0_WAVE_ROW = 16777216, 8, 512            # g4s_ilu0_analyse: one launch per level; the row classes of the factorisation (g4s.h)
 EWISE_UNION, EWISE_INTERSECT, EWISE_DIFFERENCE = 0, 1, 2                 # g4s_csr_ewise_*: op (a plain int, not a flag bit; g4s.h)
 COMBINE_PLUS, COMBINE_TIMES, COMBINE_MIN, COMBINE_MAX, COMBINE_FIRST, COMBINE_SECOND = 0, 1, 2, 3, 4, 5
@@ -276,12 +277,14 @@ SIGNATURES = {
     "g4s_color": (C.c_int, [C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint, C.POINTER(ColorInfo), vp]),
     "g4s_sptrsv_analyse": (C.c_int, [C.POINTER(vp), C.c_int32, vp, vp, vp, vp, C.c_uint, C.POINTER(TRSVInfo), vp]),
     "g4s_sptrsv_solve": (C.c_int, [vp, vp, vp, vp]),
+    "g4s_sptrsv_solve_multi": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.c_uint, vp]),
     "g4s_sptrsv_update_values": (C.c_int, [vp, vp, C.c_uint, vp]),
     "g4s_sptrsv_get_info": (C.c_int, [vp, C.POINTER(TRSVInfo)]),
     "g4s_sptrsv_destroy": (C.c_int, [vp]),
     "g4s_ilu0_analyse": (C.c_int, [C.POINTER(vp), C.c_int32, vp, vp, vp, C.c_uint, C.POINTER(ILU0Info), vp]),
     "g4s_ilu0_factor": (C.c_int, [vp, vp, C.c_uint, vp, vp]),
     "g4s_ilu0_apply": (C.c_int, [vp, vp, vp, vp]),
+    "g4s_ilu0_apply_multi": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.c_uint, vp]),
     "g4s_ilu0_get_factors": (C.c_int, [vp, vp, C.c_uint, vp]),
     "g4s_ilu0_get_info": (C.c_int, [vp, C.POINTER(ILU0Info)]),
     "g4s_ilu0_destroy": (C.c_int, [vp]),

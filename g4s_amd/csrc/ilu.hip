@@ -8,7 +8,7 @@
 //            strictly ascending, the diagonal stored, its position to dpos; one read of the state. A refusal ends at either read.
 //   factor   per launch of the lower plan ilu_level_kernel (one wide level) or ilu_chain_kernel (one workgroup, a run of narrow levels, a fence and a
 //            barrier behind each); then g4s_sptrsv_update_values on both plans.
-//   apply    g4s_sptrsv_solve on the lower plan (r → z), then on the upper plan (z → z).
+//   apply    g4s_sptrsv_solve on the lower plan (r → z), then on the upper plan (z → z); for a block of k vectors g4s_sptrsv_solve_multi, likewise.
 // The frame — the launch walk, the deal of a tile's rows, the levels of a chain — is the solve's (level_schedule.hpp, level_tile.hpp), and so is the
 // memory model of the finished values of earlier rows (ld_prior<kChain>, for_chain_levels). A row's own working values w are shared
 // between the lanes that update them inside one kernel, so they live in registers (one lane's row), in LDS (one wave's row, behind a wave barrier per
@@ -28,7 +28,7 @@
 #include <new>
 
 struct g4s_ilu0_s {
-    int n = 0;
+    int n = 0;                          // first: the refusals of g4s_ilu0_apply_multi read nothing else (tests/test_trsv_multi_cpu.py asks them of a bare n)
     unsigned flags = 0;
     long long nnz = 0;
     g4s::DevBuf head, body;             // rowptr, dpos, the pivot word and the check's state; colids, a, f
@@ -421,6 +421,21 @@ G4S_API g4s_status g4s_ilu0_apply(g4s_ilu0_t P, const double *r_dev, double *z_d
     G4S_REQUIRE(r_dev && z_dev, "r or z is NULL");
     G4S_TRY(g4s_sptrsv_solve(P->lower, r_dev, z_dev, stream));
     return g4s_sptrsv_solve(P->upper, z_dev, z_dev, stream);
+}
+
+G4S_API g4s_status g4s_ilu0_apply_multi(g4s_ilu0_t P, int32_t k, const double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, unsigned flags,
+                                        void *stream)
+{
+    G4S_REQUIRE(P, "the handle is NULL");
+    G4S_REQUIRE(k >= 0 && k <= G4S_TRSV_MAX_RHS, "k is negative or above G4S_TRSV_MAX_RHS");
+    G4S_REQUIRE((flags & ~G4S_TRSV_COL_MAJOR) == 0u, "flags other than G4S_TRSV_COL_MAJOR");
+    if (P->n == 0 || k == 0) return G4S_OK;
+    G4S_REQUIRE(R_dev && Z_dev, "R or Z is NULL");
+    const int64_t need = (flags & G4S_TRSV_COL_MAJOR) ? P->n : k;
+    G4S_REQUIRE(ldr >= need && ldz >= need, "a leading dimension is too small: ld >= k row-major, ld >= n column-major");
+    G4S_REQUIRE(R_dev != Z_dev || ldr == ldz, "Z is R with another leading dimension");
+    G4S_TRY(g4s_sptrsv_solve_multi(P->lower, k, R_dev, ldr, Z_dev, ldz, flags, stream));
+    return g4s_sptrsv_solve_multi(P->upper, k, Z_dev, ldz, Z_dev, ldz, flags, stream);
 }
 
 G4S_API g4s_status g4s_ilu0_get_factors(g4s_ilu0_t P, double *values_out, unsigned flags, void *stream)

@@ -17,6 +17,8 @@
 // x values written behind a kernel boundary or — inside a chain — by its own workgroup behind a fence and a barrier: the frame and its memory model
 // are level_tile.hpp's (deal_tile, for_chain_levels, ld_prior), shared with ilu.hip. No wave waits for another workgroup; nothing spins.
 // The arithmetic shape of a row (g4s.h) depends on its own entry count alone: solve_tile is the one place that computes it, for both kernels.
+// g4s_sptrsv_solve_multi solves a block of k right-hand sides on the same launch list: solve_tile_multi is solve_tile for a tile of
+// G4S_TRSV_RHS_TILE columns, tr_level_multi_kernel and tr_chain_multi_kernel the two kernels with a column tile per workgroup.
 #include "common.hpp"
 #include "frontier.hpp"
 #include "call_util.hpp"
@@ -28,7 +30,7 @@
 #include <new>
 
 struct g4s_trsv_s {
-    int n = 0;
+    int n = 0;                          // first: the refusals of g4s_sptrsv_solve_multi read nothing else (tests/test_trsv_multi_cpu.py asks them of a bare n)
     unsigned flags = 0;
     long long nnz_in = 0;               // entries of the arrays the handle was analysed from: what update_values reads
     long long nnz_tri = 0;
@@ -378,6 +380,152 @@ __global__ __launch_bounds__(WG) void tr_chain_kernel(const TrView T, int level_
     for_chain_levels(T.loff, level_lo, level_hi, [&](int lo, int hi, int stride) { solve_tile<true>(T, lo, hi, stride, b, x, s_hub, &s_nh, s_part); });
 }
 
+// ------------------------------------------------------------------------------------------------------------- the solve of a block
+// k right-hand sides on the launches of one: a thread that owns a row owns it for a tile of kRhsTile columns of the block, the workgroups of a level
+// launch carry the column tile in blockIdx.y, a chain is one workgroup per column tile (blockIdx.x) — column tiles share nothing, so no workgroup
+// waits for another. An entry's column and value are loaded once and used for every column of the tile. Column j of X is what the kernels above give
+// for column j of B, bit for bit: every column's products are added in the order and the shape of its row's class, whatever kRhsTile and the unrolls.
+constexpr int kRhsTile = G4S_TRSV_RHS_TILE;
+
+// The n × k blocks B and X, and the column tile [j0, j0 + kn) of this workgroup. Element (i, j) is at [i·ld + j], kCol: at [i + j·ld].
+struct TrBlock {
+    const double *b;
+    double *x;
+    long long ldb, ldx;
+    int k;
+};
+
+template <bool kCol>
+__device__ __forceinline__ long long block_at(long long ld, int i, int j) { return kCol ? (long long)i + (long long)j * ld : (long long)i * ld + j; }
+
+// strided_sum for a column tile: s[q] is the sum over the column of x whose element of row 0 is xq[q]. xq repeats the tile's last column behind kn
+// (the same for every thread of the workgroup), so a lane never loads outside the block and the tail needs no branch; what it sums there is never
+// stored.
+template <bool kChain, bool kCol, int kStride, int kUnroll>
+__device__ __forceinline__ void strided_sum_multi(const TrView &T, const double *const (&xq)[kRhsTile], long long ldx, int e, int first, int m,
+                                                  double (&s)[kRhsTile])
+{
+#pragma unroll
+    for (int q = 0; q < kRhsTile; ++q) s[q] = 0.0;
+    int k = first;
+    for (; k + (kUnroll - 1) * kStride < m; k += kUnroll * kStride) {
+        int c[kUnroll];
+        double v[kUnroll], y[kUnroll][kRhsTile];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) c[u] = T.lcol[e + k + u * kStride];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) v[u] = T.lval[e + k + u * kStride];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+#pragma unroll
+            for (int q = 0; q < kRhsTile; ++q) y[u][q] = ld_prior<kChain>(xq[q] + block_at<kCol>(ldx, c[u], 0));
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+#pragma unroll
+            for (int q = 0; q < kRhsTile; ++q) s[q] = s[q] + v[u] * y[u][q];
+    }
+    for (; k < m; k += kStride) {
+        const int c = T.lcol[e + k];
+        const double v = T.lval[e + k];
+        double y[kRhsTile];
+#pragma unroll
+        for (int q = 0; q < kRhsTile; ++q) y[q] = ld_prior<kChain>(xq[q] + block_at<kCol>(ldx, c, 0));
+#pragma unroll
+        for (int q = 0; q < kRhsTile; ++q) s[q] = s[q] + v * y[q];
+    }
+}
+
+// solve_tile for the column tile `tile` of the block: the same deal, the same three classes, kRhsTile sums a row; s_part is [WG / 64][kRhsTile].
+template <bool kChain, bool kCol>
+__device__ __forceinline__ void solve_tile_multi(const TrView &T, int lo, int hi, int stride, const TrBlock &B, int tile, int *s_hub, int *s_nh,
+                                                 double *s_part)
+{
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int j0 = tile * kRhsTile, kn = std::min(kRhsTile, B.k - j0);
+    const double *xq[kRhsTile];
+#pragma unroll
+    for (int q = 0; q < kRhsTile; ++q) xq[q] = B.x + block_at<kCol>(B.ldx, 0, j0 + std::min(q, kn - 1));
+    double s[kRhsTile];
+#pragma unroll
+    for (int q = 0; q < kRhsTile; ++q) s[q] = 0.0;
+    const int p = deal_tile<kWaveRow, kHubCut>(lo, hi, stride, s_hub, s_nh,
+        [&](int p) { return TrRow{T.noff[p], T.ebeg[p]}; },
+        [&](const TrRow &r) { strided_sum_multi<kChain, kCol, 1, 2>(T, xq, B.ldx, r.e, 0, r.m, s); },
+        [&](const TrRow &r, int j) {
+            double part[kRhsTile];
+            strided_sum_multi<kChain, kCol, 64, 4>(T, xq, B.ldx, __shfl(r.e, j), lane, __shfl(r.m, j), part);
+#pragma unroll
+            for (int q = 0; q < kRhsTile; ++q) {
+                const double w = __shfl(wave_sum(part[q]), 0);
+                if (lane == j) s[q] = w;
+            }
+        },
+        [&](const TrRow &r, int th) {
+            double part[kRhsTile];
+            strided_sum_multi<kChain, kCol, WG, 4>(T, xq, B.ldx, r.e, t, r.m, part);
+#pragma unroll
+            for (int q = 0; q < kRhsTile; ++q) {
+                const double w = wave_sum(part[q]);
+                if (lane == 0) s_part[wave * kRhsTile + q] = w;
+            }
+            __syncthreads();
+            if (t == th) {
+#pragma unroll
+                for (int q = 0; q < kRhsTile; ++q)
+                    s[q] = ((s_part[q] + s_part[kRhsTile + q]) + s_part[2 * kRhsTile + q]) + s_part[3 * kRhsTile + q];
+            }
+        });
+    if (p >= 0) {
+        const int r = T.rowid[p];
+        const double d = T.unit ? 1.0 : T.diag[p];
+        const double *bp = B.b + block_at<kCol>(B.ldb, r, j0);
+        double *xp = B.x + block_at<kCol>(B.ldx, r, j0);
+#pragma unroll
+        for (int q = 0; q < kRhsTile; ++q) {
+            if (q < kn) {
+                double v = *bp - s[q];
+                if (!T.unit) v = v / d;
+                *xp = canonical_nan(v);
+            }
+            bp += kCol ? B.ldb : 1;                                 // the next column; never dereferenced behind the tile
+            xp += kCol ? B.ldx : 1;
+        }
+    }
+}
+
+// one level that is not in a chain, for a block: a tile of WG / stride rows (blockIdx.x) times a tile of kRhsTile columns (blockIdx.y) per workgroup
+template <bool kCol>
+__global__ __launch_bounds__(WG) void tr_level_multi_kernel(const TrView T, int lo, int hi, int stride, const TrBlock B)
+{
+    __shared__ int s_hub[WG], s_nh;
+    __shared__ double s_part[(WG / 64) * kRhsTile];
+    const int2 tile = level_tile_bounds(lo, hi, stride);
+    solve_tile_multi<false, kCol>(T, tile.x, tile.y, stride, B, (int)blockIdx.y, s_hub, &s_nh, s_part);
+}
+
+// a chain for a block: one workgroup per column tile (blockIdx.x), each through all the levels of the chain for its own columns, which nobody else
+// reads or writes: for_chain_levels' memory model holds per workgroup, and no workgroup waits for another
+template <bool kCol>
+__global__ __launch_bounds__(WG) void tr_chain_multi_kernel(const TrView T, int level_lo, int level_hi, const TrBlock B)
+{
+    __shared__ int s_hub[WG], s_nh;
+    __shared__ double s_part[(WG / 64) * kRhsTile];
+    const int tile = (int)blockIdx.x;
+    for_chain_levels(T.loff, level_lo, level_hi,
+                     [&](int lo, int hi, int stride) { solve_tile_multi<true, kCol>(T, lo, hi, stride, B, tile, s_hub, &s_nh, s_part); });
+}
+
+template <bool kCol>
+void enqueue_multi(const g4s_trsv_s *T, const TrView &V, const TrBlock &B, hipStream_t s)
+{
+    const unsigned tiles = (unsigned)((B.k + kRhsTile - 1) / kRhsTile);
+    g4s::for_each_launch(T->sched, g4s::trsv_stride,
+        [&](int level_lo, int level_hi) { hipLaunchKernelGGL(tr_chain_multi_kernel<kCol>, dim3(tiles), dim3(WG), 0, s, V, level_lo, level_hi, B); },
+        [&](int lo, int hi, int stride, int grid) {
+            hipLaunchKernelGGL(tr_level_multi_kernel<kCol>, dim3((unsigned)grid, tiles), dim3(WG), 0, s, V, lo, hi, stride, B);
+        });
+}
+
 int bits_of(int v)
 {
     int b = 1;
@@ -638,6 +786,30 @@ G4S_API g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x
     g4s::for_each_launch(T->sched, g4s::trsv_stride,
         [&](int level_lo, int level_hi) { hipLaunchKernelGGL(tr_chain_kernel, dim3(1), dim3(WG), 0, s, V, level_lo, level_hi, b_dev, x_dev); },
         [&](int lo, int hi, int stride, int grid) { hipLaunchKernelGGL(tr_level_kernel, dim3((unsigned)grid), dim3(WG), 0, s, V, lo, hi, stride, b_dev, x_dev); });
+    G4S_HIP_TRY(hipGetLastError());
+    return G4S_OK;
+}
+
+static_assert((G4S_TRSV_COL_MAJOR & (kFlagMask | G4S_ILU0_NO_CHAINS)) == 0u, "a bit of its own");
+static_assert(G4S_TRSV_RHS_TILE >= 1 && (G4S_TRSV_MAX_RHS + G4S_TRSV_RHS_TILE - 1) / G4S_TRSV_RHS_TILE <= 65535, "the column tiles are a grid dimension");
+
+G4S_API g4s_status g4s_sptrsv_solve_multi(g4s_trsv_t T, int32_t k, const double *B_dev, int64_t ldb, double *X_dev, int64_t ldx, unsigned flags,
+                                          void *stream)
+{
+    G4S_REQUIRE(T, "the handle is NULL");
+    G4S_REQUIRE(k >= 0 && k <= G4S_TRSV_MAX_RHS, "k is negative or above G4S_TRSV_MAX_RHS");
+    G4S_REQUIRE((flags & ~G4S_TRSV_COL_MAJOR) == 0u, "flags other than G4S_TRSV_COL_MAJOR");
+    if (T->n == 0 || k == 0) return G4S_OK;
+    G4S_REQUIRE(B_dev && X_dev, "B or X is NULL");
+    const bool col = (flags & G4S_TRSV_COL_MAJOR) != 0;
+    const int64_t need = col ? T->n : k;
+    G4S_REQUIRE(ldb >= need && ldx >= need, "a leading dimension is too small: ld >= k row-major, ld >= n column-major");
+    G4S_REQUIRE(B_dev != X_dev || ldb == ldx, "X is B with another leading dimension");
+    const hipStream_t s = g4s::as_stream(stream);
+    const TrView V{T->sched.rowid, T->ebeg, T->noff, T->lcol, T->sched.loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
+    const TrBlock B{B_dev, X_dev, (long long)ldb, (long long)ldx, k};
+    if (col) enqueue_multi<true>(T, V, B, s);
+    else enqueue_multi<false>(T, V, B, s);
     G4S_HIP_TRY(hipGetLastError());
     return G4S_OK;
 }

@@ -912,9 +912,39 @@ def kcore(A, max_k=None, return_round=False, return_info=False):
     return res[0] if len(res) == 1 else res
 
 
+def _rhs_block(b, out, n, name):
+    """What the block entry points (g4s_sptrsv_solve_multi, g4s_ilu0_apply_multi) need of a 2-D right-hand side b of n × k and its output: (out, k, ldb,
+    ldo, flags). Row-major when stride(1) == 1, column-major when stride(0) == 1, read the way CSR.spmm reads its blocks (_spmm_ld); out has b's
+    layout, and a new one is allocated in it. ValueError, before any GPU call, for a wrong shape or dtype, k above capi.TRSV_MAX_RHS, blocks that are
+    neither row- nor column-major, and two blocks of different layouts."""
+    if not (isinstance(b, torch.Tensor) and b.dtype == torch.float64 and b.dim() == 2 and b.shape[0] == n):
+        raise ValueError(f"{name} must be a float64 tensor of {n} entries or of {n} x k")
+    k = int(b.shape[1])
+    if k > capi.TRSV_MAX_RHS:
+        raise ValueError(f"{name} has {k} columns, more than the {capi.TRSV_MAX_RHS} one call takes")
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (n, k) and out.device == b.device):
+        raise ValueError(f"out must be a float64 tensor of {n} x {k} on {name}'s device")
+    for cm in (False, True):                                        # row-major when both blocks are, else column-major when both are
+        ldb = _spmm_ld(b, cm)
+        ldo = ldb if out is None else _spmm_ld(out, cm)
+        if ldb is not None and ldo is not None:
+            break
+    else:
+        raise ValueError(f"{name} and out must both be row-major (stride(1) == 1) or both column-major (stride(0) == 1); strides {tuple(b.stride())}"
+                         + ("" if out is None else f", {tuple(out.stride())}"))
+    _require_gpu()
+    assert b.is_cuda
+    if out is None:
+        out = torch.empty(k, n, dtype=torch.float64, device=b.device).t() if cm else torch.empty(n, k, dtype=torch.float64, device=b.device)
+        ldo = _spmm_ld(out, cm)
+    return out, k, ldb, ldo, (capi.TRSV_COL_MAJOR if cm else 0)
+
+
 class TriangularPlan:
     """A g4s_trsv_t: the (level, row) copy of a triangle and its launch list. solve(b, out=None) enqueues on the current torch stream and waits for
-    nothing (it can be captured into a graph); out may be b. info: the dict of g4s_trsv_info. close() releases the handle."""
+    nothing (it can be captured into a graph); out may be b. b is a vector of n doubles or a 2-D block of n × k right-hand sides (row- or
+    column-major, see _rhs_block), solved on the launches of one (g4s_sptrsv_solve_multi): column j of the result is, bit for bit, the solve of
+    column j. info: the dict of g4s_trsv_info. close() releases the handle."""
 
     def __init__(self, handle, n, nnz, info):
         self._handle, self.n, self.nnz = handle, int(n), int(nnz)
@@ -923,6 +953,10 @@ class TriangularPlan:
     def solve(self, b, out=None):
         if self._handle is None:
             raise ValueError("the plan is closed")
+        if isinstance(b, torch.Tensor) and b.dim() == 2:
+            out, k, ldb, ldo, flags = _rhs_block(b, out, self.n, "b")
+            capi.check(capi.load().g4s_sptrsv_solve_multi(self._handle, k, _ptr(b), ldb, _ptr(out), ldo, flags, _stream()))
+            return out
         if not (isinstance(b, torch.Tensor) and b.dtype == torch.float64 and b.dim() == 1 and b.numel() == self.n and b.is_contiguous()):
             raise ValueError(f"b must be a contiguous float64 tensor of {self.n} entries")
         if out is None:
@@ -1018,15 +1052,23 @@ def sptrsv_analyse(A, lower=True, unit_diagonal=False, return_level=False, no_ch
 
 
 def spsolve_triangular(A, b, lower=True, unit_diagonal=False):
-    """x (float64 device tensor) with T x = b for the lower / upper triangle T of A — scipy.sparse.linalg.spsolve_triangular's meaning for one
-    right-hand side, except that entries outside the triangle are ignored instead of refused. One analysis, one solve, the plan released.
-    A: as for sptrsv_analyse; b: a device tensor or a numpy array of n doubles."""
+    """x (float64 device tensor) with T x = b for the lower / upper triangle T of A — scipy.sparse.linalg.spsolve_triangular's meaning, except that
+    entries outside the triangle are ignored instead of refused. One analysis, one solve, the plan released.
+    A: as for sptrsv_analyse; b: a device tensor or a numpy array of n doubles, or a 2-D one of n × k — a matrix right-hand side, solved as one
+    block (TriangularPlan.solve); x has b's shape."""
     rowptr, colids, values, n = _triangle_args(A, (("lower", lower), ("unit_diagonal", unit_diagonal)))
-    if (int(b.numel()) if isinstance(b, torch.Tensor) else int(np.asarray(b).size)) != n:
+    block = (b.dim() if isinstance(b, torch.Tensor) else np.asarray(b).ndim) == 2
+    if block:
+        if int(b.shape[0] if isinstance(b, torch.Tensor) else np.asarray(b).shape[0]) != n:
+            raise ValueError(f"b must have {n} rows")
+        if int(b.shape[1] if isinstance(b, torch.Tensor) else np.asarray(b).shape[1]) > capi.TRSV_MAX_RHS:
+            raise ValueError(f"b has more than the {capi.TRSV_MAX_RHS} columns one call takes")
+    elif (int(b.numel()) if isinstance(b, torch.Tensor) else int(np.asarray(b).size)) != n:
         raise ValueError(f"b must have {n} entries")
     _require_gpu()
     if not isinstance(b, torch.Tensor):
-        b = torch.from_numpy(np.ascontiguousarray(b, np.float64).reshape(-1)).cuda()
+        b = np.ascontiguousarray(b, np.float64)
+        b = torch.from_numpy(b if block else b.reshape(-1)).cuda()
     plan = sptrsv_analyse((rowptr, colids, values), lower, unit_diagonal)
     try:
         return plan.solve(b.contiguous())
@@ -1039,7 +1081,8 @@ def gauss_seidel(A, b, x, sweeps=1, symmetric=False, plans=None):
     """`sweeps` Gauss–Seidel sweeps on A x = b, in place on x (float64 device tensor; returned): x ← x + (D + L)⁻¹ (b − A x), and with
     symmetric=True behind each of them the backward half x ← x + (D + U)⁻¹ (b − A x) — a symmetric Gauss–Seidel sweep. A is a CSR. Wiring, no kernel of
     its own: the residual is g4s_spmv (r = −1·A·x + 1·b), the corrections are solves on the lower and upper plans of A, the rest torch vector
-    operations. plans: a (lower, upper or None) pair of TriangularPlans of A to reuse; without it they are analysed here and released at the end."""
+    operations. b and x may be 2-D blocks of the same shape n × k (x row- or column-major): every column is swept, the residual through g4s_spmm,
+    the corrections through the block solve. plans: a (lower, upper or None) pair of TriangularPlans of A to reuse; without it they are analysed here and released at the end."""
     if not isinstance(A, CSR):
         raise ValueError("A must be a CSR")
     if A.rows != A.cols:
@@ -1048,19 +1091,29 @@ def gauss_seidel(A, b, x, sweeps=1, symmetric=False, plans=None):
         raise ValueError(f"sweeps must be a non-negative integer, not {sweeps!r}")
     if not isinstance(symmetric, (bool, np.bool_)):
         raise ValueError(f"symmetric must be a bool, not {symmetric!r}")
+    block = isinstance(x, torch.Tensor) and x.dim() == 2
     for name, v in (("b", b), ("x", x)):
-        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.dim() == 1 and v.numel() == A.rows):
-            raise ValueError(f"{name} must be a float64 tensor of {A.rows} entries")
+        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and (v.shape == x.shape if block else v.dim() == 1) and v.shape[0] == A.rows):
+            raise ValueError(f"{name} must be a float64 tensor of {A.rows} entries, or both of {A.rows} x k")
+    if block and _spmm_ld(x, False) is None and _spmm_ld(x, True) is None:
+        raise ValueError(f"x must be row-major (stride(1) == 1) or column-major (stride(0) == 1); strides {tuple(x.stride())}")
     own = plans is None
     lo, up = (A.triangular_plan(lower=True), A.triangular_plan(lower=False) if symmetric else None) if own else plans
     if symmetric and up is None:
         raise ValueError("a symmetric sweep needs the upper plan")
     try:
-        r = torch.empty_like(b)
+        if block:                                                   # the residual in x's layout: spmm and the block solve take one layout a call
+            k = x.shape[1]
+            r = torch.empty(k, A.rows, dtype=torch.float64, device=x.device).t() if _spmm_ld(x, False) is None else torch.empty_like(x, memory_format=torch.contiguous_format)
+        else:
+            r = torch.empty_like(b)
         for _ in range(int(sweeps)):
             for plan in (lo, up) if symmetric else (lo,):
                 r.copy_(b)
-                A.spmv(x, r, alpha=-1.0, beta=1.0)
+                if block:
+                    A.spmm(x, r, alpha=-1.0, beta=1.0)
+                else:
+                    A.spmv(x, r, alpha=-1.0, beta=1.0)
                 plan.solve(r, out=r)
                 x.add_(r)
     finally:
@@ -1074,7 +1127,8 @@ def gauss_seidel(A, b, x, sweeps=1, symmetric=False, plans=None):
 
 class ILU0:
     """A g4s_ilu0_t: the factors A ≈ L U on A's own pattern and the two solve plans on them. apply(r, out=None): z = U⁻¹ (L⁻¹ r) on the current torch
-    stream, waits for nothing (it can be captured into a graph); out may be r. factor(values=None): refactorise — new values in the layout of the
+    stream, waits for nothing (it can be captured into a graph); out may be r; r is a vector of n doubles or a 2-D block of n × k of them (row- or
+    column-major, see _rhs_block) applied on the launches of one (g4s_ilu0_apply_multi), every column bit for bit its own apply. factor(values=None): refactorise — new values in the layout of the
     analysed arrays as a device tensor (asynchronous, capturable) or a numpy array (copied in, synchronous), None: the values the handle holds;
     returns the int32 device word of the smallest row with a zero or non-finite pivot (−1: none), which the caller reads when they like. factors():
     a device tensor of the nnz factor values, L strictly below the diagonal, U on and above it. info: the dict of g4s_ilu0_info. close() releases
@@ -1090,6 +1144,10 @@ class ILU0:
 
     def apply(self, r, out=None):
         self._open()
+        if isinstance(r, torch.Tensor) and r.dim() == 2:
+            out, k, ldr, ldo, flags = _rhs_block(r, out, self.n, "r")
+            capi.check(capi.load().g4s_ilu0_apply_multi(self._handle, k, _ptr(r), ldr, _ptr(out), ldo, flags, _stream()))
+            return out
         if not (isinstance(r, torch.Tensor) and r.dtype == torch.float64 and r.dim() == 1 and r.numel() == self.n and r.is_contiguous()):
             raise ValueError(f"r must be a contiguous float64 tensor of {self.n} entries")
         if out is None:

@@ -1037,7 +1037,18 @@ g4s_status g4s_ktruss(int32_t n, const int32_t *rowptr, const int32_t *colids, i
  *   Threads and streams: a solve only reads the handle, so solves on ONE handle may be enqueued on different streams and from different threads at
  *     the same time, given different x. g4s_sptrsv_update_values writes the handle: it must be ordered against every solve on it (same stream, or
  *     an event). Different handles are independent; analyses may run in different host threads at the same time (tests/test_trsv_threads_gpu.py).
- *   Out of scope: several right-hand sides per solve, a transposed solve (transpose with g4s_csr_transpose and solve the other triangle),
+ *   A block of k right-hand sides (g4s_sptrsv_solve_multi): T X = B for n × k blocks on the launches of ONE solve — exactly
+ *     info.launches_per_solve kernels whatever k is, the same launch list, chaining rule and row spreading; a chain is one workgroup per tile of
+ *     G4S_TRSV_RHS_TILE columns, and column tiles share nothing, so still no workgroup waits for another and nothing spins. Layout as g4s_spmm:
+ *     element (i, j) at [i·ld + j] with ld >= k (row-major, the default) or, with G4S_TRSV_COL_MAJOR, at [i + j·ld] with ld >= n; the one flag
+ *     covers both blocks; elements outside the n × k window are never written. X_dev may be B_dev with ldx == ldb ((i, j) is the only reader of
+ *     B(i, j) and the only writer of X(i, j)); the same pointer with different leading dimensions is G4S_ERR_INVALID, any other overlap undefined.
+ *     Column j of X holds, bit for bit, what g4s_sptrsv_solve gives for column j of B — the arithmetic above, per column —; columns never meet: a
+ *     NaN or inf in one leaves every other column's bits alone. Refused before any HIP call (G4S_ERR_INVALID): a NULL handle, k < 0 or
+ *     k > G4S_TRSV_MAX_RHS, a flag bit other than G4S_TRSV_COL_MAJOR, and with n > 0 and k > 0 a NULL B or X, an ld too small for its layout, and
+ *     the aliasing case. k == 0 or n == 0 is valid and enqueues nothing. It waits for nothing on the host, allocates nothing, can be captured into
+ *     a graph, and only reads the handle: the rule for threads and streams above is g4s_sptrsv_solve's.
+ *   Out of scope: a transposed solve (transpose with g4s_csr_transpose and solve the other triangle),
  *     IC(0), ILU(k) (ILU(0) is g4s_ilu0 below), a preconditioner slot in g4s_conj_grad, several devices. */
 #define G4S_TRSV_UPPER          2097152u /* solve with the upper triangle (default: lower) */
 #define G4S_TRSV_UNIT_DIAGONAL  4194304u /* the diagonal is 1: stored diagonal entries are ignored, none is required */
@@ -1045,6 +1056,9 @@ g4s_status g4s_ktruss(int32_t n, const int32_t *rowptr, const int32_t *colids, i
 #define G4S_TRSV_WAVE_ROW     32         /* a row of more off-diagonal triangle entries is summed by a wave */
 #define G4S_TRSV_CHAIN_WIDTH  256        /* a level of at most this many rows is narrow */
 #define G4S_TRSV_CHAIN_LEVELS 1024       /* levels per chain, at most */
+#define G4S_TRSV_COL_MAJOR   (33554432u) /* g4s_sptrsv_solve_multi, g4s_ilu0_apply_multi: both blocks column-major, (i, j) at [i + j·ld]; default row-major: [i·ld + j] */
+#define G4S_TRSV_RHS_TILE    (8)         /* columns of a block that one thread carries for its row */
+#define G4S_TRSV_MAX_RHS     (32768)     /* k, at most */
 typedef struct g4s_trsv_s *g4s_trsv_t;
 typedef struct g4s_trsv_info {
     int64_t nnz_triangle;        /* entries kept: off-diagonal ones of the triangle and (without UNIT_DIAGONAL) diagonal ones */
@@ -1062,6 +1076,8 @@ typedef struct g4s_trsv_info {
 g4s_status g4s_sptrsv_analyse(g4s_trsv_t *out, int32_t n, const int32_t *rowptr, const int32_t *colids, const double *values,
                               int32_t *level /* n, may be NULL */, unsigned flags, g4s_trsv_info *info /* may be NULL */, void *stream);
 g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x_dev /* may be b_dev */, void *stream);
+g4s_status g4s_sptrsv_solve_multi(g4s_trsv_t T, int32_t k, const double *B_dev, int64_t ldb, double *X_dev /* may be B_dev, ldx == ldb */, int64_t ldx,
+                                  unsigned flags, void *stream);
 g4s_status g4s_sptrsv_update_values(g4s_trsv_t T, const double *values, unsigned flags, void *stream);
 g4s_status g4s_sptrsv_get_info(g4s_trsv_t T, g4s_trsv_info *info);
 g4s_status g4s_sptrsv_destroy(g4s_trsv_t T);
@@ -1105,6 +1121,9 @@ g4s_status g4s_sptrsv_destroy(g4s_trsv_t T);
  *     refactorise the values the handle holds), enqueues info.launches_per_factor factor kernels and refreshes both plans with
  *     g4s_sptrsv_update_values. With device pointers (and with NULL) it waits for nothing and can be captured; with host pointers it copies in and
  *     waits. g4s_ilu0_apply is two solves, L then U, with z as the intermediate (no scratch; z_dev may be r_dev); it never waits and can be captured.
+ *     g4s_ilu0_apply_multi applies to an n × k block: g4s_sptrsv_solve_multi on the lower plan (R → Z), then on the upper plan (Z → Z) — its
+ *     layout, flag (G4S_TRSV_COL_MAJOR), aliasing rule, refusals and bits (column j is g4s_ilu0_apply of column j), info.launches_per_apply kernels
+ *     whatever k is, no scratch, nothing waited for, capturable; it only reads the handle, like g4s_ilu0_apply.
  *   Threads and streams: g4s_ilu0_apply only reads the handle, so applies on ONE handle may be enqueued on different streams and from different
  *     threads at the same time, given different z. g4s_ilu0_factor writes the handle: it must be ordered against every apply and every
  *     g4s_ilu0_get_factors on it (same stream, or an event). Different handles are independent; analyses may run in different host threads at the same
@@ -1133,6 +1152,8 @@ g4s_status g4s_ilu0_analyse(g4s_ilu0_t *out, int32_t n, const int32_t *rowptr, c
 g4s_status g4s_ilu0_factor(g4s_ilu0_t P, const double *values /* NULL: what is held */, unsigned flags, int32_t *bad_pivot_dev /* may be NULL */,
                            void *stream);
 g4s_status g4s_ilu0_apply(g4s_ilu0_t P, const double *r_dev, double *z_dev /* may be r_dev */, void *stream);
+g4s_status g4s_ilu0_apply_multi(g4s_ilu0_t P, int32_t k, const double *R_dev, int64_t ldr, double *Z_dev /* may be R_dev, ldz == ldr */, int64_t ldz,
+                                unsigned flags, void *stream);
 g4s_status g4s_ilu0_get_factors(g4s_ilu0_t P, double *values_out, unsigned flags, void *stream);
 g4s_status g4s_ilu0_get_info(g4s_ilu0_t P, g4s_ilu0_info *info);
 g4s_status g4s_ilu0_destroy(g4s_ilu0_t P);

@@ -10,8 +10,8 @@
 //   StronglyConnectedComponents(a,labels)  labels[v] = the smallest vertex id of v's strongly connected component of the directed pattern `a` (g4s_strongly_connected_components)
 //   MinimumSpanningForest(a,edges,labels), MaximumSpanningForest(…)   the positions of the entries of the minimum / maximum spanning forest of the weighted undirected graph `a` (g4s_minimum_spanning_forest)
 //   KCore(a,core,round,max_k)        core[v] = v's core number in the symmetric pattern `a`, round[v] = the peel frontier that removed it (g4s_kcore)
-//   TriangularSolve(a,lower,unit)    an RAII plan of the level-scheduled solve T x = b on the lower / upper triangle of `a`: solve, update_values (g4s_sptrsv_*)
-//   ILU0<IT,NT>(a)                   an RAII handle of the ILU(0) factorisation of `a` (canonical rows): apply z = U⁻¹ L⁻¹ r, factor, factors (g4s_ilu0_*)
+//   TriangularSolve(a,lower,unit)    an RAII plan of the level-scheduled solve T x = b on the lower / upper triangle of `a`: solve (a vector or a block of k), update_values (g4s_sptrsv_*)
+//   ILU0<IT,NT>(a)                   an RAII handle of the ILU(0) factorisation of `a` (canonical rows): apply z = U⁻¹ L⁻¹ r (a vector or a block of k), factor, factors (g4s_ilu0_*)
 //   KTruss(a,truss,round,support,max_k)   per stored entry: the truss number of its edge in the symmetric pattern `a`, the peel frontier that removed it, its triangles (g4s_ktruss)
 //   GreedyColor(a,color,key,seed,round), MaximalIndependentSet(a,in_set,key,seed)   first-fit colouring in decreasing priority (key, hash), and its colour class 0 (g4s_color)
 //   Transpose(a,at)                  Aᵀ as a CSR, stable (the role of CSR(const CSC&, bool transpose), mm/inc/CSR.h:171-230, and mm/inc/convert.h)
@@ -258,12 +258,22 @@ void KCore(const CSR<IT, NT> &a, int32_t *core, int32_t *round = nullptr, int32_
           "KCore");
 }
 
+// A device allocation that lives for one call: the block a host-side block solve or apply copies through.
+struct DeviceBlock {
+    void *p = nullptr;
+    DeviceBlock(size_t bytes, const char *what) { check(g4s_dev_alloc(&p, bytes), what); }
+    DeviceBlock(const DeviceBlock &) = delete;
+    DeviceBlock &operator=(const DeviceBlock &) = delete;
+    ~DeviceBlock() { (void)g4s_dev_free(p); }
+};
+
 // The plan of the solve T x = b with the lower (lower = false: upper) triangle T of the square matrix `a` (g4s_sptrsv_analyse): only the entries of
 // that triangle are read, so the (D + L) of a general matrix is solved from the matrix itself. The plan keeps its own copy of the triangle on the
 // device; `a` need not outlive the constructor. unit_diagonal: stored diagonal entries are ignored; without it a row that stores none throws.
 // level (may be NULL): a.rows ints, the depth of every row in the dependency DAG. solve(b, x): host arrays of a.rows doubles, x may be b; copied
 // through a device buffer of the plan, synchronous. solve_device: device arrays, enqueued on `stream`, asynchronous. update_values: new values in
-// the layout of a.values, all a.nnz of them.
+// the layout of a.values, all a.nnz of them. solve(B, X, k): host blocks of a.rows × k, row-major with ld = k, X may be B, all k columns on the launches
+// of one solve, synchronous. solve_device_multi: device blocks with their leading dimensions and G4S_TRSV_COL_MAJOR or 0 (g4s_sptrsv_solve_multi).
 class TriangularSolve {
 public:
     template <typename IT, typename NT>
@@ -294,6 +304,21 @@ public:
         check(g4s_memcpy_d2h(x, buf_, sizeof(double) * (size_t)n_), "TriangularSolve::solve");
     }
     void solve_device(const double *b_dev, double *x_dev, void *stream = nullptr) { check(g4s_sptrsv_solve(plan_, b_dev, x_dev, stream), "TriangularSolve::solve"); }
+    void solve(const double *B, double *X, int k)           // n × k host blocks, row-major with ld = k
+    {
+        if (k < 0 || k > G4S_TRSV_MAX_RHS) throw std::runtime_error("TriangularSolve::solve: k is negative or above G4S_TRSV_MAX_RHS");
+        if (n_ == 0 || k == 0) return;
+        const size_t bytes = sizeof(double) * (size_t)n_ * (size_t)k;
+        DeviceBlock blk(bytes, "TriangularSolve::solve");
+        check(g4s_memcpy_h2d(blk.p, B, bytes), "TriangularSolve::solve");
+        solve_device_multi(k, static_cast<const double *>(blk.p), k, static_cast<double *>(blk.p), k);
+        check(g4s_device_synchronize(), "TriangularSolve::solve");
+        check(g4s_memcpy_d2h(X, blk.p, bytes), "TriangularSolve::solve");
+    }
+    void solve_device_multi(int32_t k, const double *B_dev, int64_t ldb, double *X_dev, int64_t ldx, unsigned flags = 0, void *stream = nullptr)
+    {
+        check(g4s_sptrsv_solve_multi(plan_, k, B_dev, ldb, X_dev, ldx, flags, stream), "TriangularSolve::solve");
+    }
     void update_values(const double *values) { check(g4s_sptrsv_update_values(plan_, values, G4S_HOST_POINTERS, nullptr), "TriangularSolve::update_values"); }
     const g4s_trsv_info &info() const { return info_; }
 
@@ -310,6 +335,7 @@ private:
 // buffer of the object, synchronous. apply_device: device arrays, enqueued on `stream`, asynchronous. factor(values): refactorise with new values
 // in the layout of a.values (all a.nnz of them; NULL: the values held); returns the smallest row whose pivot is zero or not finite, −1 when there
 // is none — which is no error. factors(out): a.nnz values in the layout of a.values, L strictly below the diagonal, U on and above it.
+// apply(R, Z, k) and apply_device_multi: the apply of a block of a.rows × k vectors, as TriangularSolve's block solve (g4s_ilu0_apply_multi).
 template <typename IT, typename NT>
 class ILU0 {
 public:
@@ -339,6 +365,21 @@ public:
         check(g4s_memcpy_d2h(z, buf, sizeof(double) * (size_t)n_), "ILU0::apply");
     }
     void apply_device(const double *r_dev, double *z_dev, void *stream = nullptr) { check(g4s_ilu0_apply(h_, r_dev, z_dev, stream), "ILU0::apply"); }
+    void apply(const double *R, double *Z, int k)           // n × k host blocks, row-major with ld = k
+    {
+        if (k < 0 || k > G4S_TRSV_MAX_RHS) throw std::runtime_error("ILU0::apply: k is negative or above G4S_TRSV_MAX_RHS");
+        if (n_ == 0 || k == 0) return;
+        const size_t bytes = sizeof(double) * (size_t)n_ * (size_t)k;
+        DeviceBlock blk(bytes, "ILU0::apply");
+        check(g4s_memcpy_h2d(blk.p, R, bytes), "ILU0::apply");
+        apply_device_multi(k, static_cast<const double *>(blk.p), k, static_cast<double *>(blk.p), k);
+        check(g4s_device_synchronize(), "ILU0::apply");
+        check(g4s_memcpy_d2h(Z, blk.p, bytes), "ILU0::apply");
+    }
+    void apply_device_multi(int32_t k, const double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, unsigned flags = 0, void *stream = nullptr)
+    {
+        check(g4s_ilu0_apply_multi(h_, k, R_dev, ldr, Z_dev, ldz, flags, stream), "ILU0::apply");
+    }
     int32_t factor(const double *values = nullptr)
     {
         if (n_ == 0) return -1;

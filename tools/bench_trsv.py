@@ -9,7 +9,12 @@ One JSON line per matrix: analyse_ms (one cold call included in `analyse_ms_firs
 windows of --solves solves each, the two variants alternating, after one untimed window), spmv_ms the same way, solve_over_spmv, analysis_in_solves,
 launches per solve with and without chains, levels_ok (the levels against their definition, computed with torch at this size), scipy_ms (one timed run, skipped above --scipy-max entries) with the largest relative difference of the
 two solutions, and the time of a Gauss–Seidel sweep (g4s_spmv + one solve + two vector operations) against a Jacobi sweep (g4s_spmv + a scale).
-Usage: python tools/bench_trsv.py [--matrices lap5,lap7,rmat_sym,bidiag] [--small] [--reps 5] [--solves 20] [--no-scipy]"""
+Usage: python tools/bench_trsv.py [--matrices lap5,lap7,rmat_sym,bidiag] [--small] [--reps 5] [--solves 20] [--no-scipy]
+With --rhs 1,2,4,… it measures the block solve instead (g4s_sptrsv_solve_multi; profiles/trsm.txt), on lap5, lap7 and bidiag unless
+--matrices says otherwise: one JSON line per matrix and k with multi_ms (row-major) and multi_colmajor_ms (median, min, max over --reps windows, one
+untimed window first, the two layouts and the single solve alternating in every round), k_singles_ms = k × the single solve measured in the same
+rounds on the same plan, their ratio, the kernels either way enqueues, and whether every column of both blocks has the single solve's bits. The same
+for g4s_ilu0_apply_multi on lap5 ("op": "ilu0_apply"). A window is --solves calls, fewer where one call takes long: about --window-ms of work."""
 import argparse
 import json
 import os
@@ -62,15 +67,75 @@ def windows(variants, reps, count):
     return {k: (statistics.median(v), min(v), max(v)) for k, v in times.items()}
 
 
+def rhs_lines(name, op, n, one, multi, info_launches, ks, args):
+    """The lines of one matrix and one operation. one(b, out): the single call; multi(B, out): the block call; b is scaled per column so that every
+    column differs; the blocks are allocated per k and released before the next."""
+    import torch
+    from g4s_amd import host
+    b = host.synth_vector(7, n)
+    x = torch.empty_like(b)
+    est, _ = wall(lambda: one(b, x))
+    est, _ = wall(lambda: one(b, x))
+    for k in ks:
+        scale = 1.0 + torch.arange(k, dtype=torch.float64, device="cuda") / 8.0
+        Br = (b[:, None] * scale[None, :]).contiguous()
+        Bc = Br.t().contiguous().t()                                         # the same block, column-major with ld = n
+        Xr, Xc = torch.empty_like(Br), torch.empty_like(Bc.t()).t()
+        assert Bc.stride() == (1, n) or k == 1
+        est_k, _ = wall(lambda: multi(Br, Xr))
+        count = lambda ms: max(1, min(args.solves, int(args.window_ms / max(ms, 1e-3))))
+        t = windows({"single": lambda: one(b, x), "multi": lambda: multi(Br, Xr), "multi_colmajor": lambda: multi(Bc, Xc)}, args.reps,
+                    {"single": count(est), "multi": count(est_k), "multi_colmajor": count(est_k)})
+        same = True
+        for j in sorted({0, k // 2, k - 1}):                                # three columns by bits: the block against the single solve of that column
+            one(Br[:, j].contiguous(), x)
+            same = same and bool(torch.equal(x.view(torch.int64), Xr[:, j].contiguous().view(torch.int64)))
+            same = same and bool(torch.equal(x.view(torch.int64), Xc[:, j].contiguous().view(torch.int64)))
+        line = {"bench": "trsm", "op": op, "matrix": name, "n": n, "k": k, "kernels_multi": info_launches, "kernels_k_singles": k * info_launches,
+                "columns_equal_single_solves": same}
+        for key in ("multi", "multi_colmajor", "single"):
+            med, lo, hi = t[key]
+            line[key + "_ms"], line[key + "_ms_min"], line[key + "_ms_max"] = round(med, 4), round(lo, 4), round(hi, 4)
+        line["k_singles_ms"] = round(k * t["single"][0], 4)
+        line["multi_over_k_singles"] = round(t["multi"][0] / (k * t["single"][0]), 4)
+        line["colmajor_over_rowmajor"] = round(t["multi_colmajor"][0] / t["multi"][0], 3)
+        line["multi_ms_per_column"] = round(t["multi"][0] / k, 4)
+        print(json.dumps(line), flush=True)
+        del Br, Bc, Xr, Xc
+
+
+def rhs_main(args):
+    from g4s_amd import capi, host
+    capi.check(capi.load().g4s_warm_up())
+    ks = [int(v) for v in args.rhs.split(",")]
+    names = (args.matrices or "lap5,lap7,bidiag").split(",")
+    for name in names:
+        A, unit = build(name, host, args.small)
+        plan = host.sptrsv_analyse(A, unit_diagonal=unit)
+        rhs_lines(name, "sptrsv_solve", A.rows, lambda b, out: plan.solve(b, out=out), lambda B, out: plan.solve(B, out=out),
+                  plan.info["launches_per_solve"], ks, args)
+        plan.close()
+        if name == "lap5":
+            M = host.ilu0(A)
+            rhs_lines(name, "ilu0_apply", A.rows, lambda r, out: M.apply(r, out=out), lambda R, out: M.apply(R, out=out), M.info["launches_per_apply"], ks, args)
+            M.close()
+        del A
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrices", default="lap5,lap7,rmat_sym,bidiag")
+    ap.add_argument("--matrices", default=None, help="default: lap5,lap7,rmat_sym,bidiag; with --rhs: lap5,lap7,bidiag")
+    ap.add_argument("--rhs", default=None, help="k1,k2,…: measure the block solve of k right-hand sides against k single solves")
+    ap.add_argument("--window-ms", type=float, default=200.0, help="--rhs: a timed window is about this much work, at least one call")
     ap.add_argument("--small", action="store_true", help="small matrices (a quick check, not the benchmark sizes)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--solves", type=int, default=20)
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--scipy-max", type=int, default=20_000_000)
     args = ap.parse_args()
+    if args.rhs:
+        return rhs_main(args)
+    args.matrices = args.matrices or "lap5,lap7,rmat_sym,bidiag"
     import numpy as np
     import torch
     from g4s_amd import capi, host
