@@ -35,9 +35,13 @@ def rmat_csr(scale, edge_factor, seed, weighted=True):
     return csr_of_edges(1 << scale, src, dst, w)
 
 
-def gamma(n, max_in_degree, max_out_degree):
-    """γ of the accuracy bound: a float64 run and the exact iteration differ by at most γ / (1 − damping) in L1 (tests/test_pagerank_gpu.py)."""
-    return (max_in_degree + max_out_degree + math.ceil(math.log2(max(n, 1))) + 16) * 2.0 ** -53
+def gamma(n, max_in_degree, max_out_degree, sum_depth=None):
+    """γ of the accuracy bound: a float64 run and the exact iteration differ by at most γ / (1 − damping) in L1 (tests/test_pagerank_gpu.py).
+    sum_depth: the additions a term of the dangling-mass (and residual) sum passes through; None: ⌈log₂ n⌉ + 8, which holds while the epilogue's grid
+    is far below its cap (n <= 2¹⁴). Under the capped grid the caller passes the depth read off the code (tests/iteration_cases.py, sum_depth)."""
+    if sum_depth is None:
+        sum_depth = math.ceil(math.log2(max(n, 1))) + 8
+    return (max_in_degree + max_out_degree + sum_depth + 8) * 2.0 ** -53
 
 
 def _segment_sums(v, starts, n_segments, dtype):

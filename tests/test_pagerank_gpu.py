@@ -5,9 +5,14 @@ relative error of at most (depth)·u, u = 2⁻⁵³, where depth is the largest 
 grouping (a sequential row sum, a butterfly over lanes, the blocked path's LDS atomics). Per iteration and per component:
     x_u = r_u · (1 / s_u)        s_u is a sum of out-degree terms, then one division and one product: (max_out_degree + 1)·u
     y_v = Σ a_uv · x_u           one product per term and a sum of in-degree terms: max_in_degree·u on top
-    m   = Σ_{dangling} r_u       at most 8 terms per thread, 6 shuffle levels, 4 waves and n / 2048 partials: below (⌈log₂ n⌉ + 8)·u for n <= 2¹⁴
+    m   = Σ_{dangling} r_u       ⌈n / (G·256)⌉ terms per thread, 6 shuffle levels, 4 waves and the G = min(⌈n / 2048⌉, 512) partials added in index
+                                 order: depth·u with depth = ⌈n / (G·256)⌉ + 6 + 4 + G (tests/iteration_cases.py, sum_depth). While the grid is far below
+                                 its cap that is 8 terms per thread and n / 2048 partials, below (⌈log₂ n⌉ + 8)·u for n <= 2¹⁴ — the default of
+                                 pagerank_ref.gamma. Under the capped grid (G = 512, more than 8 terms per thread) the 512 partials alone pass the
+                                 default, and the tests that go there (tests/test_pagerank_limits_gpu.py) hand gamma the depth read off the code.
+                                 The residual Σ|r' − r| is summed the same way.
     r'  = d·(y + m·p) + (1 − d)·p, with p = pers / Σ pers: seven more roundings
-so r'_v is computed with a relative error of at most γ = (max_in_degree + max_out_degree + ⌈log₂ n⌉ + 16)·u, i.e. the computed step is
+so r'_v is computed with a relative error of at most γ = (max_in_degree + max_out_degree + depth + 8)·u (⌈log₂ n⌉ + 16 by default), i.e. the computed step is
 T(r) + e with ‖e‖₁ <= γ·‖r'‖₁ = γ (the ranks sum to one). T contracts in L1 by d = damping (it is d times a column-stochastic map plus a constant), hence
 E_k <= d·E_{k−1} + γ <= γ / (1 − d) for every k: a float64 run and the exact iteration differ by at most γ / (1 − damping) in L1 after the same
 number of iterations, and so does |Σr − 1|. The longdouble reference's own error is 2⁻¹¹ of that. A float64 numpy run of 60 iterations sits at
@@ -43,32 +48,33 @@ def _dev(v):
     return None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).cuda()
 
 
-def _bound(ref, n, damping):
-    return gamma(n, ref.max_in_degree, ref.max_out_degree) / (1.0 - damping)
+def _bound(ref, n, damping, depth=None):
+    """depth: the depth of the mass and residual sums where the default of gamma does not cover it (the module's docstring)"""
+    return gamma(n, ref.max_in_degree, ref.max_out_degree, depth) / (1.0 - damping)
 
 
-def _compare(label, r, want, ref, n, damping):
+def _compare(label, r, want, ref, n, damping, depth=None):
     """err <= γ / (1 − d) and |Σr − 1| under the same bound; returns err / bound."""
     got = r.cpu().numpy().astype(np.longdouble)
     err, off = float(np.abs(got - want).sum()), abs(float(got.sum() - np.longdouble(1)))
-    bound = _bound(ref, n, damping)
+    bound = _bound(ref, n, damping, depth)
     print(f"pagerank {label}: n {n}, L1 err {err:.3e}, |sum - 1| {off:.3e}, bound {bound:.3e}, err / bound {err / bound:.2e}")
     assert err <= bound, (label, err, bound)
     assert off <= bound, (label, off, bound)
     return err / bound
 
 
-def _run_fixed(label, A, arrays, iters=ITERS, damping=0.85, pers=None, ref=None, symmetric=False):
+def _run_fixed(label, A, arrays, iters=ITERS, damping=0.85, pers=None, ref=None, symmetric=False, start=None, depth=None):
     rp, ci, va = arrays
     n = len(rp) - 1
     if ref is None:
-        ref = pagerank_ref.pagerank(rp, ci, va, n, damping=damping, tol=0.0, max_iterations=iters, personalization=pers)
-    r, info = A.pagerank(damping=damping, tol=0.0, max_iterations=iters, personalization=_dev(pers), symmetric=symmetric)
+        ref = pagerank_ref.pagerank(rp, ci, va, n, damping=damping, tol=0.0, max_iterations=iters, personalization=pers, start=start)
+    r, info = A.pagerank(damping=damping, tol=0.0, max_iterations=iters, personalization=_dev(pers), start=_dev(start), symmetric=symmetric)
     print(f"pagerank {label}: {info}")
     assert info["iterations"] == iters == len(ref.residuals) and info["converged"] == 0, info
     assert info["dangling"] == ref.dangling, (info, ref.dangling)
-    assert abs(info["residual"] - float(ref.residuals[-1])) <= 2 * _bound(ref, n, damping)
-    _compare(label, r, ref.rank, ref, n, damping)
+    assert abs(info["residual"] - float(ref.residuals[-1])) <= 2 * _bound(ref, n, damping, depth)
+    _compare(label, r, ref.rank, ref, n, damping, depth)
     return r, info, ref
 
 
