@@ -46,6 +46,11 @@ constexpr int kPbThreads = 1024;
 constexpr int kSpan = 8;                     // entries per span (= 4 lanes × a pair each); cells are padded to a multiple of it
 constexpr int kWindow = 32;                  // entries per merge window (= the 16 lanes of a DPP row × a pair each = 4 spans): a micro-run
                                              // is a run of one row inside one cell and one window; column bands start at multiples of it
+// A/B (tools/build_variant.sh -DG4S_PB_PAIR16=0): the 8-byte forms of the producer's staging loads and the consumer's y stores, as they were before
+// profiles/pb_hot_l2_ab_steps.txt.
+#ifndef G4S_PB_PAIR16
+#define G4S_PB_PAIR16 1
+#endif
 constexpr int kProducerChunk = 1 << 17;      // entries per producer workgroup (x band load amortised over ≥ 1.3 MiB of stream)
 constexpr int kConsumerChunk = 1 << 17;      // micro-runs per consumer workgroup of a split (heavy) row band
 
@@ -353,7 +358,8 @@ template <int W, class Sr>
 __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerItem *__restrict__ items, int cols, int H, const double *__restrict__ hot_x,
                                                                   const unsigned short *__restrict__ p_lcol, const double *__restrict__ p_val,
                                                                   const int *__restrict__ mbase /* consumer slot of each span's first micro-run */,
-                                                                  const double *__restrict__ x, double *__restrict__ prod)
+                                                                  const double *__restrict__ x, double *__restrict__ prod,
+                                                                  int x_pairs /* x is 16-byte aligned: natural bands may be staged in pairs */)
 {
     extern __shared__ double pb_lds[];
     double *xs = pb_lds;                                           // W doubles of x, then the word the pads point at (0.0 for plus-times: the zero word)
@@ -385,18 +391,45 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
         // so that the loads carry no branch. (Then tried: one persistent workgroup per CU walking the items with the NEXT item's descriptor and band of x loaded into
         // registers under the current item's main loop — 0.416 against 0.400 ms on one box, 256 or 512 workgroups: the static order loses more balance than the hidden
         // ≈ 3 µs per item buy.) W need not be a multiple of the workgroup: the last round's loads are clamped like the rest, its LDS writes cut at W.
-        constexpr int kPerThread = (W + kPbThreads - 1) / kPbThreads;
+        // That last round's load is only used under the cut, and the compiler sank it there: issued after the other rounds had landed, one more round trip per
+        // item (W = 20 448, in the ISA). The empty asm below takes its value as an operand where the loads end, so it goes out with them (−0.4 %, profiles/pb_hot_l2_ab_steps.txt).
+        // 16-byte form: the same, a pair of columns per load (half as many requests; 8-byte accesses run at 0.54–0.70 of the 16-byte rate). W is even, so
+        // the band starts on a 16-byte boundary exactly when its source does: hot_x always (the plan's own buffer), x when the caller's pointer is
+        // (x_pairs, decided by the host per launch). Only the whole pairs below the band's last live column are loaded in pairs: an odd last column comes
+        // from a load of its own, so nothing is read past xlimit and no pair carries a value past it into LDS.
         const int ilast = min(c0 + W, xlimit) - 1;
-        double xv[kPerThread];
+        const int nlive = ilast - c0 + 1, npairs = nlive >> 1;    // live columns of the band (≥ 1), whole pairs among them
+        if (((G4S_PB_PAIR16 && hot) || x_pairs) && npairs > 0) {   // (uniform)
+            constexpr int kPairsPerThread = (W / 2 + kPbThreads - 1) / kPbThreads;
+            static_assert(W % 2 == 0, "pairs");
+            const double2_t *xp = reinterpret_cast<const double2_t *>(xsrc + c0);
+            double2_t xv[kPairsPerThread];
 #pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int i = c0 + (int)threadIdx.x + k * kPbThreads;
-            xv[k] = xsrc[min(i, ilast)];
-        }
+            for (int k = 0; k < kPairsPerThread; ++k) xv[k] = xp[min((int)threadIdx.x + k * kPbThreads, npairs - 1)];
+            const double xt = xsrc[ilast];                         // the odd last column, where there is one
+            if constexpr ((W / 2) % kPbThreads != 0) asm volatile("" : "+v"(xv[kPairsPerThread - 1]));
 #pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int i = (int)threadIdx.x + k * kPbThreads;
-            if (W % kPbThreads == 0 || i < W) xs[i] = (c0 + i < xlimit) ? xv[k] : 0.0;
+            for (int k = 0; k < kPairsPerThread; ++k) {
+                const int j = (int)threadIdx.x + k * kPbThreads;
+                if ((W / 2) % kPbThreads == 0 || j < W / 2) {
+                    xs[2 * j] = j < npairs ? xv[k][0] : (2 * j < nlive ? xt : 0.0);
+                    xs[2 * j + 1] = j < npairs ? xv[k][1] : 0.0;
+                }
+            }
+        } else {
+            constexpr int kPerThread = (W + kPbThreads - 1) / kPbThreads;
+            double xv[kPerThread];
+#pragma unroll
+            for (int k = 0; k < kPerThread; ++k) {
+                const int i = c0 + (int)threadIdx.x + k * kPbThreads;
+                xv[k] = xsrc[min(i, ilast)];
+            }
+            if constexpr (W % kPbThreads != 0) asm volatile("" : "+v"(xv[kPerThread - 1]));
+#pragma unroll
+            for (int k = 0; k < kPerThread; ++k) {
+                const int i = (int)threadIdx.x + k * kPbThreads;
+                if (W % kPbThreads == 0 || i < W) xs[i] = (c0 + i < xlimit) ? xv[k] : 0.0;
+            }
         }
     }
 #endif
@@ -458,7 +491,9 @@ __global__ __launch_bounds__(kPbThreads) void pb_producer_kernel(const ProducerI
 }
 
 // One launch ahead of the producer: blocks [0, n_split·⌈W/256⌉) pre-scale y for the row bands whose sums arrive from several consumer
-// workgroups (those add into y with atomics), the remaining blocks gather the x values of the hot columns into hot_x. Semirings: the split bands start from
+// workgroups (those add into y with atomics), the remaining blocks gather the x values of the hot columns into hot_x. (Gathered in COLUMN order instead — a
+// second list sorted by column id with each column's rank, reads that share lines, scattered 8-byte writes into hot_x: the kernel's fetched bytes fell from 36 to
+// 16 MB and its time stayed at 11 µs, profiles/pb_hot_l2_ab_steps.txt; not kept.) Semirings: the split bands start from
 // the identity, or from y itself (normalised for or-and) under ACCUMULATE (beta != 0).
 template <int W, class Sr>
 __global__ void pb_prepare_kernel(int n_split, const int *__restrict__ split_bands, int rows, double *__restrict__ y, double beta,
@@ -491,7 +526,8 @@ constexpr int kPbUnroll = G4S_PB_CONS_UNROLL;   // consumer: groups of 4 consecu
 template <int W, class Sr>
 __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerItem *__restrict__ items, int rows,
                                                                   const unsigned short *__restrict__ c_lrow, const double *__restrict__ prod,
-                                                                  double *__restrict__ y, double alpha, double beta, const int *__restrict__ band_end)
+                                                                  double *__restrict__ y, double alpha, double beta, const int *__restrict__ band_end,
+                                                                  int y_pairs /* y is 16-byte aligned: unsplit bands are written (and read) in pairs */)
 {
     constexpr bool kPlus = semiring::is_plus_times<Sr>;
     extern __shared__ double pb_lds[];
@@ -570,10 +606,43 @@ __global__ __launch_bounds__(kPbThreads) void pb_consumer_kernel(const ConsumerI
     const int r0 = it.rband * W;
     // All of a thread's sums out of LDS first, and — beta != 0 — all its old y values in flight together: as a loop with a break every row waited for its own
     // LDS read, and for its own round trip to y when beta != 0 (sixteen in a row per work item). Neutral for the bench line (beta = 0: 0.3910 against 0.3919 ms).
-    constexpr int kRowsPerThread = (W + kPbThreads - 1) / kPbThreads;
-    double yv[kRowsPerThread], yo[kRowsPerThread];
     const bool read_y = !it.split && beta != 0.0;                  // (uniform)
     const int rlast = min(r0 + W, rows) - 1;
+    // 16-byte form for the bands that are written once: a pair of rows per store (and per read of the old y). W is even, so the band of y starts on a
+    // 16-byte boundary exactly when y does (y_pairs, decided by the host per launch). Whole pairs below the band's last row only; an odd last row goes
+    // out in the 8-byte form, by the one thread whose pair it opens. Split bands keep their atomics.
+    const int nlive = rlast - r0 + 1, npairs = nlive >> 1;
+    if (!it.split && y_pairs && npairs > 0) {                      // (uniform)
+        constexpr int kPairsPerThread = (W / 2 + kPbThreads - 1) / kPbThreads;
+        double2_t *yp = reinterpret_cast<double2_t *>(y + r0);
+        double2_t yv[kPairsPerThread], yo[kPairsPerThread];
+#pragma unroll
+        for (int k = 0; k < kPairsPerThread; ++k) {
+            const int j = (int)threadIdx.x + k * kPbThreads;
+            yv[k] = *reinterpret_cast<const double2_t *>(ys + 2 * min(j, W / 2 - 1));
+            yo[k] = read_y ? yp[min(j, npairs - 1)] : double2_t{0.0, 0.0};
+        }
+        const double yt = read_y ? y[rlast] : 0.0;                 // the old y of an odd last row
+#pragma unroll
+        for (int k = 0; k < kPairsPerThread; ++k) {
+            const int j = (int)threadIdx.x + k * kPbThreads;
+            if (j < npairs) {
+                double2_t o;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if constexpr (!kPlus) o[h] = beta == 0.0 ? yv[k][h] : Sr::combine(yv[k][h], Sr::normalize(yo[k][h]));
+                    else o[h] = beta == 0.0 ? alpha * yv[k][h] : alpha * yv[k][h] + beta * yo[k][h];
+                }
+                yp[j] = o;
+            } else if (2 * j < nlive) {                             // j == npairs: the odd last row
+                if constexpr (!kPlus) y[rlast] = beta == 0.0 ? yv[k][0] : Sr::combine(yv[k][0], Sr::normalize(yt));
+                else y[rlast] = beta == 0.0 ? alpha * yv[k][0] : alpha * yv[k][0] + beta * yt;
+            }
+        }
+        return;
+    }
+    constexpr int kRowsPerThread = (W + kPbThreads - 1) / kPbThreads;
+    double yv[kRowsPerThread], yo[kRowsPerThread];
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
         yv[k] = ys[min((int)threadIdx.x + k * kPbThreads, W - 1)];
@@ -856,6 +925,9 @@ int pb_build(PbPlan **out, int rows, int cols, long long nnz, const int *d_rowpt
     }
     std::stable_sort(cit.begin(), cit.end(), [](const ConsumerItem &a, const ConsumerItem &b) { return (a.k1 - a.k0) > (b.k1 - b.k0); });
     std::stable_sort(pit.begin(), pit.end(), [](const ProducerItem &a, const ProducerItem &b) { return (a.s1 - a.s0) > (b.s1 - b.s0); });
+    // (Tried: the hot items dealt so that position p of the leading run of full items holds an item of a hot band ≡ p (mod 8) — blocks b and b + 8 have been seen
+    // to share an XCD, whose L2 would then keep H / 8 bands of hot_x instead of H. The producer's fetched bytes fell by 1.4 % and the product ran 1.5 % SLOWER
+    // on a quiet box, profiles/pb_hot_l2_ab_steps.txt; not kept.)
     P->n_pitems = (int)pit.size(); P->n_citems = (int)cit.size(); P->n_split = (int)split.size();
     G4S_TRY(P->pitems.alloc(sizeof(ProducerItem) * pit.size()));
     G4S_TRY(P->citems.alloc(sizeof(ConsumerItem) * cit.size()));
@@ -901,6 +973,8 @@ int pb_update_values(PbPlan *P, const double *d_values, hipStream_t s)
 template <int W, class Sr>
 static void pb_launch(PbPlan *P, const double *x, double *y, double alpha, double beta, hipStream_t s)
 {
+    // the 16-byte forms of the producer's staging and the consumer's write-out need their vector on a 16-byte boundary (the caller's x or y may be a view)
+    const int x_pairs = G4S_PB_PAIR16 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0, y_pairs = G4S_PB_PAIR16 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0;
     if (P->n_split || P->H) {
         // split bands: one block per 256 rows of each band; hot columns: one per 256 of them (H·W of them, whole blocks either way)
         const int blocks = P->n_split * ((W + 255) / 256) + (P->H * W + 255) / 256;
@@ -909,10 +983,10 @@ static void pb_launch(PbPlan *P, const double *x, double *y, double alpha, doubl
     }
     if (P->n_pitems)
         hipLaunchKernelGGL((pb_producer_kernel<W, Sr>), dim3(P->n_pitems), dim3(kPbThreads), P->lds_producer, s, P->pitems.as<ProducerItem>(), P->cols, P->H, P->hot_x.as<double>(),
-                           P->p_lcol.as<unsigned short>(), P->p_val.as<double>(), P->mbase.as<int>(), x, P->prod.as<double>());
+                           P->p_lcol.as<unsigned short>(), P->p_val.as<double>(), P->mbase.as<int>(), x, P->prod.as<double>(), x_pairs);
     if (P->n_citems)
         hipLaunchKernelGGL((pb_consumer_kernel<W, Sr>), dim3(P->n_citems), dim3(kPbThreads), P->lds_consumer, s, P->citems.as<ConsumerItem>(), P->rows,
-                           P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta, P->band_end.as<int>());
+                           P->c_lrow.as<unsigned short>(), P->prod.as<double>(), y, alpha, beta, P->band_end.as<int>(), y_pairs);
 }
 
 int pb_spmv(PbPlan *P, const double *x, double *y, unsigned sr_flag, double alpha, double beta, hipStream_t s)

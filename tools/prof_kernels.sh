@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/kt_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 3 "$@" > $OUT/bench.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 3 "$@" > $OUT/bench.log 2>&1 || { echo "profiled run failed"; tail -5 $OUT/bench.log; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + '/*/*kernel_stats.csv')[0]
