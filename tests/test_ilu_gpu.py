@@ -130,10 +130,9 @@ def _check_info(got, want):
     assert got["host_waits"] <= got["launches"] // 16 + ref.HOST_WAITS_SLACK and got["launches"] >= got["launches_per_factor"], got
 
 
-@pytest.mark.parametrize("name", sorted(ref.CASES))
-def test_case_equals_reference(name):
-    """both pointer kinds, chains and one launch per level: the reference's info, pivot word and bits — of the factors, and of z for r != z and r = z"""
-    mat, f, info, r, z = ref.case(name)
+def check_case(name, mat, f, info, r, z):
+    """both pointer kinds, chains and one launch per level: the reference's info, pivot word and bits — of the factors, and of z for r != z and r = z
+    (tests/test_ilu_limits_gpu.py runs its cases through the same checks)"""
     for device in (True, False):
         for no_chains in (False, True):
             p = Fact(mat, no_chains, device)
@@ -151,6 +150,11 @@ def test_case_equals_reference(name):
             if device and not no_chains:
                 print(f"{name}: {p.info}")
             p.close()
+
+
+@pytest.mark.parametrize("name", sorted(ref.CASES))
+def test_case_equals_reference(name):
+    check_case(name, *ref.case(name))
 
 
 def test_apply_is_the_two_solves_of_the_reference():

@@ -254,6 +254,14 @@ def poison_other_triangle(mat, lower):
     return n, rp, ci, va
 
 
+def mirror(mat):
+    """The upper twin of a lower case (and back): row and column i become n − 1 − i, every row keeps its stored order and its values. The upper triangle of
+    the result is the lower triangle of `mat` with the ids reversed: the same DAG, the same levels, the rows of a level in the opposite order."""
+    n, rp, ci, va = mat
+    rows = [[(n - 1 - int(ci[k]), float(va[k])) for k in range(int(rp[i]), int(rp[i + 1]))] for i in range(n - 1, -1, -1)]
+    return csr(rows, n)
+
+
 def unit_poisoned(n, seed=8):
     """a strictly-lower part; every second row also stores a NaN on the diagonal, the others store none"""
     rng = _rng(seed)
