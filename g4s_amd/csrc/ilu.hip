@@ -427,13 +427,8 @@ G4S_API g4s_status g4s_ilu0_apply_multi(g4s_ilu0_t P, int32_t k, const double *R
                                         void *stream)
 {
     G4S_REQUIRE(P, "the handle is NULL");
-    G4S_REQUIRE(k >= 0 && k <= G4S_TRSV_MAX_RHS, "k is negative or above G4S_TRSV_MAX_RHS");
-    G4S_REQUIRE((flags & ~G4S_TRSV_COL_MAJOR) == 0u, "flags other than G4S_TRSV_COL_MAJOR");
-    if (P->n == 0 || k == 0) return G4S_OK;
-    G4S_REQUIRE(R_dev && Z_dev, "R or Z is NULL");
-    const int64_t need = (flags & G4S_TRSV_COL_MAJOR) ? P->n : k;
-    G4S_REQUIRE(ldr >= need && ldz >= need, "a leading dimension is too small: ld >= k row-major, ld >= n column-major");
-    G4S_REQUIRE(R_dev != Z_dev || ldr == ldz, "Z is R with another leading dimension");
+    const g4s::BlockCall call = g4s::check_block_call(__func__, P->n, k, "R", R_dev, ldr, "Z", Z_dev, ldz, flags);   // before P->lower is read
+    if (!call.go_on) return call.status;
     G4S_TRY(g4s_sptrsv_solve_multi(P->lower, k, R_dev, ldr, Z_dev, ldz, flags, stream));
     return g4s_sptrsv_solve_multi(P->upper, k, Z_dev, ldz, Z_dev, ldz, flags, stream);
 }

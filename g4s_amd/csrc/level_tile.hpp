@@ -1,4 +1,4 @@
-// level_tile.hpp — the device side of a level-scheduled call (trsv.hip: tr_level_kernel, tr_chain_kernel; ilu.hip: ilu_level_kernel,
+// level_tile.hpp — the device side of a level-scheduled call (trsv.hip: tr_level_kernel<Rhs>, tr_chain_kernel<Rhs>; ilu.hip: ilu_level_kernel,
 // ilu_chain_kernel): which workgroup takes which rows of a level, which thread, wave or workgroup works a row off (deal_tile), the walk
 // of one workgroup through the levels of a chain and the loads that make it correct. What a row is and the arithmetic on it stay with the two files,
 // as callables; level_schedule.hpp is the host side.

@@ -16,9 +16,10 @@
 // The solve enqueues the launch list (for_each_launch, level_schedule.hpp) and waits for nothing. Every launch solves whole levels, so a row reads only
 // x values written behind a kernel boundary or — inside a chain — by its own workgroup behind a fence and a barrier: the frame and its memory model
 // are level_tile.hpp's (deal_tile, for_chain_levels, ld_prior), shared with ilu.hip. No wave waits for another workgroup; nothing spins.
-// The arithmetic shape of a row (g4s.h) depends on its own entry count alone: solve_tile is the one place that computes it, for both kernels.
-// g4s_sptrsv_solve_multi solves a block of k right-hand sides on the same launch list: solve_tile_multi is solve_tile for a tile of
-// G4S_TRSV_RHS_TILE columns, tr_level_multi_kernel and tr_chain_multi_kernel the two kernels with a column tile per workgroup.
+// The arithmetic shape of a row (g4s.h) depends on its own entry count alone: solve_tile is the one place that computes it, for both kernels and for
+// both entry points. g4s_sptrsv_solve_multi solves a block of k right-hand sides on the same launch list: the solve is written over the
+// right-hand sides' type — RhsVector, a tile of one column, or RhsBlock<kCol>, a tile of G4S_TRSV_RHS_TILE columns per workgroup — and
+// tr_level_kernel and tr_chain_kernel are instantiated for each.
 #include "common.hpp"
 #include "frontier.hpp"
 #include "call_util.hpp"
@@ -303,114 +304,52 @@ struct TrView {
     int unit;
 };
 
-// One lane's share of a row's sum: the entries first, first + kStride, … below m of the row whose entries begin at e, added left to right from +0.0.
-// kUnroll entries are loaded before the first of them is added — a lane has one dependent pair of loads (the column, then x) per entry, and a hub row
-// of 10⁵ entries is 400 such pairs per lane —; the additions keep their order, so the bits do not depend on kUnroll.
-template <bool kChain, int kStride, int kUnroll>
-__device__ __forceinline__ double strided_sum(const TrView &T, const double *x, int e, int first, int m)
-{
-    double s = 0.0;
-    int k = first;
-    for (; k + (kUnroll - 1) * kStride < m; k += kUnroll * kStride) {
-        int c[kUnroll];
-        double v[kUnroll], y[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) c[u] = T.lcol[e + k + u * kStride];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) v[u] = T.lval[e + k + u * kStride];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) y[u] = ld_prior<kChain>(x + c[u]);
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) s = s + v[u] * y[u];
-    }
-    for (; k < m; k += kStride) s = s + T.lval[e + k] * ld_prior<kChain>(x + T.lcol[e + k]);
-    return s;
-}
-
-// Rows [lo, hi) of the layout, all of one level, dealt by deal_tile (level_tile.hpp); the owner of a row keeps its sum s through the three classes and
-// writes its x. Who sums a row never changes how it is summed:
-//   m <= kWaveRow            the lane alone, left to right from +0.0
-//   kWaveRow < m <= kHubCut  the row's wave: lane l takes entries l, l + 64, … left to right from +0.0, then the wave_sum ladder
-//   m > kHubCut              the workgroup: thread t takes entries t, t + 256, …, a wave_sum ladder per wave, then ((w0 + w1) + w2) + w3
-// b and x may be the same array: row r is the only reader of b[r] and the only writer of x[r].
-struct TrRow {
-    int m, e;                                                      // off-diagonal entries, and where they begin
+// The right-hand sides of a solve, by value into the kernels: b and x, kTile columns a workgroup — a thread that owns a row owns it for a tile of
+// columns, and an entry's column and value are loaded once for all of them —, the entries each row class loads ahead of its additions, and where an
+// element lies. Column j of a block is solved as the vector is, bit for bit: every column's products are added in the order and the shape of its
+// row's class, whatever kTile and the unrolls.
+// A vector: one column and no leading dimension — element i is at [i], and nothing of a tile is left at run time.
+struct RhsVector {
+    static constexpr int kTile = 1, kLaneUnroll = 4, kWaveUnroll = 8, kHubUnroll = 8;
+    const double *b;
+    double *x;
+    __device__ int tile_cols(int) const { return 1; }
+    __device__ long long b_at(int i, int) const { return i; }
+    __device__ long long x_at(int i, int) const { return i; }
+    __device__ long long b_step() const { return 1; }
+    __device__ long long x_step() const { return 1; }
 };
 
-template <bool kChain>
-__device__ __forceinline__ void solve_tile(const TrView &T, int lo, int hi, int stride, const double *b, double *x, int *s_hub, int *s_nh, double *s_part)
-{
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    double s = 0.0;
-    const int p = deal_tile<kWaveRow, kHubCut>(lo, hi, stride, s_hub, s_nh,
-        [&](int p) { return TrRow{T.noff[p], T.ebeg[p]}; },
-        [&](const TrRow &r) { s = strided_sum<kChain, 1, 4>(T, x, r.e, 0, r.m); },
-        [&](const TrRow &r, int j) {
-            const double part = __shfl(wave_sum(strided_sum<kChain, 64, 8>(T, x, __shfl(r.e, j), lane, __shfl(r.m, j))), 0);
-            if (lane == j) s = part;
-        },
-        [&](const TrRow &r, int th) {
-            const double part = wave_sum(strided_sum<kChain, WG, 8>(T, x, r.e, t, r.m));
-            if (lane == 0) s_part[wave] = part;
-            __syncthreads();
-            if (t == th) s = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-        });
-    if (p >= 0) {
-        const int r = T.rowid[p];
-        double v = b[r] - s;
-        if (!T.unit) v = v / T.diag[p];
-        x[r] = canonical_nan(v);
-    }
-}
-
-// one level that is not in a chain: a tile of WG / stride rows per workgroup
-__global__ __launch_bounds__(WG) void tr_level_kernel(const TrView T, int lo, int hi, int stride, const double *b, double *x)
-{
-    __shared__ int s_hub[WG], s_nh;
-    __shared__ double s_part[WG / 64];
-    const int2 tile = level_tile_bounds(lo, hi, stride);
-    solve_tile<false>(T, tile.x, tile.y, stride, b, x, s_hub, &s_nh, s_part);
-}
-
-// a chain: one workgroup, levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one stored (for_chain_levels)
-__global__ __launch_bounds__(WG) void tr_chain_kernel(const TrView T, int level_lo, int level_hi, const double *b, double *x)
-{
-    __shared__ int s_hub[WG], s_nh;
-    __shared__ double s_part[WG / 64];
-    for_chain_levels(T.loff, level_lo, level_hi, [&](int lo, int hi, int stride) { solve_tile<true>(T, lo, hi, stride, b, x, s_hub, &s_nh, s_part); });
-}
-
-// ------------------------------------------------------------------------------------------------------------- the solve of a block
-// k right-hand sides on the launches of one: a thread that owns a row owns it for a tile of kRhsTile columns of the block, the workgroups of a level
-// launch carry the column tile in blockIdx.y, a chain is one workgroup per column tile (blockIdx.x) — column tiles share nothing, so no workgroup
-// waits for another. An entry's column and value are loaded once and used for every column of the tile. Column j of X is what the kernels above give
-// for column j of B, bit for bit: every column's products are added in the order and the shape of its row's class, whatever kRhsTile and the unrolls.
-constexpr int kRhsTile = G4S_TRSV_RHS_TILE;
-
-// The n × k blocks B and X, and the column tile [j0, j0 + kn) of this workgroup. Element (i, j) is at [i·ld + j], kCol: at [i + j·ld].
-struct TrBlock {
+// The n × k blocks B and X. Element (i, j) is at [i·ld + j], kCol: at [i + j·ld].
+template <bool kCol>
+struct RhsBlock {
+    static constexpr int kTile = G4S_TRSV_RHS_TILE, kLaneUnroll = 2, kWaveUnroll = 4, kHubUnroll = 4;
     const double *b;
     double *x;
     long long ldb, ldx;
     int k;
+    static __device__ long long at(long long ld, int i, int j) { return kCol ? (long long)i + (long long)j * ld : (long long)i * ld + j; }
+    __device__ int tile_cols(int j0) const { return std::min(kTile, k - j0); }
+    __device__ long long b_at(int i, int j) const { return at(ldb, i, j); }
+    __device__ long long x_at(int i, int j) const { return at(ldx, i, j); }
+    __device__ long long b_step() const { return kCol ? ldb : 1; }   // from a column to the next
+    __device__ long long x_step() const { return kCol ? ldx : 1; }
 };
 
-template <bool kCol>
-__device__ __forceinline__ long long block_at(long long ld, int i, int j) { return kCol ? (long long)i + (long long)j * ld : (long long)i * ld + j; }
-
-// strided_sum for a column tile: s[q] is the sum over the column of x whose element of row 0 is xq[q]. xq repeats the tile's last column behind kn
-// (the same for every thread of the workgroup), so a lane never loads outside the block and the tail needs no branch; what it sums there is never
-// stored.
-template <bool kChain, bool kCol, int kStride, int kUnroll>
-__device__ __forceinline__ void strided_sum_multi(const TrView &T, const double *const (&xq)[kRhsTile], long long ldx, int e, int first, int m,
-                                                  double (&s)[kRhsTile])
+// One lane's share of a row's sums: the entries first, first + kStride, … below m of the row whose entries begin at e, added left to right from +0.0;
+// s[q] is the sum over the column of x whose element of row 0 is xq[q]. kUnroll entries are loaded before the first of them is added — a lane has one
+// dependent pair of loads (the column, then x) per entry and column, and a hub row of 10⁵ entries is 400 such pairs per lane —; the additions keep
+// their order, so the bits do not depend on kUnroll.
+template <bool kChain, typename Rhs, int kStride, int kUnroll>
+__device__ __forceinline__ void strided_sum(const TrView &T, const Rhs &R, const double *const (&xq)[Rhs::kTile], int e, int first, int m,
+                                            double (&s)[Rhs::kTile])
 {
 #pragma unroll
-    for (int q = 0; q < kRhsTile; ++q) s[q] = 0.0;
+    for (int q = 0; q < Rhs::kTile; ++q) s[q] = 0.0;
     int k = first;
     for (; k + (kUnroll - 1) * kStride < m; k += kUnroll * kStride) {
         int c[kUnroll];
-        double v[kUnroll], y[kUnroll][kRhsTile];
+        double v[kUnroll], y[kUnroll][Rhs::kTile];
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) c[u] = T.lcol[e + k + u * kStride];
 #pragma unroll
@@ -418,112 +357,123 @@ __device__ __forceinline__ void strided_sum_multi(const TrView &T, const double 
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u)
 #pragma unroll
-            for (int q = 0; q < kRhsTile; ++q) y[u][q] = ld_prior<kChain>(xq[q] + block_at<kCol>(ldx, c[u], 0));
+            for (int q = 0; q < Rhs::kTile; ++q) y[u][q] = ld_prior<kChain>(xq[q] + R.x_at(c[u], 0));
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u)
 #pragma unroll
-            for (int q = 0; q < kRhsTile; ++q) s[q] = s[q] + v[u] * y[u][q];
+            for (int q = 0; q < Rhs::kTile; ++q) s[q] = s[q] + v[u] * y[u][q];
     }
     for (; k < m; k += kStride) {
         const int c = T.lcol[e + k];
         const double v = T.lval[e + k];
-        double y[kRhsTile];
+        double y[Rhs::kTile];
 #pragma unroll
-        for (int q = 0; q < kRhsTile; ++q) y[q] = ld_prior<kChain>(xq[q] + block_at<kCol>(ldx, c, 0));
+        for (int q = 0; q < Rhs::kTile; ++q) y[q] = ld_prior<kChain>(xq[q] + R.x_at(c, 0));
 #pragma unroll
-        for (int q = 0; q < kRhsTile; ++q) s[q] = s[q] + v * y[q];
+        for (int q = 0; q < Rhs::kTile; ++q) s[q] = s[q] + v * y[q];
     }
 }
 
-// solve_tile for the column tile `tile` of the block: the same deal, the same three classes, kRhsTile sums a row; s_part is [WG / 64][kRhsTile].
-template <bool kChain, bool kCol>
-__device__ __forceinline__ void solve_tile_multi(const TrView &T, int lo, int hi, int stride, const TrBlock &B, int tile, int *s_hub, int *s_nh,
-                                                 double *s_part)
+// Rows [lo, hi) of the layout, all of one level, dealt by deal_tile (level_tile.hpp), for the column tile `tile` of R; the owner of a row keeps its
+// sums s through the three classes and writes its x. Who sums a row never changes how it is summed, per column:
+//   m <= kWaveRow            the lane alone, left to right from +0.0
+//   kWaveRow < m <= kHubCut  the row's wave: lane l takes entries l, l + 64, … left to right from +0.0, then the wave_sum ladder
+//   m > kHubCut              the workgroup: thread t takes entries t, t + 256, …, a wave_sum ladder per wave, then ((w0 + w1) + w2) + w3
+// s_part is [WG / 64][kTile]. xq repeats the tile's last column behind its kn columns (the same for every thread of the workgroup), so a lane never
+// loads outside the block and the tail needs no branch; what it sums there is never stored.
+// b and x may be the same array: row r is the only reader of b[r] and the only writer of x[r], column by column.
+struct TrRow {
+    int m, e;                                                      // off-diagonal entries, and where they begin
+};
+
+template <bool kChain, typename Rhs>
+__device__ __forceinline__ void solve_tile(const TrView &T, int lo, int hi, int stride, const Rhs &R, int tile, int *s_hub, int *s_nh, double *s_part)
 {
+    constexpr int kTile = Rhs::kTile;
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int j0 = tile * kRhsTile, kn = std::min(kRhsTile, B.k - j0);
-    const double *xq[kRhsTile];
+    const int j0 = tile * kTile, kn = R.tile_cols(j0);
+    const double *xq[kTile];
 #pragma unroll
-    for (int q = 0; q < kRhsTile; ++q) xq[q] = B.x + block_at<kCol>(B.ldx, 0, j0 + std::min(q, kn - 1));
-    double s[kRhsTile];
+    for (int q = 0; q < kTile; ++q) xq[q] = R.x + R.x_at(0, j0 + std::min(q, kn - 1));
+    double s[kTile];
 #pragma unroll
-    for (int q = 0; q < kRhsTile; ++q) s[q] = 0.0;
+    for (int q = 0; q < kTile; ++q) s[q] = 0.0;
     const int p = deal_tile<kWaveRow, kHubCut>(lo, hi, stride, s_hub, s_nh,
         [&](int p) { return TrRow{T.noff[p], T.ebeg[p]}; },
-        [&](const TrRow &r) { strided_sum_multi<kChain, kCol, 1, 2>(T, xq, B.ldx, r.e, 0, r.m, s); },
+        [&](const TrRow &r) { strided_sum<kChain, Rhs, 1, Rhs::kLaneUnroll>(T, R, xq, r.e, 0, r.m, s); },
         [&](const TrRow &r, int j) {
-            double part[kRhsTile];
-            strided_sum_multi<kChain, kCol, 64, 4>(T, xq, B.ldx, __shfl(r.e, j), lane, __shfl(r.m, j), part);
+            double part[kTile];
+            strided_sum<kChain, Rhs, 64, Rhs::kWaveUnroll>(T, R, xq, __shfl(r.e, j), lane, __shfl(r.m, j), part);
 #pragma unroll
-            for (int q = 0; q < kRhsTile; ++q) {
+            for (int q = 0; q < kTile; ++q) {
                 const double w = __shfl(wave_sum(part[q]), 0);
                 if (lane == j) s[q] = w;
             }
         },
         [&](const TrRow &r, int th) {
-            double part[kRhsTile];
-            strided_sum_multi<kChain, kCol, WG, 4>(T, xq, B.ldx, r.e, t, r.m, part);
+            double part[kTile];
+            strided_sum<kChain, Rhs, WG, Rhs::kHubUnroll>(T, R, xq, r.e, t, r.m, part);
 #pragma unroll
-            for (int q = 0; q < kRhsTile; ++q) {
+            for (int q = 0; q < kTile; ++q) {
                 const double w = wave_sum(part[q]);
-                if (lane == 0) s_part[wave * kRhsTile + q] = w;
+                if (lane == 0) s_part[wave * kTile + q] = w;
             }
             __syncthreads();
             if (t == th) {
 #pragma unroll
-                for (int q = 0; q < kRhsTile; ++q)
-                    s[q] = ((s_part[q] + s_part[kRhsTile + q]) + s_part[2 * kRhsTile + q]) + s_part[3 * kRhsTile + q];
+                for (int q = 0; q < kTile; ++q) s[q] = ((s_part[q] + s_part[kTile + q]) + s_part[2 * kTile + q]) + s_part[3 * kTile + q];
             }
         });
     if (p >= 0) {
         const int r = T.rowid[p];
         const double d = T.unit ? 1.0 : T.diag[p];
-        const double *bp = B.b + block_at<kCol>(B.ldb, r, j0);
-        double *xp = B.x + block_at<kCol>(B.ldx, r, j0);
+        const double *bp = R.b + R.b_at(r, j0);
+        double *xp = R.x + R.x_at(r, j0);
 #pragma unroll
-        for (int q = 0; q < kRhsTile; ++q) {
+        for (int q = 0; q < kTile; ++q) {
             if (q < kn) {
                 double v = *bp - s[q];
                 if (!T.unit) v = v / d;
                 *xp = canonical_nan(v);
             }
-            bp += kCol ? B.ldb : 1;                                 // the next column; never dereferenced behind the tile
-            xp += kCol ? B.ldx : 1;
+            bp += R.b_step();                                      // the next column; never dereferenced behind the tile
+            xp += R.x_step();
         }
     }
 }
 
-// one level that is not in a chain, for a block: a tile of WG / stride rows (blockIdx.x) times a tile of kRhsTile columns (blockIdx.y) per workgroup
-template <bool kCol>
-__global__ __launch_bounds__(WG) void tr_level_multi_kernel(const TrView T, int lo, int hi, int stride, const TrBlock B)
+// one level that is not in a chain: a tile of WG / stride rows (blockIdx.x) times a tile of columns (blockIdx.y) per workgroup
+template <typename Rhs>
+__global__ __launch_bounds__(WG) void tr_level_kernel(const TrView T, int lo, int hi, int stride, const Rhs R)
 {
     __shared__ int s_hub[WG], s_nh;
-    __shared__ double s_part[(WG / 64) * kRhsTile];
+    __shared__ double s_part[(WG / 64) * Rhs::kTile];
     const int2 tile = level_tile_bounds(lo, hi, stride);
-    solve_tile_multi<false, kCol>(T, tile.x, tile.y, stride, B, (int)blockIdx.y, s_hub, &s_nh, s_part);
+    solve_tile<false>(T, tile.x, tile.y, stride, R, (int)blockIdx.y, s_hub, &s_nh, s_part);
 }
 
-// a chain for a block: one workgroup per column tile (blockIdx.x), each through all the levels of the chain for its own columns, which nobody else
-// reads or writes: for_chain_levels' memory model holds per workgroup, and no workgroup waits for another
-template <bool kCol>
-__global__ __launch_bounds__(WG) void tr_chain_multi_kernel(const TrView T, int level_lo, int level_hi, const TrBlock B)
+// a chain: one workgroup per column tile (blockIdx.x), levels [level_lo, level_hi), each at most WG rows; a later level reads what an earlier one
+// stored (for_chain_levels). Nobody else reads or writes a tile's columns: the memory model holds per workgroup, and no workgroup waits for another.
+template <typename Rhs>
+__global__ __launch_bounds__(WG) void tr_chain_kernel(const TrView T, int level_lo, int level_hi, const Rhs R)
 {
     __shared__ int s_hub[WG], s_nh;
-    __shared__ double s_part[(WG / 64) * kRhsTile];
+    __shared__ double s_part[(WG / 64) * Rhs::kTile];
     const int tile = (int)blockIdx.x;
-    for_chain_levels(T.loff, level_lo, level_hi,
-                     [&](int lo, int hi, int stride) { solve_tile_multi<true, kCol>(T, lo, hi, stride, B, tile, s_hub, &s_nh, s_part); });
+    for_chain_levels(T.loff, level_lo, level_hi, [&](int lo, int hi, int stride) { solve_tile<true>(T, lo, hi, stride, R, tile, s_hub, &s_nh, s_part); });
 }
 
-template <bool kCol>
-void enqueue_multi(const g4s_trsv_s *T, const TrView &V, const TrBlock &B, hipStream_t s)
+// The launch list of the plan for the k columns of R: the column tiles are blockIdx.y of a level launch and the workgroups of a chain.
+template <typename Rhs>
+int enqueue(const g4s_trsv_s *T, const Rhs &R, int k, hipStream_t s)
 {
-    const unsigned tiles = (unsigned)((B.k + kRhsTile - 1) / kRhsTile);
+    const TrView V{T->sched.rowid, T->ebeg, T->noff, T->lcol, T->sched.loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
+    const unsigned tiles = (unsigned)((k + Rhs::kTile - 1) / Rhs::kTile);
     g4s::for_each_launch(T->sched, g4s::trsv_stride,
-        [&](int level_lo, int level_hi) { hipLaunchKernelGGL(tr_chain_multi_kernel<kCol>, dim3(tiles), dim3(WG), 0, s, V, level_lo, level_hi, B); },
-        [&](int lo, int hi, int stride, int grid) {
-            hipLaunchKernelGGL(tr_level_multi_kernel<kCol>, dim3((unsigned)grid, tiles), dim3(WG), 0, s, V, lo, hi, stride, B);
-        });
+        [&](int level_lo, int level_hi) { hipLaunchKernelGGL(tr_chain_kernel<Rhs>, dim3(tiles), dim3(WG), 0, s, V, level_lo, level_hi, R); },
+        [&](int lo, int hi, int stride, int grid) { hipLaunchKernelGGL(tr_level_kernel<Rhs>, dim3((unsigned)grid, tiles), dim3(WG), 0, s, V, lo, hi, stride, R); });
+    G4S_HIP_TRY(hipGetLastError());
+    return G4S_OK;
 }
 
 int bits_of(int v)
@@ -781,13 +731,7 @@ G4S_API g4s_status g4s_sptrsv_solve(g4s_trsv_t T, const double *b_dev, double *x
     G4S_REQUIRE(T, "the handle is NULL");
     if (T->n == 0) return G4S_OK;
     G4S_REQUIRE(b_dev && x_dev, "b or x is NULL");
-    const hipStream_t s = g4s::as_stream(stream);
-    const TrView V{T->sched.rowid, T->ebeg, T->noff, T->lcol, T->sched.loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
-    g4s::for_each_launch(T->sched, g4s::trsv_stride,
-        [&](int level_lo, int level_hi) { hipLaunchKernelGGL(tr_chain_kernel, dim3(1), dim3(WG), 0, s, V, level_lo, level_hi, b_dev, x_dev); },
-        [&](int lo, int hi, int stride, int grid) { hipLaunchKernelGGL(tr_level_kernel, dim3((unsigned)grid), dim3(WG), 0, s, V, lo, hi, stride, b_dev, x_dev); });
-    G4S_HIP_TRY(hipGetLastError());
-    return G4S_OK;
+    return enqueue(T, RhsVector{b_dev, x_dev}, 1, g4s::as_stream(stream));
 }
 
 static_assert((G4S_TRSV_COL_MAJOR & (kFlagMask | G4S_ILU0_NO_CHAINS)) == 0u, "a bit of its own");
@@ -797,21 +741,11 @@ G4S_API g4s_status g4s_sptrsv_solve_multi(g4s_trsv_t T, int32_t k, const double 
                                           void *stream)
 {
     G4S_REQUIRE(T, "the handle is NULL");
-    G4S_REQUIRE(k >= 0 && k <= G4S_TRSV_MAX_RHS, "k is negative or above G4S_TRSV_MAX_RHS");
-    G4S_REQUIRE((flags & ~G4S_TRSV_COL_MAJOR) == 0u, "flags other than G4S_TRSV_COL_MAJOR");
-    if (T->n == 0 || k == 0) return G4S_OK;
-    G4S_REQUIRE(B_dev && X_dev, "B or X is NULL");
-    const bool col = (flags & G4S_TRSV_COL_MAJOR) != 0;
-    const int64_t need = col ? T->n : k;
-    G4S_REQUIRE(ldb >= need && ldx >= need, "a leading dimension is too small: ld >= k row-major, ld >= n column-major");
-    G4S_REQUIRE(B_dev != X_dev || ldb == ldx, "X is B with another leading dimension");
+    const g4s::BlockCall call = g4s::check_block_call(__func__, T->n, k, "B", B_dev, ldb, "X", X_dev, ldx, flags);
+    if (!call.go_on) return call.status;
     const hipStream_t s = g4s::as_stream(stream);
-    const TrView V{T->sched.rowid, T->ebeg, T->noff, T->lcol, T->sched.loff, T->diag, T->lval, (T->flags & G4S_TRSV_UNIT_DIAGONAL) != 0};
-    const TrBlock B{B_dev, X_dev, (long long)ldb, (long long)ldx, k};
-    if (col) enqueue_multi<true>(T, V, B, s);
-    else enqueue_multi<false>(T, V, B, s);
-    G4S_HIP_TRY(hipGetLastError());
-    return G4S_OK;
+    if (flags & G4S_TRSV_COL_MAJOR) return enqueue(T, RhsBlock<true>{B_dev, X_dev, (long long)ldb, (long long)ldx, k}, k, s);
+    return enqueue(T, RhsBlock<false>{B_dev, X_dev, (long long)ldb, (long long)ldx, k}, k, s);
 }
 
 G4S_API g4s_status g4s_sptrsv_update_values(g4s_trsv_t T, const double *values, unsigned flags, void *stream)

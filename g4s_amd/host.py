@@ -940,6 +940,25 @@ def _rhs_block(b, out, n, name):
     return out, k, ldb, ldo, (capi.TRSV_COL_MAJOR if cm else 0)
 
 
+def _solve_rhs(handle, single, multi, b, out, n, name):
+    """TriangularPlan.solve and ILU0.apply behind their open handle: a 2-D b goes as a block (_rhs_block) to the C function named multi, a vector of
+    n doubles to the one named single; out is allocated where it is None, and returned. `name` is what the ValueErrors call b."""
+    if isinstance(b, torch.Tensor) and b.dim() == 2:
+        out, k, ldb, ldo, flags = _rhs_block(b, out, n, name)
+        capi.check(getattr(capi.load(), multi)(handle, k, _ptr(b), ldb, _ptr(out), ldo, flags, _stream()))
+        return out
+    if not (isinstance(b, torch.Tensor) and b.dtype == torch.float64 and b.dim() == 1 and b.numel() == n and b.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float64 tensor of {n} entries")
+    if out is None:
+        out = torch.empty_like(b)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.dim() == 1 and out.numel() == n and out.is_contiguous()
+              and out.device == b.device):
+        raise ValueError(f"out must be a contiguous float64 tensor of {n} entries on {name}'s device")
+    assert b.is_cuda
+    capi.check(getattr(capi.load(), single)(handle, _ptr_nn(b), _ptr_nn(out), _stream()))
+    return out
+
+
 class TriangularPlan:
     """A g4s_trsv_t: the (level, row) copy of a triangle and its launch list. solve(b, out=None) enqueues on the current torch stream and waits for
     nothing (it can be captured into a graph); out may be b. b is a vector of n doubles or a 2-D block of n × k right-hand sides (row- or
@@ -953,20 +972,7 @@ class TriangularPlan:
     def solve(self, b, out=None):
         if self._handle is None:
             raise ValueError("the plan is closed")
-        if isinstance(b, torch.Tensor) and b.dim() == 2:
-            out, k, ldb, ldo, flags = _rhs_block(b, out, self.n, "b")
-            capi.check(capi.load().g4s_sptrsv_solve_multi(self._handle, k, _ptr(b), ldb, _ptr(out), ldo, flags, _stream()))
-            return out
-        if not (isinstance(b, torch.Tensor) and b.dtype == torch.float64 and b.dim() == 1 and b.numel() == self.n and b.is_contiguous()):
-            raise ValueError(f"b must be a contiguous float64 tensor of {self.n} entries")
-        if out is None:
-            out = torch.empty_like(b)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.dim() == 1 and out.numel() == self.n and out.is_contiguous()
-                  and out.device == b.device):
-            raise ValueError(f"out must be a contiguous float64 tensor of {self.n} entries on b's device")
-        assert b.is_cuda
-        capi.check(capi.load().g4s_sptrsv_solve(self._handle, _ptr_nn(b), _ptr_nn(out), _stream()))
-        return out
+        return _solve_rhs(self._handle, "g4s_sptrsv_solve", "g4s_sptrsv_solve_multi", b, out, self.n, "b")
 
     def update_values(self, values):
         """New values in the layout of the arrays the plan was analysed from (all nnz of them): a device tensor (refreshed on the current torch
@@ -1144,20 +1150,7 @@ class ILU0:
 
     def apply(self, r, out=None):
         self._open()
-        if isinstance(r, torch.Tensor) and r.dim() == 2:
-            out, k, ldr, ldo, flags = _rhs_block(r, out, self.n, "r")
-            capi.check(capi.load().g4s_ilu0_apply_multi(self._handle, k, _ptr(r), ldr, _ptr(out), ldo, flags, _stream()))
-            return out
-        if not (isinstance(r, torch.Tensor) and r.dtype == torch.float64 and r.dim() == 1 and r.numel() == self.n and r.is_contiguous()):
-            raise ValueError(f"r must be a contiguous float64 tensor of {self.n} entries")
-        if out is None:
-            out = torch.empty_like(r)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.dim() == 1 and out.numel() == self.n and out.is_contiguous()
-                  and out.device == r.device):
-            raise ValueError(f"out must be a contiguous float64 tensor of {self.n} entries on r's device")
-        assert r.is_cuda
-        capi.check(capi.load().g4s_ilu0_apply(self._handle, _ptr_nn(r), _ptr_nn(out), _stream()))
-        return out
+        return _solve_rhs(self._handle, "g4s_ilu0_apply", "g4s_ilu0_apply_multi", r, out, self.n, "r")
 
     def factor(self, values=None):
         self._open()

@@ -150,7 +150,8 @@ def _main_loop_trips(m, first, stride, unroll):
 
 
 def test_unroll_edges_reach_every_split_of_every_instantiation():
-    """(stride, unroll) of strided_sum<…, 1, 4>, <…, 64, 8>, <…, WG, 8> and strided_sum_multi<…, 1, 2>, <…, 64, 4>, <…, WG, 4>, each on the rows of its class.
+    """(stride, unroll) of strided_sum<…, RhsVector, 1, 4>, <…, 64, 8>, <…, WG, 8> and strided_sum<…, RhsBlock<…>, 1, 2>, <…, 64, 4>, <…, WG, 4>, each on the rows
+    of its class.
     A lane's main loop runs while k + (unroll − 1)·stride < m, in trips of unroll·stride entries. Per instantiation the lengths give lane 0 a smallest
     number of trips, one more and two more, and sit one entry short of a whole number of full trips, on it and one past it — where the LAST lane's trip
     count changes and the tail is empty, whole or one entry. The smallest number is zero wherever the class allows it; it cannot for the workgroup's

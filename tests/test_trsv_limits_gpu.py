@@ -56,6 +56,23 @@ def test_block_solve_equals_single_solves_and_reference(name, lower):
         plan.close()
 
 
+@pytest.mark.parametrize("lower", (True, False))
+def test_unroll_edges_block_equals_reference_in_every_column(lower):
+    """The block solve is the same template as the single solve, so "every column is the device's single solve" compares two instantiations of one sum.
+    On unroll_edges — every main-loop/tail split of all six (class, stride, unroll) instantiations in one matrix — all G4S_TRSV_RHS_TILE + 1 columns, the
+    full tile and the masked one, are therefore the Python reference's own solve of that column by bits, row-major and column-major, with chains, out
+    of place and in place, the padding still the sentinel. The single solve is pinned to the same reference by test_case_equals_reference."""
+    k = tm._kt() + 1
+    mat, b, x = lc.solved("unroll_edges", lower)
+    B = np.random.default_rng(61).uniform(-1.0, 1.0, (mat[0], k))
+    B[:, 0] = b
+    want = np.stack([x] + [ref.solve(*mat, B[:, j], lower) for j in range(1, k)], axis=1)
+    plan = tm._plan(mat, lower)
+    assert plan.info["chains"] == 1
+    tm.solve_checked(lambda b_, x_: plan.solve(b_, out=x_), B, want, ("unroll_edges", lower), layouts=(("row", 3), ("col", 5)))
+    plan.close()
+
+
 @pytest.mark.parametrize("name,lower", PEEL)
 def test_analysis_counts_equal_the_model(name, lower):
     """resumes, launches and host_waits of the analysis are what the host loop of peel() gives on this device's CU count (level_cases.peel); a
